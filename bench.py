@@ -8,16 +8,23 @@ a batch of `--bins` bins per GPU already resident in HBM: fused SOS_OS solve of 
 aggregation (+ one RCCL all-reduce of the band result when N > 1).  Bins are sharded over ranks with no
 data-path collective besides that reduce; per-GPU work is fixed as N grows ("weak").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, config).  --full adds
+everything else the benchmark measures: the roofline of the dominant kernel (extra launches timed on their own), per-rank
+solve / reduce times (N > 1), and with N = 1 the 4096-bin batch, the realistic mix, the small-band latency, the surface and
+angle-count variants, the hyperspectral leg and the CPU baselines (--no-mix / --no-hyper / --no-cpu drop parts of it).
+--dump-outputs DIR: after the timed steps, what the last step computed as float64 .npy files (dump_outputs); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 With N > 1 and no launcher environment (WORLD_SIZE unset) the script starts its own N ranks through
 `python -m torch.distributed.run` as a CHILD process, before anything touches the GPU, and exits with the child's
 code; under a launcher (the driver's torch.distributed.run) it is one rank.  Rank 0 prints ONE JSON line.
 
---workload realistic (also appended to the default N = 1 line as "realistic_mix"): the same wavelength with the level
+--workload realistic (also appended to the --full N = 1 line as "realistic_mix"): the same wavelength with the level
 grids SOS_PROFILE really produces (NT 117...426 from seeded gas columns, made on the device by sosgpu_profile), i.e. the
 streamed-field variant of the solver.
---workload hyperspectral (also appended to the default N = 1 line as "hyperspectral"): BASELINE config 5 through the drop-in --
+--workload hyperspectral (also appended to the --full N = 1 line as "hyperspectral"): BASELINE config 5 through the drop-in --
 run_sos.sos_spectrum over the 2496 spectral intervals of 2500-27500 cm-1 (synthetic CKD tables with the reference's own
 number of exponential terms per gas and interval, scripts/synth_ckd.py; 5732 bins), wavelengths dealt to the ranks.
 --scaling strong: ONE global band of --bins bins (headline) split over the N ranks by cost (dist.balanced_shards), the
@@ -207,19 +214,40 @@ def dry_run(args, world, rank):
 
 
 def timed_steps(step, fence, steps, warmup, world, dist, device, torch):
+    """Returns (seconds of the `steps` timed steps, what the last step returned)."""
     for _ in range(warmup):
         step()
     fence()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     fence()
     dt = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt
+    return dt, last
+
+
+DUMP_BINS = 64      # per-bin records written by --dump-outputs (161 KB each at N = 41, OS_NB = 80)
+
+
+def dump_outputs(path, pkg, torch, buf, out, perm):
+    """--dump-outputs: what the last timed step computed, as float64 .npy files under `path`: the band result a caller of the
+    step receives (aggregated records and scalar block, after the reduce over ranks: band_rec, band_scal) and the solver's
+    per-bin outputs (bin_rec, bin_norders, bin_iglast, bin_flux) for a fixed, seeded sample of DUMP_BINS of this rank's bins,
+    taken in generation order (perm: device position -> generation index, as upload_bins returns it; None = identity)."""
+    os.makedirs(path, exist_ok=True)
+    nb = out["rec"].shape[0]
+    band_rec, band_scal = pkg.dist.unpack_partial(buf, (buf.shape[0],) + tuple(out["rec"].shape[1:]))
+    gen = np.sort(np.random.default_rng(0).choice(nb, min(DUMP_BINS, nb), replace=False))
+    pos = gen if perm is None else np.argsort(perm)[gen]
+    sel = torch.from_numpy(pos).to(out["rec"].device)
+    arrays = dict(band_rec=band_rec, band_scal=band_scal, bin_rec=out["rec"][sel], bin_norders=out["norders"][sel],
+                  bin_iglast=out["iglast"][sel], bin_flux=out["flux"][sel])
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float64))
 
 
 def kernel_ms(cx, bins, out, reps=3):
@@ -244,9 +272,10 @@ def pmc_traffic(tag, **match):
     return None
 
 
-def run_realistic(pkg, torch, dist, world, rank, nbins, steps, warmup, g, strong=False):
+def run_realistic(pkg, torch, dist, world, rank, nbins, steps, warmup, g, strong=False, full=True, dump=None):
     """The level grids real CKD bins get (NT >= CTE_OS_NT_MIN = 100, SOS.h:229): profiles made on the device by
-    sosgpu_profile from seeded gas columns, solved by the streamed-field variant.  Returns the result dict."""
+    sosgpu_profile from seeded gas columns, solved by the streamed-field variant.  Returns the result dict; the roofline
+    (launches of its own) only with `full`; dump: directory for dump_outputs (rank 0)."""
     S = pkg.synth
     mu, w, n0 = S.gauss_angles(40, 35.0)
     os_nb = 80
@@ -276,32 +305,35 @@ def run_realistic(pkg, torch, dist, world, rank, nbins, steps, warmup, g, strong
             dist.barrier()
         torch.cuda.synchronize()
 
-    dt = timed_steps(step, fence, steps, warmup, world, dist, cx.device, torch)
-    kms = kernel_ms(cx, bins, out, 2)
-    flops_ref, flops_exe = cx.solve_flops(bins, out)
+    dt, buf = timed_steps(step, fence, steps, warmup, world, dist, cx.device, torch)
+    if dump and rank == 0:
+        dump_outputs(dump, pkg, torch, buf, out, order)
     nt = bins["nt"].cpu().numpy().astype(np.int64)
     igl = out["iglast"].cpu().numpy().astype(np.int64)
     nsteps = np.clip(igl - 1, 0, None).sum(axis=1)                # contraction steps (scattering orders >= 2) per bin
     passes = np.clip(igl, 0, None).sum(axis=1)                    # field passes per bin: every scattering order, order 1 included
-    # algorithmic field traffic of the streamed variant: each pass writes the 6N-row field of NT+1 levels once and every
-    # pass but the first of a Fourier order reads it once
-    field = (nt + 1) * 6 * cx.n * 8.0
     nord = out["norders"].cpu().numpy().astype(np.int64)
-    bytes_alg = float((field * (2 * passes - np.clip(nord, 0, None))).sum())
-    ach = bytes_alg / (kms * 1e-3) / 1e9
-    tf = flops_exe / (kms * 1e-3) / 1e12
     res = dict(value=nb_tot * steps / dt, unit="bins/s", ms_per_step=1e3 * dt / steps, steps=steps, warmup=warmup,
                config=dict(workload="same wavelength as the headline, level grids of SOS_PROFILE for seeded gas columns "
                                     "(k log-uniform 1e-3..30): NT %d...%d, mean %.0f; %d bins/GPU/step" % (
                                         nt.min(), nt.max(), nt.mean(), nbins),
                            bins_per_gpu=len(sel), nt_min=int(nt.min()), nt_mean=float(nt.mean()), nt_max=int(nt.max()),
-                           mean_fourier_orders=float(nord.mean()), mean_scattering_steps=float(nsteps.mean())),
-               roofline=dict(bound="hbm", achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
-                             traffic=pmc_traffic("_realistic", bins_per_gpu=nbins),
-                             kernel="k_sos_stream<4,2,false,false,false>", kernel_ms=kms, bytes_per_launch=bytes_alg,
-                             bytes_counted="field written once per scattering order and read once per order >= 2: "
-                                           "(NT+1) x 6N x 8 B each",
-                             mfma_tflops=tf, mfma_frac=tf / FP64_PEAK_TFLOPS))
+                           mean_fourier_orders=float(nord.mean()), mean_scattering_steps=float(nsteps.mean())))
+    if full:
+        kms = kernel_ms(cx, bins, out, 2)
+        flops_ref, flops_exe = cx.solve_flops(bins, out)
+        # algorithmic field traffic of the streamed variant: each pass writes the 6N-row field of NT+1 levels once and every
+        # pass but the first of a Fourier order reads it once
+        field = (nt + 1) * 6 * cx.n * 8.0
+        bytes_alg = float((field * (2 * passes - np.clip(nord, 0, None))).sum())
+        ach = bytes_alg / (kms * 1e-3) / 1e9
+        tf = flops_exe / (kms * 1e-3) / 1e12
+        res["roofline"] = dict(bound="hbm", achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
+                               traffic=pmc_traffic("_realistic", bins_per_gpu=nbins),
+                               kernel="k_sos_stream<4,2,false,false,false>", kernel_ms=kms, bytes_per_launch=bytes_alg,
+                               bytes_counted="field written once per scattering order and read once per order >= 2: "
+                                             "(NT+1) x 6N x 8 B each",
+                               mfma_tflops=tf, mfma_frac=tf / FP64_PEAK_TFLOPS)
     cx.close()
     return res
 
@@ -332,10 +364,11 @@ def small_band_latency(pkg, torch, g, nbins=25):
                        % (nbins, nt.min(), nt.max()))
 
 
-def measure_headline(pkg, S, torch, dist, world, rank, dev, nbins, steps, warmup, args, base):
+def measure_headline(pkg, S, torch, dist, world, rank, dev, nbins, steps, warmup, args, base, full=True, dump=None):
     """One measurement of the headline workload: returns (result dict, workload, per-bin Fourier-order counts).
     weak scaling: every rank owns `nbins` bins of one global band of world * nbins bins (weights normalised globally);
-    strong scaling (args.scaling): ONE band of `nbins` bins, dealt to the ranks by cost (dist.balanced_shards)."""
+    strong scaling (args.scaling): ONE band of `nbins` bins, dealt to the ranks by cost (dist.balanced_shards).
+    The roofline and the per-rank times (launches of their own) only with `full`; dump: directory for dump_outputs (rank 0)."""
     strong = getattr(args, "scaling", "weak") == "strong" and world > 1
     if strong:
         nb_tot = nbins
@@ -372,27 +405,28 @@ def measure_headline(pkg, S, torch, dist, world, rank, dev, nbins, steps, warmup
             dist.barrier()
         torch.cuda.synchronize()
 
-    dt = timed_steps(step, fence, steps, warmup, world, dist, cx.device, torch)
-
-    # roofline of the dominant kernel (k_sos_os): HIP-event duration on its own stream (sosgpu_last_solve_ms), averaged
-    # over a few launches; algorithmic flops counted from the run's own Fourier/scattering-order counts.
-    kern_ms = kernel_ms(cx, bins, out)
-    flops_ref, flops_exe = cx.solve_flops(bins, out)
-    achieved = flops_exe / (kern_ms * 1e-3) / 1e12
-    traffic = pmc_traffic("", bins_per_gpu=nbins, nt=args.nt)
+    dt, buf = timed_steps(step, fence, steps, warmup, world, dist, cx.device, torch)
+    if dump and rank == 0:
+        dump_outputs(dump, pkg, torch, buf, out, bins["perm"])
 
     res = dict(base, value=nb_tot * steps / dt, steps=steps, warmup=warmup, ms_per_step=1e3 * dt / steps,
                config=dict(workload="single-wavelength aerosol+Rayleigh, 40 Gauss angles (N=41), NT=%d layers, OS_NB=80, "
                                     "Lambertian rho=0.1, HG g=%.2f, %d CKD bins/GPU/step" % (args.nt, args.g, nbins),
                            bins_per_gpu=nloc if strong else nbins, nt=args.nt, n_dirs=41, os_nb=80, parallelism="bins sharded x%d" % world,
-                           bin_order="generation" if args.no_sort else "cost-sorted"),
-               roofline=dict(bound="mfma", achieved=achieved, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s",
-                             frac=achieved / FP64_PEAK_TFLOPS, traffic=traffic,
-                             kernel="k_sos_os<4,2,2,false,false>", kernel_ms=kern_ms, flops_per_launch=flops_exe,
-                             flops_counted="parity form (two 3N x 3Nw half systems, Nw = weighted directions) + rank-4 molecular form + formal solution, unpadded",
-                             reference_algorithm_flops_per_launch=flops_ref,
-                             reference_algorithm_tflops=flops_ref / (kern_ms * 1e-3) / 1e12))
-    if world > 1:
+                           bin_order="generation" if args.no_sort else "cost-sorted"))
+    if full:
+        # roofline of the dominant kernel (k_sos_os): HIP-event duration on its own stream (sosgpu_last_solve_ms), averaged
+        # over a few launches; algorithmic flops counted from the run's own Fourier/scattering-order counts.
+        kern_ms = kernel_ms(cx, bins, out)
+        flops_ref, flops_exe = cx.solve_flops(bins, out)
+        achieved = flops_exe / (kern_ms * 1e-3) / 1e12
+        res["roofline"] = dict(bound="mfma", achieved=achieved, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s",
+                               frac=achieved / FP64_PEAK_TFLOPS, traffic=pmc_traffic("", bins_per_gpu=nbins, nt=args.nt),
+                               kernel="k_sos_os<4,2,2,false,false>", kernel_ms=kern_ms, flops_per_launch=flops_exe,
+                               flops_counted="parity form (two 3N x 3Nw half systems, Nw = weighted directions) + rank-4 molecular form + formal solution, unpadded",
+                               reference_algorithm_flops_per_launch=flops_ref,
+                               reference_algorithm_tflops=flops_ref / (kern_ms * 1e-3) / 1e12)
+    if full and world > 1:
         # per-rank solve and reduce times (imbalance shows here): kernel time of the rank's own solve from its HIP events, the
         # band all-reduce timed on its own after a barrier
         rec, scal = cx.aggregate(out, aik)
@@ -523,18 +557,27 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --bins bins per GPU; strong: one band of --bins bins split over the GPUs by cost")
     ap.add_argument("--cpu-worker", type=int, default=-1, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything else the benchmark measures besides the headline (rooflines, per-rank times, CPU baselines, "
+                         "the appended N = 1 measurements); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; headline and realistic workloads)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall time of the all-cores CPU baseline")
-    ap.add_argument("--no-hyper", action="store_true", help="skip the appended hyperspectral measurement (N = 1 default run)")
+    ap.add_argument("--no-hyper", action="store_true", help="skip the appended hyperspectral measurement (N = 1 --full run)")
     ap.add_argument("--spectrum-every", type=int, default=1, help="hyperspectral: take every k-th spectral interval")
     ap.add_argument("--ranks-per-gpu", type=int, default=1,
                     help="hyperspectral only: host processes (ranks) sharing each GPU -- the wavelength partition is the same as "
                          "over GPUs, the host preparation (Python, one interpreter per rank) runs in parallel; gloo gather")
     ap.add_argument("--cpu-sample", type=int, default=224, help="bins timed on the CPU baseline (about 15 s of one core)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-mix", action="store_true", help="skip the appended realistic_mix measurement (N = 1 default run)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines (N = 1 --full run)")
+    ap.add_argument("--no-mix", action="store_true", help="skip the appended realistic_mix measurement (N = 1 --full run)")
     ap.add_argument("--no-sort", action="store_true", help="keep the bins in generation order (default: cost-sorted upload)")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the multi-rank path (gloo, no solver)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.dry_run or args.workload == "hyperspectral"):
+        ap.error("--dump-outputs: the headline and realistic workloads only")
 
     if args.cpu_worker >= 0:
         cpu_worker(args)
@@ -564,10 +607,11 @@ def main():
     # process imports torch and builds its workload (its ~12 s overlap the GPU warm-up, not the timed steps: collected first)
     cpu_procs = None
     hyper_procs4 = None
-    if world == 1 and rank == 0 and args.workload == "headline" and not args.no_hyper and not args.no_mix:
+    full_n1 = args.full and world == 1 and rank == 0 and args.workload == "headline"
+    if full_n1 and not args.no_hyper and not args.no_mix:
         import torch                                   # (pages the library in for the child ranks too; no GPU call yet)
         hyper_procs4 = hyperspectral_four_processes(args, user_queues)         # (a child job, finished before this process uses the GPU)
-    if world == 1 and rank == 0 and not args.no_cpu and args.workload == "headline":
+    if full_n1 and not args.no_cpu:
         cpu_procs = cpu_baseline_all_cores(args.cpu_seconds)
 
     import torch
@@ -585,7 +629,8 @@ def main():
                 higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f64", data="synthetic")
 
     if args.workload == "realistic":
-        r = run_realistic(pkg, torch, dist, world, rank, args.bins, args.steps, args.warmup, args.g, strong=args.scaling == "strong")
+        r = run_realistic(pkg, torch, dist, world, rank, args.bins, args.steps, args.warmup, args.g, strong=args.scaling == "strong",
+                          full=args.full, dump=args.dump_outputs)
         r["config"]["parallelism"] = "bins sharded x%d" % world
         if args.scaling == "strong" and world > 1:
             r["scaling"] = "strong"
@@ -605,8 +650,9 @@ def main():
         return
     cpu_all = finish_cpu_all_cores(cpu_procs) if cpu_procs else None      # (before the timed steps: the host is quiet again)
 
-    res, wl, nord = measure_headline(pkg, S, torch, dist, world, rank, dev, args.bins, args.steps, args.warmup, args, base)
-    if world == 1 and not args.no_mix:
+    res, wl, nord = measure_headline(pkg, S, torch, dist, world, rank, dev, args.bins, args.steps, args.warmup, args, base,
+                                     full=args.full, dump=args.dump_outputs)
+    if args.full and world == 1 and not args.no_mix:
         if args.bins != SMALL_BATCH:
             # the same workload in round 1's batch size: one dispatch round of the chip is 512 bins, so a 4096-bin step spends
             # about 5 % of its time in the tail of its last round; kept for continuity with earlier rounds
@@ -633,7 +679,7 @@ def main():
                 res["hyperspectral"]["four_host_processes"] = hyper_procs4
     if rank == 0:
         res["config"]["mean_fourier_orders"] = float(nord.mean())
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             res["cpu_baseline"] = cpu_baseline(wl, args.cpu_sample)
             if cpu_all:
                 res["cpu_baseline"]["all_cores"] = cpu_all

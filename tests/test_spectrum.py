@@ -25,13 +25,13 @@ def _free_port():
     return p
 
 
-def test_spectrum_costs_and_balanced_shards(pkg, monkeypatch):
+def test_spectrum_costs_and_balanced_shards(pkg, monkeypatch, tmp_path):
     """Host side of the wavelength partition: costs from the keywords alone (bins of the interval x level / order estimate),
     longest-processing-time dealing, every wavelength owned exactly once, identical on every rank (deterministic)."""
     rs, D = pkg.run_sos, pkg.dist
     monkeypatch.setenv("SOS_ABS_ROOT", GOLD)
-    kws, _, _, _ = spectrum_cases.build(rs, "/tmp/sos_spectrum_costs", names=["cfg1_lambert", "ckd_o2a_5bins",
-                                                                              "ckd_h2o_o2_25bins_flatsea", "cfg2_lnd_lambert"])
+    kws, _, _, _ = spectrum_cases.build(rs, tmp_path, names=["cfg1_lambert", "ckd_o2a_5bins",
+                                                             "ckd_h2o_o2_25bins_flatsea", "cfg2_lnd_lambert"])
     c = rs.spectrum_costs(kws)
     assert c.shape == (4,) and np.all(c > 0)
     assert c[2] > c[1] > c[0]                              # 25 bins > 5 bins > 1 molecular bin

@@ -174,7 +174,7 @@ def compare_records(a, b, rtol=1e-9, what=""):
     scale = np.abs(b[:, 0]).max() if b.size else 1.0
     err = np.abs(a - b)
     tol = rtol * np.abs(b) + rtol * 1e-3 * scale
-    bad = err > tol
+    bad = ~(err <= tol)                    # (NaN on either side is a mismatch)
     assert not bad.any(), "%s: %d entries exceed tolerance; worst err/tol %.3g" % (what, bad.sum(), (err / tol).max())
     return float((err / np.maximum(np.abs(b), 1e-3 * scale)).max())
 

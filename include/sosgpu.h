@@ -129,6 +129,30 @@ int  sosgpu_os_solve(sosgpu_ctx *cx, int nb, int lp, const int32_t *d_nt, const 
                      const double *d_prof, const int32_t *d_jout, const double *d_zz,
                      double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream);
 
+/* Several output altitudes from ONE solve.  The output altitude (-SOS.OutputAlt, ZOUT) does not enter the solve: it only
+ * chooses the two levels whose field is captured and interpolated (SOS_OS.F:1511-1534); the stop tests, the orders run and
+ * the fluxes come from TOA and ground.  Each bin here carries nz output slots (jout, zz), and the record set of slot k is,
+ * bit for bit, the d_rec of sosgpu_os_solve with d_jout / d_zz = that slot's (jout 0: the standard output).
+ *  nz                    1 .. SOSGPU_MAX_OUTPUT_LEVELS (SOSGPU_E_ARG otherwise)
+ *  d_jout[nz][nb], d_zz[nz][nb]   output levels of every slot and bin (sosgpu_output_levels), both required
+ *  d_rec[nz][nb][iborm_max+1][3][W]  one ordinary record array per slot: sosgpu_aggregate / sosgpu_reduce / sosgpu_trphi take
+ *                        slot k at d_rec + k nb (iborm_max+1) 3 W as they take the d_rec of sosgpu_os_solve
+ *  d_norders, d_iglast, d_flux   as sosgpu_os_solve (common to the slots); a bin with a jout outside 0 .. NT is malformed
+ *                        (norders = -1)
+ * Every other argument and rule as sosgpu_os_solve.  The cost over a single-altitude solve is the capture of the slots'
+ * levels: two field reads and a few lane-private state accesses per slot, row and scattering order. */
+#define SOSGPU_MAX_OUTPUT_LEVELS 16
+int  sosgpu_os_solve_levels(sosgpu_ctx *cx, int nb, int lp, const int32_t *d_nt, const int32_t *d_iborm,
+                            const double *d_prof, int nz, const int32_t *d_jout, const double *d_zz,
+                            double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream);
+/* Output levels of nz altitudes for bins profiled by sosgpu_profile: from its d_prof (H), d_zprof and d_nt, the level,
+ * weight and optical depth sosgpu_profile computes for zout (SOS.F:570-582, SOS_OS.F:1514-1520), with the same arithmetic:
+ *  zout[nz]          altitudes (km, host array), -1 = standard output (jout 0, zz 0, TAUOUT = H(0))
+ *  d_jout[nz][nb], d_zz[nz][nb], d_tauout[nz][nb]   device outputs; a flagged bin (NT < 1) gets 0, 0, 0
+ * One small kernel on `stream`. */
+int  sosgpu_output_levels(sosgpu_ctx *cx, int nb, int lp, const double *d_prof, const double *d_zprof, const int32_t *d_nt,
+                          int nz, const double *zout, int32_t *d_jout, double *d_zz, double *d_tauout, void *stream);
+
 /* The scratch of the streamed solver (level grids beyond 64 levels) is kept by the library when a context is destroyed and
  * handed to the next context that needs one (at most 8 buffers and 8 GiB per process): a context per wavelength would
  * otherwise pay a 60-1000 MB hipMalloc per call.  sosgpu_trim() returns that memory to the device. */

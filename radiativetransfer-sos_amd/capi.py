@@ -20,8 +20,10 @@ EXPORTS = [
     "sosgpu_pack", "sosgpu_unpack", "sosgpu_reduce", "sosgpu_absprofile", "sosgpu_land_surface", "sosgpu_mie", "sosgpu_granu",
     "sosgpu_granu_batch",
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
+    "sosgpu_os_solve_levels", "sosgpu_output_levels",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
+MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
 SCAL_BASE = 10          # SOSGPU_SCAL_BASE: scalar block of sosgpu_aggregate = SCAL_BASE + N doubles
 
 
@@ -90,6 +92,10 @@ def lib():
         L.sosgpu_noyaux_fetch.argtypes = [vp, i32, vp]
         L.sosgpu_os_solve.restype = i32
         L.sosgpu_os_solve.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sosgpu_os_solve_levels.restype = i32
+        L.sosgpu_os_solve_levels.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.sosgpu_output_levels.restype = i32
+        L.sosgpu_output_levels.argtypes = [vp, i32, i32, vp, vp, vp, i32, C.POINTER(dbl), vp, vp, vp, vp]
         L.sosgpu_trim.restype = i32
         L.sosgpu_trim.argtypes = []
         L.sosgpu_ctx_table_entry_bytes.restype = C.c_size_t

@@ -549,10 +549,16 @@ extern "C" int sosgpu_noyaux_fetch(sosgpu_ctx *cx, int is, double *out)
     return SOSGPU_OK;
 }
 
+// output slots (sosgpu_os_solve_levels): lane-private state per work region, [nz][SOS_LV_N][threads] doubles, placed behind
+// the streamed kernel's regions at a 64-byte boundary
+static size_t lv_stride(int nz, int threads) { return (size_t)nz * SOS_LV_N * threads; }
+static size_t lv_off(size_t doubles) { return (doubles + 7) & ~(size_t)7; }
+
 // sosgpu_os_solve (table == null) and sosgpu_os_solve_multi (per-bin contexts from a device table)
+// nz > 0: sosgpu_os_solve_levels (d_jout / d_zz / d_rec hold nz slots)
 static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_ctx_of_bin, const int32_t *d_order, int nb, int lp, const int32_t *d_nt,
                          const int32_t *d_iborm, const double *d_prof, const int32_t *d_jout, const double *d_zz,
-                         double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream)
+                         double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream, int nz = 0)
 {
     if (!cx || nb < 0 || lp < 2 || !d_nt || !d_iborm || !d_prof || !d_rec || !d_norders || !d_iglast || !d_flux)
         return SOSGPU_E_ARG;
@@ -612,10 +618,27 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
         const size_t regions = spec_k ? (size_t)nb * spec_k : (size_t)per_launch;
         const size_t i3_doubles = spec_k ? (size_t)nb * s1n * sos_stream_threads(cx->d.n) : 0;
         // + the task queues and per-bin order flags of the persistent form (ints, behind the bins' scratch)
-        const size_t need = per_bin * regions + i3_doubles + (256 + (size_t)per_launch) / 2 + 1;
+        size_t need = per_bin * regions + i3_doubles + (256 + (size_t)per_launch) / 2 + 1;
+        if (nz > 0) need = lv_off(need) + lv_stride(nz, sos_stream_threads(cx->d.n)) * regions;
         if (need > cx->scratch_doubles) {
             if (cx->scratch) {
                 HIPCHK(sync_ctx_streams(cx));   // an earlier solve of this context may still be using it, on any of its streams
+                pool_give(cx->device, cx->scratch, cx->scratch_doubles);
+            }
+            cx->scratch = nullptr;
+            cx->scratch_doubles = 0;
+            size_t got = 0;
+            cx->scratch = pool_take(cx->device, need, &got);
+            if (!cx->scratch) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
+            cx->scratch_doubles = got;
+        }
+    }
+    // output slots of the LDS-resident kernel: their lane-private state, one region per bin of a launch, in the scratch
+    if (nz > 0 && !big) {
+        const size_t need = lv_stride(nz, 64 * nw) * (size_t)nb;
+        if (need > cx->scratch_doubles) {
+            if (cx->scratch) {
+                HIPCHK(sync_ctx_streams(cx));
                 pool_give(cx->device, cx->scratch, cx->scratch_doubles);
             }
             cx->scratch = nullptr;
@@ -648,6 +671,13 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
         bn.spec_k = 0; bn.spec_i3 = nullptr;
         if (const char *e = getenv("SOSGPU_STREAM_QTAIL")) bn.q_tail = atoi(e);
         bn.s_begin = 0; bn.s_end = S1;
+        bn.nz = nz; bn.zbs = nb; bn.zrs = (size_t)nb * S1 * 3 * W; bn.zst = nullptr; bn.zst_stride = 0;
+        if (nz > 0) {
+            const size_t regions = big ? (spec_k ? (size_t)nb * spec_k : (size_t)per_launch) : (size_t)nb;
+            bn.zst_stride = lv_stride(nz, big ? sos_stream_threads(cx->d.n) : 64 * nw);
+            bn.zst = cx->scratch + (big ? lv_off(per_bin * regions + (spec_k ? (size_t)nb * S1 * sos_stream_threads(cx->d.n) : 0) +
+                                                 (256 + (size_t)per_launch) / 2 + 1) : 0);
+        }
         if (big && spec_k) {
             // order-parallel form: set-up launch, then rounds of (K order tasks per bin, replay of their stop tests)
             bn.spec_i3 = cx->scratch + per_bin * (size_t)nb * spec_k;
@@ -678,7 +708,7 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
             // workgroup per bin stays the default.  Launches with a context table always use the default form.
             int persist = 0;
             if (const char *e = getenv("SOSGPU_STREAM_PERSIST")) persist = atoi(e);
-            if (persist && !table && opl == S1) {
+            if (persist && !table && opl == S1 && nz == 0) {        // (output slots: the plain launch)
                 bn.queue = reinterpret_cast<int *>(cx->scratch + per_bin * per_launch);
                 bn.qflag = bn.queue + 256;
                 HIPCHK(hipMemsetAsync(bn.queue, 0, (256 + (size_t)bn.nb) * sizeof(int), st));
@@ -705,6 +735,32 @@ extern "C" int sosgpu_os_solve(sosgpu_ctx *cx, int nb, int lp, const int32_t *d_
 {
     return os_solve_impl(cx, nullptr, nullptr, nullptr, nb, lp, d_nt, d_iborm, d_prof, d_jout, d_zz, d_rec, d_norders, d_iglast,
                          d_flux, stream);
+}
+
+extern "C" int sosgpu_os_solve_levels(sosgpu_ctx *cx, int nb, int lp, const int32_t *d_nt, const int32_t *d_iborm,
+                                      const double *d_prof, int nz, const int32_t *d_jout, const double *d_zz,
+                                      double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream)
+{
+    if (nz < 1 || nz > SOSGPU_MAX_OUTPUT_LEVELS || !d_jout || !d_zz) return SOSGPU_E_ARG;
+    return os_solve_impl(cx, nullptr, nullptr, nullptr, nb, lp, d_nt, d_iborm, d_prof, d_jout, d_zz, d_rec, d_norders, d_iglast,
+                         d_flux, stream, nz);
+}
+
+extern "C" int sosgpu_output_levels(sosgpu_ctx *cx, int nb, int lp, const double *d_prof, const double *d_zprof, const int32_t *d_nt,
+                                    int nz, const double *zout, int32_t *d_jout, double *d_zz, double *d_tauout, void *stream)
+{
+    if (!cx || nb < 0 || lp < 2 || !d_prof || !d_zprof || !d_nt || !zout || !d_jout || !d_zz || !d_tauout) return SOSGPU_E_ARG;
+    if (nz < 1 || nz > SOSGPU_MAX_OUTPUT_LEVELS) return SOSGPU_E_ARG;
+    if (nb == 0) return SOSGPU_OK;
+    HIPCHK(hipSetDevice(cx->device));
+    OutputLevelArgs a;
+    a.nb = nb; a.lp = lp; a.nz = nz;
+    for (int k = 0; k < SOSGPU_MAX_OUTPUT_LEVELS; k++) a.zout[k] = k < nz ? zout[k] : -1.0;
+    a.prof = d_prof; a.zprof = d_zprof; a.nt = d_nt; a.jout = d_jout; a.zz = d_zz; a.tauout = d_tauout;
+    launch_output_levels(a, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    note_stream(cx, (hipStream_t)stream);
+    return SOSGPU_OK;
 }
 
 extern "C" size_t sosgpu_ctx_table_entry_bytes(void) { return sizeof(SosDev); }

@@ -57,6 +57,16 @@ struct ProfileArgs {
     int32_t *nt, *iborm, *jout;
 };
 void launch_profile(const ProfileArgs &a, hipStream_t st);
+// output levels of nz altitudes (profile.hip k_output_levels): jout / zz / tauout[nz][nb] from zprof[nb][lp], prof[nb][3][lp], nt[nb]
+struct OutputLevelArgs {
+    int nb, lp, nz;
+    double zout[SOSGPU_MAX_OUTPUT_LEVELS];
+    const double *prof, *zprof;
+    const int32_t *nt;
+    int32_t *jout;
+    double *zz, *tauout;
+};
+void launch_output_levels(const OutputLevelArgs &a, hipStream_t st);
 // the no-gas profile of the wavelength into d_ng = z | h | pca | pcm, `ng` doubles each (nt + 1 <= ng used)
 void launch_profile_nogas(double tr, double hr, double ta, double ha, int nt, double t_first, double t_layer, double *d_ng, int ng,
                           hipStream_t st);

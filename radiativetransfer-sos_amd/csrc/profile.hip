@@ -521,3 +521,37 @@ void launch_absprofile(int nb, int nlev, int nterm, const int32_t *d_ik, const d
 {
     k_absprofile<<<nb, 64, 0, st>>>(nb, nlev, nterm, d_ik, d_xk, d_ro, d_tabs);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Output levels of several altitudes (sosgpu_output_levels): the statements of k_profile's ZOUT branch (SOS.F:570-582,
+// SOS_OS.F:1514-1520) on the profile k_profile left -- Z in zprof, H (after the rescale) in prof -- one thread per
+// (slot, bin).  zout = -1: the standard output (level 0, TAUOUT = H(0)); a flagged bin (NT < 1): 0, 0 and TAUOUT = 0, as
+// k_profile leaves it.  (fp contract is off for this file: the same roundings as k_profile.)
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_output_levels(OutputLevelArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nz * a.nb) return;
+    const int k = i / a.nb, b = i - k * a.nb;
+    const int nt = a.nt[b];
+    const double zout = a.zout[k];
+    const double *Z = a.zprof + (size_t)b * a.lp, *H = a.prof + (size_t)b * 3 * a.lp;
+    int j = 0;
+    double zz = 0., tauout = 0.;
+    if (nt >= 1 && nt < a.lp) {
+        tauout = H[0];
+        if (zout != -1.0) {
+            j = 1;
+            while (j < nt && zout < Z[j]) j++;
+            zz = (zout - Z[j - 1]) / (Z[j] - Z[j - 1]);
+            tauout = (1 - zz) * H[j - 1] + zz * H[j];
+        }
+    }
+    a.jout[i] = j; a.zz[i] = zz; a.tauout[i] = tauout;
+}
+
+void launch_output_levels(const OutputLevelArgs &a, hipStream_t st)
+{
+    const int n = a.nz * a.nb;
+    k_output_levels<<<(n + 255) / 256, 256, 0, st>>>(a);
+}

@@ -85,7 +85,16 @@ struct SosBins {
     const int32_t *ctx_of_bin;
     const int32_t *order;        // multi-wavelength launches: workgroup i solves bin order[i] (costliest bins first: workgroups
                                  // are dispatched in index order and the bins stay grouped by wavelength for the aggregate), or null
+    // multi-level output (sosgpu_os_solve_levels, the ZO mode 2 instantiations), nz = 0 otherwise: slot k of bin b reads
+    // jout[k zbs + b], zz[k zbs + b] and writes its records at rec + k zrs; zst holds the lane-private state of the slots,
+    // zst_stride doubles per work region (bin, or order task of the streamed kernel): [nz][8][threads]
+    int nz, zbs;
+    size_t zrs;
+    double *zst;
+    size_t zst_stride;
 };
+// lane-private state of an output slot (ZO mode 2): entries of zst, each [threads]
+enum { SOS_LV_XLO = 0, SOS_LV_XHI, SOS_LV_I3LO, SOS_LV_DLO, SOS_LV_I3HI, SOS_LV_DHI, SOS_LV_PLO, SOS_LV_PHI, SOS_LV_N };
 
 // The kernels read the wavelength context through `cx`: the by-value kernel argument, or -- SOS_MULTI builds -- the bin's
 // entry of the context table, addressed in the constant address space so that every field stays a scalar load that the

@@ -65,9 +65,14 @@
 #else
 #define SOS_MIN_WG_R(NW, RTWH, CT) (((NW) == 4 && (RTWH) == 1 && (CT) == 2) ? 3 : SOS_MIN_WG(NW, CT))
 #endif
-template <int NW, int RTWH, int CT, bool ZO, bool SURF, bool SPLIT>
+// ZM: output mode -- 0 standard output (TOA up-going, ground down-going), 1 one output altitude (ZO above: bn.jout / bn.zz),
+//     2 bn.nz output slots (sosgpu_os_solve_levels): every slot runs the statements of ZO = true with its own (jout, zz), its
+//     i3lo / dlo / i3hi / dhi kept lane-private in bn.zst (no registers across the order loop: there are none to spare), a slot
+//     with jout = 0 gets the standard output.
+template <int NW, int RTWH, int CT, int ZM, bool SURF, bool SPLIT>
 __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(const SosDev cx_arg, const SosBins bn)
 {
+    constexpr bool ZO = ZM == 1, LV = ZM == 2;
     SOS_BIND_CTX(cx, cx_arg, bn);
     extern __shared__ double smem[];
     constexpr int NTH = 64 * NW, HW = NW / 2;
@@ -130,8 +135,13 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
         const int jout = ZO ? uniform_i32(bn.jout ? bn.jout[b] : 0) : 0;
         const double zz = ZO ? uniform_f64(jout ? bn.zz[b] : 0.) : 0.;
         const int jlo = (ZO && jout) ? jout - 1 : 0, jhi = (ZO && jout) ? jout : 0;
+        int lv_bad = 0;                        // LV: a slot's level outside 0 .. NT
+        if constexpr (LV) {
+#pragma unroll 1
+            for (int k = 0; k < bn.nz; k++) { const int j = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]); if (j < 0 || j > nt) lv_bad = 1; }
+        }
         // shape guard (uniform): a malformed bin is flagged (norders = -1), never indexed out of bounds
-        if (nt < 1 || nt >= LPB || nt >= bn.lp || iborm < 0 || iborm > cx.smax || jout < 0 || jout > nt) {
+        if (nt < 1 || nt >= LPB || nt >= bn.lp || iborm < 0 || iborm > cx.smax || jout < 0 || jout > nt || lv_bad) {
             if (t == 0) { bn.norders[b] = -1; bn.flux[2 * b] = 0.; bn.flux[2 * b + 1] = 0.; }
             for (int i = t; i < cx.smax + 1; i += NTH) bn.iglast[(size_t)b * (cx.smax + 1) + i] = 0;
             return;
@@ -212,6 +222,28 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
             if (ZO && jout && active) { xlo = fld[(size_t)jlo * FS + rl]; xhi = fld[(size_t)jhi * FS + rl]; }
         };
 
+        // LV: the output slots, one after the other (#pragma unroll 1: nothing of a slot stays in registers).  The two levels of
+        // slot k are read back from this thread's own row of the field, which no one writes between the formal solution and
+        // the contraction of the next order; the per-order steps are those of ZO = true, on the slot's lane-private state.
+        double *const zs = LV ? bn.zst + (size_t)b * bn.zst_stride + t : nullptr;
+        auto lv_step = [&](int mode) {        // 0: first order, 1: converged exit (geometric tail), 2: next order
+#pragma unroll 1
+            for (int k = 0; k < bn.nz; k++) {
+                const int jk = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]);
+                if (!(jk && active)) continue;
+                double *z = zs + (size_t)k * SOS_LV_N * NTH;
+                const double xlo = fld[(size_t)(jk - 1) * FS + rl], xhi = fld[(size_t)jk * FS + rl];
+                if (mode == 0) { z[SOS_LV_I3LO * NTH] = xlo; z[SOS_LV_DLO * NTH] = xlo; z[SOS_LV_I3HI * NTH] = xhi; z[SOS_LV_DHI * NTH] = xhi; }
+                else if (mode == 1) {
+                    z[SOS_LV_I3LO * NTH] = z[SOS_LV_I3LO * NTH] + queue_term(z[SOS_LV_DLO * NTH], xlo);
+                    z[SOS_LV_I3HI * NTH] = z[SOS_LV_I3HI * NTH] + queue_term(z[SOS_LV_DHI * NTH], xhi);
+                } else {
+                    z[SOS_LV_DLO * NTH] = xlo; z[SOS_LV_DHI * NTH] = xhi;
+                    z[SOS_LV_I3LO * NTH] = z[SOS_LV_I3LO * NTH] + xlo; z[SOS_LV_I3HI * NTH] = z[SOS_LV_I3HI * NTH] + xhi;
+                }
+            }
+        };
+
         double i4 = 0., i5 = 0.;
         double sign = -1.;
         int red_slot = 0;
@@ -289,6 +321,7 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
                     PH(1);
                     i3 = xb; a1 = 0.; d1 = xb; g1 = 0.;
                     if (ZO) { i3lo = xlo; dlo = xlo; i3hi = xhi; dhi = xhi; }
+                    if (LV) lv_step(0);
                     bc = ground_bc();
                     PH(5);
                 } else {
@@ -307,11 +340,13 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
                     if (ig != 2 && !(pm & 1)) {                                          // SOS_OS.F:1293-1315
                         i3 = i3 + queue_term(d1, g1);
                         if (ZO) { i3lo = i3lo + queue_term(dlo, xlo); i3hi = i3hi + queue_term(dhi, xhi); }
+                        if (LV) lv_step(1);
                         break;
                     }
                     a1 = d1; d1 = g1;                                                    // SOS_OS.F:1323-1363
                     i3 = i3n;
                     if (ZO) { dlo = xlo; dhi = xhi; i3lo = i3lo + xlo; i3hi = i3hi + xhi; }
+                    if (LV) lv_step(2);
                     if (!(pm & 2)) break;                                                // SOS_OS.F:1370
                     if (!(pm & 4)) break;                                                // SOS_OS.F:1389
                     if (!(ig < cx.igmax)) break;                                         // SOS_OS.F:1406
@@ -419,10 +454,36 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
             const double coef = (s == 0) ? 1. : 2.;                                  // SOS_OS.F:1460-1473
             i4 = i4 + coef * i3;
             i5 = i5 + coef * i3 * sign;
-            if (active) {                                                            // SOS_OS.F:1484-1534,1572
+            if (active && !LV) {                                                     // SOS_OS.F:1484-1534,1572
                 const double outv = (ZO && jout) ? ((1 - zz) * i3lo + zz * i3hi) : i3out0;
                 recb[(size_t)s * 3 * W + recoff] = outv * usign;
                 if (up && jj == 0) recb[(size_t)s * 3 * W + c * W + N] = 0.;
+            }
+            if (LV && active) {
+                // each slot's record as ZO = true writes it: RIIOUT at the slot's two levels (SURF up-going rows), then outv
+#pragma unroll 1
+                for (int k = 0; k < bn.nz; k++) {
+                    const int jk = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]);
+                    double *rk = recb + (size_t)k * bn.zrs;
+                    double outv = i3out0;
+                    if (jk) {
+                        const double zk = uniform_f64(bn.zz[(size_t)k * bn.zbs + b]);
+                        const double *z = zs + (size_t)k * SOS_LV_N * NTH;
+                        double i3lo = z[SOS_LV_I3LO * NTH], i3hi = z[SOS_LV_I3HI * NTH];
+                        if (SURF && up) {
+                            const double hlo = uniform_f64(pf[jk - 1]), hhi = uniform_f64(pf[jk]);
+                            const double riilo = exp(-(htot - hlo) / mu) * dirterm;
+                            const double riihi = exp(-(htot - hhi) / mu) * dirterm;
+                            i3lo = i3lo - riilo; i3hi = i3hi - riihi;
+                        }
+                        // the rounding of ZO = true's (1 - zz) i3lo + zz i3hi: its shared-tile (SPLIT) instantiations contract it as
+                        // fma(zz, i3hi, (1 - zz) i3lo), the others -- like this one -- as fma(1 - zz, i3lo, zz i3hi)
+                        if constexpr (SPLIT) outv = __builtin_fma(zk, i3hi, (1 - zk) * i3lo);
+                        else outv = (1 - zk) * i3lo + zk * i3hi;
+                    }
+                    rk[(size_t)s * 3 * W + recoff] = outv * usign;
+                    if (up && jj == 0) rk[(size_t)s * 3 * W + c * W + N] = 0.;
+                }
             }
             if (t == 0) bn.iglast[(size_t)b * S1 + s] = iglast;
             nord = s + 1;
@@ -497,13 +558,16 @@ static bool sos_split_applies(const SosDev &cx, int nw, int rtw, int ct)
 #endif
 }
 
-template <int NW, int RTWH, int CT, bool ZO, bool SURF, bool SPLIT = false>
+template <int NW, int RTWH, int CT, int ZM, bool SURF, bool SPLIT = false>
 static int launch_variant(const SosDev &cx, const SosBins &bn, size_t lds, hipStream_t st, int *hip_err)
 {
     if constexpr (!SPLIT && NW == 4 && RTWH == 2 && CT == 2) {
-        if (sos_split_applies(cx, NW, RTWH, CT)) return launch_variant<NW, RTWH, CT, ZO, SURF, true>(cx, bn, lds, st, hip_err);
+        if (sos_split_applies(cx, NW, RTWH, CT)) return launch_variant<NW, RTWH, CT, ZM, SURF, true>(cx, bn, lds, st, hip_err);
     }
-    auto kern = k_sos_os<NW, RTWH, CT, ZO, SURF, SPLIT>;
+#ifdef SOS_MULTI
+    static_assert(ZM != 2, "multi-level output: single-context launches only");
+#endif
+    auto kern = k_sos_os<NW, RTWH, CT, ZM, SURF, SPLIT>;
 #ifdef SOS_PROFILE_PHASES
     if (const char *e = getenv("SOSGPU_DEBUG_LDS_PAD")) lds += (size_t)atoi(e);   // diagnostic builds: force 1 workgroup per CU
 #endif
@@ -537,13 +601,23 @@ int launch_sos_os(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t s
 #ifdef SOS_WIDE_REGS
     if (nw == 8 && rtw == 1 && ct == 4) { nw = 4; rtw = 2; }      // same KHM, same LDS layout
 #endif
+#ifdef SOS_MULTI
+    if (bn.nz > 0) return SOSGPU_E_UNSUPPORTED;
+#define V_LV(NWV, R, C)
+#else
+#define V_LV(NWV, R, C)                                                                \
+        if (bn.nz > 0)                                                                 \
+            return cx.imat_surf ? launch_variant<NWV, R, C, 2, true>(cx, bn, lds, st, hip_err)  \
+                                : launch_variant<NWV, R, C, 2, false>(cx, bn, lds, st, hip_err);
+#endif
 #define V(NWV, R, C)                                                                   \
     if (nw == NWV && rtw == R && ct == C) {                                            \
+        V_LV(NWV, R, C)                                                                \
         if (cx.imat_surf)                                                              \
-            return zo ? launch_variant<NWV, R, C, true, true>(cx, bn, lds, st, hip_err)         \
-                      : launch_variant<NWV, R, C, false, true>(cx, bn, lds, st, hip_err);       \
-        return zo ? launch_variant<NWV, R, C, true, false>(cx, bn, lds, st, hip_err)            \
-                  : launch_variant<NWV, R, C, false, false>(cx, bn, lds, st, hip_err);          \
+            return zo ? launch_variant<NWV, R, C, 1, true>(cx, bn, lds, st, hip_err)            \
+                      : launch_variant<NWV, R, C, 0, true>(cx, bn, lds, st, hip_err);          \
+        return zo ? launch_variant<NWV, R, C, 1, false>(cx, bn, lds, st, hip_err)               \
+                  : launch_variant<NWV, R, C, 0, false>(cx, bn, lds, st, hip_err);             \
     }
     V(4, 1, 2) V(4, 2, 2) V(8, 2, 2)
     V(4, 1, 4) V(8, 1, 4)
@@ -551,5 +625,6 @@ int launch_sos_os(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t s
     V(4, 2, 4)
 #endif
 #undef V
+#undef V_LV
     return SOSGPU_E_UNSUPPORTED;
 }

@@ -138,10 +138,52 @@ __device__ __forceinline__ void glds_copy(const double *g, double *l, int units,
 #ifndef SOS_STREAM_3WG_KHT
 #define SOS_STREAM_3WG_KHT 5
 #endif
+// Output slots (ZM = 2, below): this thread's row at the slots' levels inside the chunk [l0, L] -> XLO / XHI (for the up-going
+// rows the particular part Q; the link pass adds P Xin)
+template <int NTH, int FS>
+__device__ __forceinline__ void lv_capture(const SosBins &bn, int b, double *zs, const double *cbuf, int rl, int l0, int L)
+{
+#pragma unroll 1
+    for (int k = 0; k < bn.nz; k++) {
+        const int jk = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]);
+        if (!jk) continue;
+        double *z = zs + (size_t)k * SOS_LV_N * NTH;
+        if (jk - 1 >= l0 && jk - 1 <= L) z[SOS_LV_XLO * NTH] = cbuf[(size_t)(jk - 1 - l0) * FS + rl];
+        if (jk >= l0 && jk <= L) z[SOS_LV_XHI * NTH] = cbuf[(size_t)(jk - l0) * FS + rl];
+    }
+}
+
+// ... and the per-order steps of ZO = true on every slot: mode 0 first order, 1 converged exit (geometric tail), 2 next order
+template <int NTH>
+__device__ __forceinline__ void lv_step(const SosBins &bn, int b, double *zs, bool active, int mode)
+{
+#pragma unroll 1
+    for (int k = 0; k < bn.nz; k++) {
+        const int jk = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]);
+        if (!(jk && active)) continue;
+        double *z = zs + (size_t)k * SOS_LV_N * NTH;
+        const double xlo = z[SOS_LV_XLO * NTH], xhi = z[SOS_LV_XHI * NTH];
+        if (mode == 0) { z[SOS_LV_I3LO * NTH] = xlo; z[SOS_LV_DLO * NTH] = xlo; z[SOS_LV_I3HI * NTH] = xhi; z[SOS_LV_DHI * NTH] = xhi; }
+        else if (mode == 1) {
+            z[SOS_LV_I3LO * NTH] = z[SOS_LV_I3LO * NTH] + queue_term(z[SOS_LV_DLO * NTH], xlo);
+            z[SOS_LV_I3HI * NTH] = z[SOS_LV_I3HI * NTH] + queue_term(z[SOS_LV_DHI * NTH], xhi);
+        } else {
+            z[SOS_LV_DLO * NTH] = xlo; z[SOS_LV_DHI * NTH] = xhi;
+            z[SOS_LV_I3LO * NTH] = z[SOS_LV_I3LO * NTH] + xlo; z[SOS_LV_I3HI * NTH] = z[SOS_LV_I3HI * NTH] + xhi;
+        }
+    }
+}
+
 #define SOS_STREAM_MIN_WG(NW, KHT) ((NW) == 4 ? ((COLS == 16 || (KHT) <= SOS_STREAM_3WG_KHT) ? 3 : 2) : 1)
-template <int NW, int RTWH, bool ZO, bool SURF, bool PERSIST, int KHT = NW * RTWH>
+// ZM: output mode as in sos_os.hip -- 0 standard output, 1 one output altitude (ZO), 2 bn.nz output slots.  Mode 2 keeps a
+// slot's two captured levels, the attenuations plo / phi and i3lo / dlo / i3hi / dhi lane-private in bn.zst of the task's
+// work region; the up-going rows' homogeneous part is added from the chunk inflows the link pass leaves in xin.
+// Mode 2 has no persistent form.
+template <int NW, int RTWH, int ZM, bool SURF, bool PERSIST, int KHT = NW * RTWH>
 __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_stream(const SosDev cx_arg, const SosBins bn)
 {
+    constexpr bool ZO = ZM == 1, LV = ZM == 2;
+    static_assert(!(LV && PERSIST), "multi-level output: no persistent form");
     SOS_BIND_CTX(cx, cx_arg, bn);
     const auto &cx_kernel = cx;
     const SosBins &bn_kernel = bn;
@@ -230,7 +272,12 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
     const int jout = ZO ? uniform_i32(bn.jout ? bn.jout[b] : 0) : 0;
     const double zz = ZO ? uniform_f64(jout ? bn.zz[b] : 0.) : 0.;
     const int jlo = (ZO && jout) ? jout - 1 : 0, jhi = (ZO && jout) ? jout : 0;
-    if (nt < 1 || nt >= LPB || nt >= bn.lp || iborm < 0 || iborm > cx.smax || jout < 0 || jout > nt) {
+    int lv_bad = 0;                            // LV: a slot's level outside 0 .. NT
+    if constexpr (LV) {
+#pragma unroll 1
+        for (int k = 0; k < bn.nz; k++) { const int j = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]); if (j < 0 || j > nt) lv_bad = 1; }
+    }
+    if (nt < 1 || nt >= LPB || nt >= bn.lp || iborm < 0 || iborm > cx.smax || jout < 0 || jout > nt || lv_bad) {
         if (t == 0) { bn.norders[b] = -1; bn.flux[2 * b] = 0.; bn.flux[2 * b + 1] = 0.; }
         for (int i = t; i < cx.smax + 1; i += NTH) bn.iglast[(size_t)b * (cx.smax + 1) + i] = 0;
         return true;
@@ -323,6 +370,20 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
         const int Llo = min((jlo / COLS) * COLS + COLS - 1, nt), Lhi = min((jhi / COLS) * COLS + COLS - 1, nt);
         for (int k = Llo - 1; k >= jlo; --k) plo = plo - plo * att[(size_t)(k + 1) * NS + jj];
         for (int k = Lhi - 1; k >= jhi; --k) phi = phi - phi * att[(size_t)(k + 1) * NS + jj];
+    }
+    double *const zs = LV ? bn.zst + rw * bn.zst_stride + t : nullptr;
+    if constexpr (LV) if (active && up) {
+#pragma unroll 1
+        for (int k = 0; k < bn.nz; k++) {
+            const int jk = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]);
+            if (!jk) continue;
+            const int kjlo = jk - 1, kjhi = jk;
+            double klo = 1., khi = 1.;
+            const int Llo = min((kjlo / COLS) * COLS + COLS - 1, nt), Lhi = min((kjhi / COLS) * COLS + COLS - 1, nt);
+            for (int q = Llo - 1; q >= kjlo; --q) klo = klo - klo * att[(size_t)(q + 1) * NS + jj];
+            for (int q = Lhi - 1; q >= kjhi; --q) khi = khi - khi * att[(size_t)(q + 1) * NS + jj];
+            zs[((size_t)k * SOS_LV_N + SOS_LV_PLO) * NTH] = klo; zs[((size_t)k * SOS_LV_N + SOS_LV_PHI) * NTH] = khi;
+        }
     }
     __syncthreads();
 
@@ -512,6 +573,7 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                         if (jlo >= l0 && jlo <= L) xlo = cbuf[(size_t)(jlo - l0) * FS + rl];
                         if (jhi >= l0 && jhi <= L) xhi = cbuf[(size_t)(jhi - l0) * FS + rl];
                     }
+                    if constexpr (LV) lv_capture<NTH, FS>(bn, b, zs, cbuf, rl, l0, L);
                 } else if (active) {
                     // up-going rows: the chunk with zero inflow at its bottom level L (Q_L = 0), then the link to level l0-1
                     lds_f64 *q = (lds_f64 *)(cbuf + (size_t)(L - l0) * FS + rl);
@@ -544,6 +606,7 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                         if (jlo >= l0 && jlo <= L) qlo = cbuf[(size_t)(jlo - l0) * FS + rl];
                         if (jhi >= l0 && jhi <= L) qhi = cbuf[(size_t)(jhi - l0) * FS + rl];
                     }
+                    if constexpr (LV) lv_capture<NTH, FS>(bn, b, zs, cbuf, rl, l0, L);
                 }
                 __syncthreads();
                 if (!O1) PH(4);
@@ -630,8 +693,21 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                 *lane_ptr(xin, kk8) = x;
                 if (ZO && jout) { if (jlo / COLS == 0) xlo = qlo + plo * x; if (jhi / COLS == 0) xhi = qhi + phi * x; }
                 xb = q_top + *lane_ptr(bcf, jj8) * x;
+                if constexpr (LV) {
+                    // X = Q + P Xin at the slots' levels, Xin of their chunks as the link pass above stored it
+#pragma unroll 1
+                    for (int k = 0; k < bn.nz; k++) {
+                        const int jk = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]);
+                        if (!jk) continue;
+                        double *z = zs + (size_t)k * SOS_LV_N * NTH;
+                        const double xl = *lane_ptr(xin + ((jk - 1) / COLS) * KHM, kk8), xh = *lane_ptr(xin + (jk / COLS) * KHM, kk8);
+                        z[SOS_LV_XLO * NTH] = z[SOS_LV_XLO * NTH] + z[SOS_LV_PLO * NTH] * xl;
+                        z[SOS_LV_XHI * NTH] = z[SOS_LV_XHI * NTH] + z[SOS_LV_PHI * NTH] * xh;
+                    }
+                }
             }
         };
+
 
         // ---- scattering orders ------------------------------------------------------------------------------------------
         double i3 = 0., a1 = 0., d1 = 0., g1 = 0.;
@@ -644,6 +720,7 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                 __syncthreads();
                 i3 = xb; a1 = 0.; d1 = xb; g1 = 0.;
                 if (ZO) { i3lo = xlo; dlo = xlo; i3hi = xhi; dhi = xhi; }
+                if constexpr (LV) lv_step<NTH>(bn, b, zs, active, 0);
                 bc = ground_bc();
             } else {
                 g1 = xb;
@@ -657,11 +734,13 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                 if (ig != 2 && !(pm & 1)) {                                          // SOS_OS.F:1293-1315
                     i3 = i3 + queue_term(d1, g1);
                     if (ZO) { i3lo = i3lo + queue_term(dlo, xlo); i3hi = i3hi + queue_term(dhi, xhi); }
+                    if constexpr (LV) lv_step<NTH>(bn, b, zs, active, 1);
                     break;
                 }
                 a1 = d1; d1 = g1;                                                    // SOS_OS.F:1323-1363
                 i3 = i3n;
                 if (ZO) { dlo = xlo; dhi = xhi; i3lo = i3lo + xlo; i3hi = i3hi + xhi; }
+                if constexpr (LV) lv_step<NTH>(bn, b, zs, active, 2);
                 if (!(pm & 2)) break;                                                // SOS_OS.F:1370
                 if (!(pm & 4)) break;                                                // SOS_OS.F:1389
                 if (!(ig < cx.igmax)) break;                                         // SOS_OS.F:1406
@@ -697,10 +776,32 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
         const double coef = (s == 0) ? 1. : 2.;                                      // SOS_OS.F:1460-1473
         i4 = i4 + coef * i3;
         i5 = i5 + coef * i3 * sign;
-        if (active) {                                                                // SOS_OS.F:1484-1534,1572
+        if (active && !LV) {                                                         // SOS_OS.F:1484-1534,1572
             const double outv = (ZO && jout) ? ((1 - zz) * i3lo + zz * i3hi) : i3out0;
             recb[(size_t)s * 3 * W + recoff] = outv * usign;
             if (up && jj == 0) recb[(size_t)s * 3 * W + c * W + N] = 0.;
+        }
+        if constexpr (LV) if (active) {                                              // each slot as ZO = true writes it
+#pragma unroll 1
+            for (int k = 0; k < bn.nz; k++) {
+                const int jk = uniform_i32(bn.jout[(size_t)k * bn.zbs + b]);
+                double *rk = recb + (size_t)k * bn.zrs;
+                double outv = i3out0;
+                if (jk) {
+                    const double zk = uniform_f64(bn.zz[(size_t)k * bn.zbs + b]);
+                    const double *z = zs + (size_t)k * SOS_LV_N * NTH;
+                    double i3lo = z[SOS_LV_I3LO * NTH], i3hi = z[SOS_LV_I3HI * NTH];
+                    if (SURF && up) {
+                        const double hlo = uniform_f64(pf[jk - 1]), hhi = uniform_f64(pf[jk]);
+                        const double riilo = exp(-(htot - hlo) / mu) * dirterm;
+                        const double riihi = exp(-(htot - hhi) / mu) * dirterm;
+                        i3lo = i3lo - riilo; i3hi = i3hi - riihi;
+                    }
+                    outv = (1 - zk) * i3lo + zk * i3hi;
+                }
+                rk[(size_t)s * 3 * W + recoff] = outv * usign;
+                if (up && jj == 0) rk[(size_t)s * 3 * W + c * W + N] = 0.;
+            }
         }
         if (t == 0) bn.iglast[(size_t)b * S1 + s] = iglast;
         nord = s + 1;
@@ -827,6 +928,23 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
     }
 }
 
+#ifndef SOS_MULTI
+// Order-parallel form with output slots: k_sos_stream_replay clears the records its round wrote past the stop in slot 0 (bn.rec);
+// this does the same for slots 1 .. nz-1, after the replay of the round [s0, s1) -- a bin that stopped in it has s0 < norders,
+// an earlier stop leaves norders <= s0 (its tasks of the round did not run), a running series norders = s1 (nothing to clear)
+__global__ void k_sos_stream_lv_clear(const SosDev cx, const SosBins bn, int s0, int s1)
+{
+    const int b = blockIdx.x;
+    const int nord = bn.norders[b], iborm = bn.iborm[b];
+    if (nord <= s0) return;                                         // (a malformed bin: -1)
+    const int W3 = 3 * cx.w, S1 = cx.smax + 1, s_hi = min(s1, iborm + 1);
+    for (int k = 1; k < bn.nz; k++) {
+        double *recb = bn.rec + (size_t)k * bn.zrs + (size_t)b * S1 * W3;
+        for (int i = nord * W3 + threadIdx.x; i < s_hi * W3; i += blockDim.x) recb[i] = 0.;
+    }
+}
+#endif
+
 // Order-parallel form, second half: the Fourier stop test (SOS_ARRET_FOURIER, SOS_OS.F:3709; accumulation :1460-1473, exit
 // :1585) of orders [s0, s1) of every bin, replayed in sequence from the I3 terms the order tasks left in bn.spec_i3 -- the same
 // statements as at the end of run_task's order loop, with the same thread -> row mapping.  One workgroup per bin.
@@ -906,18 +1024,20 @@ size_t sos_stream_scratch_doubles(int n, int lpb)
 }
 #endif
 
-template <int NW, int RTWH, bool ZO, bool SURF, int KHT = NW * RTWH>
+template <int NW, int RTWH, int ZM, bool SURF, int KHT = NW * RTWH>
 static int launch_stream_variant(const SosDev &cx, const SosBins &bn, hipStream_t st, int *hip_err)
 {
 #ifdef SOS_MULTI
+    static_assert(ZM != 2, "multi-level output: single-context launches only");
     const bool persist = false;                            // (the per-bin context is bound to blockIdx.x)
     if (bn.queue) return SOSGPU_E_UNSUPPORTED;
-    auto kern = k_sos_stream<NW, RTWH, ZO, SURF, false, KHT>;
+    auto kern = k_sos_stream<NW, RTWH, ZM, SURF, false, KHT>;
 #else
     const bool persist = bn.queue != nullptr;
     if (persist && KHT != NW * RTWH) return SOSGPU_E_UNSUPPORTED;       // (stream_shape keeps the full width for that form)
-    auto kern = k_sos_stream<NW, RTWH, ZO, SURF, false, KHT>;
-    if constexpr (KHT == NW * RTWH) { if (persist) kern = k_sos_stream<NW, RTWH, ZO, SURF, true, KHT>; }
+    if (persist && ZM == 2) return SOSGPU_E_UNSUPPORTED;                // (the caller launches output slots in the plain form)
+    auto kern = k_sos_stream<NW, RTWH, ZM, SURF, false, KHT>;
+    if constexpr (KHT == NW * RTWH && ZM != 2) { if (persist) kern = k_sos_stream<NW, RTWH, ZM, SURF, true, KHT>; }
 #endif
     const size_t lds = stream_lds_bytes(KHT);
     // the dynamic-LDS limit of a kernel is set once per device and size (the call costs tens of microseconds: with few bins per
@@ -968,6 +1088,7 @@ int launch_sos_stream_replay(const SosDev &cx, const SosBins &bn, int s0, int s1
     else if (kht == 6) k_sos_stream_replay<4, 6><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
     else if (kht == 8) k_sos_stream_replay<4, 8><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
     else k_sos_stream_replay<8, 16><<<bn.nb, 512, 0, st>>>(cx, bn, s0, s1);
+    if (bn.nz > 1) k_sos_stream_lv_clear<<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { if (hip_err) *hip_err = (int)e; return -2; }
     return 0;
@@ -983,15 +1104,26 @@ int launch_sos_stream(const SosDev &cx, const SosBins &bn, int nt_max, hipStream
     if (!bn.scratch || bn.lpb < nt_max + 1 || bn.lpb % COLS || bn.scr_stride < stream_scratch_doubles(nw, kht, bn.lpb))
         return SOSGPU_E_UNSUPPORTED;
     const int zo = bn.jout != nullptr;
+#ifdef SOS_MULTI
+    if (bn.nz > 0) return SOSGPU_E_UNSUPPORTED;
+#define V_LV(NWV, R, K)
+#else
+#define V_LV(NWV, R, K)                                                                        \
+        if (bn.nz > 0)                                                                         \
+            return cx.imat_surf ? launch_stream_variant<NWV, R, 2, true, K>(cx, bn, st, hip_err)     \
+                                : launch_stream_variant<NWV, R, 2, false, K>(cx, bn, st, hip_err);
+#endif
 #define V(NWV, R, K)                                                                           \
     if (nw == NWV && rtw == R && kht == K) {                                                   \
+        V_LV(NWV, R, K)                                                                        \
         if (cx.imat_surf)                                                                      \
-            return zo ? launch_stream_variant<NWV, R, true, true, K>(cx, bn, st, hip_err)      \
-                      : launch_stream_variant<NWV, R, false, true, K>(cx, bn, st, hip_err);    \
-        return zo ? launch_stream_variant<NWV, R, true, false, K>(cx, bn, st, hip_err)         \
-                  : launch_stream_variant<NWV, R, false, false, K>(cx, bn, st, hip_err);       \
+            return zo ? launch_stream_variant<NWV, R, 1, true, K>(cx, bn, st, hip_err)         \
+                      : launch_stream_variant<NWV, R, 0, true, K>(cx, bn, st, hip_err);       \
+        return zo ? launch_stream_variant<NWV, R, 1, false, K>(cx, bn, st, hip_err)            \
+                  : launch_stream_variant<NWV, R, 0, false, K>(cx, bn, st, hip_err);          \
     }
     V(4, 1, 4) V(4, 2, 5) V(4, 2, 6) V(4, 2, 8) V(8, 2, 16)
 #undef V
+#undef V_LV
     return SOSGPU_E_UNSUPPORTED;
 }

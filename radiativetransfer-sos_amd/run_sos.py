@@ -1271,6 +1271,61 @@ def sos_proc(aer_phase=None, device=0, **kw):
         pl.ctx.close()
 
 
+def sos_proc_levels(altitudes, aer_phase=None, device=0, **kw):
+    """sos_proc for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output) at once: ONE
+    profile, context and solve, whose K output slots capture the field at each altitude (sosgpu_os_solve_levels), then
+    one aggregate and SOS_TRPHI per altitude.  Returns a list of K 23-tuples in the order of `altitudes`; element k equals
+    sos_proc(aer_phase, device, **{**kw, "zout": altitudes[k]}) bit for bit.
+    1 <= K <= 16, duplicates allowed; each altitude must pass the -SOS.OutputAlt rule (SosProcError 2611, raised before any
+    device work).  kw is sos_proc's keyword set with zout = -1 (another zout: ValueError) and no -SOS_Main.ResRoot (result
+    files stay sos_proc's: ValueError).  Under torch.distributed the call is a collective as sos_proc is: the bins are
+    sharded and one all-reduce covers the K record sets."""
+    from .solver import SosBinError
+    from . import capi
+    alts = [float(z) for z in altitudes]
+    if not 1 <= len(alts) <= capi.MAX_OUTPUT_LEVELS:
+        raise ValueError("sos_proc_levels: 1 to %d altitudes, got %d" % (capi.MAX_OUTPUT_LEVELS, len(alts)))
+    if float(kw.get("zout", -1.0)) != -1.0:
+        raise ValueError("sos_proc_levels: the altitudes are given by `altitudes`; zout must be -1")
+    if str(kw.get("resroot", "")).strip():
+        raise ValueError("sos_proc_levels writes no result files: -SOS_Main.ResRoot must be empty (use sos_proc)")
+    for z in alts:                                 # the -SOS.OutputAlt rule of validate_parameters
+        if (z < 0.0 and z != -1.0) or z > CTE_TOA_ALT:
+            e = SosProcError("SOS_PROC : ERROR_2611 on parameters -- -SOS.OutputAlt must be -1 (standard levels) or within "
+                             "[0, %g] km (got %g)" % (CTE_TOA_ALT, z))
+            e.code = 2611
+            raise e
+    rank, world = _dist_rank_world()
+    pl, levels, err = None, None, None
+    try:
+        pl = _prepare(kw, aer_phase, device, shard_bins=True)
+        try:
+            levels = pl.ctx.output_levels(pl.bins, alts)
+        except BaseException:
+            pl.ctx.close()
+            pl = None
+            raise
+    except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
+        err = e
+    if world > 1:
+        bad = _any_rank_failed(err is not None, device)
+        if bad and err is None:
+            pl.ctx.close()
+            raise SosProcError("sos_proc_levels: another rank failed while preparing this call", ier=-1)
+    if err is not None:
+        raise err
+    try:
+        try:
+            rec, fin = pl.ctx.solve_band_levels(pl.bins, levels, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
+        except SosBinError as e:
+            raise SosProcError(str(e), ier=-1)
+        outs = [_trphi_launch(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]), float(fin["tauout"][k]))
+                for k in range(len(alts))]
+        return [_finish(pl, outs[k].cpu().numpy(), rec[k], fin, k) for k in range(len(alts))]
+    finally:
+        pl.ctx.close()
+
+
 def _any_rank_failed(failed, device):
     import torch
     import torch.distributed as dist

@@ -90,6 +90,27 @@ def nogas_profile(tr, hr, ta, ha, device=0):
 SEG = None          # run_sos._seg when SOS_PREPARE_SEGMENTS is set (host-time diagnostic), else None
 
 
+def output_levels_host(zprof, altitudes):
+    """Output levels of several altitudes for host profiles (upload_bins with zprof: the aerosol-layer profile): the rule
+    upload_bins applies to one zout (SOS_OS.F:1514-1520, first level J with ZOUT >= ZPROF(J), linear weight ZZ), once per
+    altitude.  zprof[nb][L]; returns jout[K][nb] (int32) and zz[K][nb]; -1 gives the standard output (0, 0)."""
+    zprof = np.atleast_2d(np.asarray(zprof, dtype=np.float64))
+    nb = zprof.shape[0]
+    alts = [float(z) for z in altitudes]
+    jout = np.zeros((len(alts), nb), dtype=np.int32)
+    zz = np.zeros((len(alts), nb))
+    for k, zout in enumerate(alts):
+        if zout == -1.0:
+            continue
+        for b in range(nb):
+            j = 1
+            while zout < zprof[b, j]:
+                j += 1
+            jout[k, b] = j
+            zz[k, b] = (zout - zprof[b, j - 1]) / (zprof[b, j] - zprof[b, j - 1])
+    return jout, zz
+
+
 class SosContext:
     """Everything SOS_OS needs that does not depend on the CKD bin (angles, phase-matrix expansion,
     surface), resident on one GPU, with the Fourier kernels of every order precomputed
@@ -200,7 +221,8 @@ class SosContext:
                 zz[b] = (zout - zprof[b, j - 1]) / (zprof[b, j] - zprof[b, j - 1])
         d = self.device
         return dict(nb=nb, lp=lp, perm=perm, nt=_dev_i32(nt, d), iborm=_dev_i32(iborm, d), prof=_dev_f64(prof, d),
-                    jout=None if jout is None else _dev_i32(jout, d), zz=None if zz is None else _dev_f64(zz, d))
+                    jout=None if jout is None else _dev_i32(jout, d), zz=None if zz is None else _dev_f64(zz, d),
+                    zprof_host=None if zprof is None else np.atleast_2d(np.asarray(zprof, dtype=np.float64)))
 
     def absorption_profiles(self, ik, xk, ro):
         """SOS_ABSPROFILE (SOS_ABSPROFILE.F:325-371) of every CKD bin on the device (sosgpu_absprofile): ik[nb][8] 1-based
@@ -282,6 +304,80 @@ class SosContext:
         if (fin["min_orders"] < 0).any():
             raise SosBinError("SOS_OS: %d band(s) hold a malformed bin (NT outside 1..CTE_OS_NT or IBORM out of range)"
                               % int((fin["min_orders"] < 0).sum()))
+        return rec, fin
+
+    def output_levels(self, bins, altitudes):
+        """Output levels of K altitudes (1 <= K <= capi.MAX_OUTPUT_LEVELS, -1 = the standard output) for every bin: the level
+        pair, weight and TAUOUT a single-altitude profile gives for each.  Bins of make_profiles: sosgpu_output_levels on the
+        device; bins of upload_bins with zprof (the aerosol-layer profile): output_levels_host, TAUOUT from the uploaded H
+        as run_sos computes it for one altitude (SOS.F:567-581).  Returns dict(nz, jout[K][nb], zz[K][nb], tauout[K][nb])
+        of device tensors, the `levels` solve_levels takes (no tensors for an empty batch: a rank without bins)."""
+        alts = [float(z) for z in altitudes]
+        nz, nb, d = len(alts), bins["nb"], self.device
+        if not 1 <= nz <= capi.MAX_OUTPUT_LEVELS:
+            raise ValueError("1 to %d output altitudes per solve" % capi.MAX_OUTPUT_LEVELS)
+        if nb == 0:
+            return dict(nz=nz, jout=None, zz=None, tauout=None)
+        if isinstance(bins.get("zprof"), torch.Tensor):
+            jout = torch.empty((nz, nb), dtype=torch.int32, device=d)
+            zz = torch.empty((nz, nb), dtype=torch.float64, device=d)
+            tauout = torch.empty((nz, nb), dtype=torch.float64, device=d)
+            capi.check(capi.lib().sosgpu_output_levels(self._h, nb, bins["lp"], _ptr(bins["prof"]), _ptr(bins["zprof"]),
+                                                       _ptr(bins["nt"]), nz, (C.c_double * nz)(*alts), _ptr(jout), _ptr(zz),
+                                                       _ptr(tauout), self._stream()), "sosgpu_output_levels")
+            return dict(nz=nz, jout=jout, zz=zz, tauout=tauout)
+        if bins.get("zprof_host") is None and any(z != -1.0 for z in alts):
+            raise ValueError("output altitudes need the bins' level altitudes (make_profiles, or upload_bins with zprof)")
+        zp = bins.get("zprof_host")
+        jh, zh = output_levels_host(zp, alts) if zp is not None else (np.zeros((nz, nb), np.int32), np.zeros((nz, nb)))
+        h = bins["prof"][:, 0, :].cpu().numpy()
+        th = np.zeros((nz, nb))
+        for k in range(nz):
+            for b in range(nb):
+                j, zzv = int(jh[k, b]), float(zh[k, b])
+                th[k, b] = h[b, 0] if alts[k] == -1.0 else (1 - zzv) * h[b, j - 1] + zzv * h[b, j]
+        return dict(nz=nz, jout=_dev_i32(jh, d), zz=_dev_f64(zh, d), tauout=_dev_f64(th, d))
+
+    def solve_levels(self, bins, levels, out=None):
+        """One solve for the K output levels of output_levels (sosgpu_os_solve_levels).  Returns dict(rec[K][nb][smax+1][3][W],
+        norders, iglast, flux): rec[k] equals the rec of solve() with that altitude's jout / zz, bit for bit."""
+        nz, nb = levels["nz"], bins["nb"]
+        if out is None:
+            out = self.alloc_outputs(nb)
+            out["rec"] = torch.zeros((nz, nb, self.smax + 1, 3, self.w), dtype=torch.float64, device=self.device)
+        capi.check(capi.lib().sosgpu_os_solve_levels(self._h, nb, bins["lp"], _ptr(bins["nt"]), _ptr(bins["iborm"]),
+                                                     _ptr(bins["prof"]), nz, _ptr(levels["jout"]), _ptr(levels["zz"]),
+                                                     _ptr(out["rec"]), _ptr(out["norders"]), _ptr(out["iglast"]),
+                                                     _ptr(out["flux"]), self._stream()), "sosgpu_os_solve_levels")
+        return out
+
+    def solve_band_levels(self, bins, levels, aik, tdifmug=None, reduce=True, group=None):
+        """solve_band for K output altitudes: ONE solve (solve_levels), then every altitude's records aggregated with its
+        own TAUOUT, and -- sharded over ranks -- one all-reduce covering the K record sets.  levels: output_levels of these
+        bins (a rank without bins contributes K neutral elements).  Returns (rec[K][smax+1][3][W], finish_scalars dict with
+        one entry per altitude); raises SosBinError as solve_band does."""
+        from . import dist as _dist
+        nz = levels["nz"]
+        out = self.solve_levels(bins, levels) if bins["nb"] else None
+        recs, scals = [], []
+        for k in range(nz):
+            if out is None:
+                r, s = self.aggregate(None, aik)
+            else:
+                sc = _dev_f64(bins["scal"], self.device).clone()
+                sc[:, 3] = levels["tauout"][k]
+                r, s = self.aggregate(dict(rec=out["rec"][k], norders=out["norders"], flux=out["flux"]), aik, scal=sc,
+                                      tdifmug=tdifmug)
+            recs.append(r)
+            scals.append(s)
+        rec, scal = torch.cat(recs), torch.cat(scals)
+        if reduce:
+            buf = _dist.all_reduce_partial(_dist.pack_partial(rec, scal), scal.shape[1], group=group)
+            rec, scal = _dist.unpack_partial(buf, rec.shape)
+        fin = _dist.finish_scalars(scal)
+        if (fin["min_orders"] < 0).any():
+            raise SosBinError("SOS_OS: a bin of the band is malformed (NT outside 1..CTE_OS_NT, IBORM or an output level out "
+                              "of range)")
         return rec, fin
 
     def diffuse_transmissions(self, bins):

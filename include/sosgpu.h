@@ -179,6 +179,16 @@ int  sosgpu_os_solve_multi(sosgpu_ctx *cx, const void *d_table, const int32_t *d
                            const int32_t *d_nt, const int32_t *d_iborm, const double *d_prof, const int32_t *d_jout,
                            const double *d_zz, double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux,
                            void *stream);
+/*   sosgpu_os_solve_multi_levels   the two joined: one launch over the bins of many wavelengths (table rules of
+ *                      sosgpu_os_solve_multi), each bin with nz output slots (argument rules of sosgpu_os_solve_levels:
+ *                      1 <= nz <= SOSGPU_MAX_OUTPUT_LEVELS, d_jout and d_zz required).  Layout as sosgpu_os_solve_levels:
+ *                      d_jout[nz][nb], d_zz[nz][nb], d_rec[nz][nb][iborm_max+1][3][W]; slot k of bin b equals, bit for bit,
+ *                      the record of sosgpu_os_solve with that bin's context and the slot's (jout, zz).  Feed sosgpu_aggregate
+ *                      slot by slot (d_rec + k nb (iborm_max+1) 3 W), one segment per wavelength, with that slot's TAUOUT. */
+int  sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table, const int32_t *d_ctx_of_bin, const int32_t *d_order,
+                                  int nb, int lp, const int32_t *d_nt, const int32_t *d_iborm, const double *d_prof, int nz,
+                                  const int32_t *d_jout, const double *d_zz, double *d_rec, int32_t *d_norders,
+                                  int32_t *d_iglast, double *d_flux, void *stream);
 
 /* Replaces SOS_AGGREGATE (SOS_AGGREGATE.F:372-488) for nseg independent wavelengths/bands at once:
  * segment g covers bins seg[g]..seg[g+1]-1 of d_rec; seg[0] = 0, seg[nseg] = nb.  One big band (nseg = 1,

@@ -20,7 +20,7 @@ EXPORTS = [
     "sosgpu_pack", "sosgpu_unpack", "sosgpu_reduce", "sosgpu_absprofile", "sosgpu_land_surface", "sosgpu_mie", "sosgpu_granu",
     "sosgpu_granu_batch",
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
-    "sosgpu_os_solve_levels", "sosgpu_output_levels",
+    "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -104,6 +104,8 @@ def lib():
         L.sosgpu_ctx_table.argtypes = [C.POINTER(vp), i32, vp, vp]
         L.sosgpu_os_solve_multi.restype = i32
         L.sosgpu_os_solve_multi.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sosgpu_os_solve_multi_levels.restype = i32
+        L.sosgpu_os_solve_multi_levels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.sosgpu_aggregate.restype = i32
         L.sosgpu_aggregate.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.sosgpu_comm_unique_id.restype = i32

@@ -555,7 +555,8 @@ static size_t lv_stride(int nz, int threads) { return (size_t)nz * SOS_LV_N * th
 static size_t lv_off(size_t doubles) { return (doubles + 7) & ~(size_t)7; }
 
 // sosgpu_os_solve (table == null) and sosgpu_os_solve_multi (per-bin contexts from a device table)
-// nz > 0: sosgpu_os_solve_levels (d_jout / d_zz / d_rec hold nz slots)
+// nz > 0: sosgpu_os_solve_levels / sosgpu_os_solve_multi_levels (d_jout / d_zz / d_rec hold nz slots; a split batch reads
+// slot k of its bins at k nb + b0 -- bn.zbs is the whole batch's bin count)
 static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_ctx_of_bin, const int32_t *d_order, int nb, int lp, const int32_t *d_nt,
                          const int32_t *d_iborm, const double *d_prof, const int32_t *d_jout, const double *d_zz,
                          double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream, int nz = 0)
@@ -582,7 +583,9 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
         size_t gib = 64;
         if (const char *e = getenv("SOSGPU_SCRATCH_GIB")) { const long v = atol(e); if (v > 0) gib = (size_t)v; }
         const size_t cap = (gib << 30) / sizeof(double);
-        per_launch = (int)std::min<size_t>((size_t)nb, std::max<size_t>(1, cap / per_bin));
+        // (output slots: a bin's work region also carries the slots' lane-private state)
+        const size_t per_region = per_bin + (nz > 0 ? lv_stride(nz, sos_stream_threads(cx->d.n)) : 0);
+        per_launch = (int)std::min<size_t>((size_t)nb, std::max<size_t>(1, cap / per_region));
         // Few bins (a band of one wavelength): the order-parallel form -- up to 48 Fourier orders of every bin at a time, each in a
         // work region of its own, so that the band fills ~1024 workgroup slots (sos_stream.hip; SOSGPU_STREAM_SPEC=0 turns it
         // off, SOSGPU_STREAM_SPEC_MAXBINS moves the limit).  A single bin takes 11 ms as one workgroup, ~1.5 ms this way.
@@ -800,6 +803,17 @@ extern "C" int sosgpu_os_solve_multi(sosgpu_ctx *cx, const void *d_table, const 
     if (!d_table || !d_ctx_of_bin) return SOSGPU_E_ARG;
     return os_solve_impl(cx, static_cast<const SosDev *>(d_table), d_ctx_of_bin, d_order, nb, lp, d_nt, d_iborm, d_prof, d_jout,
                          d_zz, d_rec, d_norders, d_iglast, d_flux, stream);
+}
+
+extern "C" int sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table, const int32_t *d_ctx_of_bin, const int32_t *d_order,
+                                            int nb, int lp, const int32_t *d_nt, const int32_t *d_iborm, const double *d_prof,
+                                            int nz, const int32_t *d_jout, const double *d_zz, double *d_rec, int32_t *d_norders,
+                                            int32_t *d_iglast, double *d_flux, void *stream)
+{
+    if (!d_table || !d_ctx_of_bin) return SOSGPU_E_ARG;
+    if (nz < 1 || nz > SOSGPU_MAX_OUTPUT_LEVELS || !d_jout || !d_zz) return SOSGPU_E_ARG;
+    return os_solve_impl(cx, static_cast<const SosDev *>(d_table), d_ctx_of_bin, d_order, nb, lp, d_nt, d_iborm, d_prof, d_jout,
+                         d_zz, d_rec, d_norders, d_iglast, d_flux, stream, nz);
 }
 
 extern "C" int sosgpu_last_solve_ms(sosgpu_ctx *cx, float *ms)

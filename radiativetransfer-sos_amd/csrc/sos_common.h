@@ -85,7 +85,7 @@ struct SosBins {
     const int32_t *ctx_of_bin;
     const int32_t *order;        // multi-wavelength launches: workgroup i solves bin order[i] (costliest bins first: workgroups
                                  // are dispatched in index order and the bins stay grouped by wavelength for the aggregate), or null
-    // multi-level output (sosgpu_os_solve_levels, the ZO mode 2 instantiations), nz = 0 otherwise: slot k of bin b reads
+    // multi-level output (sosgpu_os_solve_levels / _multi_levels, the ZO mode 2 instantiations), nz = 0 otherwise: slot k of bin b reads
     // jout[k zbs + b], zz[k zbs + b] and writes its records at rec + k zrs; zst holds the lane-private state of the slots,
     // zst_stride doubles per work region (bin, or order task of the streamed kernel): [nz][8][threads]
     int nz, zbs;

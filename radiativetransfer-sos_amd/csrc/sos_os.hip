@@ -66,7 +66,7 @@
 #define SOS_MIN_WG_R(NW, RTWH, CT) (((NW) == 4 && (RTWH) == 1 && (CT) == 2) ? 3 : SOS_MIN_WG(NW, CT))
 #endif
 // ZM: output mode -- 0 standard output (TOA up-going, ground down-going), 1 one output altitude (ZO above: bn.jout / bn.zz),
-//     2 bn.nz output slots (sosgpu_os_solve_levels): every slot runs the statements of ZO = true with its own (jout, zz), its
+//     2 bn.nz output slots (sosgpu_os_solve_levels, sosgpu_os_solve_multi_levels): every slot runs the statements of ZO = true with its own (jout, zz), its
 //     i3lo / dlo / i3hi / dhi kept lane-private in bn.zst (no registers across the order loop: there are none to spare), a slot
 //     with jout = 0 gets the standard output.
 template <int NW, int RTWH, int CT, int ZM, bool SURF, bool SPLIT>
@@ -564,9 +564,6 @@ static int launch_variant(const SosDev &cx, const SosBins &bn, size_t lds, hipSt
     if constexpr (!SPLIT && NW == 4 && RTWH == 2 && CT == 2) {
         if (sos_split_applies(cx, NW, RTWH, CT)) return launch_variant<NW, RTWH, CT, ZM, SURF, true>(cx, bn, lds, st, hip_err);
     }
-#ifdef SOS_MULTI
-    static_assert(ZM != 2, "multi-level output: single-context launches only");
-#endif
     auto kern = k_sos_os<NW, RTWH, CT, ZM, SURF, SPLIT>;
 #ifdef SOS_PROFILE_PHASES
     if (const char *e = getenv("SOSGPU_DEBUG_LDS_PAD")) lds += (size_t)atoi(e);   // diagnostic builds: force 1 workgroup per CU
@@ -601,15 +598,10 @@ int launch_sos_os(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t s
 #ifdef SOS_WIDE_REGS
     if (nw == 8 && rtw == 1 && ct == 4) { nw = 4; rtw = 2; }      // same KHM, same LDS layout
 #endif
-#ifdef SOS_MULTI
-    if (bn.nz > 0) return SOSGPU_E_UNSUPPORTED;
-#define V_LV(NWV, R, C)
-#else
 #define V_LV(NWV, R, C)                                                                \
         if (bn.nz > 0)                                                                 \
             return cx.imat_surf ? launch_variant<NWV, R, C, 2, true>(cx, bn, lds, st, hip_err)  \
                                 : launch_variant<NWV, R, C, 2, false>(cx, bn, lds, st, hip_err);
-#endif
 #define V(NWV, R, C)                                                                   \
     if (nw == NWV && rtw == R && ct == C) {                                            \
         V_LV(NWV, R, C)                                                                \

@@ -1028,7 +1028,6 @@ template <int NW, int RTWH, int ZM, bool SURF, int KHT = NW * RTWH>
 static int launch_stream_variant(const SosDev &cx, const SosBins &bn, hipStream_t st, int *hip_err)
 {
 #ifdef SOS_MULTI
-    static_assert(ZM != 2, "multi-level output: single-context launches only");
     const bool persist = false;                            // (the per-bin context is bound to blockIdx.x)
     if (bn.queue) return SOSGPU_E_UNSUPPORTED;
     auto kern = k_sos_stream<NW, RTWH, ZM, SURF, false, KHT>;
@@ -1104,15 +1103,10 @@ int launch_sos_stream(const SosDev &cx, const SosBins &bn, int nt_max, hipStream
     if (!bn.scratch || bn.lpb < nt_max + 1 || bn.lpb % COLS || bn.scr_stride < stream_scratch_doubles(nw, kht, bn.lpb))
         return SOSGPU_E_UNSUPPORTED;
     const int zo = bn.jout != nullptr;
-#ifdef SOS_MULTI
-    if (bn.nz > 0) return SOSGPU_E_UNSUPPORTED;
-#define V_LV(NWV, R, K)
-#else
 #define V_LV(NWV, R, K)                                                                        \
         if (bn.nz > 0)                                                                         \
             return cx.imat_surf ? launch_stream_variant<NWV, R, 2, true, K>(cx, bn, st, hip_err)     \
                                 : launch_stream_variant<NWV, R, 2, false, K>(cx, bn, st, hip_err);
-#endif
 #define V(NWV, R, K)                                                                           \
     if (nw == NWV && rtw == R && kht == K) {                                                   \
         V_LV(NWV, R, K)                                                                        \

@@ -1271,6 +1271,28 @@ def sos_proc(aer_phase=None, device=0, **kw):
         pl.ctx.close()
 
 
+def _levels_arguments(fn, altitudes, kwargs_list):
+    """The argument rules of the output-slot entry points, checked before any device work: 1 to 16 altitudes, each passing the
+    -SOS.OutputAlt rule (SosProcError 2611), and calls with zout = -1 and no -SOS_Main.ResRoot (ValueError).  Returns the
+    altitudes as floats."""
+    from . import capi
+    alts = [float(z) for z in altitudes]
+    if not 1 <= len(alts) <= capi.MAX_OUTPUT_LEVELS:
+        raise ValueError("%s: 1 to %d altitudes, got %d" % (fn, capi.MAX_OUTPUT_LEVELS, len(alts)))
+    for kw in kwargs_list:
+        if float(kw.get("zout", -1.0)) != -1.0:
+            raise ValueError("%s: the altitudes are given by `altitudes`; zout must be -1" % fn)
+        if str(kw.get("resroot", "")).strip():
+            raise ValueError("%s writes no result files: -SOS_Main.ResRoot must be empty (use sos_proc)" % fn)
+    for z in alts:                                 # the -SOS.OutputAlt rule of validate_parameters
+        if (z < 0.0 and z != -1.0) or z > CTE_TOA_ALT:
+            e = SosProcError("SOS_PROC : ERROR_2611 on parameters -- -SOS.OutputAlt must be -1 (standard levels) or within "
+                             "[0, %g] km (got %g)" % (CTE_TOA_ALT, z))
+            e.code = 2611
+            raise e
+    return alts
+
+
 def sos_proc_levels(altitudes, aer_phase=None, device=0, **kw):
     """sos_proc for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output) at once: ONE
     profile, context and solve, whose K output slots capture the field at each altitude (sosgpu_os_solve_levels), then
@@ -1281,20 +1303,7 @@ def sos_proc_levels(altitudes, aer_phase=None, device=0, **kw):
     files stay sos_proc's: ValueError).  Under torch.distributed the call is a collective as sos_proc is: the bins are
     sharded and one all-reduce covers the K record sets."""
     from .solver import SosBinError
-    from . import capi
-    alts = [float(z) for z in altitudes]
-    if not 1 <= len(alts) <= capi.MAX_OUTPUT_LEVELS:
-        raise ValueError("sos_proc_levels: 1 to %d altitudes, got %d" % (capi.MAX_OUTPUT_LEVELS, len(alts)))
-    if float(kw.get("zout", -1.0)) != -1.0:
-        raise ValueError("sos_proc_levels: the altitudes are given by `altitudes`; zout must be -1")
-    if str(kw.get("resroot", "")).strip():
-        raise ValueError("sos_proc_levels writes no result files: -SOS_Main.ResRoot must be empty (use sos_proc)")
-    for z in alts:                                 # the -SOS.OutputAlt rule of validate_parameters
-        if (z < 0.0 and z != -1.0) or z > CTE_TOA_ALT:
-            e = SosProcError("SOS_PROC : ERROR_2611 on parameters -- -SOS.OutputAlt must be -1 (standard levels) or within "
-                             "[0, %g] km (got %g)" % (CTE_TOA_ALT, z))
-            e.code = 2611
-            raise e
+    alts = _levels_arguments("sos_proc_levels", altitudes, [kw])
     rank, world = _dist_rank_world()
     pl, levels, err = None, None, None
     try:
@@ -1415,6 +1424,41 @@ def spectrum_costs(kwargs_list):
     return costs
 
 
+def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st):
+    """The shared host work of a spectrum chunk `idx`, queued ahead of its per-wavelength preparation: the size-distribution
+    integrals (aerosols.prefetch_size_integrals), the gas tables interpolated to the layers in one pass, and SOS_AEROSOLS at the
+    simulation wavelength of each call.  Returns {index: aerosols at the simulation wavelength} for _prepare(aer_at_wa=...)."""
+    import torch
+    from . import aerosols as _aer
+    from . import absorption as _abs
+    # the size-distribution integrals of the chunk's wavelengths, queued ahead (aerosols.prefetch_size_integrals)
+    valid = {i: v for i, v in ((i, _validated(kwargs_list[i])) for i in idx) if v is not None}
+    acalls = {i: c for i, c in ((i, _aerosol_call(v, aer_phases[i])) for i, v in valid.items()) if c is not None}
+    reqs = []
+    for c in acalls.values():
+        reqs += _size_integral_requests(c, device)
+    if reqs:
+        with torch.cuda.stream(aer_st):
+            _aer.prefetch_size_integrals(reqs)
+    # ... and the gas tables of the chunk's wavelengths, interpolated to the layers in one pass
+    greqs = [r for r in (_gas_table_request(v) for v in valid.values()) if r is not None]
+    if greqs:
+        _abs.prefetch_gas_tables(greqs)
+    # ... and SOS_AEROSOLS at the simulation wavelength of each, the Legendre expansions formed together (the gas tables
+    # above were made while the size integrals ran)
+    aer_wa = {}
+    by_angles = collections.OrderedDict()
+    for i, (pp, nbm, nbo) in acalls.items():
+        by_angles.setdefault((nbm, nbo), []).append((i, pp))
+    for (nbm, nbo), members in by_angles.items():
+        with torch.cuda.stream(aer_st):
+            res = _aer.aerosols_many([(pp, pp["wa_simu"], 0.1) for _, pp in members], nbm, nbo, device=device)
+        for (i, _), r in zip(members, res):
+            if r is not None:
+                aer_wa[i] = r
+    return aer_wa
+
+
 def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16, parts=4):
     """A spectrum of sos_proc calls -- one per wavelength, as the reference issues them one after the other
     (binding/run_sos.py:640-695; the bin loop of each is SOS_PROC.F:3459-3594) -- as ONE pass over the GPU:
@@ -1496,31 +1540,7 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
                 # device, and the launches below wait for all of them
                 for st in side + [aer_st]:
                     st.wait_stream(main_st)
-                # the size-distribution integrals of the chunk's wavelengths, queued ahead (aerosols.prefetch_size_integrals)
-                valid = {i: v for i, v in ((i, _validated(kwargs_list[i])) for i in idx) if v is not None}
-                acalls = {i: c for i, c in ((i, _aerosol_call(v, aer_phases[i])) for i, v in valid.items()) if c is not None}
-                reqs = []
-                for c in acalls.values():
-                    reqs += _size_integral_requests(c, device)
-                if reqs:
-                    with torch.cuda.stream(aer_st):
-                        _aer.prefetch_size_integrals(reqs)
-                # ... and the gas tables of the chunk's wavelengths, interpolated to the layers in one pass
-                greqs = [r for r in (_gas_table_request(v) for v in valid.values()) if r is not None]
-                if greqs:
-                    _abs.prefetch_gas_tables(greqs)
-                # ... and SOS_AEROSOLS at the simulation wavelength of each, the Legendre expansions formed together (the gas tables
-                # above were made while the size integrals ran)
-                aer_wa = {}
-                by_angles = collections.OrderedDict()
-                for i, (pp, nbm, nbo) in acalls.items():
-                    by_angles.setdefault((nbm, nbo), []).append((i, pp))
-                for (nbm, nbo), members in by_angles.items():
-                    with torch.cuda.stream(aer_st):
-                        res = _aer.aerosols_many([(pp, pp["wa_simu"], 0.1) for _, pp in members], nbm, nbo, device=device)
-                    for (i, _), r in zip(members, res):
-                        if r is not None:
-                            aer_wa[i] = r
+                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st)
                 # The chunk goes to the solver in a few parts: the solves of a part run on the device while the host prepares the
                 # next one, so that only the last part's solve is waited for below.
                 solved = []                       # (plans, rec [nw][S][3][W], scal [nw][10+N]) device tensors
@@ -1620,6 +1640,208 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     if world > 1 and gather:
         _gather_results(results, mine, nrows, world)
     return results
+
+
+def _first_failed_index(index, device):
+    """Ranks agree on a failure: the largest wavelength index any rank failed at (index -1: this rank did not fail), or -1."""
+    import torch
+    import torch.distributed as dist
+    on_gpu = dist.get_backend() == "nccl"
+    t = torch.tensor([int(index)], dtype=torch.int64, device=torch.device("cuda", device) if on_gpu else "cpu")
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return int(t.item())
+
+
+def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16,
+                        parts=4):
+    """sos_spectrum for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output): every wavelength is
+    prepared once, ALL bins of a group of wavelengths go through ONE launch of the fused solver per kernel variant with K output
+    slots each (sosgpu_os_solve_multi_levels), then K segmented aggregates (each altitude with its own TAUOUT) and K azimuth
+    recompositions per wavelength.  Returns one list of K 23-tuples per call: result[i][k] equals
+    sos_proc(**{**kwargs_list[i], "zout": altitudes[k]}) bit for bit, hence also sos_proc_levels(altitudes, **kwargs_list[i])[k].
+
+    Argument rules of sos_proc_levels, checked for the whole list before any device work: 1 <= K <= 16 altitudes, duplicates
+    allowed, each passing the -SOS.OutputAlt rule (SosProcError 2611); every call with zout = -1 and an empty -SOS_Main.ResRoot
+    (ValueError otherwise).  An empty list returns [].
+    Calls with -SOS.Trans (diffuse transmissions) and groups of one wavelength run through the per-wavelength path
+    (SosContext.solve_band_levels).
+    Record memory: the records of a launch grow K-fold (at N = 41, 6 400 bins hold about 1 GB per altitude), so a chunk holds
+    max(1, chunk // K) wavelengths -- a part's records then stay near what sos_spectrum holds with the same `chunk`.
+    aer_phases, device, gather, timings, prep_streams, parts: as sos_spectrum.  With torch.distributed the wavelengths are dealt
+    to the ranks by cost (spectrum_costs), without an all-reduce; the ranks then agree on failures (one integer all-reduce),
+    so that a call failing on one rank makes EVERY rank raise SosProcError naming that wavelength instead of leaving the
+    others waiting in the gather (all_gather_object of the compacted tuples, K per wavelength).  gather=False leaves None in
+    the slots of other ranks."""
+    import time
+    import torch
+    from . import capi
+    from .solver import ContextTable, SosBinError, _upload, concat_bins, concat_levels, solve_spectrum_levels
+    from . import dist as _dist
+    from . import aerosols as _aer
+    from . import absorption as _abs
+    alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list)
+    nz, nwl = len(alts), len(kwargs_list)
+    if aer_phases is None:
+        aer_phases = [None] * nwl
+    if len(aer_phases) != nwl:
+        raise ValueError("aer_phases must be parallel to kwargs_list")
+    if nwl == 0:
+        return []
+    capi.lib()
+    rank, world = _dist_rank_world()
+    if world > 1:
+        mine = [int(i) for i in _dist.balanced_shards(spectrum_costs(kwargs_list), world)[rank]]
+    else:
+        mine = list(range(nwl))
+    results = [None] * nwl
+    nrows = {}
+    tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0)
+    dev = torch.device("cuda", device)
+    main_st = torch.cuda.current_stream(dev)
+    side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(prep_streams)))]
+    aer_st = torch.cuda.Stream(device=dev)
+    step_chunk = max(1, int(chunk) // nz)               # the record-memory rule of the docstring
+    where = [-1]                                        # the wavelength being worked on (named by a failure)
+    err = None
+    import gc
+    pause_gc = gc.isenabled() and not os.environ.get("SOS_SPECTRUM_KEEP_GC")
+    if pause_gc:
+        gc.disable()
+    try:
+        for c0 in range(0, len(mine), step_chunk):
+            idx = mine[c0:c0 + step_chunk]
+            plans = []
+            try:
+                t0 = time.perf_counter()
+                where[0] = idx[0]
+                for st in side + [aer_st]:
+                    st.wait_stream(main_st)
+                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st)
+                solved = []         # (plans, rec [K][nw][S][3][W], scal [K][nw][10+N] device) or ([pl], rec [K][S][3][W], fin)
+                nsub = max(1, min(int(parts), len(idx) // max(1, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32")))))
+                step = max(1, -(-len(idx) // nsub))
+                for s0 in range(0, len(idx), step):
+                    part = []
+                    for k, i in enumerate(idx[s0:s0 + step], s0):
+                        where[0] = i
+                        with torch.cuda.stream(side[k % len(side)]):
+                            pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
+                                          aer_at_wa=aer_wa.get(i))
+                            pl.writes_files = True
+                            pl.index = i
+                            plans.append(pl)
+                            pl.levels = pl.ctx.output_levels(pl.bins, alts)
+                        part.append(pl)
+                    for st in side:
+                        main_st.wait_stream(st)
+                    t1 = time.perf_counter()
+                    tm["prepare"] += t1 - t0
+                    groups = collections.OrderedDict()
+                    single = []
+                    for pl in part:
+                        b = pl.bins
+                        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor):
+                            single.append(pl)
+                            continue
+                        key = (pl.n, pl.ctx.smax, pl.ctx.os_nb, bool(pl.ctx._rsurf is not None), b["lp"])
+                        groups.setdefault(key, []).append(pl)
+                    for key, gp in groups.items():
+                        if len(gp) == 1:
+                            single.append(gp[0])
+                            continue
+                        where[0] = gp[0].index
+                        table = ContextTable([pl.ctx for pl in gp])
+                        bins, cob, seg = concat_bins([pl.bins for pl in gp])
+                        levels = concat_levels([pl.levels for pl in gp])
+                        aik = _upload(torch.from_numpy(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp])), dev)
+                        rec, scal = solve_spectrum_levels(table, bins, cob, seg, aik, levels, order=None)
+                        solved.append((gp, rec, scal))
+                    for pl in single:
+                        where[0] = pl.index
+                        try:
+                            rec, fin = pl.ctx.solve_band_levels(pl.bins, pl.levels, pl.aik, tdifmug=pl.tdifmug, reduce=False)
+                        except SosBinError as e:
+                            raise SosProcError("SOS_OS: wavelength %d (%r microns): %s" % (pl.index, pl.p["wa_simu"], e), ier=-1)
+                        solved.append(([pl], rec, fin))
+                    t0 = time.perf_counter()
+                    tm["solve_launch"] += t0 - t1
+                t2 = time.perf_counter()
+                # --- one copy of the band scalars of all launches (waits for the solves), then the K azimuth recompositions of
+                # every wavelength back to back
+                dev_scal = [s for _, _, s in solved if isinstance(s, torch.Tensor)]
+                scal_all = torch.cat([s.reshape(-1) for s in dev_scal]).cpu().numpy() if dev_scal else None
+                t3 = time.perf_counter()
+                tm["wait"] += t3 - t2
+                todo, pos = [], 0                               # (plan, slot, record, finish_scalars, segment)
+                for gp, rec, scal in solved:
+                    if not isinstance(scal, torch.Tensor):       # per-wavelength path: segment k = altitude k
+                        todo += [(gp[0], k, rec[k], scal, k) for k in range(nz)]
+                        continue
+                    sw = scal.shape[2]
+                    blk = scal_all[pos:pos + nz * len(gp) * sw].reshape(nz, len(gp), sw)
+                    pos += nz * len(gp) * sw
+                    fins = [_dist.finish_scalars(blk[k]) for k in range(nz)]
+                    for g, pl in enumerate(gp):
+                        if any(fins[k]["min_orders"][g] < 0 for k in range(nz)):
+                            where[0] = pl.index
+                            raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
+                                               "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
+                        todo += [(pl, k, rec[k][g], fins[k], g) for k in range(nz)]
+                outs = [_trphi_launch(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
+                        for pl, _, r, f, g in todo]
+                flat = torch.cat([o.reshape(-1) for o in outs]).cpu().numpy()
+                t4 = time.perf_counter()
+                tm["trphi"] += t4 - t3
+                pos = 0
+                blocks = _zero_pages((len(outs), 2, 7, 361, 81))
+                for j, ((pl, k, r, f, g), o) in enumerate(zip(todo, outs)):
+                    where[0] = pl.index
+                    if results[pl.index] is None:
+                        results[pl.index] = [None] * nz
+                    results[pl.index][k] = _finish(pl, flat[pos:pos + o.numel()].reshape(o.shape), r, f, g, blocks[j])
+                    nrows[pl.index] = len(pl.rows)
+                    pos += o.numel()
+                tm["finish"] += time.perf_counter() - t4
+            finally:
+                _aer.drop_prefetched_size_integrals()
+                _abs.drop_prefetched_gas_tables()
+                for st in side + [aer_st]:
+                    st.synchronize()
+                main_st.synchronize()                             # the table launches read every context's operators
+                for pl in plans:
+                    pl.ctx.close()
+    except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
+        err = e
+    finally:
+        if pause_gc:
+            gc.enable()
+    if world > 1:
+        # a call failing on one rank must not leave the others waiting in the gather: the ranks agree first (one integer)
+        bad = _first_failed_index(where[0] if err is not None else -1, device)
+        if bad >= 0:
+            if err is not None:
+                raise SosProcError("sos_spectrum_levels: wavelength %d failed: %s" % (where[0], err),
+                                   ier=getattr(err, "ier", 1)) from err
+            raise SosProcError("sos_spectrum_levels: wavelength %d failed on another rank" % bad, ier=-1)
+    if err is not None:
+        raise err
+    if timings is not None:
+        timings.update(tm)
+    if world > 1 and gather:
+        _gather_levels_results(results, mine, nrows, world, nz)
+    return results
+
+
+def _gather_levels_results(results, mine, nrows, world, nz):
+    """_gather_results for lists of K 23-tuples per wavelength (all_gather_object of the compacted tuples)."""
+    import torch.distributed as dist
+    part = [(i, [_compact_outputs(t, nrows[i]) for t in results[i]]) for i in mine]
+    parts = [None] * world
+    dist.all_gather_object(parts, part)
+    todo = [(i, cs) for pr in parts for i, cs in pr if results[i] is None]
+    blocks = _zero_pages((len(todo) * nz, len(_TABLE_NAMES), 361, 81)) if todo else None
+    for j, (i, cs) in enumerate(todo):
+        results[i] = [_expand_outputs(c, blocks[j * nz + k]) for k, c in enumerate(cs)]
 
 
 def write_trans_file(path, tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):

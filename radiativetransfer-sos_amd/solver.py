@@ -111,6 +111,25 @@ def output_levels_host(zprof, altitudes):
     return jout, zz
 
 
+def host_output_levels(bins, altitudes):
+    """The `levels` of SosContext.output_levels for bins of upload_bins (host level altitudes zprof_host, or none: standard
+    output only), on the device of bins["prof"]: output_levels_host, TAUOUT from the uploaded H as run_sos computes it for
+    one altitude (SOS.F:567-581)."""
+    alts = [float(z) for z in altitudes]
+    nz, nb, d = len(alts), bins["nb"], bins["prof"].device
+    if bins.get("zprof_host") is None and any(z != -1.0 for z in alts):
+        raise ValueError("output altitudes need the bins' level altitudes (make_profiles, or upload_bins with zprof)")
+    zp = bins.get("zprof_host")
+    jh, zh = output_levels_host(zp, alts) if zp is not None else (np.zeros((nz, nb), np.int32), np.zeros((nz, nb)))
+    h = bins["prof"][:, 0, :].cpu().numpy()
+    th = np.zeros((nz, nb))
+    for k in range(nz):
+        for b in range(nb):
+            j, zzv = int(jh[k, b]), float(zh[k, b])
+            th[k, b] = h[b, 0] if alts[k] == -1.0 else (1 - zzv) * h[b, j - 1] + zzv * h[b, j]
+    return dict(nz=nz, jout=_dev_i32(jh, d), zz=_dev_f64(zh, d), tauout=_dev_f64(th, d))
+
+
 class SosContext:
     """Everything SOS_OS needs that does not depend on the CKD bin (angles, phase-matrix expansion,
     surface), resident on one GPU, with the Fourier kernels of every order precomputed
@@ -326,17 +345,7 @@ class SosContext:
                                                        _ptr(bins["nt"]), nz, (C.c_double * nz)(*alts), _ptr(jout), _ptr(zz),
                                                        _ptr(tauout), self._stream()), "sosgpu_output_levels")
             return dict(nz=nz, jout=jout, zz=zz, tauout=tauout)
-        if bins.get("zprof_host") is None and any(z != -1.0 for z in alts):
-            raise ValueError("output altitudes need the bins' level altitudes (make_profiles, or upload_bins with zprof)")
-        zp = bins.get("zprof_host")
-        jh, zh = output_levels_host(zp, alts) if zp is not None else (np.zeros((nz, nb), np.int32), np.zeros((nz, nb)))
-        h = bins["prof"][:, 0, :].cpu().numpy()
-        th = np.zeros((nz, nb))
-        for k in range(nz):
-            for b in range(nb):
-                j, zzv = int(jh[k, b]), float(zh[k, b])
-                th[k, b] = h[b, 0] if alts[k] == -1.0 else (1 - zzv) * h[b, j - 1] + zzv * h[b, j]
-        return dict(nz=nz, jout=_dev_i32(jh, d), zz=_dev_f64(zh, d), tauout=_dev_f64(th, d))
+        return host_output_levels(bins, alts)
 
     def solve_levels(self, bins, levels, out=None):
         """One solve for the K output levels of output_levels (sosgpu_os_solve_levels).  Returns dict(rec[K][nb][smax+1][3][W],
@@ -561,19 +570,68 @@ def solve_spectrum(table, bins, ctx_of_bin, seg, aik, out=None, order="cost"):
     # that the long bins start first and the launch does not end on them; the bins stay where they are.  None: as given.
     # (Measured, scripts/spectrum_stream_bench.py / spectrum_bench.py: +4 % on real level grids, 160 x 25 bins; -5 % for the
     #  LDS-resident kernel at NT = 30, where neighbouring bins of one wavelength share their operators in L2 -- not applied there.)
-    ord_t = None
-    if isinstance(order, str) and order == "cost" and bins["lp"] <= 64:
-        order = None
-    if isinstance(order, str) and order == "cost":
-        htot = bins["prof"][:, 0, :].gather(1, bins["nt"].long().clamp(min=0, max=bins["lp"] - 1)[:, None])[:, 0]
-        ord_t = torch.argsort(htot, descending=True, stable=True).to(torch.int32)
-    elif order is not None:
-        ord_t = _dev_i32(order, cx.device)
+    ord_t = _spectrum_order(cx, bins, order)
     capi.check(capi.lib().sosgpu_os_solve_multi(cx._h, _ptr(table.table), _ptr(ctx_of_bin), _ptr(ord_t), bins["nb"], bins["lp"],
                                                 _ptr(bins["nt"]), _ptr(bins["iborm"]), _ptr(bins["prof"]),
                                                 _ptr(bins["jout"]), _ptr(bins["zz"]), _ptr(out["rec"]), _ptr(out["norders"]),
                                                 _ptr(out["iglast"]), _ptr(out["flux"]), cx._stream()), "sosgpu_os_solve_multi")
     return cx.aggregate(out, aik, seg=seg, scal=bins.get("scal"))
+
+
+def concat_levels(levels_list):
+    """Concatenate the output slots of per-wavelength bin dicts (SosContext.output_levels of each, all with the same altitude
+    count K) in the bin order of concat_bins(bins_list): jout / zz / tauout [K][nb_total].  The levels stay valid on the padded
+    level axis of concat_bins (the padding appends levels past every bin's NT; jout <= NT).  Returns the `levels` of
+    solve_spectrum_levels."""
+    nz = levels_list[0]["nz"]
+    if any(lv["nz"] != nz for lv in levels_list):
+        raise ValueError("every wavelength must have the same number of output altitudes")
+    parts = [lv for lv in levels_list if lv["jout"] is not None]          # (a batch without bins has no tensors)
+    if not parts:
+        return dict(nz=nz, jout=None, zz=None, tauout=None)
+    cat = lambda k: torch.cat([lv[k] for lv in parts], dim=1).contiguous()
+    return dict(nz=nz, jout=cat("jout"), zz=cat("zz"), tauout=cat("tauout"))
+
+
+def _spectrum_order(cx, bins, order):
+    """The workgroup order of a table launch (solve_spectrum): a device int32 permutation, or None."""
+    if isinstance(order, str) and order == "cost" and bins["lp"] <= 64:
+        order = None
+    if isinstance(order, str) and order == "cost":
+        htot = bins["prof"][:, 0, :].gather(1, bins["nt"].long().clamp(min=0, max=bins["lp"] - 1)[:, None])[:, 0]
+        return torch.argsort(htot, descending=True, stable=True).to(torch.int32)
+    if order is not None:
+        return _dev_i32(order, cx.device)
+    return None
+
+
+def solve_spectrum_levels(table, bins, ctx_of_bin, seg, aik, levels, out=None, order="cost"):
+    """solve_spectrum for K output altitudes: ONE launch of the fused solver over the bins of many wavelengths, every bin with
+    K output slots (sosgpu_os_solve_multi_levels), then one segmented SOS_AGGREGATE per altitude with that altitude's TAUOUT in
+    scal[:, 3] (as SosContext.solve_band_levels).  bins / ctx_of_bin / seg from concat_bins, levels from concat_levels,
+    aik[nb] device tensor in the same order; order as in solve_spectrum.  Returns (rec[K][nwavelengths][smax+1][3][W],
+    scal[K][nwavelengths][10+N]) device tensors; no synchronisation.  Slot k of wavelength g equals solve_spectrum's record of
+    g with that altitude's profile, bit for bit."""
+    cx = table.ctxs[0]
+    nz, nb = levels["nz"], bins["nb"]
+    if out is None:
+        out = cx.alloc_outputs(nb, zero=False)
+        out["rec"] = torch.empty((nz, nb, cx.smax + 1, 3, cx.w), dtype=torch.float64, device=cx.device)
+    ord_t = _spectrum_order(cx, bins, order)
+    capi.check(capi.lib().sosgpu_os_solve_multi_levels(cx._h, _ptr(table.table), _ptr(ctx_of_bin), _ptr(ord_t), nb, bins["lp"],
+                                                       _ptr(bins["nt"]), _ptr(bins["iborm"]), _ptr(bins["prof"]), nz,
+                                                       _ptr(levels["jout"]), _ptr(levels["zz"]), _ptr(out["rec"]),
+                                                       _ptr(out["norders"]), _ptr(out["iglast"]), _ptr(out["flux"]),
+                                                       cx._stream()), "sosgpu_os_solve_multi_levels")
+    base = bins.get("scal")
+    recs, scals = [], []
+    for k in range(nz):
+        sc = torch.zeros((nb, 4), dtype=torch.float64, device=cx.device) if base is None else _dev_f64(base, cx.device).clone()
+        sc[:, 3] = levels["tauout"][k]
+        r, s = cx.aggregate(dict(rec=out["rec"][k], norders=out["norders"], flux=out["flux"]), aik, seg=seg, scal=sc)
+        recs.append(r)
+        scals.append(s)
+    return torch.stack(recs), torch.stack(scals)
 
 
 def solve_many(items, n_streams=16):

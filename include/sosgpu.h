@@ -233,7 +233,9 @@ int  sosgpu_reduce(sosgpu_ctx *cx, void *comm, int nseg, double *d_buf, void *st
  *                             sosgpu_set_surface_matrices with imat_surf = 1)
  *  d_il[N(N+1)/2]             series length IL of each angle pair (I1 = 1..N, I2 = 1..I1), SOS_GLITTER.F:676
  *  d_e[N(N+1)/2][os_nm+1]     Fourier coefficients E(0:IL) of the facet function, zero beyond IL
- * Synchronous with respect to the host arrays; kernels run on `stream`. */
+ * Synchronous with respect to the host arrays; kernels run on `stream`.
+ * SOSGPU_E_ARG, before any device work, unless 2 <= OS_NS, OS_NB + OS_NS <= OS_NM <= 2000 and the reflection kernel's
+ * work area fits the 160 KiB of LDS of a workgroup: 8 (OS_NM + 1 + 12 (OS_NS + 1)) <= 163840 bytes. */
 int  sosgpu_glitter(int device, int n, const double *mu, const double *chr, double wind, double ind,
                     int os_nb, int os_ns, int os_nm, float *d_rsurf, int32_t *d_il, double *d_e, void *stream);
 /* Host helper used by sosgpu_glitter, exposed for parity tests: SOS_MAT_FRESNEL (SOS_SURFACE.F:1235-1603)
@@ -266,7 +268,8 @@ int  sosgpu_trphi(sosgpu_ctx *cx, int nf, const double *d_rec, double tau, doubl
  * (src/SOS_SURFACE.F:2503) for -SURF.Type 3..7, no temporary files: Fourier reflection matrices of the land surface,
  *  d_rsurf[os_nb+1][9][N][N]  REAL*4, reference surface-file record order (feed to sosgpu_set_surface_matrices).
  * Host inputs mu[n], chr[n]; ind = surface refractive index (BPDF types).  *ier_out (host) = 0, or -1 when the Roujean BRDF
- * goes negative for some geometry (the reference's IER = -1, SOS_ROUJEAN.F:548).  Synchronous. */
+ * goes negative for some geometry (the reference's IER = -1, SOS_ROUJEAN.F:548).  Synchronous.  The bounds on OS_NB, OS_NS,
+ * OS_NM are those of sosgpu_glitter. */
 int  sosgpu_land_surface(int device, const sosgpu_land *land, int n, const double *mu, const double *chr, double ind,
                          int os_nb, int os_ns, int os_nm, float *d_rsurf, int32_t *ier_out, void *stream);
 

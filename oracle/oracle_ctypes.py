@@ -15,15 +15,16 @@ _lib = None
 
 
 def build():
-    """Compile the C restatement (and, when /root/reference is present, oracle/_ref)."""
+    """Compile the C restatement (and, when the reference sources are present, oracle/_ref)."""
     subprocess.check_call(["make", "-s", "-C", HERE, "all"])
 
 
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO):
-            build()
+        # the library is git-ignored but may be carried along with a tree: make is a no-op when it is up to date and
+        # rebuilds one that is older than its sources (and so may lack symbols)
+        subprocess.check_call(["make", "-s", "-C", HERE, SO])
         _lib = C.CDLL(SO)
         _lib.sos_oracle_os.restype = C.c_int
         _lib.sos_oracle_profile_rescale.restype = C.c_int
@@ -150,6 +151,64 @@ def glitter(rmu, chr_, wind, ind, os_nb, os_ns, os_nm):
                              C.c_int(os_nm), out.ctypes.data_as(C.c_void_p), il.ctypes.data_as(C.c_void_p),
                              e.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p))
     return dict(rsurf=out, il=il, e=e, coef=coef)
+
+
+def _margins(fn, k):
+    m = (C.c_double * k)()
+    fn(m)
+    return np.array(m[:])
+
+
+def glitter_margin():
+    """Tie audit of the last glitter() call: min |tested / threshold - 1| of the per-level 1e-4 test, of the 1e-3 closure
+    that sets IL and of the 1 % bisection test (1e300 where a test never ran)."""
+    return _margins(lib().sos_oracle_quad_margin, 3)
+
+
+def land(isurf, rmu, chr_, k0, k1, k2, coef_c, ind, os_nb, os_ns, os_nm):
+    """Land-surface matrices (SOS_ROUJEAN / SOS_SURFACE_BPDF / SOS_BPDF_AJOUT_BRDF) for isurf 3, 4, 5, 7: dict(rsurf
+    float32[os_nb+1][9][N][N], ier (0, or -1: negative Roujean BRDF), il_nn[N][N], e_nn[N][N][os_nb+1])."""
+    n = len(rmu)
+    a_mu, p_mu = _d(rmu)
+    a_ch, p_ch = _d(chr_)
+    out = np.zeros((os_nb + 1, 9, n, n), dtype=np.float32)
+    il = np.zeros((n, n), dtype=np.int32)
+    e = np.zeros((n, n, os_nb + 1))
+    lib().sos_oracle_land.restype = C.c_int
+    ier = lib().sos_oracle_land(C.c_int(int(isurf)), C.c_int(n), p_mu, p_ch, C.c_double(k0), C.c_double(k1), C.c_double(k2),
+                                C.c_double(coef_c), C.c_double(ind), C.c_int(os_nb), C.c_int(os_ns), C.c_int(os_nm),
+                                out.ctypes.data_as(C.c_void_p), il.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p))
+    return dict(rsurf=out, ier=ier, il_nn=il, e_nn=e)
+
+
+def land_margin():
+    """Tie audit of the last land() call: Roujean B1 against 1e-3, B1 against the previous B1, then the three of the
+    Maignan quadrature as glitter_margin()."""
+    return _margins(lib().sos_oracle_land_margin, 5)
+
+
+def calc_f_roujean(k0, k1, k2, c1, c2, phi):
+    lib().sos_oracle_calc_f_roujean.restype = C.c_double
+    return lib().sos_oracle_calc_f_roujean(*[C.c_double(x) for x in (k0, k1, k2, c1, np.sqrt(1 - c1 * c1), c2,
+                                                                      np.sqrt(1 - c2 * c2), phi)])
+
+
+def trphi_land(rmu, rec, tau, tauout, phi, *, igli=0, n0=1, wind=0.0, ind_surf=1.34, ifresnel=0, ipolar=1, isurf=0,
+               k0=0.0, k1=0.0, k2=0.0, coef_c=0.0):
+    """SOS_TRPHI with the direct term of a land surface.  Returns dict(out=[XIT, XQT, XUT, ANGDIFF], cosdif[W] (the cosine
+    ANGDIFF is the acos of), pre[3][W] (XIT, XQT, XUT before the zeroing thresholds))."""
+    n = len(rmu)
+    w = 2 * n + 1
+    a_mu, p_mu = _d(rmu)
+    a_rec, p_rec = _d(rec)
+    outs = [np.zeros(w) for _ in range(5)]
+    pre = np.zeros((3, w))
+    lib().sos_oracle_trphi_land(C.c_int(n), p_mu, C.c_int(a_rec.shape[0]), p_rec, C.c_double(tau), C.c_double(tauout),
+                                C.c_double(phi), C.c_int(igli), C.c_int(n0), C.c_double(wind), C.c_double(ind_surf),
+                                C.c_int(ifresnel), C.c_int(ipolar), C.c_int(int(isurf)), C.c_double(k0), C.c_double(k1),
+                                C.c_double(k2), C.c_double(coef_c), *[o.ctypes.data_as(C.c_void_p) for o in outs],
+                                pre.ctypes.data_as(C.c_void_p))
+    return dict(out=outs[:4], cosdif=outs[4], pre=pre)
 
 
 def trphi(rmu, rec, tau, tauout, phi, *, igli=0, n0=1, wind=0.0, ind_surf=1.34, ifresnel=0, ipolar=1):

@@ -38,34 +38,46 @@ static double calcg(double cs12, double c12, double s12, double sig, double phi)
     return x * x * exp(-(x - 1) / sig);
 }
 
-/* SOS_GSF for one pair (mu1 = RMU(I1), mu2 = RMU(I2)).  e[0..os_nm]; returns IL. */
-int sos_oracle_gsf_pair(double mu1, double mu2, double sig, int os_nm, double *e)
+/* Tie audit of the data-dependent stops of the facet quadrature (SOS_GSF and SOS_GSF_MAIGNAN share it): the smallest
+ * |tested value / threshold - 1| seen since the last reset, for [0] the per-level 1e-4 test (:666), [1] the 1e-3 series
+ * closure that sets IL (:677) and [2] the 1 % test of the bisection (:596).  Reset by sos_oracle_glitter and
+ * sos_oracle_land; a direct caller of sos_oracle_gsf_pair resets it itself. */
+static double quad_margin[3] = {1e300, 1e300, 1e300};
+void sos_oracle_quad_margin_reset(void) { quad_margin[0] = quad_margin[1] = quad_margin[2] = 1e300; }
+void sos_oracle_quad_margin(double *m3) { m3[0] = quad_margin[0]; m3[1] = quad_margin[1]; m3[2] = quad_margin[2]; }
+static void audit(int k, double tested, double threshold)
+{
+    double m = fabs(tested / threshold - 1.);
+    if (m < quad_margin[k]) quad_margin[k] = m;   /* NaN (0/0) compares false: it is no tie */
+}
+
+/* The azimuth quadrature of SOS_GSF (SOS_GLITTER.F:523-683) over a facet function g(ctx, phi); SOS_GSF_MAIGNAN
+ * (SOS_SURFACE_BPDF.F:1305-1600) is the same routine around SOS_CALCG_MAIGNAN.  e[0..os_nm]; returns IL. */
+int sos_oracle_gsf_quad(sos_oracle_facet_fn g, const void *ctx, int os_nm, double *e)
 {
     const double pi = acos(-1.0);
     static double u[PH_NU + 1];
-    double c1 = mu1, s1 = sqrt(1 - c1 * c1), c2 = mu2, s2 = sqrt(1 - c2 * c2);
-    double c12 = c1 * c2, s12 = s1 * s2, cs12 = (c1 + c2);
     double gmax, gmin, phib, q, t1 = 0., z, y, x;
     int i, is, il;
-    cs12 = .5 * cs12 * cs12;
-    u[0] = gmax = calcg(cs12, c12, s12, sig, 0.0);
-    u[PH_NU] = gmin = calcg(cs12, c12, s12, sig, pi);
+    u[0] = gmax = g(ctx, 0.0);
+    u[PH_NU] = gmin = g(ctx, pi);
     x = PH_TEST * gmin;
     if (x >= gmax) { /* :568-578 */
         phib = pi;
         q = pi / PH_NU;
-        for (i = 1; i <= PH_NU; i++) u[i] = calcg(cs12, c12, s12, sig, q * i);
+        for (i = 1; i <= PH_NU; i++) u[i] = g(ctx, q * i);
     } else { /* bisection :586-638 */
-        double phi1 = 0, phi2 = pi, g;
+        double phi1 = 0, phi2 = pi, gb;
         for (;;) {
             phib = .5 * (phi1 + phi2);
-            g = calcg(cs12, c12, s12, sig, phib);
-            x = PH_TEST * g;
+            gb = g(ctx, phib);
+            x = PH_TEST * gb;
+            audit(2, fabs(x - gmax), (double).01f * gmax);
             if (fabs(x - gmax) < (double).01f * gmax) break;
             if (x <= gmax) phi2 = phib; else phi1 = phib;
         }
         q = phib / PH_NU;
-        for (i = 1; i <= PH_NU; i++) u[i] = calcg(cs12, c12, s12, sig, q * i);
+        for (i = 1; i <= PH_NU; i++) u[i] = g(ctx, q * i);
         gmin = u[PH_NU];
     }
     il = os_nm;
@@ -83,15 +95,34 @@ int sos_oracle_gsf_pair(double mu1, double mu2, double sig, int os_nm, double *e
             }
             y = 2 * y / ia;
             xt = fabs(z - y) / z;
+            audit(0, xt, (double).0001f);
             if (xt < (double).0001f) break;
             z = .5 * (y + z);
         }
         e[is] = phib * z / pi;
         if (is == 0) { t1 = e[0]; continue; }
         t1 = t1 + 2 * e[is];
+        audit(1, fabs(t1 - gmax) / gmax, (double).001f);
         if (!(fabs(t1 - gmax) / gmax > (double).001f)) { il = is; break; }
     }
     return il;
+}
+
+struct coxmunk { double cs12, c12, s12, sig; };
+static double coxmunk_g(const void *p, double phi)
+{
+    const struct coxmunk *c = p;
+    return calcg(c->cs12, c->c12, c->s12, c->sig, phi);
+}
+
+/* SOS_GSF for one pair (mu1 = RMU(I1), mu2 = RMU(I2)).  e[0..os_nm]; returns IL. */
+int sos_oracle_gsf_pair(double mu1, double mu2, double sig, int os_nm, double *e)
+{
+    double c1 = mu1, s1 = sqrt(1 - c1 * c1), c2 = mu2, s2 = sqrt(1 - c2 * c2);
+    struct coxmunk c;
+    c.c12 = c1 * c2; c.s12 = s1 * s2; c.cs12 = (c1 + c2); c.sig = sig;
+    c.cs12 = .5 * c.cs12 * c.cs12;
+    return sos_oracle_gsf_quad(coxmunk_g, &c, os_nm, e);
 }
 
 /* SOS_MAT_FRESNEL: alpha,beta,gamma,zeta[0..os_ns] after the 4(E15.8) text round trip.
@@ -270,29 +301,18 @@ static void noyaux_fresnel(double rmu1, double rmu2, int os_ns, const double *al
     free(psl); free(rsl); free(tsl);
 }
 
-/* SOS_GLITTER end to end.  out: REAL*4 [os_nb+1][9][N][N] in GLITTER-file record order
- * out[s][ab][(J-1)*N + (I-1)] = P_ab(I,J) (SOS_SURFACE.F:2404-2412).
- * il_out (optional): IL per pair in (I1, I2<=I1) order; e_out (optional): [npairs][os_nm+1]. */
-int sos_oracle_glitter(int n, const double *mu, const double *chr, double wind, double ind,
-                       int os_nb, int os_ns, int os_nm, float *out, int *il_out, double *e_out,
-                       double *coef_out /* [4][os_ns+1] alpha,beta,gamma,zeta or NULL */)
+/* SOS_MAT_REFLEXION (:1708-1973) + SOS_MISE_FORMAT (:2307-2443) for every pair (I >= J): il[npairs] and e[npairs][os_nm+1]
+ * are the azimuth series of the pairs (entries above IL are not read), coefs = alpha,beta,gamma,zeta [4][os_ns+1].
+ * out: REAL*4 [os_nb+1][9][N][N] with out[s][ab][(J-1)*N + (I-1)] = P_ab(I,J) (SOS_SURFACE.F:2404-2412). */
+void sos_oracle_mat_reflexion(int n, const double *mu, double coef, int os_nb, int os_ns, int os_nm, const double *coefs,
+                              const int *il, const double *e, float *out)
 {
-    const double sig = sos_oracle_sigma2(wind);
-    const double coef = (1. / sig);
-    double *alpha = calloc(os_ns + 1, sizeof(double)), *beta = calloc(os_ns + 1, sizeof(double));
-    double *gamma = calloc(os_ns + 1, sizeof(double)), *zeta = calloc(os_ns + 1, sizeof(double));
+    const double *alpha = coefs, *beta = coefs + (os_ns + 1), *gamma = coefs + 2 * (os_ns + 1), *zeta = coefs + 3 * (os_ns + 1);
     double *g = calloc(os_nm + os_ns + os_nb + 2, sizeof(double));
     double *kb = calloc((size_t)12 * (os_ns + 1), sizeof(double));
     double *bp = kb, *gr = kb + 2 * (os_ns + 1), *gt = kb + 4 * (os_ns + 1), *arr = kb + 6 * (os_ns + 1);
     double *art = kb + 8 * (os_ns + 1), *att = kb + 10 * (os_ns + 1);
     int i, j, is, k, pair = 0;
-    sos_oracle_mat_fresnel(n, mu, chr, ind, os_ns, alpha, beta, gamma, zeta);
-    if (coef_out) {
-        memcpy(coef_out, alpha, sizeof(double) * (os_ns + 1));
-        memcpy(coef_out + (os_ns + 1), beta, sizeof(double) * (os_ns + 1));
-        memcpy(coef_out + 2 * (os_ns + 1), gamma, sizeof(double) * (os_ns + 1));
-        memcpy(coef_out + 3 * (os_ns + 1), zeta, sizeof(double) * (os_ns + 1));
-    }
 #define BPk(K, c) bp[(K)*2 + (c)-1]
 #define GRk(K, c) gr[(K)*2 + (c)-1]
 #define GTk(K, c) gt[(K)*2 + (c)-1]
@@ -302,10 +322,8 @@ int sos_oracle_glitter(int n, const double *mu, const double *chr, double wind, 
 #define OUT(s, ab, I, J) out[(((size_t)(s)*9 + (ab)) * n + ((J)-1)) * n + ((I)-1)]
     for (i = 1; i <= n; i++) {
         for (j = 1; j <= i; j++, pair++) {
-            int lim = sos_oracle_gsf_pair(mu[i - 1], mu[j - 1], sig, os_nm, g);
-            if (il_out) il_out[pair] = lim;
-            if (e_out) { memset(e_out + (size_t)pair * (os_nm + 1), 0, sizeof(double) * (os_nm + 1)); memcpy(e_out + (size_t)pair * (os_nm + 1), g, sizeof(double) * (lim + 1)); }
-            for (k = lim + 1; k <= os_nm; k++) g[k] = 0.;
+            int lim = il[pair];
+            for (k = 0; k <= os_nm; k++) g[k] = (k <= lim) ? e[(size_t)pair * (os_nm + 1) + k] : 0.;
             noyaux_fresnel(mu[i - 1], mu[j - 1], os_ns, alpha, beta, gamma, zeta, bp, gr, gt, arr, art, att);
             for (is = 0; is <= os_nb; is++) { /* SOS_MAT_REFLEXION :1864-1933 */
                 double x = coef * g[is] / 4., y;
@@ -342,6 +360,41 @@ int sos_oracle_glitter(int n, const double *mu, const double *chr, double wind, 
             }
         }
     }
-    free(alpha); free(beta); free(gamma); free(zeta); free(g); free(kb);
+    free(g); free(kb);
+#undef BPk
+#undef GRk
+#undef GTk
+#undef ARRk
+#undef ARTk
+#undef ATTk
+#undef OUT
+}
+
+/* SOS_GLITTER end to end.  out: REAL*4 [os_nb+1][9][N][N] in GLITTER-file record order
+ * out[s][ab][(J-1)*N + (I-1)] = P_ab(I,J) (SOS_SURFACE.F:2404-2412).
+ * il_out (optional): IL per pair in (I1, I2<=I1) order; e_out (optional): [npairs][os_nm+1]. */
+int sos_oracle_glitter(int n, const double *mu, const double *chr, double wind, double ind,
+                       int os_nb, int os_ns, int os_nm, float *out, int *il_out, double *e_out,
+                       double *coef_out /* [4][os_ns+1] alpha,beta,gamma,zeta or NULL */)
+{
+    const double sig = sos_oracle_sigma2(wind);
+    const int npairs = n * (n + 1) / 2;
+    double *coefs = calloc((size_t)4 * (os_ns + 1), sizeof(double));
+    int *il = calloc(npairs, sizeof(int));
+    double *e = calloc((size_t)npairs * (os_nm + 1), sizeof(double));
+    double *g = calloc(os_nm + 1, sizeof(double));
+    int i, j, pair = 0;
+    sos_oracle_quad_margin_reset();
+    sos_oracle_mat_fresnel(n, mu, chr, ind, os_ns, coefs, coefs + (os_ns + 1), coefs + 2 * (os_ns + 1), coefs + 3 * (os_ns + 1));
+    if (coef_out) memcpy(coef_out, coefs, sizeof(double) * 4 * (os_ns + 1));
+    for (i = 1; i <= n; i++)
+        for (j = 1; j <= i; j++, pair++) {
+            il[pair] = sos_oracle_gsf_pair(mu[i - 1], mu[j - 1], sig, os_nm, g);
+            memcpy(e + (size_t)pair * (os_nm + 1), g, sizeof(double) * (il[pair] + 1));   /* zero beyond IL */
+        }
+    sos_oracle_mat_reflexion(n, mu, (1. / sig), os_nb, os_ns, os_nm, coefs, il, e, out);
+    if (il_out) memcpy(il_out, il, sizeof(int) * npairs);
+    if (e_out) memcpy(e_out, e, sizeof(double) * (size_t)npairs * (os_nm + 1));
+    free(coefs); free(il); free(e); free(g);
     return 0;
 }

@@ -69,6 +69,17 @@ int sos_oracle_aggregate(int nb, int fmax, int w, const int *nf, const double *a
 double sos_oracle_sigma2(double wind);
 /* SOS_GSF for one pair (SOS_GLITTER.F:523-683): e[0..os_nm], returns IL */
 int sos_oracle_gsf_pair(double mu1, double mu2, double sig, int os_nm, double *e);
+/* the quadrature of SOS_GSF over any facet function g(ctx, phi): shared by SOS_GSF and SOS_GSF_MAIGNAN */
+typedef double (*sos_oracle_facet_fn)(const void *ctx, double phi);
+int sos_oracle_gsf_quad(sos_oracle_facet_fn g, const void *ctx, int os_nm, double *e);
+/* Tie audit of that quadrature since the last reset (sos_oracle_glitter and sos_oracle_land reset it): min
+ * |tested / threshold - 1| of m3[0] the per-level 1e-4 test, m3[1] the 1e-3 closure that sets IL, m3[2] the 1 % bisection test */
+void sos_oracle_quad_margin_reset(void);
+void sos_oracle_quad_margin(double *m3);
+/* SOS_MAT_REFLEXION + SOS_MISE_FORMAT (SOS_SURFACE.F:1708-1973, 2307-2443) from the series il[npairs], e[npairs][os_nm+1]
+ * and the Fresnel expansion coefs[4][os_ns+1]; out REAL*4 [os_nb+1][9][N][N] */
+void sos_oracle_mat_reflexion(int n, const double *mu, double coef, int os_nb, int os_ns, int os_nm, const double *coefs,
+                              const int *il, const double *e, float *out);
 /* SOS_MAT_FRESNEL incl. the 4(E15.8) round trip (SOS_SURFACE.F:1235-1603) */
 void sos_oracle_mat_fresnel(int n, const double *mu, const double *chr, double ind, int os_ns,
                             double *alpha, double *beta, double *gamma, double *zeta);
@@ -82,6 +93,29 @@ void sos_oracle_polar(double xi, double xq, double xu, double *xan, double *tpol
 void sos_oracle_trphi(int n, const double *mu, int nf, const double *rec, double tau, double tauout, double phi,
                       int igli, int n0, double wind, double ind_surf, int ifresnel, int ipolar,
                       double *xit, double *xqt, double *xut, double *angdiff);
+
+/* as sos_oracle_trphi, plus the direct term of a land surface (isurf 0 none, 3, 4, 5, 7); optional cosdif[W] (the cosine
+ * behind ANGDIFF) and pre[3][W] (XIT, XQT, XUT before the zeroing thresholds) */
+void sos_oracle_trphi_land(int n, const double *mu, int nf, const double *rec, double tau, double tauout, double phi,
+                           int igli, int n0, double wind, double ind_surf, int ifresnel, int ipolar,
+                           int isurf, double k0, double k1, double k2, double coef_c,
+                           double *xit, double *xqt, double *xut, double *angdiff, double *cosdif, double *pre);
+
+/* ---- land surfaces (sos_land_oracle.c) ---- */
+double sos_oracle_calc_f_roujean(double k0, double k1, double k2, double c1, double s1, double c2, double s2, double phi);
+double sos_oracle_calcg_maignan(double c1, double c2, double s12, double phi, double coef_c);
+/* SOS_FSF_ROUJEAN for one ordered pair: e[0..os_nb], returns IL, sets *neg when the BRDF is negative somewhere; cs: optional
+ * table cos(is * (i * pi / 1024)) [os_nb+1][1025] */
+int sos_oracle_fsf_roujean_pair(double k0, double k1, double k2, double mu1, double mu2, int os_nb, const double *cs, double *e,
+                                int *neg);
+/* SOS_GSF_MAIGNAN for one pair: e[0..os_nm], returns IL */
+int sos_oracle_gsf_maignan_pair(double mu1, double mu2, double coef_c, int os_nm, double *e);
+/* SOS_ROUJEAN / SOS_SURFACE_BPDF / SOS_BPDF_AJOUT_BRDF end to end for isurf 3, 4, 5, 7: out REAL*4 [os_nb+1][9][N][N];
+ * optional il_nn[N*N], e_nn[N*N][os_nb+1]; returns 0 or -1 (negative Roujean BRDF, the reference's IER) */
+int sos_oracle_land(int isurf, int n, const double *mu, const double *chr, double k0, double k1, double k2, double coef_c,
+                    double ind, int os_nb, int os_ns, int os_nm, float *out, int *il_nn, double *e_nn);
+/* stop margins of the last sos_oracle_land call: Roujean B1 <= 1e-3, B1 < previous B1, then the three of the quadrature */
+void sos_oracle_land_margin(double *m5);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,9 @@
  * TEST INFRASTRUCTURE ONLY (see sos_oracle.h).
  *
  * Follows SOS_TRPHI (src/SOS_TRPHI.F:749-1243) with SOS_GLITTE (:1278), SOS_ANGLE (:1347), SOS_REFLEX
- * (:1433), SOS_MATRIC (:1505) and SOS_POLAR (:1843).  Land BRDF/BPDF direct terms (Roujean, Rondeaux,
- * Breon, Nadal, Maignan; :1047-1200) are outside the round-1 scope.
+ * (:1433), SOS_MATRIC (:1505) and SOS_POLAR (:1843).  The direct terms of the land models are carried by
+ * sos_oracle_trphi_land: Roujean (:1047-1076) and Rondeaux-Herman / Breon / Maignan (:1084-1136), with the model functions
+ * of sos_land_oracle.c.  Nadal (:1145-1200) is refused by the reference's own SOS_PROC and is not restated.
  */
 #include "sos_oracle.h"
 #include <math.h>
@@ -92,9 +93,10 @@ void sos_oracle_polar(double xi, double xq, double xu, double *xan, double *tpol
  *  rec [nf][3][W] aggregated Fourier records (I,Q,U); mu[n]; n0 (1-based solar index)
  *  outputs xit,xqt,xut,angdiff [W] (slot jj = 0: angdiff as the reference computes it from RMU(0)=0
  *  is not reproduced -- set to 0). */
-void sos_oracle_trphi(int n, const double *mu, int nf, const double *rec, double tau, double tauout, double phi,
-                      int igli, int n0, double wind, double ind_surf, int ifresnel, int ipolar,
-                      double *xit, double *xqt, double *xut, double *angdiff)
+static void trphi_core(int n, const double *mu, int nf, const double *rec, double tau, double tauout, double phi,
+                       int igli, int n0, double wind, double ind_surf, int ifresnel, int ipolar,
+                       int isurf, double k0, double k1, double k2, double coef_c,
+                       double *xit, double *xqt, double *xut, double *angdiff, double *cosdif_out, double *pre)
 {
     const double pi = acos(-1.0);
     const int W = 2 * n + 1;
@@ -103,8 +105,9 @@ void sos_oracle_trphi(int n, const double *mu, int nf, const double *rec, double
 #define RMU(j) ((j) > 0 ? mu[(j)-1] : -mu[-(j)-1])
     for (j = -n; j <= n; j++) { /* :884-891 */
         double cosdif;
-        if (j == 0) { angdiff[n] = 0.; continue; }
+        if (j == 0) { angdiff[n] = 0.; if (cosdif_out) cosdif_out[n] = 0.; continue; }
         cosdif = -c0 * RMU(j) + sin(acos(c0)) * sin(acos(RMU(j))) * cos(phi);
+        if (cosdif_out) cosdif_out[j + n] = cosdif;
         angdiff[j + n] = acos(cosdif) * 180.0 / pi;
     }
     for (j = 0; j < W; j++) { xit[j] = rec[0 * W + j]; xqt[j] = rec[1 * W + j]; xut[j] = rec[2 * W + j]; }
@@ -147,10 +150,58 @@ void sos_oracle_trphi(int n, const double *mu, int nf, const double *rec, double
             if (ipolar == 1) xqt[n0 + n] = xqt[n0 + n] + r12 * coef_sun * atj;
         }
     }
+    if (isurf >= 3) { /* Roujean BRDF, :1047-1076 */
+        for (j = 1; j <= n; j++) {
+            double c1 = mu[j - 1];
+            double atj = exp(-tau / c0) * exp(-(tau - tauout) / c1);
+            double f = sos_oracle_calc_f_roujean(k0, k1, k2, c0, sqrt(1. - c0 * c0), c1, sqrt(1. - c1 * c1), pi - phi);
+            xit[j + n] = xit[j + n] + atj * f / c1;
+        }
+    }
+    if (isurf == 4 || isurf == 5 || isurf == 7) { /* Rondeaux-Herman / Breon / Maignan BPDF, :1084-1136 */
+        for (j = 1; j <= n; j++) {
+            double c1 = mu[j - 1], p = 0., coskip, cosdif, r11, r12, r33, m11, m21, m31;
+            double atj = exp(-tau / c0) * exp(-(tau - tauout) / c1);
+            angle(c0, c1, phi, &coskip, &cosdif);
+            reflex(cosdif, ind_surf, &r11, &r12, &r33);
+            matric(coskip, r11, &r12, &m11, &m21, &m31);
+            if (isurf == 4) p = 1. / (4. * (1 + c1 / c0));
+            if (isurf == 5) p = 1. / (4. * c1);
+            if (isurf == 7) p = sos_oracle_calcg_maignan(c0, c1, sqrt(1. - c0 * c0) * sqrt(1. - c1 * c1), phi, coef_c) / (4. * c1);
+            xit[j + n] = xit[j + n] + m11 * atj * p;
+            if (ipolar == 1) {
+                xqt[j + n] = xqt[j + n] + m21 * atj * p;
+                xut[j + n] = xut[j + n] + m31 * atj * p;
+            }
+        }
+    }
+    if (pre) { /* values the thresholds below are applied to (tie audit of the callers) */
+        for (j = 0; j < 2 * n + 1; j++) { pre[j] = xit[j]; pre[(2 * n + 1) + j] = xqt[j]; pre[2 * (2 * n + 1) + j] = xut[j]; }
+    }
     for (j = -n; j <= n; j++) { /* :1212-1218 */
         if (xit[j + n] <= 1.e-99) xit[j + n] = 0.0;
         if (fabs(xqt[j + n]) < THRESHOLD_Q_U_NULL) xqt[j + n] = 0.0;
         if (fabs(xut[j + n]) < THRESHOLD_Q_U_NULL) xut[j + n] = 0.0;
     }
 #undef RMU
+}
+
+void sos_oracle_trphi(int n, const double *mu, int nf, const double *rec, double tau, double tauout, double phi,
+                      int igli, int n0, double wind, double ind_surf, int ifresnel, int ipolar,
+                      double *xit, double *xqt, double *xut, double *angdiff)
+{
+    trphi_core(n, mu, nf, rec, tau, tauout, phi, igli, n0, wind, ind_surf, ifresnel, ipolar, 0, 0., 0., 0., 0.,
+               xit, xqt, xut, angdiff, NULL, NULL);
+}
+
+/* SOS_TRPHI with the direct term of a land surface: isurf = 0 (none), 3 Roujean, 4 + Rondeaux-Herman, 5 + Breon,
+ * 7 + Maignan.  cosdif (optional, [W]): the cosine ANGDIFF is the acos of.  pre (optional, [3][W]): XIT, XQT, XUT
+ * before the zeroing thresholds (:1212-1218). */
+void sos_oracle_trphi_land(int n, const double *mu, int nf, const double *rec, double tau, double tauout, double phi,
+                           int igli, int n0, double wind, double ind_surf, int ifresnel, int ipolar,
+                           int isurf, double k0, double k1, double k2, double coef_c,
+                           double *xit, double *xqt, double *xut, double *angdiff, double *cosdif, double *pre)
+{
+    trphi_core(n, mu, nf, rec, tau, tauout, phi, igli, n0, wind, ind_surf, ifresnel, ipolar, isurf, k0, k1, k2, coef_c,
+               xit, xqt, xut, angdiff, cosdif, pre);
 }

@@ -1111,6 +1111,7 @@ extern "C" int sosgpu_glitter(int device, int n, const double *mu, const double 
 {
     if (n < 1 || n > 85 || !mu || !chr || !d_rsurf || !d_il || !d_e) return SOSGPU_E_ARG;
     if (os_nb < 0 || os_ns < 2 || os_nm < os_nb + os_ns || os_nm > 2000) return SOSGPU_E_ARG;
+    if (mat_reflexion_lds_bytes(os_ns, os_nm) > kLdsMaxBytes) return SOSGPU_E_ARG;    // k_mat_reflexion could not be launched
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
     if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
@@ -1166,6 +1167,7 @@ extern "C" int sosgpu_land_surface(int device, const sosgpu_land *land, int n, c
     if (!land || land->isurf < 3 || land->isurf > 7 || n < 1 || n > 85 || !mu || !chr || !d_rsurf) return SOSGPU_E_ARG;
     if (land->isurf == 6) return SOSGPU_E_UNSUPPORTED;               // Nadal: refused by the reference's SOS_PROC as well
     if (os_nb < 0 || os_ns < 2 || os_nm < os_nb + os_ns || os_nm > 2000) return SOSGPU_E_ARG;
+    if (mat_reflexion_lds_bytes(os_ns, os_nm) > kLdsMaxBytes) return SOSGPU_E_ARG;    // k_mat_reflexion could not be launched
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
     if (device < 0 || device >= ndev) return SOSGPU_E_ARG;

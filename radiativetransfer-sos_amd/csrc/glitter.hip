@@ -269,7 +269,7 @@ void launch_gsf(int model, int n, const double *d_mu, double par, int os_nm, int
 void launch_mat_reflexion(int n, const double *d_mu, double coef, int os_nb, int os_ns, int os_nm, const double *d_fcoef,
                           const int32_t *d_il, const double *d_e, float *d_rsurf, hipStream_t st)
 {
-    const size_t sh = ((size_t)(os_nm + 1) + 12 * (size_t)(os_ns + 1)) * sizeof(double);
+    const size_t sh = mat_reflexion_lds_bytes(os_ns, os_nm);
     k_mat_reflexion<<<n * (n + 1) / 2, 128, sh, st>>>(n, d_mu, coef, os_nb, os_ns, os_nm, d_fcoef, d_il, d_e, d_rsurf);
 }
 

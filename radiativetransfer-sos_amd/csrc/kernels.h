@@ -35,6 +35,13 @@ void launch_glitter(int n, const double *d_mu, double sig, int os_nb, int os_ns,
 void launch_gsf(int model, int n, const double *d_mu, double par, int os_nm, int32_t *d_il, double *d_e, hipStream_t st);
 void launch_mat_reflexion(int n, const double *d_mu, double coef, int os_nb, int os_ns, int os_nm, const double *d_fcoef,
                           const int32_t *d_il, const double *d_e, float *d_rsurf, hipStream_t st);
+// dynamic LDS k_mat_reflexion asks for (the series g[os_nm+1] and twelve Fresnel kernels per Fourier index), and the most a
+// workgroup can have on gfx950 (160 KiB; the kernel has no static LDS): a larger shape cannot be launched
+inline size_t mat_reflexion_lds_bytes(int os_ns, int os_nm)
+{
+    return ((size_t)(os_nm + 1) + 12 * (size_t)(os_ns + 1)) * sizeof(double);
+}
+constexpr size_t kLdsMaxBytes = 160 * 1024;
 // land surfaces (-SURF.Type 3, 4, 5, 7): Roujean BRDF, + Rondeaux-Herman / Breon / Maignan BPDF
 void launch_land(int isurf, int n, const double *d_mu, double k0, double k1, double k2, double coef_c, int os_nb, int os_ns, int os_nm, const double *d_fcoef, double *d_e_nn, int32_t *d_il_nn,
                  double *d_e, int32_t *d_il, float *d_tmp, float *d_rsurf, int32_t *d_err, hipStream_t st);

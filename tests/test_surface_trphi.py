@@ -43,6 +43,32 @@ def test_oracle_trphi_vs_golden(oracle):
                 assert np.abs(out[q] - exp[q]).max() <= 1e-13 * max(1.0, np.abs(exp[q]).max()), (i, k, q)
 
 
+def test_oracle_trphi_land_entry_without_land_is_the_plain_entry(oracle):
+    """sos_oracle_trphi_land with isurf = 0 runs the statements of sos_oracle_trphi: identical outputs on the golden's cases,
+    and the extra outputs are consistent (ANGDIFF = acos of the returned cosine, thresholds applied to `pre`)."""
+    g = np.load(os.path.join(GOLD, "trphi_n13.npz"))
+    for i in range(int(g["ncases"])):
+        kw = dict(igli=int(g["igli%d" % i]), wind=float(g["wind%d" % i]), ifresnel=int(g["ifresnel%d" % i]),
+                  ipolar=int(g["ipolar%d" % i]), n0=int(g["n0"]))
+        for phi in g["phis"]:
+            a = oracle.trphi(g["mu"], g["rec"], 0.4, 0.05, float(phi), **kw)
+            b = oracle.trphi_land(g["mu"], g["rec"], 0.4, 0.05, float(phi), isurf=0, **kw)
+            for q in range(4):
+                assert np.array_equal(a[q], b["out"][q])
+            dirs = np.arange(len(a[3])) != len(g["mu"])                       # slot jj = 0 carries nothing
+            assert np.allclose(np.degrees(np.arccos(b["cosdif"][dirs])), b["out"][3][dirs], rtol=0, atol=1e-12)
+            kept = np.where(np.abs(b["pre"][1]) < 1e-15, 0.0, b["pre"][1])
+            assert np.array_equal(kept, b["out"][1])
+
+
+def test_oracle_glitter_margins_are_reported(oracle):
+    """The tie audit of the facet quadrature: three finite margins after a run that used all three tests (wind 2 bisects)."""
+    g = np.load(os.path.join(GOLD, "glitter_n13.npz"))
+    oracle.glitter(g["mu"], g["chr"], 2.0, 1.34, 24, 24, 48)
+    m = oracle.glitter_margin()
+    assert m.shape == (3,) and np.all(m > 0) and np.all(m[:2] < 1e300)
+
+
 def test_oracle_polar_branches(oracle):
     """SOS_POLAR (SOS_TRPHI.F:1865-1903): all branches incl. the undefined value -999."""
     assert oracle.polar(1.0, 0.0, 0.0) == (-999.0, 0.0, 0.0)

@@ -247,3 +247,43 @@ def sos_profile(tr, hr, ta, ha, altabs=None, tabs=None, absprofil=1):
                                    p_alt, p_tab, C.byref(nt), vp(z), vp(h), vp(pa), vp(pm))
     k = nt.value + 1
     return dict(ier=ier, nt=nt.value, zprof=z[:k].copy(), h=h[:k].copy(), xdel=pa[:k].copy(), ydel=pm[:k].copy())
+
+
+def mie(xmu, rn, in_, alphas):
+    """SOS_MIE + SOS_FPHASE_MIE records for the size parameters `alphas` at the cosines xmu[2 nbmu + 1].  Returns dict(rec float32
+    [na][4 + 3 W] in the layout of sosgpu_mie, g float64 [na], info int32 [na][4] = n2 finally used, overflow break taken,
+    number of SNA rescales, n1) plus the record's fields as views: alpha, qext, qsca [na], imie, qmie, umie [na][W], and f64 [na][3 + 3 W] =
+    Qext, Qsca, g, Imie, Qmie, Umie as doubles before the record's REAL*4 rounding."""
+    a_mu, p_mu = _d(xmu)
+    a_al, p_al = _d(np.atleast_1d(alphas))
+    w, na = len(a_mu), len(a_al)
+    assert w % 2 == 1 and w >= 3
+    rec = np.zeros((na, 4 + 3 * w), dtype=np.float32)
+    g = np.zeros(na)
+    info = np.zeros((na, 4), dtype=np.int32)
+    f64 = np.zeros((na, 3 + 3 * w))
+    lib().sos_oracle_mie_f64.restype = C.c_int
+    rc = lib().sos_oracle_mie_f64(C.c_int((w - 1) // 2), p_mu, C.c_double(rn), C.c_double(in_), C.c_int(na), p_al,
+                                  rec.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p),
+                                  f64.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError("sos_oracle_mie: %d" % rc)
+    return dict(rec=rec, g=g, info=info, f64=f64, alpha=rec[:, 0], qext=rec[:, 1], qsca=rec[:, 2], imie=rec[:, 4:4 + w],
+                qmie=rec[:, 4 + w:4 + 2 * w], umie=rec[:, 4 + 2 * w:4 + 3 * w])
+
+
+def granu(rec, igranu, v1, v2, v3, wa, alphaf):
+    """SOS_GRANU on the records rec[na][4 + 3 W] (layout of sosgpu_mie).  Returns (out[3 + 3 W], nuse)."""
+    rec = np.ascontiguousarray(rec, dtype=np.float32)
+    na, rs = rec.shape
+    w = (rs - 4) // 3
+    assert rs == 4 + 3 * w and w % 2 == 1
+    out = np.zeros(3 + 3 * w)
+    nuse = C.c_int(-1)
+    lib().sos_oracle_granu.restype = C.c_int
+    rc = lib().sos_oracle_granu(C.c_int((w - 1) // 2), C.c_int(na), rec.ctypes.data_as(C.c_void_p), C.c_int(int(igranu)),
+                                C.c_double(v1), C.c_double(v2), C.c_double(v3), C.c_double(wa), C.c_double(alphaf),
+                                out.ctypes.data_as(C.c_void_p), C.byref(nuse))
+    if rc:
+        raise ValueError("sos_oracle_granu: %d" % rc)
+    return out, nuse.value

@@ -117,6 +117,23 @@ int sos_oracle_land(int isurf, int n, const double *mu, const double *chr, doubl
 /* stop margins of the last sos_oracle_land call: Roujean B1 <= 1e-3, B1 < previous B1, then the three of the quadrature */
 void sos_oracle_land_margin(double *m5);
 
+/* ---- Mie theory and the size-distribution integral (sos_mie_oracle.c) ---- */
+/* SOS_MIE + SOS_FPHASE_MIE for the size parameters alphas[nalpha] (any order), xmu[2 nbmu + 1] = RMU(-nbmu:nbmu):
+ * rec REAL*4 [nalpha][4 + 3 (2 nbmu + 1)] = {alpha, Qext, Qsca, 0, Imie, Qmie, Umie}, g[nalpha];
+ * optional info[nalpha][4] = {n2 finally used, overflow break of the CNA recurrence taken (0/1), number of SNA rescales, n1}.
+ * Returns 0, -1 (argument), -2 (memory). */
+int sos_oracle_mie(int nbmu, const double *xmu, double rn, double in, int nalpha, const double *alphas, float *rec, double *g,
+                   int *info);
+/* the same, plus optional unrounded[nalpha][3 + 3 (2 nbmu + 1)] = Qext, Qsca, g, Imie, Qmie, Umie as doubles, before the
+ * record's REAL*4 rounding (what an independent high-precision series can be compared with) */
+int sos_oracle_mie_f64(int nbmu, const double *xmu, double rn, double in, int nalpha, const double *alphas, float *rec, double *g,
+                       int *info, double *unrounded);
+/* SOS_GRANU on the records rec[na][4 + 3 (2 nbmu + 1)], sums in record order: out[3 + 3 (2 nbmu + 1)] = KMAT1 / SOMME_NR,
+ * KMAT2 / SOMME_NR, SOMME_NR, then P11 | P12 | P33 (normalised by KMAT2); *nuse = number of records used.
+ * igranu 1: log-normal (v1 modal radius, v2 ln-std); 2: Junge (v1 = r0, v2 slope, v3 = rmax).  Returns 0 or -1. */
+int sos_oracle_granu(int nbmu, int na, const float *rec, int igranu, double v1, double v2, double v3, double wa, double alphaf,
+                     double *out, int *nuse);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1243,30 +1243,46 @@ def sos_proc(aer_phase=None, device=0, **kw):
     a_tronc) -- the content of the reference's Aerosols.txt when `-AER.AOTref` > 0 (bypasses the Mie / size-distribution
     step).  With torch.distributed initialised the call is a collective: the band's CKD bins are sharded over the ranks
     (one all-reduce) and every rank returns the same outputs."""
+    return _band_call("sos_proc", kw, aer_phase, device)[0]
+
+
+def _band_call(fn, kw, aer_phase, device, alts=None):
+    """One band for sos_proc (alts None: solve_band, the kernels without output slots) or sos_proc_levels (alts: the K
+    altitudes, solve_band_levels): prepare, let the ranks agree on an error flag, solve, SOS_TRPHI and _finish per output.
+    Returns the list of 23-tuples (one without alts)."""
     from .solver import SosBinError
-    rank, world = _dist_rank_world()
-    pl, err = None, None
+    pl, levels, err = None, None, None
     try:
         pl = _prepare(kw, aer_phase, device, shard_bins=True)
+        if alts is not None:
+            try:
+                levels = pl.ctx.output_levels(pl.bins, alts)
+            except BaseException:
+                pl.ctx.close()
+                raise
     except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
         err = e
-    if world > 1:
+    if _dist_rank_world()[1] > 1:
         # A failure that strikes one rank only (device memory, a HIP error) must not leave the others waiting in the band's
         # all-reduce: the ranks agree on an error flag first (one integer, MAX).  Parameter errors are the same on every rank.
-        bad = _any_rank_failed(err is not None, device)
+        bad = _first_failed_index(-1 if err is None else 0, device) >= 0
         if bad and err is None:
             pl.ctx.close()
-            raise SosProcError("sos_proc: another rank failed while preparing this call", ier=-1)
+            raise SosProcError("%s: another rank failed while preparing this call" % fn, ier=-1)
     if err is not None:
         raise err
     try:
-        # one fused solve of the band's bins, one aggregate (+ the all-reduce of a sharded band)
+        # one fused solve of the band's bins, one aggregate per output (+ the all-reduce of a sharded band)
         try:
-            rec, fin = pl.ctx.solve_band(pl.bins, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
+            if alts is None:
+                rec, fin = pl.ctx.solve_band(pl.bins, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
+            else:
+                rec, fin = pl.ctx.solve_band_levels(pl.bins, levels, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
         except SosBinError as e:
             raise SosProcError(str(e), ier=-1)
-        out = _trphi_launch(pl, rec[0], int(fin["n_orders"][0]), float(fin["ttot_tronc"][0]), float(fin["tauout"][0]))
-        return _finish(pl, out.cpu().numpy(), rec[0], fin, 0)
+        outs = [_trphi_launch(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]), float(fin["tauout"][k]))
+                for k in range(len(rec))]
+        return [_finish(pl, outs[k].cpu().numpy(), rec[k], fin, k) for k in range(len(rec))]
     finally:
         pl.ctx.close()
 
@@ -1302,46 +1318,7 @@ def sos_proc_levels(altitudes, aer_phase=None, device=0, **kw):
     device work).  kw is sos_proc's keyword set with zout = -1 (another zout: ValueError) and no -SOS_Main.ResRoot (result
     files stay sos_proc's: ValueError).  Under torch.distributed the call is a collective as sos_proc is: the bins are
     sharded and one all-reduce covers the K record sets."""
-    from .solver import SosBinError
-    alts = _levels_arguments("sos_proc_levels", altitudes, [kw])
-    rank, world = _dist_rank_world()
-    pl, levels, err = None, None, None
-    try:
-        pl = _prepare(kw, aer_phase, device, shard_bins=True)
-        try:
-            levels = pl.ctx.output_levels(pl.bins, alts)
-        except BaseException:
-            pl.ctx.close()
-            pl = None
-            raise
-    except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
-        err = e
-    if world > 1:
-        bad = _any_rank_failed(err is not None, device)
-        if bad and err is None:
-            pl.ctx.close()
-            raise SosProcError("sos_proc_levels: another rank failed while preparing this call", ier=-1)
-    if err is not None:
-        raise err
-    try:
-        try:
-            rec, fin = pl.ctx.solve_band_levels(pl.bins, levels, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
-        except SosBinError as e:
-            raise SosProcError(str(e), ier=-1)
-        outs = [_trphi_launch(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]), float(fin["tauout"][k]))
-                for k in range(len(alts))]
-        return [_finish(pl, outs[k].cpu().numpy(), rec[k], fin, k) for k in range(len(alts))]
-    finally:
-        pl.ctx.close()
-
-
-def _any_rank_failed(failed, device):
-    import torch
-    import torch.distributed as dist
-    on_gpu = dist.get_backend() == "nccl"
-    t = torch.tensor([1 if failed else 0], dtype=torch.int32, device=torch.device("cuda", device) if on_gpu else "cpu")
-    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return bool(int(t.item()))
+    return _band_call("sos_proc_levels", kw, aer_phase, device, _levels_arguments("sos_proc_levels", altitudes, [kw]))
 
 
 def sos_proc_many(kwargs_list, n_workers=8, device=0):
@@ -1385,18 +1362,20 @@ def _expand_outputs(c, block=None):
     return tuple(out)
 
 
-def _gather_results(results, mine, nrows, world):
+def _gather_results(results, mine, nrows, world, nz=None):
     """Every rank receives the 23-tuples of the wavelengths the other ranks computed (all_gather_object of the compacted
-    tuples; the only exchange of a wavelength-partitioned spectrum)."""
+    tuples; the only exchange of a wavelength-partitioned spectrum).  nz: every result is a list of nz 23-tuples (output
+    altitudes) instead of one tuple."""
     import torch.distributed as dist
-    part = [(i, _compact_outputs(results[i], nrows[i])) for i in mine]
+    per = 1 if nz is None else nz
+    part = [(i, [_compact_outputs(t, nrows[i]) for t in ([results[i]] if nz is None else results[i])]) for i in mine]
     parts = [None] * world
     dist.all_gather_object(parts, part)
-    todo = [(i, c) for pr in parts for i, c in pr if results[i] is None]
-    blocks = _zero_pages((len(todo), len(_TABLE_NAMES), 361, 81)) if todo else None
-    for k, (i, c) in enumerate(todo):
-        if results[i] is None:
-            results[i] = _expand_outputs(c, blocks[k])
+    todo = [(i, cs) for pr in parts for i, cs in pr if results[i] is None]
+    blocks = _zero_pages((len(todo) * per, len(_TABLE_NAMES), 361, 81)) if todo else None
+    for j, (i, cs) in enumerate(todo):
+        full = [_expand_outputs(c, blocks[j * per + k]) for k, c in enumerate(cs)]
+        results[i] = full[0] if nz is None else full
 
 
 def spectrum_costs(kwargs_list):
@@ -1459,6 +1438,221 @@ def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st):
     return aer_wa
 
 
+def _first_failed_index(index, device):
+    """Ranks agree on a failure (one integer, MAX): the largest wavelength index any rank failed at (index -1: this rank did not
+    fail; a band call passes 0 for a failure), or -1."""
+    import torch
+    import torch.distributed as dist
+    on_gpu = dist.get_backend() == "nccl"
+    t = torch.tensor([int(index)], dtype=torch.int64, device=torch.device("cuda", device) if on_gpu else "cpu")
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return int(t.item())
+
+
+def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None):
+    """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
+    describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
+    launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop."""
+    import time
+    import torch
+    from . import capi, solver
+    from . import dist as _dist
+    from . import aerosols as _aer
+    from . import absorption as _abs
+    nwl = len(kwargs_list)
+    if aer_phases is None:
+        aer_phases = [None] * nwl
+    if len(aer_phases) != nwl:
+        raise ValueError("aer_phases must be parallel to kwargs_list")
+    if nwl == 0:
+        return []
+    capi.lib()
+    dev = torch.device("cuda", device)
+    # solve_spectrum / solve_spectrum_levels are looked up when called: the tests count launches by replacing them
+    if alts is None:
+        nz, per_chunk = 1, max(1, int(chunk))
+
+        def solve_group(table, gp, bins, cob, seg, aik):
+            rec, scal = solver.solve_spectrum(table, bins, cob, seg, aik, order=None)
+            return rec[None], scal[None]
+
+        def solve_single(pl):
+            out = pl.ctx.solve(pl.bins, pl.ctx.alloc_outputs(pl.bins["nb"], zero=False))
+            rec, scal = pl.ctx.aggregate(out, pl.aik, scal=pl.bins.get("scal"), tdifmug=pl.tdifmug)
+            return rec[None], scal[None]
+    else:
+        nz, per_chunk = len(alts), max(1, int(chunk) // len(alts))      # the record-memory rule of sos_spectrum_levels
+
+        def solve_group(table, gp, bins, cob, seg, aik):
+            return solver.solve_spectrum_levels(table, bins, cob, seg, aik, solver.concat_levels([pl.levels for pl in gp]),
+                                                order=None)
+
+        def solve_single(pl):
+            out = pl.ctx.solve_levels(pl.bins, pl.levels) if pl.bins["nb"] else None
+            return pl.ctx.aggregate_levels(out, pl.levels, pl.aik, scal=pl.bins.get("scal"), tdifmug=pl.tdifmug)
+    rank, world = _dist_rank_world()
+    if world > 1:
+        mine = [int(i) for i in _dist.balanced_shards(spectrum_costs(kwargs_list), world)[rank]]
+    else:
+        mine = list(range(nwl))
+    results = [None] * nwl                              # K 23-tuples per wavelength
+    debug = bool(os.environ.get("SOS_SPECTRUM_DEBUG"))
+    nrows = {}
+    tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0)
+    main_st = torch.cuda.current_stream(dev)
+    side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(prep_streams)))]
+    aer_st = torch.cuda.Stream(device=dev)
+    if len(mine) >= 64 and "GPU_MAX_HW_QUEUES" not in os.environ and not getattr(_spectrum_pass, "_warned_queues", False):
+        import warnings
+        _spectrum_pass._warned_queues = True
+        warnings.warn("GPU_MAX_HW_QUEUES is not set: the HIP runtime maps the %d preparation streams of %s onto 4 hardware "
+                      "queues and the device side of the preparation becomes the limit (about 2/3 of the throughput); export "
+                      "GPU_MAX_HW_QUEUES=16 before the first GPU call of the process (16 // processes when several processes share "
+                      "the GPU)" % (len(side), fn), RuntimeWarning, stacklevel=3)
+    where, err = -1, None                               # the wavelength being worked on (named by a failure)
+    # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
+    # a growing list of result tuples, and the collections this triggers re-walk the results again and again (SOS_SPECTRUM_KEEP_GC=1
+    # leaves the collector alone).  Nothing here relies on it: contexts are closed explicitly, tensors are freed by reference count.
+    import gc
+    pause_gc = gc.isenabled() and not os.environ.get("SOS_SPECTRUM_KEEP_GC")
+    if pause_gc:
+        gc.disable()
+    try:
+        for c0 in range(0, len(mine), per_chunk):
+            idx = mine[c0:c0 + per_chunk]
+            plans = []
+            try:
+                t0 = time.perf_counter()
+                where = idx[0]
+                # the preparation of wavelength k queues its device work (source operators, absorption and level profiles of its
+                # bins: latency-bound kernels of 0.1-2 ms on a few wavefronts) on side stream k mod n: the wavelengths overlap on the
+                # device, and the launches below wait for all of them
+                for st in side + [aer_st]:
+                    st.wait_stream(main_st)
+                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st)
+                # The chunk goes to the solver in a few parts: the solves of a part run on the device while the host prepares the
+                # next one, so that only the last part's solve is waited for below.
+                solved = []                       # (plans, rec [K][nw][S][3][W], scal [K][nw][10+N], table) device tensors
+                # (at least 32 wavelengths per part -- a launch per kernel variant each; SOS_SPECTRUM_MIN_PART: the tests' override)
+                nsub = max(1, min(int(parts), len(idx) // max(1, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32")))))
+                step = max(1, -(-len(idx) // nsub))
+                for s0 in range(0, len(idx), step):
+                    part = []
+                    for k, i in enumerate(idx[s0:s0 + step], s0):
+                        where = i
+                        with torch.cuda.stream(side[k % len(side)]):
+                            pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
+                                          aer_at_wa=aer_wa.get(i))
+                            pl.writes_files = True
+                            pl.index = i
+                            plans.append(pl)
+                            if alts is not None:
+                                pl.levels = pl.ctx.output_levels(pl.bins, alts)
+                        if debug:
+                            torch.cuda.synchronize(dev)
+                            print("[%s] prepared" % fn, i, flush=True)
+                        part.append(pl)
+                    for st in side:
+                        main_st.wait_stream(st)
+                    t1 = time.perf_counter()
+                    tm["prepare"] += t1 - t0
+                    # --- groups of wavelengths one launch can cover
+                    groups = collections.OrderedDict()
+                    single = []
+                    for pl in part:
+                        b = pl.bins
+                        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor):
+                            single.append(pl)
+                            continue
+                        # (the last entry is False throughout with output slots: their calls have zout = -1)
+                        key = (pl.n, pl.ctx.smax, pl.ctx.os_nb, bool(pl.ctx._rsurf is not None), b["lp"], b["jout"] is not None)
+                        groups.setdefault(key, []).append(pl)
+                    for key, gp in groups.items():
+                        if len(gp) == 1:
+                            single.append(gp[0])
+                            continue
+                        where = gp[0].index
+                        table = solver.ContextTable([pl.ctx for pl in gp])
+                        bins, cob, seg = solver.concat_bins([pl.bins for pl in gp])
+                        aik = solver._upload(torch.from_numpy(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp])),
+                                             dev)
+                        if debug:
+                            print("[%s] group" % fn, key, "wavelengths", [pl.index for pl in gp], "bins", bins["nb"], flush=True)
+                        rec, scal = solve_group(table, gp, bins, cob, seg, aik)
+                        if debug:
+                            torch.cuda.synchronize(dev)
+                            print("[%s]   done" % fn, flush=True)
+                        solved.append((gp, rec, scal, table))
+                    for pl in single:
+                        where = pl.index
+                        rec, scal = solve_single(pl)
+                        solved.append(([pl], rec, scal, None))
+                    t0 = time.perf_counter()
+                    tm["solve_launch"] += t0 - t1
+                t2 = time.perf_counter()
+                # --- one copy of all band scalars (waits for the solves), then every azimuth recomposition back to back
+                scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in solved]).cpu().numpy()
+                t3 = time.perf_counter()
+                tm["wait"] += t3 - t2
+                todo, pos = [], 0                               # (plan, slot, record, finish_scalars, segment)
+                for gp, rec, scal, _ in solved:
+                    sw = scal.shape[2]
+                    blk = scal_all[pos:pos + nz * len(gp) * sw].reshape(nz, len(gp), sw)
+                    pos += nz * len(gp) * sw
+                    fins = [_dist.finish_scalars(blk[k]) for k in range(nz)]
+                    recs = [rec[k] for k in range(nz)]
+                    for g, pl in enumerate(gp):
+                        if any(f["min_orders"][g] < 0 for f in fins):
+                            where = pl.index
+                            raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
+                                               "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
+                        todo += [(pl, k, recs[k][g], fins[k], g) for k in range(nz)]
+                outs = [_trphi_launch(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
+                        for pl, _, r, f, g in todo]
+                flat = torch.cat([o.reshape(-1) for o in outs]).cpu().numpy()
+                t4 = time.perf_counter()
+                tm["trphi"] += t4 - t3
+                pos = 0
+                blocks = _zero_pages((len(outs), 2, 7, 361, 81))  # the result tables of the chunk's wavelengths (views of it)
+                for j, ((pl, k, r, f, g), o) in enumerate(zip(todo, outs)):
+                    where = pl.index
+                    if results[pl.index] is None:
+                        results[pl.index] = [None] * nz
+                    results[pl.index][k] = _finish(pl, flat[pos:pos + o.numel()].reshape(o.shape), r, f, g, blocks[j])
+                    nrows[pl.index] = len(pl.rows)
+                    pos += o.numel()
+                tm["finish"] += time.perf_counter() - t4
+            finally:
+                _aer.drop_prefetched_size_integrals()
+                _abs.drop_prefetched_gas_tables()
+                for st in side + [aer_st]:
+                    st.synchronize()
+                main_st.synchronize()                             # the table launches read every context's operators
+                for pl in plans:
+                    pl.ctx.close()
+    except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
+        err = e
+    finally:
+        if pause_gc:
+            gc.enable()
+    if world > 1:
+        # a call failing on one rank must not leave the others waiting in the gather: the ranks agree first (one integer)
+        bad = _first_failed_index(max(where, 0) if err is not None else -1, device)
+        if bad >= 0:
+            if err is not None:
+                raise SosProcError("%s: wavelength %d failed: %s" % (fn, where, err), ier=getattr(err, "ier", 1)) from err
+            raise SosProcError("%s: wavelength %d failed on another rank" % (fn, bad), ier=-1)
+    if err is not None:
+        raise err
+    if timings is not None:
+        timings.update(tm)
+    if alts is None:
+        results = [None if r is None else r[0] for r in results]
+    if world > 1 and gather:
+        _gather_results(results, mine, nrows, world, None if alts is None else nz)
+    return results
+
+
 def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16, parts=4):
     """A spectrum of sos_proc calls -- one per wavelength, as the reference issues them one after the other
     (binding/run_sos.py:640-695; the bin loop of each is SOS_PROC.F:3459-3594) -- as ONE pass over the GPU:
@@ -1481,7 +1675,9 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     (spectrum_costs, dist.balanced_shards) -- no bin of a band leaves its rank, so there is no all-reduce, only the gather of
     the results ("partition by wavelength first"): gather=True returns the full list on every rank
     (all_gather_object of the compacted tuples), gather=False returns None in the slots of other ranks.  Result files of a
-    call (-SOS_Main.ResRoot) are written by the rank that owns it.
+    call (-SOS_Main.ResRoot) are written by the rank that owns it.  Before the gather the ranks agree on failures (one integer
+    all-reduce): a call failing on one rank makes EVERY rank raise SosProcError naming that wavelength; on one rank the call's
+    own exception is raised.
     aer_phases: optional list parallel to kwargs_list of `aer_phase` dictionaries (see sos_proc) or None.
     timings: optional dict, filled with host-side phase times in seconds (prepare, solve_launch, wait, trphi, finish).
     parts: a chunk is handed to the solver in this many parts (the solves of one part overlap the host preparation of the next).
@@ -1489,167 +1685,7 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     hardware queues of their own, solver.solve_many).  The preparation kernels of one wavelength are a serial chain of about
     3 ms on a few wavefronts (level placement of the no-gas profile and of every bin: bisections), so the device side alone
     sustains prep_streams / 3 ms wavelengths per second: 16 streams keep it ahead of a host that spends 0.6 ms per wavelength."""
-    import time
-    import torch
-    from . import capi
-    from .solver import ContextTable, SosBinError, _upload, concat_bins, solve_spectrum
-    from . import dist as _dist
-    from . import aerosols as _aer
-    from . import absorption as _abs
-    capi.lib()
-    nwl = len(kwargs_list)
-    if aer_phases is None:
-        aer_phases = [None] * nwl
-    if len(aer_phases) != nwl:
-        raise ValueError("aer_phases must be parallel to kwargs_list")
-    rank, world = _dist_rank_world()
-    if world > 1:
-        mine = [int(i) for i in _dist.balanced_shards(spectrum_costs(kwargs_list), world)[rank]]
-    else:
-        mine = list(range(nwl))
-    results = [None] * nwl
-    debug = bool(os.environ.get("SOS_SPECTRUM_DEBUG"))
-    nrows = {}
-    tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0)
-    dev = torch.device("cuda", device)
-    main_st = torch.cuda.current_stream(dev)
-    side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(prep_streams)))]
-    aer_st = torch.cuda.Stream(device=dev)
-    if len(mine) >= 64 and "GPU_MAX_HW_QUEUES" not in os.environ and not getattr(sos_spectrum, "_warned_queues", False):
-        import warnings
-        sos_spectrum._warned_queues = True
-        warnings.warn("GPU_MAX_HW_QUEUES is not set: the HIP runtime maps the %d preparation streams of sos_spectrum onto 4 hardware "
-                      "queues and the device side of the preparation becomes the limit (about 2/3 of the throughput); export "
-                      "GPU_MAX_HW_QUEUES=16 before the first GPU call of the process (16 // processes when several processes share "
-                      "the GPU)" % len(side), RuntimeWarning, stacklevel=2)
-    # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
-    # a growing list of result tuples, and the collections this triggers re-walk the results again and again (SOS_SPECTRUM_KEEP_GC=1
-    # leaves the collector alone).  Nothing here relies on it: contexts are closed explicitly, tensors are freed by reference count.
-    import gc
-    pause_gc = gc.isenabled() and not os.environ.get("SOS_SPECTRUM_KEEP_GC")
-    if pause_gc:
-        gc.disable()
-    try:
-        for c0 in range(0, len(mine), max(1, int(chunk))):
-            idx = mine[c0:c0 + max(1, int(chunk))]
-            plans = []
-            try:
-                t0 = time.perf_counter()
-                # the preparation of wavelength k queues its device work (source operators, absorption and level profiles of its
-                # bins: latency-bound kernels of 0.1-2 ms on a few wavefronts) on side stream k mod n: the wavelengths overlap on the
-                # device, and the launches below wait for all of them
-                for st in side + [aer_st]:
-                    st.wait_stream(main_st)
-                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st)
-                # The chunk goes to the solver in a few parts: the solves of a part run on the device while the host prepares the
-                # next one, so that only the last part's solve is waited for below.
-                solved = []                       # (plans, rec [nw][S][3][W], scal [nw][10+N]) device tensors
-                # (at least 32 wavelengths per part -- a launch per kernel variant each; SOS_SPECTRUM_MIN_PART: the tests' override)
-                nsub = max(1, min(int(parts), len(idx) // max(1, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32")))))
-                step = max(1, -(-len(idx) // nsub))
-                for s0 in range(0, len(idx), step):
-                    part = []
-                    for k, i in enumerate(idx[s0:s0 + step], s0):
-                        with torch.cuda.stream(side[k % len(side)]):
-                            pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
-                                          aer_at_wa=aer_wa.get(i))
-                        if debug:
-                            torch.cuda.synchronize(dev)
-                            print("[sos_spectrum] prepared", i, flush=True)
-                        pl.writes_files = True
-                        pl.index = i
-                        plans.append(pl)
-                        part.append(pl)
-                    for st in side:
-                        main_st.wait_stream(st)
-                    t1 = time.perf_counter()
-                    tm["prepare"] += t1 - t0
-                    # --- groups of wavelengths one launch can cover
-                    groups = collections.OrderedDict()
-                    single = []
-                    for pl in part:
-                        b = pl.bins
-                        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor):
-                            single.append(pl)
-                            continue
-                        key = (pl.n, pl.ctx.smax, pl.ctx.os_nb, bool(pl.ctx._rsurf is not None), b["lp"], b["jout"] is not None)
-                        groups.setdefault(key, []).append(pl)
-                    for key, gp in groups.items():
-                        if len(gp) == 1:
-                            single.append(gp[0])
-                            continue
-                        table = ContextTable([pl.ctx for pl in gp])
-                        bins, cob, seg = concat_bins([pl.bins for pl in gp])
-                        aik = _upload(torch.from_numpy(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp])), dev)
-                        if debug:
-                            print("[sos_spectrum] group", key, "wavelengths", [pl.index for pl in gp], "bins", bins["nb"], flush=True)
-                        rec, scal = solve_spectrum(table, bins, cob, seg, aik, order=None)
-                        if debug:
-                            torch.cuda.synchronize(dev)
-                            print("[sos_spectrum]   done", flush=True)
-                        solved.append((gp, rec, scal, table))
-                    for pl in single:
-                        out = pl.ctx.solve(pl.bins, pl.ctx.alloc_outputs(pl.bins["nb"], zero=False))
-                        rec, scal = pl.ctx.aggregate(out, pl.aik, scal=pl.bins.get("scal"), tdifmug=pl.tdifmug)
-                        solved.append(([pl], rec, scal, None))
-                    t0 = time.perf_counter()
-                    tm["solve_launch"] += t0 - t1
-                t2 = time.perf_counter()
-                # --- one copy of all band scalars (waits for the solves), then every azimuth recomposition back to back
-                scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in solved]).cpu().numpy()
-                t3 = time.perf_counter()
-                tm["wait"] += t3 - t2
-                outs, pos = [], 0
-                for gp, rec, scal, _ in solved:
-                    sw = scal.shape[1]
-                    fin = _dist.finish_scalars(scal_all[pos:pos + len(gp) * sw].reshape(len(gp), sw))
-                    pos += len(gp) * sw
-                    for g, pl in enumerate(gp):
-                        if fin["min_orders"][g] < 0:
-                            raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT or "
-                                               "IBORM out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
-                        pl.fin, pl.g, pl.rec0 = fin, g, rec[g]
-                        outs.append(_trphi_launch(pl, rec[g], int(fin["n_orders"][g]), float(fin["ttot_tronc"][g]),
-                                                  float(fin["tauout"][g])))
-                flat = torch.cat([o.reshape(-1) for o in outs]).cpu().numpy()
-                t4 = time.perf_counter()
-                tm["trphi"] += t4 - t3
-                pos, k = 0, 0
-                blocks = _zero_pages((len(outs), 2, 7, 361, 81))  # the result tables of the chunk's wavelengths (views of it)
-                for gp, _, _, _ in solved:
-                    for pl in gp:
-                        cnt = outs[k].numel()
-                        results[pl.index] = _finish(pl, flat[pos:pos + cnt].reshape(outs[k].shape), pl.rec0, pl.fin, pl.g, blocks[k])
-                        nrows[pl.index] = len(pl.rows)
-                        pos += cnt
-                        k += 1
-                tm["finish"] += time.perf_counter() - t4
-            finally:
-                _aer.drop_prefetched_size_integrals()
-                _abs.drop_prefetched_gas_tables()
-                for st in side + [aer_st]:
-                    st.synchronize()
-                main_st.synchronize()                             # the table launches read every context's operators
-                for pl in plans:
-                    pl.ctx.close()
-    finally:
-        if pause_gc:
-            gc.enable()
-    if timings is not None:
-        timings.update(tm)
-    if world > 1 and gather:
-        _gather_results(results, mine, nrows, world)
-    return results
-
-
-def _first_failed_index(index, device):
-    """Ranks agree on a failure: the largest wavelength index any rank failed at (index -1: this rank did not fail), or -1."""
-    import torch
-    import torch.distributed as dist
-    on_gpu = dist.get_backend() == "nccl"
-    t = torch.tensor([int(index)], dtype=torch.int64, device=torch.device("cuda", device) if on_gpu else "cpu")
-    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return int(t.item())
+    return _spectrum_pass("sos_spectrum", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts)
 
 
 def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16,
@@ -1664,7 +1700,7 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
     allowed, each passing the -SOS.OutputAlt rule (SosProcError 2611); every call with zout = -1 and an empty -SOS_Main.ResRoot
     (ValueError otherwise).  An empty list returns [].
     Calls with -SOS.Trans (diffuse transmissions) and groups of one wavelength run through the per-wavelength path
-    (SosContext.solve_band_levels).
+    (SosContext.solve_levels + aggregate_levels; their scalars join the launches' one copy).
     Record memory: the records of a launch grow K-fold (at N = 41, 6 400 bins hold about 1 GB per altitude), so a chunk holds
     max(1, chunk // K) wavelengths -- a part's records then stay near what sos_spectrum holds with the same `chunk`.
     aer_phases, device, gather, timings, prep_streams, parts: as sos_spectrum.  With torch.distributed the wavelengths are dealt
@@ -1672,176 +1708,9 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
     so that a call failing on one rank makes EVERY rank raise SosProcError naming that wavelength instead of leaving the
     others waiting in the gather (all_gather_object of the compacted tuples, K per wavelength).  gather=False leaves None in
     the slots of other ranks."""
-    import time
-    import torch
-    from . import capi
-    from .solver import ContextTable, SosBinError, _upload, concat_bins, concat_levels, solve_spectrum_levels
-    from . import dist as _dist
-    from . import aerosols as _aer
-    from . import absorption as _abs
     alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list)
-    nz, nwl = len(alts), len(kwargs_list)
-    if aer_phases is None:
-        aer_phases = [None] * nwl
-    if len(aer_phases) != nwl:
-        raise ValueError("aer_phases must be parallel to kwargs_list")
-    if nwl == 0:
-        return []
-    capi.lib()
-    rank, world = _dist_rank_world()
-    if world > 1:
-        mine = [int(i) for i in _dist.balanced_shards(spectrum_costs(kwargs_list), world)[rank]]
-    else:
-        mine = list(range(nwl))
-    results = [None] * nwl
-    nrows = {}
-    tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0)
-    dev = torch.device("cuda", device)
-    main_st = torch.cuda.current_stream(dev)
-    side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(prep_streams)))]
-    aer_st = torch.cuda.Stream(device=dev)
-    step_chunk = max(1, int(chunk) // nz)               # the record-memory rule of the docstring
-    where = [-1]                                        # the wavelength being worked on (named by a failure)
-    err = None
-    import gc
-    pause_gc = gc.isenabled() and not os.environ.get("SOS_SPECTRUM_KEEP_GC")
-    if pause_gc:
-        gc.disable()
-    try:
-        for c0 in range(0, len(mine), step_chunk):
-            idx = mine[c0:c0 + step_chunk]
-            plans = []
-            try:
-                t0 = time.perf_counter()
-                where[0] = idx[0]
-                for st in side + [aer_st]:
-                    st.wait_stream(main_st)
-                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st)
-                solved = []         # (plans, rec [K][nw][S][3][W], scal [K][nw][10+N] device) or ([pl], rec [K][S][3][W], fin)
-                nsub = max(1, min(int(parts), len(idx) // max(1, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32")))))
-                step = max(1, -(-len(idx) // nsub))
-                for s0 in range(0, len(idx), step):
-                    part = []
-                    for k, i in enumerate(idx[s0:s0 + step], s0):
-                        where[0] = i
-                        with torch.cuda.stream(side[k % len(side)]):
-                            pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
-                                          aer_at_wa=aer_wa.get(i))
-                            pl.writes_files = True
-                            pl.index = i
-                            plans.append(pl)
-                            pl.levels = pl.ctx.output_levels(pl.bins, alts)
-                        part.append(pl)
-                    for st in side:
-                        main_st.wait_stream(st)
-                    t1 = time.perf_counter()
-                    tm["prepare"] += t1 - t0
-                    groups = collections.OrderedDict()
-                    single = []
-                    for pl in part:
-                        b = pl.bins
-                        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor):
-                            single.append(pl)
-                            continue
-                        key = (pl.n, pl.ctx.smax, pl.ctx.os_nb, bool(pl.ctx._rsurf is not None), b["lp"])
-                        groups.setdefault(key, []).append(pl)
-                    for key, gp in groups.items():
-                        if len(gp) == 1:
-                            single.append(gp[0])
-                            continue
-                        where[0] = gp[0].index
-                        table = ContextTable([pl.ctx for pl in gp])
-                        bins, cob, seg = concat_bins([pl.bins for pl in gp])
-                        levels = concat_levels([pl.levels for pl in gp])
-                        aik = _upload(torch.from_numpy(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp])), dev)
-                        rec, scal = solve_spectrum_levels(table, bins, cob, seg, aik, levels, order=None)
-                        solved.append((gp, rec, scal))
-                    for pl in single:
-                        where[0] = pl.index
-                        try:
-                            rec, fin = pl.ctx.solve_band_levels(pl.bins, pl.levels, pl.aik, tdifmug=pl.tdifmug, reduce=False)
-                        except SosBinError as e:
-                            raise SosProcError("SOS_OS: wavelength %d (%r microns): %s" % (pl.index, pl.p["wa_simu"], e), ier=-1)
-                        solved.append(([pl], rec, fin))
-                    t0 = time.perf_counter()
-                    tm["solve_launch"] += t0 - t1
-                t2 = time.perf_counter()
-                # --- one copy of the band scalars of all launches (waits for the solves), then the K azimuth recompositions of
-                # every wavelength back to back
-                dev_scal = [s for _, _, s in solved if isinstance(s, torch.Tensor)]
-                scal_all = torch.cat([s.reshape(-1) for s in dev_scal]).cpu().numpy() if dev_scal else None
-                t3 = time.perf_counter()
-                tm["wait"] += t3 - t2
-                todo, pos = [], 0                               # (plan, slot, record, finish_scalars, segment)
-                for gp, rec, scal in solved:
-                    if not isinstance(scal, torch.Tensor):       # per-wavelength path: segment k = altitude k
-                        todo += [(gp[0], k, rec[k], scal, k) for k in range(nz)]
-                        continue
-                    sw = scal.shape[2]
-                    blk = scal_all[pos:pos + nz * len(gp) * sw].reshape(nz, len(gp), sw)
-                    pos += nz * len(gp) * sw
-                    fins = [_dist.finish_scalars(blk[k]) for k in range(nz)]
-                    for g, pl in enumerate(gp):
-                        if any(fins[k]["min_orders"][g] < 0 for k in range(nz)):
-                            where[0] = pl.index
-                            raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
-                                               "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
-                        todo += [(pl, k, rec[k][g], fins[k], g) for k in range(nz)]
-                outs = [_trphi_launch(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
-                        for pl, _, r, f, g in todo]
-                flat = torch.cat([o.reshape(-1) for o in outs]).cpu().numpy()
-                t4 = time.perf_counter()
-                tm["trphi"] += t4 - t3
-                pos = 0
-                blocks = _zero_pages((len(outs), 2, 7, 361, 81))
-                for j, ((pl, k, r, f, g), o) in enumerate(zip(todo, outs)):
-                    where[0] = pl.index
-                    if results[pl.index] is None:
-                        results[pl.index] = [None] * nz
-                    results[pl.index][k] = _finish(pl, flat[pos:pos + o.numel()].reshape(o.shape), r, f, g, blocks[j])
-                    nrows[pl.index] = len(pl.rows)
-                    pos += o.numel()
-                tm["finish"] += time.perf_counter() - t4
-            finally:
-                _aer.drop_prefetched_size_integrals()
-                _abs.drop_prefetched_gas_tables()
-                for st in side + [aer_st]:
-                    st.synchronize()
-                main_st.synchronize()                             # the table launches read every context's operators
-                for pl in plans:
-                    pl.ctx.close()
-    except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
-        err = e
-    finally:
-        if pause_gc:
-            gc.enable()
-    if world > 1:
-        # a call failing on one rank must not leave the others waiting in the gather: the ranks agree first (one integer)
-        bad = _first_failed_index(where[0] if err is not None else -1, device)
-        if bad >= 0:
-            if err is not None:
-                raise SosProcError("sos_spectrum_levels: wavelength %d failed: %s" % (where[0], err),
-                                   ier=getattr(err, "ier", 1)) from err
-            raise SosProcError("sos_spectrum_levels: wavelength %d failed on another rank" % bad, ier=-1)
-    if err is not None:
-        raise err
-    if timings is not None:
-        timings.update(tm)
-    if world > 1 and gather:
-        _gather_levels_results(results, mine, nrows, world, nz)
-    return results
-
-
-def _gather_levels_results(results, mine, nrows, world, nz):
-    """_gather_results for lists of K 23-tuples per wavelength (all_gather_object of the compacted tuples)."""
-    import torch.distributed as dist
-    part = [(i, [_compact_outputs(t, nrows[i]) for t in results[i]]) for i in mine]
-    parts = [None] * world
-    dist.all_gather_object(parts, part)
-    todo = [(i, cs) for pr in parts for i, cs in pr if results[i] is None]
-    blocks = _zero_pages((len(todo) * nz, len(_TABLE_NAMES), 361, 81)) if todo else None
-    for j, (i, cs) in enumerate(todo):
-        results[i] = [_expand_outputs(c, blocks[j * nz + k]) for k, c in enumerate(cs)]
+    return _spectrum_pass("sos_spectrum_levels", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
+                          alts)
 
 
 def write_trans_file(path, tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):

@@ -228,16 +228,7 @@ class SosContext:
         iborm = np.broadcast_to(np.asarray(iborm, dtype=np.int32), (nb,)).copy()
         jout = zz = None
         if zout != -1.0:
-            # SOS_OS.F:1514-1520: first level J with ZOUT >= ZPROF(J), linear weight ZZ
-            zprof = np.atleast_2d(np.asarray(zprof, dtype=np.float64))
-            jout = np.zeros(nb, dtype=np.int32)
-            zz = np.zeros(nb)
-            for b in range(nb):
-                j = 1
-                while zout < zprof[b, j]:
-                    j += 1
-                jout[b] = j
-                zz[b] = (zout - zprof[b, j - 1]) / (zprof[b, j] - zprof[b, j - 1])
+            jout, zz = (x[0] for x in output_levels_host(zprof, [zout]))
         d = self.device
         return dict(nb=nb, lp=lp, perm=perm, nt=_dev_i32(nt, d), iborm=_dev_i32(iborm, d), prof=_dev_f64(prof, d),
                     jout=None if jout is None else _dev_i32(jout, d), zz=None if zz is None else _dev_f64(zz, d),
@@ -366,20 +357,9 @@ class SosContext:
         bins (a rank without bins contributes K neutral elements).  Returns (rec[K][smax+1][3][W], finish_scalars dict with
         one entry per altitude); raises SosBinError as solve_band does."""
         from . import dist as _dist
-        nz = levels["nz"]
         out = self.solve_levels(bins, levels) if bins["nb"] else None
-        recs, scals = [], []
-        for k in range(nz):
-            if out is None:
-                r, s = self.aggregate(None, aik)
-            else:
-                sc = _dev_f64(bins["scal"], self.device).clone()
-                sc[:, 3] = levels["tauout"][k]
-                r, s = self.aggregate(dict(rec=out["rec"][k], norders=out["norders"], flux=out["flux"]), aik, scal=sc,
-                                      tdifmug=tdifmug)
-            recs.append(r)
-            scals.append(s)
-        rec, scal = torch.cat(recs), torch.cat(scals)
+        rec, scal = self.aggregate_levels(out, levels, aik, scal=bins.get("scal"), tdifmug=tdifmug)
+        rec, scal = rec[:, 0], scal[:, 0]                   # one segment: the band
         if reduce:
             buf = _dist.all_reduce_partial(_dist.pack_partial(rec, scal), scal.shape[1], group=group)
             rec, scal = _dist.unpack_partial(buf, rec.shape)
@@ -483,6 +463,24 @@ class SosContext:
                                                _ptr(out["norders"]), _ptr(out["flux"]), _ptr(scal_t), _ptr(tdg),
                                                _ptr(o_rec), _ptr(o_scal), self._stream()), "sosgpu_aggregate")
         return o_rec, o_scal
+
+    def aggregate_levels(self, out, levels, aik, seg=None, scal=None, tdifmug=None):
+        """aggregate for the K output slots of solve_levels / solve_spectrum_levels: slot k's records out["rec"][k] with that
+        altitude's TAUOUT (levels["tauout"][k]) in column 3 of a copy of the per-bin scalars `scal` (zeros when there are
+        none); out = None gives the neutral element K times (a rank without bins).  Returns (rec[K][nseg][smax+1][3][W],
+        scal[K][nseg][10+N]) on device; no synchronisation."""
+        if out is None:
+            parts = [self.aggregate(None, aik) for _ in range(levels["nz"])]
+        else:
+            nb, d = out["rec"].shape[1], self.device
+            base = None if scal is None else _dev_f64(scal, d)
+            parts = []
+            for k in range(levels["nz"]):
+                sc = torch.zeros((nb, 4), dtype=torch.float64, device=d) if base is None else base.clone()
+                sc[:, 3] = levels["tauout"][k]
+                parts.append(self.aggregate(dict(rec=out["rec"][k], norders=out["norders"], flux=out["flux"]), aik, seg=seg,
+                                            scal=sc, tdifmug=tdifmug))
+        return torch.stack([r for r, _ in parts]), torch.stack([s for _, s in parts])
 
     def trphi(self, rec, nf, tau, tauout, phis_rad, igli=0, wind=0.0, land=None):
         """SOS_TRPHI + SOS_POLAR for a list of azimuths (radians).  rec: device tensor [>=nf][3][W]
@@ -608,7 +606,7 @@ def _spectrum_order(cx, bins, order):
 def solve_spectrum_levels(table, bins, ctx_of_bin, seg, aik, levels, out=None, order="cost"):
     """solve_spectrum for K output altitudes: ONE launch of the fused solver over the bins of many wavelengths, every bin with
     K output slots (sosgpu_os_solve_multi_levels), then one segmented SOS_AGGREGATE per altitude with that altitude's TAUOUT in
-    scal[:, 3] (as SosContext.solve_band_levels).  bins / ctx_of_bin / seg from concat_bins, levels from concat_levels,
+    scal[:, 3] (SosContext.aggregate_levels).  bins / ctx_of_bin / seg from concat_bins, levels from concat_levels,
     aik[nb] device tensor in the same order; order as in solve_spectrum.  Returns (rec[K][nwavelengths][smax+1][3][W],
     scal[K][nwavelengths][10+N]) device tensors; no synchronisation.  Slot k of wavelength g equals solve_spectrum's record of
     g with that altitude's profile, bit for bit."""
@@ -623,15 +621,7 @@ def solve_spectrum_levels(table, bins, ctx_of_bin, seg, aik, levels, out=None, o
                                                        _ptr(levels["jout"]), _ptr(levels["zz"]), _ptr(out["rec"]),
                                                        _ptr(out["norders"]), _ptr(out["iglast"]), _ptr(out["flux"]),
                                                        cx._stream()), "sosgpu_os_solve_multi_levels")
-    base = bins.get("scal")
-    recs, scals = [], []
-    for k in range(nz):
-        sc = torch.zeros((nb, 4), dtype=torch.float64, device=cx.device) if base is None else _dev_f64(base, cx.device).clone()
-        sc[:, 3] = levels["tauout"][k]
-        r, s = cx.aggregate(dict(rec=out["rec"][k], norders=out["norders"], flux=out["flux"]), aik, seg=seg, scal=sc)
-        recs.append(r)
-        scals.append(s)
-    return torch.stack(recs), torch.stack(scals)
+    return cx.aggregate_levels(out, levels, aik, seg=seg, scal=bins.get("scal"))
 
 
 def solve_many(items, n_streams=16):

@@ -1,5 +1,6 @@
 """Worker of tests/test_spectrum.py::test_sos_spectrum_wavelengths_over_ranks_on_one_gpu: run_sos.sos_spectrum under
-torch.distributed (several ranks on cuda:0, gloo): the wavelengths are partitioned over the ranks, results gathered."""
+torch.distributed (several ranks on cuda:0, gloo): the wavelengths are partitioned over the ranks, results gathered; then a
+spectrum with one refused call must make every rank raise SosProcError (no rank left waiting in the gather)."""
 import argparse
 import hashlib
 import importlib
@@ -44,12 +45,22 @@ def main():
             h.update(np.ascontiguousarray(np.asarray(x, dtype=np.float64)).tobytes())
     part = rs.sos_spectrum(kws, gather=False)              # without the gather: only this rank's wavelengths are filled
     assert [i for i, o in enumerate(part) if o is not None] == mine
-    dig, own = [None] * world, [None] * world
+    # call 3 refused (-SURF.Type 6 without its surface index): every rank raises, whichever owns it
+    bad = list(kws)
+    bad[3] = dict(kws[3], isurf=6)
+    raised, msg = False, ""
+    try:
+        rs.sos_spectrum(bad)
+    except rs.SosProcError as e:
+        raised, msg = True, str(e)
+    dig, own, rz, ms = [None] * world, [None] * world, [None] * world, [None] * world
     dist.all_gather_object(dig, h.hexdigest())
     dist.all_gather_object(own, mine)
+    dist.all_gather_object(rz, raised)
+    dist.all_gather_object(ms, msg)
     if rank == 0:
         with open(a.out, "w") as f:
-            json.dump({"world": world, "n": len(kws), "digests": dig, "owners": own}, f)
+            json.dump({"world": world, "n": len(kws), "digests": dig, "owners": own, "raised": rz, "messages": ms}, f)
     dist.barrier()
     dist.destroy_process_group()
 

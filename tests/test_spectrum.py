@@ -91,8 +91,18 @@ def _gather_worker(rank, world, port, q):
             tabs.append(t)
         results[i] = (n, np.arange(81, dtype=np.int32), rng.normal(size=361), rng.normal(size=81)) + tuple(tabs) + (0.1 * i,) * 5
         nrows[i] = nrow
+    nz = 3                                  # ... and lists of nz tuples per wavelength (output altitudes): slot k scaled by k + 1
+    levels = [None if r is None else [tuple(x * (k + 1) if i == 5 else x for i, x in enumerate(r)) for k in range(nz)]
+              for r in results]
     rs._gather_results(results, mine, nrows, world)
-    q.put((rank, mine, [float(np.asarray(r[5]).sum()) + float(r[22]) for r in results]))
+    rs._gather_results(levels, mine, nrows, world, nz)
+    sums = [float(np.asarray(r[5]).sum()) + float(r[22]) for r in results]
+    for r, lv in zip(results, levels):
+        assert len(lv) == nz
+        for k, t in enumerate(lv):
+            assert len(t) == 23 and all(np.array_equal(np.asarray(x) * (k + 1) if i == 5 else np.asarray(x), np.asarray(y))
+                                        for i, (x, y) in enumerate(zip(r, t)))
+    q.put((rank, mine, sums))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -100,7 +110,8 @@ def _gather_worker(rank, world, port, q):
 @pytest.mark.parametrize("world", [2, 3])
 def test_wavelength_partition_gather_gloo(world):
     """The N > 1 path of sos_spectrum without GPUs: every rank computes its own wavelengths (fabricated tuples), one
-    all_gather_object of the compacted tuples, and every rank ends with the complete, identical list."""
+    all_gather_object of the compacted tuples, and every rank ends with the complete, identical list -- for one tuple per
+    wavelength and for lists of K tuples per wavelength (sos_spectrum_levels)."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -182,7 +193,8 @@ def test_sos_spectrum_raises_the_failing_call(gpu_pkg, tmp_path, monkeypatch):
 def test_sos_spectrum_wavelengths_over_ranks_on_one_gpu(tmp_path, world):
     """torch.distributed.run starts `world` ranks sharing cuda:0 (gloo): the wavelengths are dealt to the ranks by cost, each
     rank runs its own through sos_spectrum's launches, one all_gather_object -- every rank ends with the full list, equal to
-    the goldens and identical across ranks."""
+    the goldens and identical across ranks; a spectrum with one refused call makes every rank raise SosProcError naming it --
+    no rank is left waiting in the gather."""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
@@ -197,6 +209,7 @@ def test_sos_spectrum_wavelengths_over_ranks_on_one_gpu(tmp_path, world):
     assert r["world"] == world and len(set(r["digests"])) == 1, r["digests"]
     assert sorted(i for own in r["owners"] for i in own) == list(range(r["n"]))
     assert all(len(own) > 0 for own in r["owners"])
+    assert r["raised"] == [True] * world and all("wavelength 3" in m for m in r["messages"]), r["messages"]
 
 
 @pytest.mark.gpu

@@ -27,6 +27,7 @@
  *
  *   sosgpu_profile     <- SOS_PROFILE + SOS_DISC  src/SOS_PROFIL.F:224,1210 (+ the PROFIL read-back and rescale of
  *                                                 SOS, src/SOS.F:511-550; all bins of a wavelength at once)
+ *   sosgpu_profile_spectrum   the same and SOS_ABSPROFILE for the bins of many wavelengths: three launches in all
  *   sosgpu_noyaux      <- SOS_NOYAUX              src/SOS_OS.F:1857   (phase-matrix Fourier kernels,
  *                                                                     hoisted out of the bin loop)
  *   sosgpu_os_solve    <- SOS_OS (+ leaves)       src/SOS_OS.F:303    (one call = a batch of CKD bins,
@@ -330,6 +331,45 @@ int  sosgpu_profile_nogas(int device, double tr, double hr, double ta, double ha
  * nlev = CTE_ABS_NBLEV = 50 in the reference. */
 int  sosgpu_absprofile(int device, int nb, int nlev, int nterm, const int32_t *d_ik, const double *d_xk, const double *d_ro,
                        double *d_tabs, void *stream);
+
+/* The profile stage of MANY wavelengths (a part of a spectrum) as three launches: the no-gas profiles (one wavefront per
+ * wavelength), SOS_ABSPROFILE and SOS_PROFILE (one wavefront per bin of every wavelength, each reading the index of its
+ * wavelength and that wavelength's parameters from a device table) -- as the solver takes its contexts from a table
+ * (sosgpu_os_solve_multi).  Per bin the kernels run the device code of sosgpu_profile_nogas / sosgpu_absprofile /
+ * sosgpu_profile: the outputs are theirs, bit for bit.  No context is needed.
+ *   wl[nwl] (HOST)       one entry per wavelength, in bin order: its nbins bins are consecutive, sum of nbins = nb
+ *       tr, hr, ta, ha, a_tronc, piz, piztr, zout, absprofil   as sosgpu_profile
+ *       smax             highest Fourier order of the wavelength's context (iborm_max of sosgpu_create): caps IBORM
+ *       nterm            exponential terms of its gas tables; 0 = no gas (ABSPROFIL = 7): then nbins must be 1
+ *       xk_off, ro_off, alt_off   where its xk[8][nterm][nblev-1], ro[8][nblev-1] and altitude grid altabs[nblev] start
+ *                        in d_gas, counted in doubles (ignored with nterm = 0)
+ *   d_wl_of_bin[nb]      index into wl of every bin (int32);  d_ik[nb][8] as sosgpu_absprofile (rows of no-gas bins unused)
+ *   d_gas[gas_doubles]   the wavelengths' tables, packed; nblev (2..64) is common to the launch; both unused when no
+ *                        wavelength has gas (NULL, 0, nblev 0, d_ik and d_tabs NULL)
+ *   d_table              DEVICE work area of nwl * sosgpu_profile_table_entry_bytes() bytes: the per-wavelength table, copied
+ *                        there on `stream` from a pinned block the library recycles
+ *   d_nogas[nwl][4][SOSGPU_NOGAS_LEVELS]   DEVICE work area: the no-gas block of every wavelength
+ * Outputs (device) for the concatenated bins: d_tabs[nb][nblev] (TAUABS, as sosgpu_absprofile; rows of no-gas bins are not
+ * written), d_prof[nb][3][lp], d_nt[nb], d_iborm[nb], d_zprof[nb][lp], d_scal[nb][4] as sosgpu_profile; d_jout[nb] /
+ * d_zz[nb] are written for the bins of wavelengths with zout != -1 only (both may be NULL when no wavelength has one).
+ * A bin whose profile does not fit comes back with nt = -1.  A wavelength that cannot be profiled at all is reported with
+ * its index in *bad_wl (NULL allowed; -1 = none) and nothing is queued: SOSGPU_E_UNSUPPORTED when its no-gas grid needs
+ * more than CTE_OS_NT levels (sosgpu_profile_nogas_levels(tr, ta) < 0 tells beforehand), SOSGPU_E_ARG for the argument rules
+ * of sosgpu_profile / sosgpu_absprofile.  Asynchronous on `stream`; nothing is waited for, and the work areas and inputs
+ * must stay allocated until the three kernels have run. */
+typedef struct sosgpu_profile_wl {
+    double tr, hr, ta, ha;
+    double a_tronc, piz, piztr, zout;
+    int64_t xk_off, ro_off, alt_off;
+    int32_t nterm, nbins, absprofil, smax;
+} sosgpu_profile_wl;
+size_t sosgpu_profile_table_entry_bytes(void);
+/* level count NT of the no-gas grid of (tr, ta) (SOS_PROFIL.F:349-366), or -1: more than CTE_OS_NT levels / no scatterer */
+int  sosgpu_profile_nogas_levels(double tr, double ta);
+int  sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
+                             const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
+                             void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
+                             double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal, int *bad_wl, void *stream);
 
 /* Replaces SOS_MIE + SOS_FPHASE_MIE (src/SOS_MIE.F:205, :801) for a whole grid of size parameters, no MIE cache file:
  *   xmu[2 nbmu + 1]  cosines RMU(-nbmu:nbmu) of the Mie angle set (host); rn, in: refractive index (in <= 0)

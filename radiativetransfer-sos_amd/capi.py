@@ -21,6 +21,7 @@ EXPORTS = [
     "sosgpu_granu_batch",
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
+    "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -31,6 +32,14 @@ class GranuJob(C.Structure):
     """sosgpu_granu_job (include/sosgpu.h)."""
     _fields_ = [("d_rec", C.c_void_p), ("nalpha", C.c_int32), ("igranu", C.c_int32), ("v1", C.c_double), ("v2", C.c_double),
                 ("v3", C.c_double), ("wa", C.c_double), ("alphaf", C.c_double)]
+
+
+class ProfileWl(C.Structure):
+    """sosgpu_profile_wl (include/sosgpu.h): one wavelength of sosgpu_profile_spectrum."""
+    _fields_ = [("tr", C.c_double), ("hr", C.c_double), ("ta", C.c_double), ("ha", C.c_double),
+                ("a_tronc", C.c_double), ("piz", C.c_double), ("piztr", C.c_double), ("zout", C.c_double),
+                ("xk_off", C.c_int64), ("ro_off", C.c_int64), ("alt_off", C.c_int64),
+                ("nterm", C.c_int32), ("nbins", C.c_int32), ("absprofil", C.c_int32), ("smax", C.c_int32)]
 
 
 class SosgpuError(RuntimeError):
@@ -135,6 +144,13 @@ def lib():
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.sosgpu_profile_nogas.restype = i32
         L.sosgpu_profile_nogas.argtypes = [i32, dbl, dbl, dbl, dbl, vp, vp]
+        L.sosgpu_profile_table_entry_bytes.restype = C.c_size_t
+        L.sosgpu_profile_table_entry_bytes.argtypes = []
+        L.sosgpu_profile_nogas_levels.restype = i32
+        L.sosgpu_profile_nogas_levels.argtypes = [dbl, dbl]
+        L.sosgpu_profile_spectrum.restype = i32
+        L.sosgpu_profile_spectrum.argtypes = [i32, i32, vp, i32, vp, vp, vp, C.c_size_t, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, vp, vp, C.POINTER(i32), vp]
         L.sosgpu_os_flops.restype = i32
         L.sosgpu_os_flops.argtypes = [vp, i32, vp, vp, vp, C.POINTER(dbl)]
         L.sosgpu_last_solve_ms.restype = i32

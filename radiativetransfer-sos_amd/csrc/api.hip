@@ -1296,6 +1296,131 @@ extern "C" int sosgpu_absprofile(int device, int nb, int nlev, int nterm, const 
     return SOSGPU_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The profile stage of many wavelengths as three launches (profile.hip, the *_table kernels).
+// ---------------------------------------------------------------------------------------------
+namespace {
+// Pinned staging blocks of the per-wavelength table: the entry point has no context to keep one (sosgpu_ctx_table), so the
+// library recycles them -- a block is free again when the event recorded behind its copy has passed.  Never waited for.
+struct StageBlock { void *p; size_t bytes; hipEvent_t ev; int device; bool busy; };
+std::mutex g_stage_mutex;
+std::vector<StageBlock> g_stage;
+
+int stage_take(int device, size_t bytes, size_t *slot)
+{
+    std::lock_guard<std::mutex> lk(g_stage_mutex);
+    for (size_t i = 0; i < g_stage.size(); i++) {
+        StageBlock &s = g_stage[i];
+        if (s.busy || s.device != device || s.bytes < bytes) continue;
+        if (hipEventQuery(s.ev) != hipSuccess) { (void)hipGetLastError(); continue; }       // its copy has not passed yet
+        s.busy = true;
+        *slot = i;
+        return SOSGPU_OK;
+    }
+    StageBlock s;
+    s.bytes = std::max(bytes, (size_t)16384); s.device = device; s.busy = true; s.p = nullptr;
+    HIPCHK(hipHostMalloc(&s.p, s.bytes, hipHostMallocDefault));
+    if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(s.p); return SOSGPU_E_HIP; }
+    g_stage.push_back(s);
+    *slot = g_stage.size() - 1;
+    return SOSGPU_OK;
+}
+
+void *stage_ptr(size_t slot)
+{
+    std::lock_guard<std::mutex> lk(g_stage_mutex);
+    return g_stage[slot].p;
+}
+
+// the copy from the block is queued on st (or was not): record the event that frees it
+void stage_release(size_t slot, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(g_stage_mutex);
+    (void)hipEventRecord(g_stage[slot].ev, st);
+    g_stage[slot].busy = false;
+}
+}  // namespace
+
+extern "C" size_t sosgpu_profile_table_entry_bytes(void) { return sizeof(ProfileWl); }
+
+extern "C" int sosgpu_profile_nogas_levels(double tr, double ta)
+{
+    double t_first = 0., t_layer = 0.;
+    if (tr < 0. || ta < 0.) return -1;
+    return profile_nogas_grid(tr, ta, &t_first, &t_layer);
+}
+
+extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
+                                       const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
+                                       void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt,
+                                       int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
+                                       int *bad_wl, void *stream)
+{
+    if (bad_wl) *bad_wl = -1;
+    if (nwl < 1 || !wl || nb < 1 || lp < 2 || !d_wl_of_bin || !d_table || !d_nogas) return SOSGPU_E_ARG;
+    if (!d_prof || !d_nt || !d_iborm || !d_zprof || !d_scal) return SOSGPU_E_ARG;
+    if ((d_jout == nullptr) != (d_zz == nullptr)) return SOSGPU_E_ARG;
+    // --- the rules of sosgpu_profile / sosgpu_absprofile, per wavelength, before anything is queued
+    std::vector<ProfileWl> tab((size_t)nwl);
+    long long bins = 0;
+    bool any_gas = false;
+    for (int w = 0; w < nwl; w++) {
+        const sosgpu_profile_wl &s = wl[w];
+        ProfileWl &t = tab[w];
+        if (bad_wl) *bad_wl = w;
+        if (s.nbins < 1 || s.nterm < 0 || s.smax < 0) return SOSGPU_E_ARG;
+        if (!(s.hr > 0.) || !(s.ha > 0.) || s.tr < 0. || s.ta < 0.) return SOSGPU_E_ARG;
+        if (s.zout != -1.0 && !d_jout) return SOSGPU_E_ARG;
+        if (s.nterm > 0) {
+            any_gas = true;
+            if (!d_gas || !d_ik || !d_tabs || nblev < 2) return SOSGPU_E_ARG;
+            if (nblev > SOS_PROF_NBLEV_MAX) return SOSGPU_E_UNSUPPORTED;
+            const long long nl1 = nblev - 1, gd = (long long)gas_doubles;
+            if (s.xk_off < 0 || s.ro_off < 0 || s.alt_off < 0 || s.xk_off + 8ll * s.nterm * nl1 > gd || s.ro_off + 8 * nl1 > gd ||
+                s.alt_off + nblev > gd)
+                return SOSGPU_E_ARG;
+        } else if (s.nbins != 1) return SOSGPU_E_ARG;
+        t.tr = s.tr; t.hr = s.hr; t.ta = s.ta; t.ha = s.ha; t.a_tronc = s.a_tronc; t.piz = s.piz; t.piztr = s.piztr; t.zout = s.zout;
+        t.t_first = 0.; t.t_layer = 0.;
+        t.nt_ng = profile_nogas_grid(s.tr, s.ta, &t.t_first, &t.t_layer);
+        if (t.nt_ng < 0) return SOSGPU_E_UNSUPPORTED;          // more than CTE_OS_NT levels (IER = -1 in the reference)
+        if (lp <= t.nt_ng) return SOSGPU_E_ARG;
+        t.xk_off = s.xk_off; t.ro_off = s.ro_off; t.alt_off = s.alt_off;
+        t.nterm = s.nterm; t.absprofil = s.absprofil; t.smax = s.smax;
+        bins += s.nbins;
+    }
+    if (bad_wl) *bad_wl = -1;
+    if (bins != nb) return SOSGPU_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
+    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    // --- the table: pinned block -> d_table on the caller's stream, nothing waited for
+    const size_t bytes = (size_t)nwl * sizeof(ProfileWl);
+    size_t slot = 0;
+    if (int rc = stage_take(device, bytes, &slot)) return rc;
+    memcpy(stage_ptr(slot), tab.data(), bytes);
+    const hipError_t ce = hipMemcpyAsync(d_table, stage_ptr(slot), bytes, hipMemcpyHostToDevice, st);
+    stage_release(slot, st);
+    HIPCHK(ce);
+    const ProfileWl *d_tab = (const ProfileWl *)d_table;
+    const int NG = SOSGPU_NOGAS_LEVELS;
+    launch_profile_nogas_table(d_tab, nwl, d_nogas, NG, st);
+    HIPCHK(hipGetLastError());
+    if (any_gas) {
+        launch_absprofile_table(d_tab, nwl, d_wl_of_bin, nb, nblev, d_ik, d_gas, d_tabs, st);
+        HIPCHK(hipGetLastError());
+    }
+    ProfileTableArgs q;
+    q.nb = nb; q.nwl = nwl; q.lp = lp; q.nblev = any_gas ? nblev : 0; q.ngl = NG;
+    q.tab = d_tab; q.wl_of_bin = d_wl_of_bin; q.gas = d_gas; q.tabs = any_gas ? d_tabs : nullptr; q.nogas = d_nogas;
+    q.prof = d_prof; q.zprof = d_zprof; q.zz = d_zz; q.scal = d_scal; q.nt = d_nt; q.iborm = d_iborm; q.jout = d_jout;
+    launch_profile_table(q, st);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
 extern "C" int sosgpu_mie(int device, int nbmu, const double *xmu, double rn, double in, int nalpha, const double *alphas,
                           float *d_rec, double *d_g, void *stream)
 {

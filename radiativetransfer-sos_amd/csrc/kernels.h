@@ -64,6 +64,27 @@ struct ProfileArgs {
     int32_t *nt, *iborm, *jout;
 };
 void launch_profile(const ProfileArgs &a, hipStream_t st);
+// Table forms of the three profile kernels (sosgpu_profile_spectrum): the bins of MANY wavelengths in one launch per kernel.
+// One entry per wavelength, uploaded by the entry point; offsets count doubles from the start of the packed gas buffer.
+struct ProfileWl {
+    double tr, hr, ta, ha, a_tronc, piz, piztr, zout;
+    double t_first, t_layer;                     // steps of the no-gas grid (profile_nogas_grid)
+    long long xk_off, ro_off, alt_off;           // xk[8][nterm][nblev-1], ro[8][nblev-1], altabs[nblev] of the wavelength
+    int nterm;                                   // 0: no gas (one bin, ABSPROFIL = 7)
+    int absprofil, smax, nt_ng;                  // nt_ng < 1: refused by the host, its bins come back with nt = -1
+};
+struct ProfileTableArgs {
+    int nb, nwl, lp, nblev, ngl;                 // ngl: levels per array of a no-gas block (SOSGPU_NOGAS_LEVELS)
+    const ProfileWl *tab;
+    const int32_t *wl_of_bin;                    // [nb]
+    const double *gas, *tabs, *nogas;            // packed gas buffer, tabs[nb][nblev] (or null), nogas[nwl][4][ngl]
+    double *prof, *zprof, *zz, *scal;
+    int32_t *nt, *iborm, *jout;
+};
+void launch_profile_nogas_table(const ProfileWl *d_tab, int nwl, double *d_ng, int ngl, hipStream_t st);
+void launch_absprofile_table(const ProfileWl *d_tab, int nwl, const int32_t *d_wl_of_bin, int nb, int nlev, const int32_t *d_ik,
+                             const double *d_gas, double *d_tabs, hipStream_t st);
+void launch_profile_table(const ProfileTableArgs &q, hipStream_t st);
 // output levels of nz altitudes (profile.hip k_output_levels): jout / zz / tauout[nz][nb] from zprof[nb][lp], prof[nb][3][lp], nt[nb]
 struct OutputLevelArgs {
     int nb, lp, nz;

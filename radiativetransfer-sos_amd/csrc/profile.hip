@@ -213,9 +213,10 @@ __device__ double scan_first_wave(double tr, double hr, double ta, double ha, co
 // sosgpu_profile -- NT x 25 bisection steps x 2 exp, 0.3-0.4 ms of every wavelength of a spectrum plus a waited-for upload;
 // the level count and the two steps are closed forms of (TR, TA) and stay there (api.hip, profile_nogas_grid).
 //   z, h, pca, pcm [nt + 1]: altitude, cumulative optical depth, aerosol and molecular share of the layer ending at the level
-__global__ __launch_bounds__(64) void k_profile_nogas(double tr, double hr, double ta, double ha, int nt, double t_first,
-                                                      double t_layer, double *__restrict__ z, double *__restrict__ h,
-                                                      double *__restrict__ pca, double *__restrict__ pcm)
+// (the body is shared by k_profile_nogas and the table form k_profile_nogas_table: one statement sequence, one result)
+__device__ __forceinline__ void profile_nogas_body(double tr, double hr, double ta, double ha, int nt, double t_first,
+                                                   double t_layer, double *__restrict__ z, double *__restrict__ h,
+                                                   double *__restrict__ pca, double *__restrict__ pcm)
 {
     const double TOA = 120.0, DELTA_Z = (double)0.05f;
     if (ta == 0.0) {                                             // molecules only: closed form (SOS_PROFIL.F:367-392)
@@ -255,6 +256,30 @@ __global__ __launch_bounds__(64) void k_profile_nogas(double tr, double hr, doub
     pcm[nt] = vr / (vr + va); pca[nt] = va / (vr + va);
 }
 
+__global__ __launch_bounds__(64) void k_profile_nogas(double tr, double hr, double ta, double ha, int nt, double t_first,
+                                                      double t_layer, double *__restrict__ z, double *__restrict__ h,
+                                                      double *__restrict__ pca, double *__restrict__ pcm)
+{
+    profile_nogas_body(tr, hr, ta, ha, nt, t_first, t_layer, z, h, pca, pcm);
+}
+
+// Table form: one wavefront per WAVELENGTH of a part of a spectrum, its (TR, HR, TA, HA) and grid from the device table, its
+// block at ng + w * 4 * ngl.  A wavelength the host refused (nt_ng < 1) writes nothing.
+__global__ __launch_bounds__(64) void k_profile_nogas_table(const ProfileWl *__restrict__ tab, int nwl, double *__restrict__ ng, int ngl)
+{
+    const int w = blockIdx.x;
+    if (w >= nwl) return;
+    const ProfileWl &t = tab[w];
+    if (t.nt_ng < 1 || t.nt_ng >= ngl) return;
+    double *z = ng + (size_t)w * 4 * ngl;
+    profile_nogas_body(t.tr, t.hr, t.ta, t.ha, t.nt_ng, t.t_first, t.t_layer, z, z + ngl, z + 2 * ngl, z + 3 * ngl);
+}
+
+void launch_profile_nogas_table(const ProfileWl *d_tab, int nwl, double *d_ng, int ngl, hipStream_t st)
+{
+    k_profile_nogas_table<<<nwl, 64, 0, st>>>(d_tab, nwl, d_ng, ngl);
+}
+
 void launch_profile_nogas(double tr, double hr, double ta, double ha, int nt, double t_first, double t_layer, double *d_ng, int ng,
                           hipStream_t st)
 {
@@ -269,13 +294,10 @@ void launch_profile_nogas(double tr, double hr, double ta, double ha, int nt, do
 // WAVE = true (the form launched): ONE WAVEFRONT per bin.  All 64 lanes run the bin's level loop in lockstep on the same
 // values (stores of one instruction go to one address) and share the work where the time is: SOS_DISC (disc_wave).  A single
 // bin takes 6.5-9.7 ms with one lane (most of the latency of a 25-bin sos_proc call) and 2.3-2.9 ms this way; 4096 bins 24.8 -> 3.8-5.3 ms.
+// (the body of bin b, shared by k_profile and the table form k_profile_table: s_alt / s_tab are the caller's LDS blocks)
 template <bool WAVE>
-__global__ __launch_bounds__(64) void k_profile(ProfileArgs a, int bpw)
+__device__ __forceinline__ void profile_bin_body(const ProfileArgs &a, const int b, double *s_alt, double *s_tab_slot)
 {
-    if (!WAVE && (int)threadIdx.x >= bpw) return; // no barrier below: every thread only touches its own LDS slice
-    const int b = WAVE ? (int)blockIdx.x : blockIdx.x * bpw + threadIdx.x;
-    const int slot = WAVE ? 0 : (int)threadIdx.x;
-    if (b >= a.nb) return;
     const double TCOUCHE = (double)0.005f, T_FIRST = (double)0.0002f, DELTA_Z = (double)0.05f, DZ = (double)0.001f;
     const double TAUABS_MAX = 1.5, TOA = 120.0;
     const int OS_NT = 600, OS_NT_MIN = 100;
@@ -283,13 +305,11 @@ __global__ __launch_bounds__(64) void k_profile(ProfileArgs a, int bpw)
     double *H = a.prof + (size_t)b * 3 * a.lp, *XD = H + a.lp, *YD = XD + a.lp;
     double *Z = a.zprof + (size_t)b * a.lp;
     // the bin's absorption profile is read thousands of times: keep it (and the altitude grid) in LDS
-    __shared__ double s_alt[SOS_PROF_NBLEV_MAX];
-    __shared__ double s_tab[WAVE ? 1 : 64][SOS_PROF_NBLEV_MAX + 1];     // +1: odd stride, lanes on different banks
     GasProf g;
     g.n = a.nblev; g.alt = s_alt; g.tab = nullptr;
     if (a.tabs) {
-        for (int i = 0; i < a.nblev; i++) { s_tab[slot][i] = a.tabs[(size_t)b * a.nblev + i]; s_alt[i] = a.altabs[i]; }
-        g.tab = s_tab[slot];
+        for (int i = 0; i < a.nblev; i++) { s_tab_slot[i] = a.tabs[(size_t)b * a.nblev + i]; s_alt[i] = a.altabs[i]; }
+        g.tab = s_tab_slot;
     }
     const double tgtot = g.tab ? g.tab[a.nblev - 1] : 0.0;
     int nt;
@@ -464,6 +484,49 @@ __global__ __launch_bounds__(64) void k_profile(ProfileArgs a, int bpw)
     a.scal[4 * b + 3] = tauout;
 }
 
+template <bool WAVE>
+__global__ __launch_bounds__(64) void k_profile(ProfileArgs a, int bpw)
+{
+    if (!WAVE && (int)threadIdx.x >= bpw) return; // no barrier below: every thread only touches its own LDS slice
+    const int b = WAVE ? (int)blockIdx.x : blockIdx.x * bpw + threadIdx.x;
+    const int slot = WAVE ? 0 : (int)threadIdx.x;
+    if (b >= a.nb) return;
+    __shared__ double s_alt[SOS_PROF_NBLEV_MAX];
+    __shared__ double s_tab[WAVE ? 1 : 64][SOS_PROF_NBLEV_MAX + 1];     // +1: odd stride, lanes on different banks
+    profile_bin_body<WAVE>(a, b, s_alt, s_tab[slot]);
+}
+
+// Table form: one wavefront per bin of ALL wavelengths of a part of a spectrum.  The wavefront reads the index of its
+// wavelength and forms, from that wavelength's table entry, the ProfileArgs the per-wavelength launch gets as its kernel
+// argument -- with the output arrays of the whole part, so that bin b of the part is bin b of the body.  A wavelength without
+// gas (nterm 0) is a one-bin wavelength with tabs = null; jout / zz are written for wavelengths with zout != -1 only.
+__global__ __launch_bounds__(64) void k_profile_table(ProfileTableArgs q)
+{
+    const int b = blockIdx.x;
+    if (b >= q.nb) return;
+    const int w = q.wl_of_bin[b];
+    if (w < 0 || w >= q.nwl) return;
+    const ProfileWl &t = q.tab[w];
+    const bool gas = t.nterm > 0;
+    const double *ngp = q.nogas + (size_t)w * 4 * q.ngl;
+    ProfileArgs a;
+    a.nb = q.nb; a.lp = q.lp; a.nblev = gas ? q.nblev : 0; a.absprofil = gas ? t.absprofil : 7; a.smax = t.smax; a.nt_ng = t.nt_ng;
+    a.tr = t.tr; a.hr = t.hr; a.ta = t.ta; a.ha = t.ha; a.a_tronc = t.a_tronc; a.piz = t.piz; a.piztr = t.piztr; a.zout = t.zout;
+    a.altabs = gas ? q.gas + t.alt_off : nullptr; a.tabs = gas ? q.tabs : nullptr;
+    a.z_ng = ngp; a.h_ng = ngp + q.ngl; a.pca_ng = ngp + 2 * q.ngl; a.pcm_ng = ngp + 3 * q.ngl;
+    a.prof = q.prof; a.zprof = q.zprof; a.scal = q.scal; a.nt = q.nt; a.iborm = q.iborm;
+    const bool lev = t.zout != -1.0 && q.jout;
+    a.jout = lev ? q.jout : nullptr; a.zz = lev ? q.zz : nullptr;
+    __shared__ double s_alt[SOS_PROF_NBLEV_MAX];
+    __shared__ double s_tab[SOS_PROF_NBLEV_MAX + 1];
+    profile_bin_body<true>(a, b, s_alt, s_tab);
+}
+
+void launch_profile_table(const ProfileTableArgs &q, hipStream_t st)
+{
+    k_profile_table<<<q.nb, 64, 0, st>>>(q);
+}
+
 void launch_profile(const ProfileArgs &a, hipStream_t st)
 {
     // one wavefront per bin; SOSGPU_PROFILE_LANES=1: the one-lane-per-bin form (about 2048 wavefronts whatever the batch size)
@@ -487,12 +550,11 @@ void launch_profile(const ProfileArgs &a, hipStream_t st)
 // reference's order) and its transmission; the running product TRS is then formed in layer order -- the same left-to-right
 // product as the loop's -- each lane keeping the value of its own layer, and takes its logarithm.  Bands with more layers than
 // lanes walk the layers in blocks of 64 with the product carried over.
-__global__ __launch_bounds__(64) void k_absprofile(int nb, int nlev, int nterm, const int32_t *__restrict__ ik,
-                                                   const double *__restrict__ xk, const double *__restrict__ ro,
-                                                   double *__restrict__ tabs)
+// (the body of bin b, shared by k_absprofile and the table form k_absprofile_table)
+__device__ __forceinline__ void absprofile_bin_body(const int b, const int lane, int nlev, int nterm, const int32_t *__restrict__ ik,
+                                                    const double *__restrict__ xk, const double *__restrict__ ro,
+                                                    double *__restrict__ tabs)
 {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= nb) return;
     const int nl1 = nlev - 1;
     int term[8];
     for (int k = 0; k < 8; k++) term[k] = min(max(ik[8 * b + k], 1), nterm) - 1;
@@ -514,6 +576,36 @@ __global__ __launch_bounds__(64) void k_absprofile(int nb, int nlev, int nterm, 
         }
         if (j < nl1) tabs[(size_t)b * nlev + j + 1] = (mine > 0.) ? -log(mine) : 999.;           // CTE_TAUABS_MAX (SOS.h:297)
     }
+}
+
+__global__ __launch_bounds__(64) void k_absprofile(int nb, int nlev, int nterm, const int32_t *__restrict__ ik,
+                                                   const double *__restrict__ xk, const double *__restrict__ ro,
+                                                   double *__restrict__ tabs)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= nb) return;
+    absprofile_bin_body(b, lane, nlev, nterm, ik, xk, ro, tabs);
+}
+
+// Table form: one wavefront per bin of all wavelengths of a part; NTERM and the places of the wavelength's xk / ro tables in
+// the packed buffer `gas` come from its table entry.  Bins of a wavelength without gas (nterm 0) leave their row alone.
+__global__ __launch_bounds__(64) void k_absprofile_table(const ProfileWl *__restrict__ tab, int nwl, const int32_t *__restrict__ wl_of_bin,
+                                                         int nb, int nlev, const int32_t *__restrict__ ik,
+                                                         const double *__restrict__ gas, double *__restrict__ tabs)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= nb) return;
+    const int w = wl_of_bin[b];
+    if (w < 0 || w >= nwl) return;
+    const ProfileWl &t = tab[w];
+    if (t.nterm < 1) return;
+    absprofile_bin_body(b, lane, nlev, t.nterm, ik, gas + t.xk_off, gas + t.ro_off, tabs);
+}
+
+void launch_absprofile_table(const ProfileWl *d_tab, int nwl, const int32_t *d_wl_of_bin, int nb, int nlev, const int32_t *d_ik,
+                             const double *d_gas, double *d_tabs, hipStream_t st)
+{
+    k_absprofile_table<<<nb, 64, 0, st>>>(d_tab, nwl, d_wl_of_bin, nb, nlev, d_ik, d_gas, d_tabs);
 }
 
 void launch_absprofile(int nb, int nlev, int nterm, const int32_t *d_ik, const double *d_xk, const double *d_ro, double *d_tabs,

@@ -903,7 +903,18 @@ if PREPARE_SEGMENTS is not None:
     _solver_mod.SEG = _seg
 
 
-def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None):
+def _profiles_deferrable(tr, hr, ta, ha):
+    """True when sosgpu_profile_spectrum takes this wavelength: the argument rules of sosgpu_profile hold and its no-gas grid
+    fits CTE_OS_NT levels.  A wavelength that fails here keeps the per-wavelength path, whose error is the documented one."""
+    from . import capi
+    try:
+        ok = float(hr) > 0.0 and float(ha) > 0.0 and float(tr) >= 0.0 and float(ta) >= 0.0
+        return bool(ok) and capi.lib().sosgpu_profile_nogas_levels(float(tr), float(ta)) >= 1
+    except Exception:
+        return False
+
+
+def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False):
     """Everything of one SOS_PROC call up to the CKD bin loop (SOS_PROC.F:1310-3458): parameter checks, SOS_ANGLES,
     SOS_AEROSOLS, SOS_SURFACE, SOS_PREPA_ABSPROFILE, SOS_PREPA_OS, and the profiles of every bin of the band on the device
     (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Returns a _Plan whose `ctx` the caller closes.
@@ -911,7 +922,10 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     whole band stays on this rank (sos_spectrum distributes wavelengths, not bins).
     aer_stream: HIP stream (torch.cuda.Stream) for the aerosol step, whose device calls are host-synchronous -- sos_spectrum keeps
     them off the streams its asynchronous work is queued on.
-    aer_at_wa: the result of SOS_AEROSOLS at the simulation wavelength when sos_spectrum has formed it already (aerosols_many)."""
+    aer_at_wa: the result of SOS_AEROSOLS at the simulation wavelength when sos_spectrum has formed it already (aerosols_many).
+    defer_profiles (_spectrum_pass only): a call that qualifies -- -AP.AerProfile.Type 1, no -SOS.Trans, -SOS.AbsModeCKD 1 or
+    no gas, band not sharded -- gets no profile launches here: the plan comes back with `bins` None and `profile_request`, the
+    request solver.make_profiles_spectrum takes, and the pass makes the profiles of a whole part in three launches."""
     _seg(None)
     missing = [k for k in SOS_PROC_KWARGS if k not in kw]
     if missing:
@@ -1022,7 +1036,9 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     # head start: the level placement of the wavelength's no-gas profile (a ~1 ms serial chain on one wavefront) is queued now and
     # runs while the host prepares gas tables, surface and context (a refused profile is reported by make_profiles below)
     nogas = None
-    if iprofil == 1:
+    defer = bool(defer_profiles) and iprofil == 1 and str(p["fictrans"]).strip() == "NO_OUTPUT" and \
+        (absprofil == 7 or p["imode_ckd_calcul"] == 1) and _profiles_deferrable(tr, p["hr"], ta, ha)
+    if iprofil == 1 and not defer:
         try:
             from .solver import nogas_profile
             nogas = nogas_profile(tr, p["hr"], ta, ha, device)
@@ -1112,7 +1128,17 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
         # --- the CKD bin loop (SOS_PROC.F:3459-3594): profiles of every bin on the device
         band_sharded = False                          # True: every rank holds a slice of the band and the partials are all-reduced
         tabs_flux = None                              # TAUABS of the band's last bin (Flux file): host array or [.][nlev] device tensor
-        if not use_gas and iprofil == 1:
+        request = None                                # deferred: what solver.make_profiles_spectrum needs of this wavelength
+        common = dict(tr=tr, hr=p["hr"], ta=ta, ha=ha, a_tronc=a_tronc, piz=piz, piztr=piztr, zout=zout, smax=ctx.smax)
+        if defer and use_gas and (_dist_rank_world()[1] > 1 and shard_bins or len(prep["altabs"]) > 64 or not len(aik)):
+            defer = False                             # (a sharded band; more levels than the kernels hold: the error is make_profiles')
+        if defer and not use_gas:
+            request = dict(common, ik=None, absprofil=7)
+            bins, aik = None, np.ones(1)
+        elif defer:
+            request = dict(common, ik=ik, xk=xk, ro=ro_lay, altabs=prep["altabs"], absprofil=absprofil)
+            bins = None
+        elif not use_gas and iprofil == 1:
             # the single no-gas profile of the wavelength: SOS_PROFILE, the PROFIL-file round trip, the rescale, IBORM and the
             # output level all inside sosgpu_profile (the Python restatement profile_nogas costs 2-3 ms and stays as the checker
             # of tests/test_profile.py)
@@ -1166,7 +1192,7 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
             except Exception as e:
                 raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
             tabs_flux = tabs_last if band_sharded else tabs
-        if pl.want_trans and bins["nb"]:                                             # SOS.F:600-635
+        if pl.want_trans and bins is not None and bins["nb"]:                        # SOS.F:600-635
             tdifmus_b, pl.tdifmug = ctx.diffuse_transmissions(bins)
             sc = bins["scal"] if hasattr(bins["scal"], "clone") else torch.from_numpy(np.asarray(bins["scal"])).to(ctx.device)
             sc = sc.clone()
@@ -1177,6 +1203,7 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
         raise
     _seg('profiles')
     pl.bins, pl.aik, pl.band_sharded, pl.tabs_flux = bins, aik, band_sharded, tabs_flux
+    pl.profile_request = request
     return pl
 
 
@@ -1509,6 +1536,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                       "queues and the device side of the preparation becomes the limit (about 2/3 of the throughput); export "
                       "GPU_MAX_HW_QUEUES=16 before the first GPU call of the process (16 // processes when several processes share "
                       "the GPU)" % (len(side), fn), RuntimeWarning, stacklevel=3)
+    # SOS_SPECTRUM_PROFILES_PER_CALL=1: every wavelength makes its own profile launches, as sos_proc does (A/B timing)
+    batch_profiles = not os.environ.get("SOS_SPECTRUM_PROFILES_PER_CALL")
     where, err = -1, None                               # the wavelength being worked on (named by a failure)
     # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
     # a growing list of result tuples, and the collections this triggers re-walk the results again and again (SOS_SPECTRUM_KEEP_GC=1
@@ -1542,16 +1571,36 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                         where = i
                         with torch.cuda.stream(side[k % len(side)]):
                             pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
-                                          aer_at_wa=aer_wa.get(i))
+                                          aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles)
                             pl.writes_files = True
                             pl.index = i
                             plans.append(pl)
-                            if alts is not None:
+                            if alts is not None and pl.bins is not None:
                                 pl.levels = pl.ctx.output_levels(pl.bins, alts)
                         if debug:
                             torch.cuda.synchronize(dev)
                             print("[%s] prepared" % fn, i, flush=True)
                         part.append(pl)
+                    # the profiles of the part's qualifying wavelengths: three launches for all their bins (the operators the side
+                    # streams are still building are not needed for them), one more for the output slots
+                    deferred = [pl for pl in part if pl.bins is None]
+                    if deferred:
+                        where = deferred[0].index
+                        info = {}
+                        try:
+                            made = solver.make_profiles_spectrum([pl.profile_request for pl in deferred], dev, part=info)
+                        except Exception as e:
+                            if info.get("bad") is not None:
+                                where = deferred[info["bad"]].index
+                            raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
+                        lv = None if alts is None else deferred[0].ctx.output_levels(info["bins"], alts)
+                        for g, pl in enumerate(deferred):
+                            # (views of the part's blocks: the plans keep them alive until the chunk's streams are synchronised)
+                            pl.bins, pl.tabs_flux, pl.profile_part = made[g], info["tabs"][g], info
+                            if lv is not None:
+                                b0, b1 = int(info["seg"][g]), int(info["seg"][g + 1])
+                                pl.levels = dict(nz=lv["nz"], jout=lv["jout"][:, b0:b1], zz=lv["zz"][:, b0:b1],
+                                                 tauout=lv["tauout"][:, b0:b1])
                     for st in side:
                         main_st.wait_stream(st)
                     t1 = time.perf_counter()
@@ -1585,6 +1634,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                         solved.append((gp, rec, scal, table))
                     for pl in single:
                         where = pl.index
+                        if alts is not None and pl.levels["jout"] is not None and not pl.levels["jout"].is_contiguous():
+                            pl.levels = dict(pl.levels, **{k: pl.levels[k].contiguous() for k in ("jout", "zz", "tauout")})
                         rec, scal = solve_single(pl)
                         solved.append(([pl], rec, scal, None))
                     t0 = time.perf_counter()
@@ -1657,8 +1708,12 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     """A spectrum of sos_proc calls -- one per wavelength, as the reference issues them one after the other
     (binding/run_sos.py:640-695; the bin loop of each is SOS_PROC.F:3459-3594) -- as ONE pass over the GPU:
 
-      1. the host preparation of every wavelength (parameter checks, angles, aerosol model, gas tables, surface) and the
-         profiles of all its CKD bins on the device (sosgpu_absprofile + sosgpu_profile), nothing waited for;
+      1. the host preparation of every wavelength (parameter checks, angles, aerosol model, gas tables, surface, context), then
+         the profiles of ALL CKD bins of a part of the chunk in three launches (sosgpu_profile_spectrum through
+         solver.make_profiles_spectrum: no-gas profiles, SOS_ABSPROFILE, SOS_PROFILE, every wavefront taking its wavelength's
+         parameters from a device table), nothing waited for.  Calls with -SOS.Trans, -SOS.AbsModeCKD 2 or an aerosol layer
+         (-AP.AerProfile.Type 2), and a call whose profile the library refuses (its error is then sos_proc's), make their own
+         profile launches (sosgpu_absprofile + sosgpu_profile) as sos_proc does;
       2. ALL bins of ALL wavelengths in one launch of the fused solver per group of wavelengths sharing a kernel variant
          (direction count, highest Fourier order, surface-matrix flag, level capacity, output level): a device table of the
          wavelength contexts, every bin carrying the index of its own (sosgpu_ctx_table + sosgpu_os_solve_multi), and one
@@ -1682,9 +1737,11 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     timings: optional dict, filled with host-side phase times in seconds (prepare, solve_launch, wait, trphi, finish).
     parts: a chunk is handed to the solver in this many parts (the solves of one part overlap the host preparation of the next).
     prep_streams: HIP streams the per-wavelength preparation kernels are spread over (export GPU_MAX_HW_QUEUES=16 to give them
-    hardware queues of their own, solver.solve_many).  The preparation kernels of one wavelength are a serial chain of about
-    3 ms on a few wavefronts (level placement of the no-gas profile and of every bin: bisections), so the device side alone
-    sustains prep_streams / 3 ms wavelengths per second: 16 streams keep it ahead of a host that spends 0.6 ms per wavelength."""
+    hardware queues of their own, solver.solve_many): source operators, surface and aerosol steps of the wavelengths overlap
+    there.  The profile kernels (level placement of the no-gas profile and of every bin: bisections, a serial chain of about
+    3 ms on one wavefront per bin) are not among them any more: they run once per part for all its bins, on the stream of the
+    solves.  SOS_SPECTRUM_PROFILES_PER_CALL=1 (environment, for A/B timing) sends every call through the per-wavelength
+    profile launches on its side stream again."""
     return _spectrum_pass("sos_spectrum", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts)
 
 

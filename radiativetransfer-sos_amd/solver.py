@@ -576,6 +576,111 @@ def solve_spectrum(table, bins, ctx_of_bin, seg, aik, out=None, order="cost"):
     return cx.aggregate(out, aik, seg=seg, scal=bins.get("scal"))
 
 
+PROFILE_WL_DTYPE = np.dtype([("tr", "<f8"), ("hr", "<f8"), ("ta", "<f8"), ("ha", "<f8"), ("a_tronc", "<f8"), ("piz", "<f8"),
+                             ("piztr", "<f8"), ("zout", "<f8"), ("xk_off", "<i8"), ("ro_off", "<i8"), ("alt_off", "<i8"),
+                             ("nterm", "<i4"), ("nbins", "<i4"), ("absprofil", "<i4"), ("smax", "<i4")])   # capi.ProfileWl
+
+
+def pack_profile_requests(requests):
+    """Host side of make_profiles_spectrum (pure numpy): the per-wavelength table, the packed gas buffer and the per-bin
+    wavelength index of a list of profile requests.  A request is a dict with the arguments of SosContext.absorption_profiles
+    and make_profiles of one wavelength -- ik[nb][8], xk[8][nterm][nlev-1], ro[8][nlev-1], altabs[nlev] (ik None: no gas,
+    one bin), tr, hr, ta, ha, a_tronc, piz, piztr, zout, absprofil -- and `smax`, the highest Fourier order of its context.
+    Returns a dict:
+      wl          structured array [nwl] (PROFILE_WL_DTYPE = sosgpu_profile_wl); xk_off / ro_off / alt_off count doubles in buf
+      buf         ONE float64 array for one upload: the gas tables of every wavelength (xk, ro, altabs, in request order), then
+                  ik[nb][8] (int32, rows of no-gas bins zero) at ik_off, then wl_of_bin[nb] (int32) at wob_off
+      gas_doubles, ik_off, wob_off   (in doubles);  nb, nblev (0 without any gas), seg[nwl + 1] (first bin of each request)"""
+    nwl = len(requests)
+    wl = np.zeros(nwl, dtype=PROFILE_WL_DTYPE)
+    gas, iks, counts = [], [], []
+    nblev, off = 0, 0
+    for w, r in enumerate(requests):
+        e = wl[w]
+        for k in ("tr", "hr", "ta", "ha", "a_tronc", "piz", "piztr", "zout"):
+            e[k] = float(r[k])
+        e["smax"] = int(r["smax"])
+        if r.get("ik") is None:
+            e["nterm"], e["nbins"], e["absprofil"] = 0, 1, 7
+            iks.append(np.zeros((1, 8), dtype=np.int32))
+            counts.append(1)
+            continue
+        ik = np.ascontiguousarray(r["ik"], dtype=np.int32)
+        xk, ro = np.ascontiguousarray(r["xk"], dtype=np.float64), np.ascontiguousarray(r["ro"], dtype=np.float64)
+        alt = np.ascontiguousarray(r["altabs"], dtype=np.float64).ravel()
+        nlev = int(alt.size)
+        if ik.ndim != 2 or ik.shape[1] != 8 or ik.shape[0] < 1 or xk.ndim != 3 or xk.shape[0] != 8 or xk.shape[1] < 1 or \
+                xk.shape[2] != nlev - 1 or ro.shape != (8, nlev - 1):
+            raise ValueError("request %d: ik must be [nb][8], xk [8][nterm][nlev-1], ro [8][nlev-1], altabs [nlev]" % w)
+        if nblev and nlev != nblev:
+            raise ValueError("request %d: every wavelength of a launch must have the same number of absorption levels" % w)
+        nblev = nlev
+        e["nterm"], e["nbins"], e["absprofil"] = xk.shape[1], ik.shape[0], int(r["absprofil"])
+        e["xk_off"], e["ro_off"], e["alt_off"] = off, off + xk.size, off + xk.size + ro.size
+        off += xk.size + ro.size + nlev
+        gas += [xk.ravel(), ro.ravel(), alt]
+        iks.append(ik)
+        counts.append(ik.shape[0])
+    nb = int(sum(counts))
+    wob = np.repeat(np.arange(nwl, dtype=np.int32), counts)
+    if nb % 2:
+        wob = np.concatenate([wob, np.zeros(1, dtype=np.int32)])          # (8-byte units)
+    buf = np.concatenate(gas + [np.concatenate(iks).ravel().view(np.float64), wob.view(np.float64)])
+    return dict(wl=wl, buf=buf, gas_doubles=off, ik_off=off, wob_off=off + 4 * nb, nb=nb, nblev=nblev,
+                seg=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64))
+
+
+def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
+    """The profile stage of MANY wavelengths in three launches (sosgpu_profile_spectrum: no-gas profiles, SOS_ABSPROFILE and
+    SOS_PROFILE of every bin of every wavelength, each wavefront taking its wavelength's parameters from a device table)
+    instead of three per wavelength.  requests: see pack_profile_requests.  One upload (its buf), one cleared output allocation
+    for all bins (the two blocks of SosContext.make_profiles), queued on `stream` (a torch stream; None: the current one),
+    nothing waited for.  Returns one `bins` dict per request, as make_profiles returns it for that wavelength alone -- the same
+    keys, dtypes and, bit for bit, values; the tensors are views of the shared blocks.
+    part: optional dict, filled with `bins` (all bins as one dict, for output_levels), `tabs` (per request: TAUABS[nb][nlev]
+    view, or None without gas), `seg`, and -- when the library refuses a wavelength -- `bad`, its index in requests."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    pk = pack_profile_requests(requests)
+    nwl, nb, nblev, seg = len(requests), pk["nb"], pk["nblev"], pk["seg"]
+    L = capi.lib()
+    ng = capi.NOGAS_LEVELS
+    tab_d = -(-nwl * int(L.sosgpu_profile_table_entry_bytes()) // 8)
+    if part is None:
+        part = {}
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        up = _upload(torch.from_numpy(pk["buf"]), dev)
+        # (two cleared blocks for the whole part; the work areas of the launch -- table, no-gas blocks -- ride at the end)
+        o_z, o_s, o_zz, o_t = nb * 3 * lp, nb * 4 * lp, nb * (4 * lp + 4), nb * (4 * lp + 5)
+        o_ng, o_tab = o_t + nb * nblev, o_t + nb * nblev + nwl * 4 * ng
+        fb = torch.zeros(o_tab + tab_d, dtype=torch.float64, device=dev)
+        ib = torch.zeros(3 * nb, dtype=torch.int32, device=dev)
+        prof, zprof, scal = fb[:o_z].view(nb, 3, lp), fb[o_z:o_s].view(nb, lp), fb[o_s:o_zz].view(nb, 4)
+        zz, tabs = fb[o_zz:o_t], (fb[o_t:o_ng].view(nb, nblev) if nblev else None)
+        nt, iborm, jout = ib[:nb], ib[nb:2 * nb], ib[2 * nb:]
+        any_out = bool((pk["wl"]["zout"] != -1.0).any())
+        ik_t = up[pk["ik_off"]:pk["wob_off"]].view(torch.int32) if nblev else None
+        bad = C.c_int(-1)
+        rc = L.sosgpu_profile_spectrum(dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), nb, _ptr(up[pk["wob_off"]:]),
+                                       _ptr(ik_t), _ptr(up) if nblev else None, pk["gas_doubles"], nblev, lp,
+                                       _ptr(fb[o_tab:]), _ptr(fb[o_ng:o_tab]), _ptr(tabs), _ptr(prof), _ptr(nt), _ptr(iborm),
+                                       _ptr(zprof), _ptr(jout) if any_out else None, _ptr(zz) if any_out else None, _ptr(scal),
+                                       C.byref(bad), st)
+    if rc != 0 and bad.value >= 0:
+        part["bad"] = int(bad.value)
+    capi.check(rc, "sosgpu_profile_spectrum")
+    out, tabs_l = [], []
+    for w in range(nwl):
+        b0, b1 = int(seg[w]), int(seg[w + 1])
+        lev = float(pk["wl"]["zout"][w]) != -1.0
+        out.append(dict(nb=b1 - b0, lp=lp, perm=None, nt=nt[b0:b1], iborm=iborm[b0:b1], prof=prof[b0:b1],
+                        jout=jout[b0:b1] if lev else None, zz=zz[b0:b1] if lev else None, zprof=zprof[b0:b1], scal=scal[b0:b1]))
+        tabs_l.append(tabs[b0:b1] if pk["wl"]["nterm"][w] else None)
+    part.update(bins=dict(nb=nb, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=None, zz=None, zprof=zprof, scal=scal),
+                tabs=tabs_l, seg=seg, upload=up)
+    return out
+
+
 def concat_levels(levels_list):
     """Concatenate the output slots of per-wavelength bin dicts (SosContext.output_levels of each, all with the same altitude
     count K) in the bin order of concat_bins(bins_list): jout / zz / tauout [K][nb_total].  The levels stay valid on the padded

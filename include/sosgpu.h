@@ -419,6 +419,10 @@ int  sosgpu_debug_phase_buffer(sosgpu_ctx *cx, unsigned long long *d_phase);
 /* Diagnostic accessor: device pointer and size (doubles) of the streamed solver's scratch of this context, and the offset of the
  * order-parallel form's I3 hand-over block [nb][iborm_max+1][threads] inside it after such a solve (0 otherwise). */
 int  sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *doubles, size_t *spec_i3_offset);
+/* Diagnostic: d_out[i] = d_in[i] as sosgpu_profile reads it back from the PROFIL file -- written with E15.8 (fmt 0: H, XDEL,
+ * YDEL) or F10.5 (fmt 1: the altitudes) and read again -- by the device code sosgpu_profile applies to its levels, one thread per
+ * element (1 <= n <= 2^31, d_in / d_out on the device, may be the same array).  Asynchronous on `stream`. */
+int  sosgpu_debug_roundtrip(int device, int fmt, size_t n, const double *d_in, double *d_out, void *stream);
 
 #ifdef __cplusplus
 }

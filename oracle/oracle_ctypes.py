@@ -249,6 +249,74 @@ def sos_profile(tr, hr, ta, ha, altabs=None, tabs=None, absprofil=1):
     return dict(ier=ier, nt=nt.value, zprof=z[:k].copy(), h=h[:k].copy(), xdel=pa[:k].copy(), ydel=pm[:k].copy())
 
 
+EXP_MODES = {"exact": (0, 0), "plus": (1, 0), "minus": (2, 0), "rand_a": (3, 0x243F6A8885A308D3), "rand_b": (3, 0x13198A2E03707344)}
+INFO_BIN = ("regime", "strong", "clamp", "scan_steps", "dropped", "dropped_first", "ing", "nt_ng", "regime_ng", "scan_steps_ng",
+            "ier_from", "nt_loop")
+INFO_BINF = ("zlim", "t_first", "t_layer", "ttot", "tgtot", "t_layer_unclamped", "ttot_ng", "t_first_ng", "t_layer_ng")
+
+
+def sos_profile_info(tr, hr, ta, ha, altabs=None, tabs=None, absprofil=1, exp_mode="exact"):
+    """sos_profile for an absorption grid of any length (>= 2 levels), plus what the run did: the keys of INFO_BIN / INFO_BINF
+    (sos_profile_oracle_info in sos_profile_oracle.c), per level of the gas step `steps`, `zero_stop`, `forced`, `near_skip`
+    [nt + 1], per level of the no-gas profile `steps_ng`, `zero_stop_ng` [nt_ng + 1], and `raw` = dict(zprof, h, xdel, ydel)
+    before the decimal round trip.  exp_mode: a key of EXP_MODES -- every exp of the run as glibc gives it ("exact"), moved by
+    +1 / -1 ulp, or by a pseudo-random +-1 ulp keyed on the argument's bits."""
+    n = 602
+    z, h, pa, pm = (np.zeros(n) for _ in range(4))
+    nt = C.c_int(0)
+    nblev = 50
+    if tabs is None:
+        p_alt, p_tab, absprofil = None, None, 7
+    else:
+        a_alt = np.ascontiguousarray(altabs, dtype=np.float64); a_tab = np.ascontiguousarray(tabs, dtype=np.float64)
+        nblev = int(a_alt.size)
+        assert a_alt.shape == (nblev,) and a_tab.shape == (nblev,) and nblev >= 2
+        p_alt, p_tab = a_alt.ctypes.data_as(C.c_void_p), a_tab.ctypes.data_as(C.c_void_p)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    ib, fb = np.zeros(len(INFO_BIN), dtype=np.int32), np.zeros(len(INFO_BINF))
+    lev, lev_ng, raw = np.zeros((4, n), dtype=np.int32), np.zeros((2, n), dtype=np.int32), np.zeros((4, n))
+    L = lib()
+    L.sos_profile_oracle_info.restype = C.c_int
+    mode, key = EXP_MODES[exp_mode]
+    L.sos_profile_oracle_exp_mode(C.c_int(mode), C.c_ulonglong(key))
+    try:
+        ier = L.sos_profile_oracle_info(C.c_double(tr), C.c_double(hr), C.c_double(ta), C.c_double(ha), C.c_int(absprofil),
+                                        C.c_int(nblev), p_alt, p_tab, C.byref(nt), vp(z), vp(h), vp(pa), vp(pm), vp(ib), vp(fb),
+                                        vp(lev), vp(lev_ng), vp(raw))
+    finally:
+        L.sos_profile_oracle_exp_mode(C.c_int(0), C.c_ulonglong(0))
+    k = nt.value + 1 if ier == 0 else 0
+    out = dict(ier=ier, nt=nt.value if ier == 0 else -1, zprof=z[:k].copy(), h=h[:k].copy(), xdel=pa[:k].copy(), ydel=pm[:k].copy())
+    out.update({name: int(v) for name, v in zip(INFO_BIN, ib)})
+    out.update({name: float(v) for name, v in zip(INFO_BINF, fb)})
+    kg = out["nt_ng"] + 1
+    out.update(steps=lev[0, :k].copy(), zero_stop=lev[1, :k].copy(), forced=lev[2, :k].copy(), near_skip=lev[3, :k].copy(),
+               steps_ng=lev_ng[0, :kg].copy(), zero_stop_ng=lev_ng[1, :kg].copy(),
+               raw=dict(zprof=raw[0, :k].copy(), h=raw[1, :k].copy(), xdel=raw[2, :k].copy(), ydel=raw[3, :k].copy()))
+    return out
+
+
+def profile_roundtrip(values, fmt="e15.8"):
+    """The PROFIL file's decimal round trip of each value: written with E15.8 (or F10.5) and read back, by snprintf / strtod."""
+    a = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    out = np.empty_like(a)
+    lib().sos_profile_oracle_roundtrip(C.c_int({"e15.8": 0, "f10.5": 1}[fmt]), C.c_long(a.size), a.ctypes.data_as(C.c_void_p),
+                                       out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def absprofile(xk, ro, ik):
+    """SOS_ABSPROFILE for one bin in plain C (sos_absprofile_oracle): xk[8][nterm][nlev-1], ro[8][nlev-1], ik[8] -> TAUABS[nlev]."""
+    xk = np.ascontiguousarray(xk, dtype=np.float64); ro = np.ascontiguousarray(ro, dtype=np.float64)
+    ik = np.ascontiguousarray(ik, dtype=np.int32)
+    nterm, nlev = xk.shape[1], xk.shape[2] + 1
+    assert xk.shape == (8, nterm, nlev - 1) and ro.shape == (8, nlev - 1) and ik.shape == (8,)
+    tau = np.zeros(nlev)
+    lib().sos_absprofile_oracle(C.c_int(nlev), C.c_int(nterm), ik.ctypes.data_as(C.c_void_p), xk.ctypes.data_as(C.c_void_p),
+                                ro.ctypes.data_as(C.c_void_p), tau.ctypes.data_as(C.c_void_p))
+    return tau
+
+
 def mie(xmu, rn, in_, alphas):
     """SOS_MIE + SOS_FPHASE_MIE records for the size parameters `alphas` at the cosines xmu[2 nbmu + 1].  Returns dict(rec float32
     [na][4 + 3 W] in the layout of sosgpu_mie, g float64 [na], info int32 [na][4] = n2 finally used, overflow break taken,

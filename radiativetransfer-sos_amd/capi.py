@@ -21,7 +21,7 @@ EXPORTS = [
     "sosgpu_granu_batch",
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
-    "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels",
+    "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -167,6 +167,8 @@ def lib():
         L.sosgpu_debug_phase_buffer.argtypes = [vp, vp]
         L.sosgpu_debug_scratch.restype = i32
         L.sosgpu_debug_scratch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.sosgpu_debug_roundtrip.restype = i32
+        L.sosgpu_debug_roundtrip.argtypes = [i32, i32, C.c_size_t, vp, vp, vp]
         _lib = L
     return _lib
 

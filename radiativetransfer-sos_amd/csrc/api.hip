@@ -1524,3 +1524,16 @@ extern "C" int sosgpu_debug_phase_buffer(sosgpu_ctx *cx, unsigned long long *d_p
     cx->phase = d_phase;
     return SOSGPU_OK;
 }
+
+// Diagnostic: the decimal round trip k_profile applies to its levels (profile.hip rt_e15_8 / rt_f10_5), element by element.
+extern "C" int sosgpu_debug_roundtrip(int device, int fmt, size_t n, const double *d_in, double *d_out, void *stream)
+{
+    if ((fmt != 0 && fmt != 1) || n < 1 || n > ((size_t)1 << 31) || !d_in || !d_out) return SOSGPU_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
+    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
+    HIPCHK(hipSetDevice(device));
+    launch_debug_roundtrip(fmt, n, d_in, d_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}

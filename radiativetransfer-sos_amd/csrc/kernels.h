@@ -95,6 +95,8 @@ struct OutputLevelArgs {
     double *zz, *tauout;
 };
 void launch_output_levels(const OutputLevelArgs &a, hipStream_t st);
+// diagnostic: out[i] = the E15.8 (fmt 0) or F10.5 (fmt 1) round trip of in[i] as k_profile applies it
+void launch_debug_roundtrip(int fmt, size_t n, const double *d_in, double *d_out, hipStream_t st);
 // the no-gas profile of the wavelength into d_ng = z | h | pca | pcm, `ng` doubles each (nt + 1 <= ng used)
 void launch_profile_nogas(double tr, double hr, double ta, double ha, int nt, double t_first, double t_layer, double *d_ng, int ng,
                           hipStream_t st);

@@ -23,6 +23,7 @@
 
 namespace {
 
+#include "pow10_dd.h"
 __device__ const double P10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
                                    1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 
@@ -39,8 +40,55 @@ __device__ __forceinline__ double round_scaled(double x, double p)
     return r;
 }
 
+// av 10^m as hi + lo for |m| <= 308, to a relative 2^-104: the power of ten as a pair of doubles (pow10_dd.h), the product
+// (m >= 0) or the quotient and its remainder (m < 0) by one FMA each
+__device__ __forceinline__ void scaled_dd(double av, int m, double &hi, double &lo)
+{
+    if (m >= 0) {
+        const double ph = P10DD[m][0], pl = P10DD[m][1];
+        hi = av * ph;
+        lo = __builtin_fma(av, ph, -hi) + av * pl;
+    } else {
+        const double ph = P10DD[-m][0], pl = P10DD[-m][1];
+        hi = av / ph;
+        lo = (__builtin_fma(-hi, ph, av) - hi * pl) / ph;
+    }
+}
+
+// rt_e15_8 where 10^m is not one double (m > 22: |v| < 1e-15; m < -22: |v| >= 1e30).  From 1e-300 to 1e300 both steps are
+// done on the pair: the eight digits are round(av 10^m) decided on hi + lo, the value read back is r 10^-m as hi + lo rounded
+// once.  Neither step can meet an exact tie it would misjudge: av 10^m is never a half-integer here (5^23 > 2^53), and
+// r 10^-m is exact as a pair wherever it can be a midpoint of doubles (10^k exact up to k = 44, no midpoint beyond).
+// Outside that range (denormals, the last decades before overflow) one double stands for the power: the value read back may
+// be the neighbour of the C library's.
+__device__ double rt_e15_8_wide(double av, double v, int m)
+{
+    if ((m > 22 && m <= 307) || (m < -22 && m >= -301)) {
+        double hi, lo;
+        scaled_dd(av, m, hi, lo);                       // the log10 estimate may be one off: no exact comparison fixed it
+        if (hi > 1e8 || (hi == 1e8 && lo >= 0.)) scaled_dd(av, --m, hi, lo);
+        else if (hi < 1e7 || (hi == 1e7 && lo < 0.)) scaled_dd(av, ++m, hi, lo);
+        double r = rint(hi);
+        const double d = (hi - r) + lo;
+        if (d > 0.5 || (d == 0.5 && fmod(r, 2.0) != 0.0)) r += 1.0;
+        else if (d < -0.5 || (d == -0.5 && fmod(r, 2.0) != 0.0)) r -= 1.0;
+        scaled_dd(r, -m, hi, lo);
+        return copysign(hi + lo, v);
+    }
+    if (m < 0) {
+        const double q = pow(10.0, (double)(-m - 22));
+        const double r = rint(av / P10[22] / q);
+        return copysign(r * q * P10[22], v);
+    }
+    const int ka = (m - 22) / 2, kb = (m - 22) - ka;    // 10^m would overflow: scale in three steps
+    const double pa = pow(10.0, (double)ka), pb = pow(10.0, (double)kb);
+    const double r = rint(av * P10[22] * pa * pb);
+    return copysign(r / pb / pa / P10[22], v);
+}
+
 // value read back from a Fortran E15.8 field: 8 significant decimal digits, correctly rounded both ways
-// (decimal -> binary is r / 10^m with r < 2^27 and 10^m exact: one correctly rounded division)
+// (decimal -> binary is r / 10^m with r < 2^27 and 10^m exact: one correctly rounded division; where 10^m is not one double,
+// rt_e15_8_wide)
 __device__ double rt_e15_8(double v)
 {
     if (v == 0.0 || !isfinite(v)) return v;
@@ -61,13 +109,19 @@ __device__ double rt_e15_8(double v)
         return copysign(r / P10[m], v);
     }
     if (m < 0) {                                     // |v| >= 1e8: divide
-        r = rint(av / P10[-m]);
-        return copysign(r * P10[-m], v);
+        const int k = -m;
+        if (k <= 22) {
+            // the quotient is rounded before rint sees it, which misplaces values on or next to a tie: decide on the
+            // remainder av - r 10^k instead, which one FMA forms exactly (r < 2^27, 10^k exact, |remainder| <= 10^k)
+            r = rint(av / P10[k]);
+            const double rem = __builtin_fma(-r, P10[k], av), half = 0.5 * P10[k];
+            if (rem > half || (rem == half && fmod(r, 2.0) != 0.0)) r += 1.0;
+            else if (rem < -half || (rem == -half && fmod(r, 2.0) != 0.0)) r -= 1.0;
+            return copysign(r * P10[k], v);
+        }
+        return rt_e15_8_wide(av, v, m);               // |v| >= 1e30
     }
-    // |v| < 1e-15: 10^m is not exact any more; these are fractions of 1e-15 of a layer, far below the parity bar
-    const double p = P10[22] * pow(10.0, (double)(m - 22));
-    r = rint(av * p);
-    return copysign(r / p, v);
+    return rt_e15_8_wide(av, v, m);                   // |v| < 1e-15
 }
 
 __device__ __forceinline__ double rt_f10_5(double v) { return copysign(round_scaled(fabs(v), 1e5) / 1e5, v); }
@@ -549,7 +603,9 @@ void launch_profile(const ProfileArgs &a, hipStream_t st)
 // device-side chain of a wavelength in sos_spectrum).  Lane j forms the optical depth of layer j (the eight gases added in the
 // reference's order) and its transmission; the running product TRS is then formed in layer order -- the same left-to-right
 // product as the loop's -- each lane keeping the value of its own layer, and takes its logarithm.  Bands with more layers than
-// lanes walk the layers in blocks of 64 with the product carried over.
+// lanes walk the layers in blocks of 64 with the product carried over.  (Today that second block never runs: the entry points
+// refuse nlev > SOS_PROF_NBLEV_MAX = 64, i.e. more than 63 layers, because k_profile keeps the levels in LDS.  The loop is kept
+// so that raising that limit stays a change of one constant; no test can reach its carry until then.)
 // (the body of bin b, shared by k_absprofile and the table form k_absprofile_table)
 __device__ __forceinline__ void absprofile_bin_body(const int b, const int lane, int nlev, int nterm, const int32_t *__restrict__ ik,
                                                     const double *__restrict__ xk, const double *__restrict__ ro,
@@ -640,6 +696,20 @@ __global__ __launch_bounds__(256) void k_output_levels(OutputLevelArgs a)
         }
     }
     a.jout[i] = j; a.zz[i] = zz; a.tauout[i] = tauout;
+}
+
+// Diagnostic (sosgpu_debug_roundtrip): the register form of the PROFIL file's decimal round trip over an array, one thread per
+// element -- fmt 0: rt_e15_8, 1: rt_f10_5 -- so that a test can hold it against the C library's print-and-read, value by value.
+__global__ __launch_bounds__(256) void k_debug_roundtrip(int fmt, size_t n, const double *__restrict__ in, double *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = fmt ? rt_f10_5(in[i]) : rt_e15_8(in[i]);
+}
+
+void launch_debug_roundtrip(int fmt, size_t n, const double *d_in, double *d_out, hipStream_t st)
+{
+    k_debug_roundtrip<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(fmt, n, d_in, d_out);
 }
 
 void launch_output_levels(const OutputLevelArgs &a, hipStream_t st)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import cases
+import profile_cells
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sos_profile.npz")
 KEYS = ("zprof", "h", "xdel", "ydel")
@@ -54,12 +55,14 @@ def _ctx(gpu_pkg):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(cases.PROFILE_CASES))
 def test_device_profile_vs_golden(gpu_pkg, oracle, name):
-    """sosgpu_profile against the reference's PROFIL output.  NT and the altitudes must be identical; H, XDEL, YDEL equal
-    to the 8 printed digits except where a device exp differs from glibc's by an ulp right at a rounding boundary
-    (tolerance 2e-8 relative = one unit of the last printed digit)."""
+    """sosgpu_profile against the reference's PROFIL output.  NT and the altitudes must be identical; H, XDEL, YDEL bit for
+    bit, except where the oracle itself prints another digit when its exp moves by an ulp -- then one of those values
+    (profile_cells.rule; for these eleven columns the oracle's variants agree on every entry)."""
     import torch
     g = np.load(GOLD)
     c = cases.profile_case(name)
+    var = {m: oracle.sos_profile_info(c["tr"], c["hr"], c["ta"], c["ha"], c["altabs"], c["tabs"], exp_mode=m) for m in oracle.EXP_MODES}
+    assert all(v["nt"] == int(g[name + "_nt"]) for v in var.values())
     cx = _ctx(gpu_pkg)
     nb = 3
     tabs = None if c["tabs"] is None else np.tile(c["tabs"], (nb, 1))
@@ -74,7 +77,8 @@ def test_device_profile_vs_golden(gpu_pkg, oracle, name):
         assert np.array_equal(z[b, :k], g[name + "_zprof"]), name
         for row, key in enumerate(("h", "xdel", "ydel")):
             ref = g[name + "_" + key]
-            assert np.allclose(prof[b, row, :k], ref, rtol=2e-8, atol=1e-300), (name, key)
+            ok, _ = profile_cells.rule(prof[b, row, :k], [ref] + [v[key] for v in var.values()])
+            assert ok.all(), (name, key, np.nonzero(~ok)[0][:5])
             assert (prof[b, row, k:] == 0).all()
     exact = sum(int(np.array_equal(prof[0, r, :k], g[name + "_" + key])) for r, key in enumerate(("h", "xdel", "ydel")))
     print(name, "NT", nt[0], "bit-identical rows: %d/3" % exact)
@@ -204,7 +208,8 @@ def test_ckd_band_end_to_end(gpu_pkg, oracle):
 @pytest.mark.gpu
 def test_device_profile_random_columns(gpu_pkg, oracle):
     """Many random gas columns in one batch against the restatement: NT and the level altitudes identical, H / XDEL / YDEL
-    to the last printed digit.  (SOS_FUZZ_N bins, default 48.)"""
+    bit for bit or, where the oracle's exp variants disagree, one of their values (profile_cells.rule).  (SOS_FUZZ_N bins,
+    default 48.)"""
     import torch
     nb = int(os.environ.get("SOS_FUZZ_N", "48"))
     rng = np.random.default_rng(11)
@@ -230,8 +235,10 @@ def test_device_profile_random_columns(gpu_pkg, oracle):
         assert nt[b] == r["nt"], (b, nt[b], r["nt"])
         k = r["nt"] + 1
         assert np.array_equal(z[b, :k], r["zprof"]), b
+        var = [oracle.sos_profile_info(tr, hr, ta, ha, alt, tabs[b], exp_mode=m) for m in oracle.EXP_MODES if m != "exact"]
         for row, key in enumerate(("h", "xdel", "ydel")):
-            assert np.allclose(prof[b, row, :k], r[key], rtol=2e-8, atol=1e-300), (b, key)
+            ok, _ = profile_cells.rule(prof[b, row, :k], [r[key]] + [v[key] for v in var if v["nt"] == r["nt"]])
+            assert ok.all(), (b, key, np.nonzero(~ok)[0][:5])
         exact += int(all(np.array_equal(prof[b, row, :k], r[key]) for row, key in enumerate(("h", "xdel", "ydel"))))
     print("bit-identical bins: %d/%d" % (exact, nb))
     cx.close()

@@ -419,6 +419,21 @@ int  sosgpu_debug_phase_buffer(sosgpu_ctx *cx, unsigned long long *d_phase);
 /* Diagnostic accessor: device pointer and size (doubles) of the streamed solver's scratch of this context, and the offset of the
  * order-parallel form's I3 hand-over block [nb][iborm_max+1][threads] inside it after such a solve (0 otherwise). */
 int  sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *doubles, size_t *spec_i3_offset);
+/* Diagnostic accessor: the per-wavelength tables of a context (built by sosgpu_create, sosgpu_noyaux and
+ * sosgpu_set_surface_matrices; csrc/sos_common.h documents every layout) and the numbers that describe them, copied to the
+ * HOST.  Read-only: nothing in the context changes.  Like sosgpu_noyaux_fetch it waits for the streams the context's work was
+ * queued on, then copies on the calling thread's utility stream.  `info` is required; every array pointer may be NULL (not
+ * copied), so a first call with info alone gives the sizes (doubles unless noted):
+ *   prt    [smax+1][3][os_nb+1][w]            mp_aer [smax+1][2][rtph*ks2h*128]
+ *   mp_vt  [3][ks2h*128]                      mp_uf  [3][rtph*64]
+ *   sv     [smax+1][4][kp]                    rowmap [kh] (int32)
+ *   mp_gnd [smax+1][rtph*ks2h*128], rdir [smax+1][3][n]: only after sosgpu_set_surface_matrices (SOSGPU_E_ARG otherwise) */
+typedef struct sosgpu_tables_info {
+    int32_t n, w, kp, kh, ks2h, rtph, nwgt, prow, os_nb, smax, n0, ipolar;
+    double  beta2, gamma2, alpha2, f11sun, f12sun, mus, ro;
+} sosgpu_tables_info;
+int  sosgpu_debug_tables(sosgpu_ctx *cx, sosgpu_tables_info *info, double *prt, double *mp_aer, double *mp_vt, double *mp_uf,
+                         double *sv, double *mp_gnd, double *rdir, int32_t *rowmap);
 /* Diagnostic: d_out[i] = d_in[i] as sosgpu_profile reads it back from the PROFIL file -- written with E15.8 (fmt 0: H, XDEL,
  * YDEL) or F10.5 (fmt 1: the altitudes) and read again -- by the device code sosgpu_profile applies to its levels, one thread per
  * element (1 <= n <= 2^31, d_in / d_out on the device, may be the same array).  Asynchronous on `stream`. */

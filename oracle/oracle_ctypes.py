@@ -58,6 +58,103 @@ def noyaux(is_, rmu0, mu, os_nb, alpha, beta, gamma, zeta):
     return out
 
 
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def noyaux_ext(is_, rmu0, mu, os_nb, alpha, beta, gamma, zeta, start=None, kernels=True):
+    """sos_oracle_noyaux_ext: as noyaux(), plus PSL/RSL/TSL [os_nb+1][W] of every l; start [3][n+1] (or None) replaces the three
+    pow start values of is_ >= 2; kernels=False skips the six sums (their keys are then absent)."""
+    n = len(mu)
+    w = 2 * n + 1
+    ins = [np.ascontiguousarray(x, dtype=np.float64) for x in (mu, alpha, beta, gamma, zeta)]
+    st = None
+    if start is not None:
+        st = np.ascontiguousarray(start, dtype=np.float64)
+        assert st.shape == (3, n + 1), st.shape
+    prt = [np.zeros((os_nb + 1, w)) for _ in range(3)]
+    vec = [np.zeros(w) for _ in range(3)]
+    mats = [np.zeros((w, w)) for _ in range(6)] if kernels else []
+    lib().sos_oracle_noyaux_ext(C.c_int(is_), C.c_int(n), C.c_double(rmu0), _p(ins[0]), C.c_int(os_nb),
+                                _p(ins[1]), _p(ins[2]), _p(ins[3]), _p(ins[4]), None if st is None else _p(st),
+                                *[_p(a) for a in prt], *[_p(v) for v in vec],
+                                *([_p(m) for m in mats] if kernels else [None] * 6))
+    out = dict(zip(["BP", "GR", "GT", "ARR", "ART", "ATT"], mats))
+    out.update(dict(zip(["XPL", "XRL", "XTL"], vec)))
+    out.update(dict(zip(["PSL", "RSL", "TSL"], prt)))
+    return out
+
+
+KERNEL_NAMES = ("BP", "GR", "GT", "ARR", "ART", "ATT")
+
+
+def _kern6(k):
+    return np.ascontiguousarray(np.stack([k[x] for x in KERNEL_NAMES]), dtype=np.float64)
+
+
+def _xprt3(k):
+    return np.ascontiguousarray(np.stack([k["XPL"], k["XRL"], k["XTL"]]), dtype=np.float64)
+
+
+def ray_coefs(ron, ipolar):
+    """BETA2, GAMMA2, ALPHA2 (SOS_OS.F:678-699)."""
+    out = np.zeros(3)
+    lib().sos_oracle_ray_coefs(C.c_double(ron), C.c_int(ipolar), _p(out))
+    return tuple(out)
+
+
+def ray_kernels(is_, k, b2g2a2):
+    """The molecular terms of SOS_OS.F:2859-2876 as six (W x W) kernels, from XPL/XRL/XTL of the dict k."""
+    x3 = _xprt3(k)
+    w = x3.shape[1]
+    out = np.zeros((6, w, w))
+    lib().sos_oracle_ray_kernels(C.c_int(is_), C.c_int((w - 1) // 2), _p(x3), *[C.c_double(v) for v in b2g2a2], _p(out))
+    return dict(zip(KERNEL_NAMES, out))
+
+
+def order1_coefs(is_, k, b2g2a2):
+    """SOS_FSOURCE_ORDRE1 per direction: (aer[3][W], ray[3][W]) = I, Q, U coefficients (U with the routine's minus sign)."""
+    k6, x3 = _kern6(k), _xprt3(k)
+    w = x3.shape[1]
+    aer, ray = np.zeros((3, w)), np.zeros((3, w))
+    lib().sos_oracle_order1_coefs(C.c_int(is_), C.c_int((w - 1) // 2), _p(k6), _p(x3), C.c_double(b2g2a2[0]),
+                                  C.c_double(b2g2a2[1]), _p(aer), _p(ray))
+    return aer, ray
+
+
+def fresnel1_coefs(is_, k, b2g2a2, f11sun, f12sun):
+    """SOS_FSOURCE_DIFF_FRESNEL1 per field direction, without COEFK and the profile: (aer[3][W], ray[3][W])."""
+    k6, x3 = _kern6(k), _xprt3(k)
+    w = x3.shape[1]
+    aer, ray = np.zeros((3, w)), np.zeros((3, w))
+    lib().sos_oracle_fresnel1_coefs(C.c_int(is_), C.c_int((w - 1) // 2), C.c_double(f11sun), C.c_double(f12sun), _p(k6), _p(x3),
+                                    *[C.c_double(v) for v in b2g2a2], _p(aer), _p(ray))
+    return aer, ray
+
+
+def fresnel1_routine(is_, k, b2g2a2, f11sun, f12sun, pcaer, pcray):
+    """The static SOS_FSOURCE_DIFF_FRESNEL1 at H = 0, MUS = 1 (COEFK = 1/4) with the profile (pcaer, pcray): [3][W]."""
+    k6, x3 = _kern6(k), _xprt3(k)
+    w = x3.shape[1]
+    out = np.zeros((3, w))
+    lib().sos_oracle_fresnel1_routine(C.c_int(is_), C.c_int((w - 1) // 2), C.c_double(f11sun), C.c_double(f12sun), _p(k6), _p(x3),
+                                      *[C.c_double(v) for v in b2g2a2], C.c_double(pcaer), C.c_double(pcray), _p(out))
+    return out
+
+
+def ordreig_level(is_, ga, k, b2g2a2, field):
+    """SOS_FSOURCE_ORDREIG at one level applied to field [3][W] (I, Q, U over jj = -N..N): (aer[3][W], ray[3][W])."""
+    k6, x3 = _kern6(k), _xprt3(k)
+    w = x3.shape[1]
+    g = np.ascontiguousarray(ga, dtype=np.float64)
+    f = np.ascontiguousarray(field, dtype=np.float64)
+    assert f.shape == (3, w) and len(g) == (w - 1) // 2
+    aer, ray = np.zeros((3, w)), np.zeros((3, w))
+    lib().sos_oracle_ordreig_level(C.c_int(is_), C.c_int(len(g)), _p(g), _p(k6), _p(x3), *[C.c_double(v) for v in b2g2a2],
+                                   _p(f), _p(aer), _p(ray))
+    return aer, ray
+
+
 def sos_os(rmu, ga, os_nb, h, xdel, ydel, alpha, beta, gamma, zeta, *, n0, tetas=0.0, ro=0.0,
            imat_surf=0, ifresnel=0, ind_surf=1.34, zprof=None, ron=float(np.float32(0.0279)), zout=-1.0,
            igmax=100, iborm=None, ipolar=1, rsurf=None):

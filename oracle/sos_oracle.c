@@ -22,10 +22,14 @@
 /* ------------------------------------------------------------------------------------------- */
 /* SOS_NOYAUX  (SOS_OS.F:1857-2158)                                                              */
 /* ------------------------------------------------------------------------------------------- */
-void sos_oracle_noyaux(int is, int n, double rmu0, const double *mu, int os_nb,
-                       const double *alpha, const double *beta, const double *gamma, const double *zeta,
-                       double *xpl, double *xrl, double *xtl,
-                       double *bp, double *gr, double *gt, double *arr, double *art, double *att)
+/* Extended form.  start (or NULL): [3][n+1] the three start values of IS >= 2 per direction j = 0..n, taken as given instead
+ * of A*XX**(IS/2), B*(1+C*C)*XX**YY, 2*B*C*XX**YY (:2040-2049) -- the one place of SOS_NOYAUX that calls pow.  psl_all, rsl_all,
+ * tsl_all (or NULL): [os_nb+1][W] PSL/RSL/TSL of every l = 0..os_nb.  bp == NULL skips the six kernel sums. */
+void sos_oracle_noyaux_ext(int is, int n, double rmu0, const double *mu, int os_nb,
+                           const double *alpha, const double *beta, const double *gamma, const double *zeta,
+                           const double *start, double *psl_all, double *rsl_all, double *tsl_all,
+                           double *xpl, double *xrl, double *xtl,
+                           double *bp, double *gr, double *gt, double *arr, double *art, double *att)
 {
     const int W = 2 * n + 1;
     const int NL = os_nb + 2; /* l = -1 .. os_nb */
@@ -86,11 +90,11 @@ void sos_oracle_noyaux(int is, int n, double rmu0, const double *mu, int os_nb,
         for (j = 0; j <= n; j++) {
             double c = RMU(j), xx = 1. - c * c, yy = is * 0.5 - 1., x;
             P(is - 1, j) = 0.; R(is - 1, j) = 0.; T(is - 1, j) = 0.;
-            x = a * pow(xx, is * 0.5);
+            x = start ? start[j] : a * pow(xx, is * 0.5);
             P(is, -j) = x; P(is, j) = x;
-            x = b * (1. + c * c) * pow(xx, yy);
+            x = start ? start[(n + 1) + j] : b * (1. + c * c) * pow(xx, yy);
             R(is, -j) = x; R(is, j) = x;
-            x = 2. * b * c * pow(xx, yy);
+            x = start ? start[2 * (n + 1) + j] : 2. * b * c * pow(xx, yy);
             T(is, -j) = -x; T(is, j) = x;
         }
     }
@@ -129,7 +133,14 @@ void sos_oracle_noyaux(int is, int n, double rmu0, const double *mu, int os_nb,
         xrl[j + n] = R(2, j);
         xtl[j + n] = T(2, j);
     }
-    for (j = -n; j <= n; j++) { /* :2121-2155 */
+    if (psl_all)
+        for (l = 0; l <= os_nb; l++)
+            for (j = -n; j <= n; j++) {
+                psl_all[(size_t)l * W + j + n] = P(l, j);
+                rsl_all[(size_t)l * W + j + n] = R(l, j);
+                tsl_all[(size_t)l * W + j + n] = T(l, j);
+            }
+    for (j = -n; bp && j <= n; j++) { /* :2121-2155 */
         for (k = -n; k <= n; k++) {
             double sbp = 0., satt = 0., sarr = 0., sgr = 0., sgt = 0., sart = 0.;
             if (is <= os_nb) {
@@ -153,6 +164,15 @@ void sos_oracle_noyaux(int is, int n, double rmu0, const double *mu, int os_nb,
 #undef T
 #undef RMU
     free(psl); free(rsl); free(tsl);
+}
+
+void sos_oracle_noyaux(int is, int n, double rmu0, const double *mu, int os_nb,
+                       const double *alpha, const double *beta, const double *gamma, const double *zeta,
+                       double *xpl, double *xrl, double *xtl,
+                       double *bp, double *gr, double *gt, double *arr, double *art, double *att)
+{
+    sos_oracle_noyaux_ext(is, n, rmu0, mu, os_nb, alpha, beta, gamma, zeta, NULL, NULL, NULL, NULL,
+                          xpl, xrl, xtl, bp, gr, gt, arr, art, att);
 }
 
 /* ------------------------------------------------------------------------------------------- */
@@ -373,6 +393,156 @@ static void fsource_diff_fresnel1(const geom_t *g, int is, double f11sun, double
             }
         }
     }
+}
+
+/* ------------------------------------------------------------------------------------------- */
+/* Exported single pieces (tests/test_context_tables.py): what the routines above take from the  */
+/* kernels, without the profile and the attenuation.                                            */
+/* ------------------------------------------------------------------------------------------- */
+void sos_oracle_ray_coefs(double ron, int ipolar, double *b2g2a2) /* :678-699 */
+{
+    double aaa = ron / (2 - ron);
+    aaa = (1 - aaa) / (1 + 2 * aaa);
+    b2g2a2[0] = 0.5 * aaa; b2g2a2[1] = -aaa * sqrt(1.5); b2g2a2[2] = 3. * aaa;
+    if (ipolar == 0) { b2g2a2[1] = 0.; b2g2a2[2] = 0.; }
+}
+
+static void kern_bind(kern_t *kn, int w, const double *kern6, const double *xprt3)
+{
+    const size_t ww = (size_t)w * w;
+    kn->bp = (double *)kern6; kn->gr = (double *)kern6 + ww; kn->gt = (double *)kern6 + 2 * ww;
+    kn->arr = (double *)kern6 + 3 * ww; kn->art = (double *)kern6 + 4 * ww; kn->att = (double *)kern6 + 5 * ww;
+    kn->xpl = (double *)xprt3; kn->xrl = (double *)xprt3 + w; kn->xtl = (double *)xprt3 + 2 * w;
+}
+
+void sos_oracle_ray_kernels(int is, int n, const double *xprt3, double beta2, double gamma2, double alpha2, double *kern6)
+{
+    const int W = 2 * n + 1;
+    const double beta0 = is == 0 ? 1. : 0.;
+    geom_t gs, *g = &gs;
+    kern_t kn;
+    int j, k;
+    g->n = n; g->W = W; g->nt = 0; g->L = 1; g->rmu = g->ga = NULL;
+    kern_bind(&kn, W, kern6, xprt3);
+    memset(kern6, 0, sizeof(double) * 6 * W * W);
+    if (is - 2 > 0) return;
+    for (j = -n; j <= n; j++)
+        for (k = -n; k <= n; k++) { /* the second terms of :2859-2876 */
+            KER(kn.bp, j, k) = beta0 + beta2 * V(kn.xpl, j) * V(kn.xpl, k);
+            KER(kn.gr, j, k) = gamma2 * V(kn.xpl, j) * V(kn.xrl, k);
+            KER(kn.gt, j, k) = gamma2 * V(kn.xpl, j) * V(kn.xtl, k);
+            KER(kn.arr, j, k) = alpha2 * V(kn.xrl, j) * V(kn.xrl, k);
+            KER(kn.art, j, k) = alpha2 * V(kn.xtl, j) * V(kn.xrl, k);
+            KER(kn.att, j, k) = alpha2 * V(kn.xtl, j) * V(kn.xtl, k);
+        }
+}
+
+void sos_oracle_order1_coefs(int is, int n, const double *kern6, const double *xprt3,
+                             double beta2, double gamma2, double *aer, double *ray)
+{
+    const int W = 2 * n + 1;
+    const double one = 1., zero = 0.;
+    geom_t gs, *g = &gs;
+    kern_t kn;
+    g->n = n; g->W = W; g->nt = 0; g->L = 1; g->rmu = g->ga = NULL;
+    kern_bind(&kn, W, kern6, xprt3);
+    /* one level, ATTDIR = 1, and (PCAER, PCRAY) = (1, 0) then (0, 1): X*1 + Y*0 is X for finite Y */
+    fsource_ordre1(g, is, &one, &zero, is == 0 ? 1. : 0., beta2, gamma2, &kn, &one, aer, aer + W, aer + 2 * W);
+    fsource_ordre1(g, is, &zero, &one, is == 0 ? 1. : 0., beta2, gamma2, &kn, &one, ray, ray + W, ray + 2 * W);
+}
+
+void sos_oracle_fresnel1_coefs(int is, int n, double f11sun, double f12sun, const double *kern6, const double *xprt3,
+                               double beta2, double gamma2, double alpha2, double *aer, double *ray)
+{
+    const int W = 2 * n + 1;
+    const double beta0 = is == 0 ? 1. : 0.;
+    geom_t gs, *g = &gs;
+    kern_t kn;
+    int j;
+    g->n = n; g->W = W; g->nt = 0; g->L = 1; g->rmu = g->ga = NULL;
+    kern_bind(&kn, W, kern6, xprt3);
+    memset(aer, 0, sizeof(double) * 3 * W);
+    memset(ray, 0, sizeof(double) * 3 * W);
+    {
+        const double spl = V(kn.xpl, 0);
+        for (j = 1; j <= n; j++) {
+            /* field direction +j takes the kernels of -j (:3237-3252, 3280-3282); -j those of +j (:3284-3289) */
+            V(aer, j) = f11sun * KER(kn.bp, 0, -j) + f12sun * KER(kn.gr, -j, 0);
+            V(aer + W, j) = f11sun * KER(kn.gr, 0, -j) + f12sun * KER(kn.arr, 0, -j);
+            V(aer + 2 * W, j) = f11sun * KER(kn.gt, 0, -j) + f12sun * KER(kn.art, -j, 0);
+            V(aer, -j) = f11sun * KER(kn.bp, 0, j) + f12sun * KER(kn.gr, j, 0);
+            V(aer + W, -j) = f11sun * KER(kn.gr, 0, j) + f12sun * KER(kn.arr, 0, j);
+            V(aer + 2 * W, -j) = f11sun * KER(kn.gt, 0, j) + f12sun * KER(kn.art, j, 0);
+            if (is <= 2) { /* the molecular terms of :3237-3252 in their own operation order, YR = YYR = 1 */
+                double bp0mj = beta0 + beta2 * V(kn.xpl, -j) * spl;
+                double bp0j = beta0 + beta2 * V(kn.xpl, j) * spl;
+                double grj0 = V(kn.xrl, 0) * V(kn.xpl, j) * gamma2;
+                double gr0j = V(kn.xrl, j) * V(kn.xpl, 0) * gamma2;
+                double gr0mj = V(kn.xrl, -j) * spl * gamma2;
+                double grmj0 = gamma2 * V(kn.xrl, 0) * V(kn.xpl, -j);
+                double gt0mj = gamma2 * spl * V(kn.xtl, -j);
+                double gt0j = gamma2 * spl * V(kn.xtl, j);
+                double arr0mj = alpha2 * V(kn.xrl, 0) * V(kn.xrl, -j);
+                double arr0j = alpha2 * V(kn.xrl, 0) * V(kn.xrl, j);
+                double artj0 = alpha2 * V(kn.xtl, j) * V(kn.xrl, 0);
+                double artmj0 = alpha2 * V(kn.xtl, -j) * V(kn.xrl, 0);
+                V(ray, j) = f11sun * bp0mj + f12sun * grmj0;
+                V(ray + W, j) = f11sun * gr0mj + f12sun * arr0mj;
+                V(ray + 2 * W, j) = f11sun * gt0mj + f12sun * artmj0;
+                V(ray, -j) = f11sun * bp0j + f12sun * grj0;
+                V(ray + W, -j) = f11sun * gr0j + f12sun * arr0j;
+                V(ray + 2 * W, -j) = f11sun * gt0j + f12sun * artj0;
+            }
+        }
+    }
+}
+
+/* The static SOS_FSOURCE_DIFF_FRESNEL1 itself on two levels at H = 0 with MUS = 1 (COEFK = 1/4) and the profile (PCAER, PCRAY)
+ * at both: out [3][W], field direction +j from level 0, -j from level 1.  With (1, 0) / (0, 1) this is a quarter of the aer /
+ * ray output of sos_oracle_fresnel1_coefs, which ties that function's re-typed expressions to the routine. */
+void sos_oracle_fresnel1_routine(int is, int n, double f11sun, double f12sun, const double *kern6, const double *xprt3,
+                                 double beta2, double gamma2, double alpha2, double pcaer, double pcray, double *out)
+{
+    const int W = 2 * n + 1;
+    const double h[2] = {0., 0.}, xd[2] = {pcaer, pcaer}, yd[2] = {pcray, pcray};
+    geom_t gs, *g = &gs;
+    kern_t kn;
+    int c, j;
+    double *f = calloc((size_t)6 * W, sizeof(double));
+    g->n = n; g->W = W; g->nt = 1; g->L = 2; g->rmu = g->ga = NULL;
+    kern_bind(&kn, W, kern6, xprt3);
+    fsource_diff_fresnel1(g, is, f11sun, f12sun, xd, yd, is == 0 ? 1. : 0., beta2, gamma2, alpha2, &kn, 1., h,
+                          f, f + 2 * W, f + 4 * W);
+    memset(out, 0, sizeof(double) * 3 * W);
+    for (c = 0; c < 3; c++)
+        for (j = 1; j <= n; j++) {
+            out[c * W + n + j] = FLD(f + 2 * c * W, 0, j);
+            out[c * W + n - j] = FLD(f + 2 * c * W, 1, -j);
+        }
+    free(f);
+}
+
+void sos_oracle_ordreig_level(int is, int n, const double *ga, const double *kern6, const double *xprt3,
+                              double beta2, double gamma2, double alpha2, const double *fld_in,
+                              double *aer, double *ray)
+{
+    const int W = 2 * n + 1;
+    const double one = 1., zero = 0.;
+    geom_t gs, *g = &gs;
+    kern_t kn;
+    int j;
+    g->n = n; g->W = W; g->nt = 0; g->L = 1; g->rmu = NULL;
+    g->ga = calloc(W, sizeof(double));
+    for (j = 1; j <= n; j++) { V(g->ga, j) = ga[j - 1]; V(g->ga, -j) = ga[j - 1]; }
+    kern_bind(&kn, W, kern6, xprt3);
+    memset(aer, 0, sizeof(double) * 3 * W);
+    memset(ray, 0, sizeof(double) * 3 * W);
+    fsource_ordreig(g, is, &one, &zero, is == 0 ? 1. : 0., beta2, gamma2, alpha2, &kn,
+                    fld_in, fld_in + W, fld_in + 2 * W, aer, aer + W, aer + 2 * W);
+    if (is <= 2)
+        fsource_ordreig(g, is, &zero, &one, is == 0 ? 1. : 0., beta2, gamma2, alpha2, &kn,
+                        fld_in, fld_in + W, fld_in + 2 * W, ray, ray + W, ray + 2 * W);
+    free(g->ga);
 }
 
 /* one term of SOS_PARAM_CONV, SOS_OS.F:3434-3453 */

@@ -31,6 +31,38 @@ void sos_oracle_noyaux(int is, int n, double rmu0, const double *mu, int os_nb,
                        double *xpl, double *xrl, double *xtl,
                        double *bp, double *gr, double *gt, double *arr, double *art, double *att);
 
+/* Extended form (sos_oracle_noyaux is this with start = psl_all = rsl_all = tsl_all = NULL, bit for bit).
+ *  start   : NULL, or [3][n+1]: the start values PSL/RSL/TSL(IS, j), j = 0..n, of IS >= 2 taken from the caller instead of the
+ *            three expressions with XX**(IS/2) and XX**YY (SOS_OS.F:2040-2049); ignored for IS < 2
+ *  psl_all, rsl_all, tsl_all : NULL, or [os_nb+1][W]: PSL/RSL/TSL(l, j) for every l = 0..os_nb (entries the reference never
+ *            assigns are 0)
+ *  bp == NULL: the six kernel sums are skipped (they cost O(W^2 OS_NB)). */
+void sos_oracle_noyaux_ext(int is, int n, double rmu0, const double *mu, int os_nb,
+                           const double *alpha, const double *beta, const double *gamma, const double *zeta,
+                           const double *start, double *psl_all, double *rsl_all, double *tsl_all,
+                           double *xpl, double *xrl, double *xtl,
+                           double *bp, double *gr, double *gt, double *arr, double *art, double *att);
+
+/* Single pieces of SOS_OS for the table tests.  kern6 = BP,GR,GT,ARR,ART,ATT [6][W][W], xprt3 = XPL,XRL,XTL [3][W] as
+ * sos_oracle_noyaux returns them; vectors [3][W] are I,Q,U over jj = -N..N (slot jj = 0 unused).
+ *  ray_coefs     BETA2, GAMMA2, ALPHA2 of SOS_OS.F:678-699 (polarisation cut applied)
+ *  ray_kernels   the molecular second terms of SOS_OS.F:2859-2876 as six kernels (BETA0 = 1 at IS = 0; zero for IS > 2)
+ *  order1_coefs  SOS_FSOURCE_ORDRE1 at one level with ATTDIR = 1: aer = (SA2, SB2, -SC2), ray = (SA1, SB1, -SC1)
+ *  fresnel1_coefs  SOS_FSOURCE_DIFF_FRESNEL1 without COEFK and the profile: aerosol and molecular part per field direction
+ *  ordreig_level SOS_FSOURCE_ORDREIG at one level applied to fld_in [3][W]: aer with (PCAER, PCRAY) = (1, 0), ray with (0, 1) */
+void sos_oracle_ray_coefs(double ron, int ipolar, double *b2g2a2);
+void sos_oracle_ray_kernels(int is, int n, const double *xprt3, double beta2, double gamma2, double alpha2, double *kern6);
+void sos_oracle_order1_coefs(int is, int n, const double *kern6, const double *xprt3,
+                             double beta2, double gamma2, double *aer, double *ray);
+void sos_oracle_fresnel1_coefs(int is, int n, double f11sun, double f12sun, const double *kern6, const double *xprt3,
+                               double beta2, double gamma2, double alpha2, double *aer, double *ray);
+/* SOS_FSOURCE_DIFF_FRESNEL1 itself at H = 0, MUS = 1 with one (PCAER, PCRAY): out [3][W] = a quarter of the coefficients above */
+void sos_oracle_fresnel1_routine(int is, int n, double f11sun, double f12sun, const double *kern6, const double *xprt3,
+                                 double beta2, double gamma2, double alpha2, double pcaer, double pcray, double *out);
+void sos_oracle_ordreig_level(int is, int n, const double *ga, const double *kern6, const double *xprt3,
+                              double beta2, double gamma2, double alpha2, const double *fld_in,
+                              double *aer, double *ray);
+
 /* SOS_OS, SOS_OS.F:303-1674 (with SOS_FSOURCE_ORDRE1/ORDREIG, SOS_INTEGR_EPOPT, the Fresnel flat-sea
  * pieces, the four stop tests and SOS_AJOUT_QUEUE).
  *  rsurf : REAL*4 surface matrices in FICSURF record order [iborm+1][9][N][N] with

@@ -22,6 +22,7 @@ EXPORTS = [
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
+    "sosgpu_debug_tables",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -40,6 +41,12 @@ class ProfileWl(C.Structure):
                 ("a_tronc", C.c_double), ("piz", C.c_double), ("piztr", C.c_double), ("zout", C.c_double),
                 ("xk_off", C.c_int64), ("ro_off", C.c_int64), ("alt_off", C.c_int64),
                 ("nterm", C.c_int32), ("nbins", C.c_int32), ("absprofil", C.c_int32), ("smax", C.c_int32)]
+
+
+class TablesInfo(C.Structure):
+    """sosgpu_tables_info (include/sosgpu.h): layout numbers and scalars of a context's tables."""
+    _fields_ = [(k, C.c_int32) for k in ("n", "w", "kp", "kh", "ks2h", "rtph", "nwgt", "prow", "os_nb", "smax", "n0", "ipolar")] + \
+               [(k, C.c_double) for k in ("beta2", "gamma2", "alpha2", "f11sun", "f12sun", "mus", "ro")]
 
 
 class SosgpuError(RuntimeError):
@@ -169,6 +176,8 @@ def lib():
         L.sosgpu_debug_scratch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.sosgpu_debug_roundtrip.restype = i32
         L.sosgpu_debug_roundtrip.argtypes = [i32, i32, C.c_size_t, vp, vp, vp]
+        L.sosgpu_debug_tables.restype = i32
+        L.sosgpu_debug_tables.argtypes = [vp, C.POINTER(TablesInfo), vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -453,6 +453,9 @@ extern "C" size_t sosgpu_ctx_bytes(const sosgpu_ctx *cx) { return cx ? cx->bytes
 // rdir[s][c][k] = R_c1(N0, k) of the direct term (SOS_OS.F:984-990).
 __global__ void k_pack_ground(SosDev cx, const float *__restrict__ r, double *__restrict__ gop, double *__restrict__ rdir)
 {
+    // no fused multiply-add: the Lambertian term is added to the rounded BRDF term, as the formula above reads (with
+    // contraction the sum was one ulp off its plain evaluation in about one entry of eight)
+#pragma clang fp contract(off)
     const int s = blockIdx.y, N = cx.n;
     const size_t per = (size_t)cx.rtph * cx.ks2h * 128;
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1514,6 +1517,39 @@ extern "C" int sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *
     *d_scratch = cx->scratch;
     *doubles = cx->scratch_doubles;
     *spec_i3_offset = cx->dbg_spec_i3;
+    return SOSGPU_OK;
+}
+
+// Diagnostic: the context's per-wavelength tables and layout numbers, copied to the host (read-only; include/sosgpu.h).
+extern "C" int sosgpu_debug_tables(sosgpu_ctx *cx, sosgpu_tables_info *info, double *prt, double *mp_aer, double *mp_vt,
+                                   double *mp_uf, double *sv, double *mp_gnd, double *rdir, int32_t *rowmap)
+{
+    if (!cx || !info) return SOSGPU_E_ARG;
+    const SosDev &d = cx->d;
+    if ((mp_gnd || rdir) && (!d.mp_gnd || !d.rdir)) return SOSGPU_E_ARG;
+    info->n = d.n; info->w = d.w; info->kp = d.kp; info->kh = d.kh; info->ks2h = d.ks2h; info->rtph = d.rtph;
+    info->nwgt = d.nwgt; info->prow = d.prow; info->os_nb = d.os_nb; info->smax = d.smax; info->n0 = d.n0;
+    info->ipolar = d.ipolar;
+    info->beta2 = d.beta2; info->gamma2 = d.gamma2; info->alpha2 = d.alpha2; info->f11sun = d.f11sun;
+    info->f12sun = d.f12sun; info->mus = d.mus; info->ro = d.ro;
+    HIPCHK(hipSetDevice(cx->device));
+    hipStream_t us = util_stream(cx->device);
+    if (!us) return SOSGPU_E_HIP;
+    HIPCHK(sync_ctx_streams(cx));            // the table builds may still be running on the streams they were queued on
+    const size_t S1 = (size_t)d.smax + 1, per = (size_t)d.rtph * d.ks2h * 128;
+    const struct { void *dst; const void *src; size_t bytes; } cp[] = {
+        {prt, d.prt, S1 * 3 * (d.os_nb + 1) * d.w * sizeof(double)},
+        {mp_aer, d.mp_aer, S1 * 2 * per * sizeof(double)},
+        {mp_vt, d.mp_vt, (size_t)3 * d.ks2h * 128 * sizeof(double)},
+        {mp_uf, d.mp_uf, (size_t)3 * d.rtph * 64 * sizeof(double)},
+        {sv, d.sv, S1 * 4 * d.kp * sizeof(double)},
+        {mp_gnd, d.mp_gnd, S1 * per * sizeof(double)},
+        {rdir, d.rdir, S1 * 3 * d.n * sizeof(double)},
+        {rowmap, d.rowmap, (size_t)d.kh * sizeof(int32_t)},
+    };
+    for (const auto &c : cp)
+        if (c.dst) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, us));
+    HIPCHK(hipStreamSynchronize(us));
     return SOSGPU_OK;
 }
 

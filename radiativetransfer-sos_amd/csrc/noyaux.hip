@@ -92,9 +92,8 @@ __global__ void k_gsf(SosDev cx)
 
 // One element of one of the six kernels of SOS_NOYAUX (SOS_OS.F:2134-2143) for order s:
 //   X: 0 BP, 1 GR, 2 GT, 3 ARR, 4 ART, 5 ATT;  a, b in -N..N (0 = solar slot)
-// coefficient set: aerosol (alpha..zeta arrays, l = s..B) or molecular (l = 0 and 2 only:
-// beta0/beta2, gamma2, alpha2, zeta = 0 -- SOS_OS.F:2859-2876).
-template <bool RAY>
+// with the aerosol coefficient arrays alpha..zeta, l = s..B.  (The molecular kernels are single l = 2 terms, SOS_OS.F:2859-2876:
+// k_pack_ray factorises them and k_sv writes them out term by term.)
 __device__ inline double ktab(const SosDev &cx, int s, int X, int a, int b)
 {
     const int W = cx.w, N = cx.n, B = cx.os_nb;
@@ -103,20 +102,6 @@ __device__ inline double ktab(const SosDev &cx, int s, int X, int a, int b)
     const double *T = cx.prt + ((size_t)(s * 3 + 2) * (B + 1)) * W + N;
     const double *AL = cx.coef, *BE = cx.coef + (B + 1), *GA = cx.coef + 2 * (B + 1), *ZE = cx.coef + 3 * (B + 1);
     double sum = 0.;
-    if (RAY) {
-        if (s > 2) return 0.;
-        // l = 2 term (and beta0 for BP at s = 0; P^0_0 = 1)
-        const double pa = P[2 * W + a], pb = P[2 * W + b], ra = R[2 * W + a], rb = R[2 * W + b];
-        const double ta = T[2 * W + a], tb = T[2 * W + b];
-        switch (X) {
-        case 0: return ((s == 0) ? 1. : 0.) + cx.beta2 * pa * pb;
-        case 1: return cx.gamma2 * pa * rb;
-        case 2: return cx.gamma2 * pa * tb;
-        case 3: return cx.alpha2 * ra * rb;
-        case 4: return cx.alpha2 * ta * rb;
-        default: return cx.alpha2 * ta * tb;
-        }
-    }
     for (int l = s; l <= B; l++) {
         const size_t o = (size_t)l * W;
         switch (X) {
@@ -137,7 +122,6 @@ __device__ inline double ktab(const SosDev &cx, int s, int X, int a, int b)
 //   Q<-I  plus(GR,j,k)    Q<-Q  plus(ARR,j,k)    Q<-U  -plus(ART,j,k)
 //   U<-I  -minus(GT,j,k)  U<-Q  -plus(ART,k,j)   U<-U  minus(ATT,j,k)
 // times w_j/4 (the reference's Gauss weight and final 1/2, and the 1/2 of the recombination).
-template <bool RAY>
 __device__ inline double half_element(const SosDev &cx, int s, int sys, int row, int col)
 {
     const int N = cx.n;
@@ -157,7 +141,7 @@ __device__ inline double half_element(const SosDev &cx, int s, int sys, int row,
     case 7: X = 4; a = k; b = j; neg = true; break;
     default: X = 5; a = j; b = k; mns = true; break;
     }
-    const double same = ktab<RAY>(cx, s, X, a, b), opp = ktab<RAY>(cx, s, X, a, -b);
+    const double same = ktab(cx, s, X, a, b), opp = ktab(cx, s, X, a, -b);
     double v = mns ? (same - sg * opp) : (same + sg * opp);
     if (neg) v = -v;
     return 0.25 * cx.ga[j - 1] * v;
@@ -196,7 +180,7 @@ __global__ void k_pack(SosDev cx)
     const int col = 8 * m + 2 * (lane >> 4) + e2;
     const int H = 3 * cx.n;
     const bool in = row < H && col < H;
-    double v = in ? half_element<false>(cx, s, sys, row, col) : 0.;
+    double v = in ? half_element(cx, s, sys, row, col) : 0.;
     // the four projection rows of the rank-4 molecular operator ride in padding rows of the half system they act on
     // (A for even s, B for odd s): the dense contraction then delivers V^T X for free
     if (cx.prow >= 0 && s <= 2 && sys == (s & 1) && row >= cx.prow && row < cx.prow + 4 && col < H)
@@ -261,23 +245,40 @@ __global__ void k_sv(SosDev cx)
     double *o = cx.sv + (size_t)s * 4 * cx.kp;
     double v0 = 0., v1 = 0., v2 = 0., v3 = 0.;
     if (r < cx.r6) {
-        const int N = cx.n;
+        const int N = cx.n, W = cx.w, B = cx.os_nb;
         const int c = r / (2 * N), d = r % (2 * N);
         const int J = d < N ? d + 1 : -(d - N + 1);
         const int D = -J;
         const double f11 = cx.f11sun, f12 = cx.f12sun;
+        // molecular parts: single l = 2 terms, multiplied in the order the reference writes each of them (SOS_OS.F:2533-2545,
+        // 3237-3252 -- GR(D,0) is written differently for the two signs of D), so that they are its values to the last bit
+        const bool ray = s <= 2;
+        const double *P2 = cx.prt + ((size_t)(s * 3 + 0) * (B + 1) + 2) * W + N;
+        const double *R2 = cx.prt + ((size_t)(s * 3 + 1) * (B + 1) + 2) * W + N;
+        const double *T2 = cx.prt + ((size_t)(s * 3 + 2) * (B + 1) + 2) * W + N;
+        const double b0 = (s == 0) ? 1. : 0., b2 = cx.beta2, g2 = cx.gamma2, a2 = cx.alpha2;
+        const double spl = P2[0], srl = R2[0];
         if (c == 0) {
-            v0 = ktab<false>(cx, s, 0, 0, J); v1 = ktab<true>(cx, s, 0, 0, J);
-            v2 = f11 * ktab<false>(cx, s, 0, 0, D) + f12 * ktab<false>(cx, s, 1, D, 0);
-            v3 = f11 * ktab<true>(cx, s, 0, 0, D) + f12 * ktab<true>(cx, s, 1, D, 0);
+            v0 = ktab(cx, s, 0, 0, J);
+            v2 = f11 * ktab(cx, s, 0, 0, D) + f12 * ktab(cx, s, 1, D, 0);
+            if (ray) {
+                v1 = b0 + b2 * P2[J] * spl;
+                v3 = f11 * (b0 + b2 * P2[D] * spl) + f12 * (D < 0 ? g2 * srl * P2[D] : srl * P2[D] * g2);
+            }
         } else if (c == 1) {
-            v0 = ktab<false>(cx, s, 1, 0, J); v1 = ktab<true>(cx, s, 1, 0, J);
-            v2 = f11 * ktab<false>(cx, s, 1, 0, D) + f12 * ktab<false>(cx, s, 3, 0, D);
-            v3 = f11 * ktab<true>(cx, s, 1, 0, D) + f12 * ktab<true>(cx, s, 3, 0, D);
+            v0 = ktab(cx, s, 1, 0, J);
+            v2 = f11 * ktab(cx, s, 1, 0, D) + f12 * ktab(cx, s, 3, 0, D);
+            if (ray) {
+                v1 = g2 * R2[J] * spl;
+                v3 = f11 * (R2[D] * spl * g2) + f12 * (a2 * srl * R2[D]);
+            }
         } else {
-            v0 = -ktab<false>(cx, s, 2, 0, J); v1 = -ktab<true>(cx, s, 2, 0, J);
-            v2 = f11 * ktab<false>(cx, s, 2, 0, D) + f12 * ktab<false>(cx, s, 4, D, 0);
-            v3 = f11 * ktab<true>(cx, s, 2, 0, D) + f12 * ktab<true>(cx, s, 4, D, 0);
+            v0 = -ktab(cx, s, 2, 0, J);
+            v2 = f11 * ktab(cx, s, 2, 0, D) + f12 * ktab(cx, s, 4, D, 0);
+            if (ray) {
+                v1 = -(g2 * T2[J] * spl);
+                v3 = f11 * (g2 * spl * T2[D]) + f12 * (a2 * T2[D] * srl);
+            }
         }
     }
     o[0 * cx.kp + r] = v0; o[1 * cx.kp + r] = v1; o[2 * cx.kp + r] = v2; o[3 * cx.kp + r] = v3;
@@ -290,7 +291,7 @@ __global__ void k_noyaux_fetch(SosDev cx, int s, double *out)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < W * W) {
         const int j = idx / W - N, k = idx % W - N;
-        for (int X = 0; X < 6; X++) out[(size_t)X * W * W + idx] = ktab<false>(cx, s, X, j, k);
+        for (int X = 0; X < 6; X++) out[(size_t)X * W * W + idx] = ktab(cx, s, X, j, k);
     }
     if (idx < W) {
         const int B = cx.os_nb;

@@ -199,6 +199,25 @@ class SosContext:
             d[k] = out[6 * w * w + i * w:6 * w * w + (i + 1) * w]
         return d
 
+    def debug_tables(self):
+        """The context's per-wavelength tables and their layout numbers on the host (sosgpu_debug_tables; read-only):
+        dict of the TablesInfo fields plus prt, mp_aer, mp_vt, mp_uf, sv, rowmap and -- with surface matrices -- mp_gnd, rdir."""
+        L = capi.lib()
+        info = capi.TablesInfo()
+        capi.check(L.sosgpu_debug_tables(self._h, C.byref(info), *([None] * 8)), "sosgpu_debug_tables")
+        t = {k: getattr(info, k) for k, _ in capi.TablesInfo._fields_}
+        s1, per = t["smax"] + 1, t["rtph"] * t["ks2h"] * 128
+        a = dict(prt=np.zeros((s1, 3, t["os_nb"] + 1, t["w"])), mp_aer=np.zeros((s1, 2, per)),
+                 mp_vt=np.zeros((3, t["ks2h"] * 128)), mp_uf=np.zeros((3, t["rtph"] * 64)), sv=np.zeros((s1, 4, t["kp"])),
+                 mp_gnd=np.zeros((s1, per)) if self._rsurf is not None else None,
+                 rdir=np.zeros((s1, 3, t["n"])) if self._rsurf is not None else None,
+                 rowmap=np.zeros(t["kh"], dtype=np.int32))
+        ptr = [None if a[k] is None else a[k].ctypes.data_as(C.c_void_p)
+               for k in ("prt", "mp_aer", "mp_vt", "mp_uf", "sv", "mp_gnd", "rdir", "rowmap")]
+        capi.check(L.sosgpu_debug_tables(self._h, C.byref(info), *ptr), "sosgpu_debug_tables")
+        t.update({k: v for k, v in a.items() if v is not None})
+        return t
+
     def upload_bins(self, h, xdel, ydel, nt=None, iborm=None, zout=-1.0, zprof=None, order=None):
         """Pack per-bin profiles (after the SOS.F rescale) into the device layout of sosgpu_os_solve.
         h/xdel/ydel: [nb][L] arrays (ragged bins: pass nt[nb] and pad).

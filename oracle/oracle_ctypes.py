@@ -27,6 +27,8 @@ def lib():
         subprocess.check_call(["make", "-s", "-C", HERE, SO])
         _lib = C.CDLL(SO)
         _lib.sos_oracle_os.restype = C.c_int
+        _lib.sos_oracle_os_levels.restype = C.c_int
+        _lib.sos_oracle_stop_margin.restype = C.c_double
         _lib.sos_oracle_profile_rescale.restype = C.c_int
         _lib.sos_oracle_aggregate.restype = C.c_int
     return _lib
@@ -195,9 +197,44 @@ def sos_os(rmu, ga, os_nb, h, xdel, ydel, alpha, beta, gamma, zeta, *, n0, tetas
                 ig_counts=ig_last[:f].copy())
 
 
+def sos_os_levels(rmu, ga, os_nb, h, xdel, ydel, alpha, beta, gamma, zeta, zouts, *, n0, tetas=0.0, ro=0.0,
+                  imat_surf=0, ifresnel=0, ind_surf=1.34, zprof=None, ron=float(np.float32(0.0279)),
+                  igmax=100, iborm=None, ipolar=1, rsurf=None):
+    """sos_os with several output altitudes from one solve: records [nz][F][3][W]; ig_counts, fluxes and ier as sos_os, plus
+    margin = the tie audit of this very call (read on the calling thread, so it is valid under a thread pool)."""
+    n = len(rmu)
+    nt = len(h) - 1
+    w = 2 * n + 1
+    if iborm is None:
+        iborm = os_nb
+    if zprof is None:
+        zprof = np.linspace(120.0, 0.0, nt + 1)
+    ins = [np.ascontiguousarray(x, dtype=np.float64) for x in (rmu, ga, h, xdel, ydel, zprof, alpha, beta, gamma, zeta, zouts)]
+    nz = len(ins[10])
+    assert nz >= 1
+    rec = np.zeros((nz, iborm + 1, 3, w))
+    n_orders = C.c_int(0)
+    ig_last = np.zeros(iborm + 1, dtype=np.int32)
+    emoins, eplus = C.c_double(0), C.c_double(0)
+    rs = None
+    if imat_surf == 1:
+        rs = np.ascontiguousarray(rsurf, dtype=np.float32)
+        assert rs.shape == (iborm + 1, 9, n, n), rs.shape
+    ier = lib().sos_oracle_os_levels(
+        C.c_int(n), _p(ins[0]), _p(ins[1]), C.c_int(os_nb), C.c_int(nt), C.c_int(n0), C.c_double(tetas),
+        C.c_double(ro), C.c_int(imat_surf), C.c_int(ifresnel), C.c_double(ind_surf),
+        _p(ins[2]), _p(ins[3]), _p(ins[4]), _p(ins[5]), C.c_double(ron),
+        _p(ins[6]), _p(ins[7]), _p(ins[8]), _p(ins[9]), C.c_int(nz), _p(ins[10]), C.c_int(igmax), C.c_int(iborm),
+        C.c_int(ipolar), None if rs is None else _p(rs), _p(rec), C.byref(n_orders), _p(ig_last),
+        C.byref(emoins), C.byref(eplus))
+    margin = lib().sos_oracle_stop_margin()
+    f = n_orders.value
+    return dict(records=rec[:, :f].copy(), emoins=emoins.value, eplus=eplus.value, ier=ier, ig_counts=ig_last[:f].copy(),
+                margin=margin)
+
+
 def stop_margin():
-    """Tie audit of the last sos_os call: min |Z1/threshold - 1| over all its stop decisions (sos_oracle.c audit)."""
-    lib().sos_oracle_stop_margin.restype = C.c_double
+    """Tie audit of the last sos_os / sos_os_levels call of this thread: min |Z1/threshold - 1| over all its stop decisions (sos_oracle.c audit)."""
     return lib().sos_oracle_stop_margin()
 
 

@@ -547,10 +547,10 @@ void sos_oracle_ordreig_level(int is, int n, const double *ga, const double *ker
 
 /* one term of SOS_PARAM_CONV, SOS_OS.F:3434-3453 */
 /* Tie audit ("near-threshold ties need a documented policy"): every stop decision of the last
- * sos_oracle_os call records how far the tested value was from its threshold, |Z1/threshold - 1|; the minimum is read
+ * sos_oracle_os / sos_oracle_os_levels call of the calling thread records how far the tested value was from its threshold, |Z1/threshold - 1|; the minimum is read
  * with sos_oracle_stop_margin().  A decision closer to its threshold than the rounding difference between two correct
  * implementations (about 1e-12) could go either way: the parity fixtures are required to stay far from that. */
-static double g_stop_margin = 1e300;
+static _Thread_local double g_stop_margin = 1e300; /* per thread: the tests call the oracle from a thread pool */
 static void audit(double z1, double thr)
 {
     if (thr > 0. && z1 > 0.) {
@@ -575,17 +575,19 @@ static double queue_term(double d, double gg) /* SOS_AJOUT_QUEUE, SOS_OS.F:3959-
     return gg / (1 - gg / d);
 }
 
-int sos_oracle_os(int n, const double *mu, const double *ga_in, int os_nb, int nt,
-                  int n0, double tetas, double ro, int imat_surf, int ifresnel, double ind_surf,
-                  const double *h, const double *xdel, const double *ydel, const double *zprof, double ron,
-                  const double *alpha_in, const double *beta_in, const double *gamma_in, const double *zeta_in,
-                  double zout, int igmax, int iborm, int ipolar, const float *rsurf,
-                  double *rec, int *n_orders, int *ig_last, double *emoins, double *eplus)
+/* One solve, nz output altitudes: the field I3OUT/Q3OUT/U3OUT of each Fourier order is kept per level, so the rule of
+ * :1484-1534 is applied to it once per altitude.  Nothing else depends on the altitude. */
+int sos_oracle_os_levels(int n, const double *mu, const double *ga_in, int os_nb, int nt,
+                         int n0, double tetas, double ro, int imat_surf, int ifresnel, double ind_surf,
+                         const double *h, const double *xdel, const double *ydel, const double *zprof, double ron,
+                         const double *alpha_in, const double *beta_in, const double *gamma_in, const double *zeta_in,
+                         int nz, const double *zouts, int igmax, int iborm, int ipolar, const float *rsurf,
+                         double *rec, int *n_orders, int *ig_last, double *emoins, double *eplus)
 {
     geom_t gs, *g = &gs;
     const int W = 2 * n + 1, L = nt + 1;
     const size_t FS = (size_t)W * L;
-    int i, j, k, is, ig, ier = 0;
+    int i, j, k, is, ig, iz, ier = 0;
     g_stop_margin = 1e300;
     g->n = n; g->nt = nt; g->L = L; g->W = W;
     g->rmu = calloc(W, sizeof(double));
@@ -621,7 +623,7 @@ int sos_oracle_os(int n, const double *mu, const double *ga_in, int os_nb, int n
     kn.art = kbuf + (size_t)4 * W * W; kn.att = kbuf + (size_t)5 * W * W;
     kn.xpl = kbuf + (size_t)6 * W * W; kn.xrl = kn.xpl + W; kn.xtl = kn.xrl + W;
 
-    memset(rec, 0, sizeof(double) * (size_t)(iborm + 1) * 3 * W);
+    memset(rec, 0, sizeof(double) * (size_t)nz * (iborm + 1) * 3 * W);
     for (is = 0; is <= iborm; is++) ig_last[is] = 0;
     *n_orders = 0; *emoins = 0.; *eplus = 0.;
 
@@ -639,7 +641,8 @@ int sos_oracle_os(int n, const double *mu, const double *ga_in, int os_nb, int n
     else tab = -cos(acos(-1.0) * tetas / 180.);
     V(g->rmu, 0) = tab;
     if (tab == 0.0) goto done; /* :807 (limb incidence: returns with IER=0) */
-    if (((zout < 0) && (zout != -1.0)) || (zout > TOA_ALT)) { ier = -1; goto done; } /* :811 */
+    for (iz = 0; iz < nz; iz++)
+        if (((zouts[iz] < 0) && (zouts[iz] != -1.0)) || (zouts[iz] > TOA_ALT)) { ier = -1; goto done; } /* :811 */
 
     if (ifresnel == 1) { /* SOS_MAT_FRESNEL_PLAN_REFL :1753-1780 */
         for (j = 0; j <= n; j++) {
@@ -866,22 +869,23 @@ int sos_oracle_os(int n, const double *mu, const double *ga_in, int os_nb, int n
                 V(i5, j) = V(i5, j) + coef * V(i3, j) * sign; V(q5, j) = V(q5, j) + coef * V(q3, j) * sign; V(u5, j) = V(u5, j) + coef * V(u3, j) * sign;
             }
         }
-        if (zout == -1) { /* :1484-1534 */
-            for (k = -n; k <= -1; k++) { V(i3z, k) = FLD(i3o, nt, k); V(q3z, k) = FLD(q3o, nt, k); V(u3z, k) = FLD(u3o, nt, k); }
-            for (k = 1; k <= n; k++) { V(i3z, k) = FLD(i3o, 0, k); V(q3z, k) = FLD(q3o, 0, k); V(u3z, k) = FLD(u3o, 0, k); }
-        } else {
-            double zz;
-            j = 1;
-            while (zout < zprof[j]) j = j + 1;
-            zz = (zout - zprof[j - 1]) / (zprof[j] - zprof[j - 1]);
-            for (k = -n; k <= n; k++) {
-                V(i3z, k) = (1 - zz) * FLD(i3o, j - 1, k) + zz * FLD(i3o, j, k);
-                V(q3z, k) = (1 - zz) * FLD(q3o, j - 1, k) + zz * FLD(q3o, j, k);
-                V(u3z, k) = (1 - zz) * FLD(u3o, j - 1, k) + zz * FLD(u3o, j, k);
+        for (iz = 0; iz < nz; iz++) {
+            const double zout = zouts[iz];
+            double *r = rec + ((size_t)iz * (iborm + 1) + is) * 3 * W;
+            if (zout == -1) { /* :1484-1534 */
+                for (k = -n; k <= -1; k++) { V(i3z, k) = FLD(i3o, nt, k); V(q3z, k) = FLD(q3o, nt, k); V(u3z, k) = FLD(u3o, nt, k); }
+                for (k = 1; k <= n; k++) { V(i3z, k) = FLD(i3o, 0, k); V(q3z, k) = FLD(q3o, 0, k); V(u3z, k) = FLD(u3o, 0, k); }
+            } else {
+                double zz;
+                j = 1;
+                while (zout < zprof[j]) j = j + 1;
+                zz = (zout - zprof[j - 1]) / (zprof[j] - zprof[j - 1]);
+                for (k = -n; k <= n; k++) {
+                    V(i3z, k) = (1 - zz) * FLD(i3o, j - 1, k) + zz * FLD(i3o, j, k);
+                    V(q3z, k) = (1 - zz) * FLD(q3o, j - 1, k) + zz * FLD(q3o, j, k);
+                    V(u3z, k) = (1 - zz) * FLD(u3o, j - 1, k) + zz * FLD(u3o, j, k);
+                }
             }
-        }
-        {
-            double *r = rec + (size_t)is * 3 * W;
             for (k = -n; k <= n; k++) {
                 if (k == 0) continue;
                 r[0 * W + k + n] = V(i3z, k); r[1 * W + k + n] = V(q3z, k); r[2 * W + k + n] = V(u3z, k);
@@ -909,6 +913,18 @@ done:
     free(g->rmu); free(g->ga); free(alpha); free(beta); free(gamma); free(zeta);
     free(fld); free(vec); free(ch); free(kbuf);
     return ier;
+}
+
+int sos_oracle_os(int n, const double *mu, const double *ga_in, int os_nb, int nt,
+                  int n0, double tetas, double ro, int imat_surf, int ifresnel, double ind_surf,
+                  const double *h, const double *xdel, const double *ydel, const double *zprof, double ron,
+                  const double *alpha_in, const double *beta_in, const double *gamma_in, const double *zeta_in,
+                  double zout, int igmax, int iborm, int ipolar, const float *rsurf,
+                  double *rec, int *n_orders, int *ig_last, double *emoins, double *eplus)
+{
+    return sos_oracle_os_levels(n, mu, ga_in, os_nb, nt, n0, tetas, ro, imat_surf, ifresnel, ind_surf, h, xdel, ydel, zprof, ron,
+                                alpha_in, beta_in, gamma_in, zeta_in, 1, &zout, igmax, iborm, ipolar, rsurf,
+                                rec, n_orders, ig_last, emoins, eplus);
 }
 
 /* SOS.F:523-550 */

@@ -78,8 +78,17 @@ int sos_oracle_os(int n, const double *mu, const double *ga, int os_nb, int nt,
                   double zout, int igmax, int iborm, int ipolar, const float *rsurf,
                   double *rec, int *n_orders, int *ig_last, double *emoins, double *eplus);
 
+/* The same solve with nz output altitudes zouts[nz] (-1 allowed per slot) in place of zout: rec is [nz][iborm+1][3][W]; order
+ * counts, ig_last and fluxes are those of the one solve.  sos_oracle_os is the nz = 1 call of this function. */
+int sos_oracle_os_levels(int n, const double *mu, const double *ga, int os_nb, int nt,
+                         int n0, double tetas, double ro, int imat_surf, int ifresnel, double ind_surf,
+                         const double *h, const double *xdel, const double *ydel, const double *zprof, double ron,
+                         const double *alpha, const double *beta, const double *gamma, const double *zeta,
+                         int nz, const double *zouts, int igmax, int iborm, int ipolar, const float *rsurf,
+                         double *rec, int *n_orders, int *ig_last, double *emoins, double *eplus);
+
 /* Tie audit: minimum over every stop decision (SOS_PARAM_CONV, SOS_ARRET_DIFFUS_1/2, SOS_ARRET_FOURIER) of the last
- * sos_oracle_os call of |tested value / threshold - 1|. */
+ * sos_oracle_os / sos_oracle_os_levels call of the calling thread of |tested value / threshold - 1|. */
 double sos_oracle_stop_margin(void);
 
 /* SOS.F:523-550: delta-truncation rescale of a profile (in place) and IBORM choice.

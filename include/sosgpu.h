@@ -28,6 +28,7 @@
  *   sosgpu_profile     <- SOS_PROFILE + SOS_DISC  src/SOS_PROFIL.F:224,1210 (+ the PROFIL read-back and rescale of
  *                                                 SOS, src/SOS.F:511-550; all bins of a wavelength at once)
  *   sosgpu_profile_spectrum   the same and SOS_ABSPROFILE for the bins of many wavelengths: three launches in all
+ *   sosgpu_ckd_layer_tables <- COEFF_ABS_CKD      src/SOS_SUB_TRS.F:171 (every gas, term and layer of many wavelengths)
  *   sosgpu_noyaux      <- SOS_NOYAUX              src/SOS_OS.F:1857   (phase-matrix Fourier kernels,
  *                                                                     hoisted out of the bin loop)
  *   sosgpu_os_solve    <- SOS_OS (+ leaves)       src/SOS_OS.F:303    (one call = a batch of CKD bins,
@@ -322,9 +323,9 @@ int  sosgpu_profile(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, dou
 int  sosgpu_profile_nogas(int device, double tr, double hr, double ta, double ha, double *d_nogas, void *stream);
 
 /* Replaces the per-bin calls `CALL SOS_ABSPROFILE` of the CKD loop (SOS_PROC.F:3494; src/SOS_ABSPROFILE.F:184, core :325-371)
- * for nb bins at once.  The coefficient of a gas depends on the gas, the exponential term and the layer only, so the host
- * tabulates it once per wavelength (COEFF_ABS_CKD, src/SOS_SUB_TRS.F:171; absorption.layer_tables) and a bin is one term
- * index per gas:
+ * for nb bins at once.  The coefficient of a gas depends on the gas, the exponential term and the layer only, so it is
+ * tabulated once per wavelength (COEFF_ABS_CKD, src/SOS_SUB_TRS.F:171: on the device by sosgpu_ckd_layer_tables below, or on
+ * the host as absorption.layer_tables does) and a bin is one term index per gas:
  *   d_ik[nb][8]              1-based term index IK1..IK8 of each bin (gas order H2O, CO2, O3, N2O, CO, CH4, O2, NO2)
  *   d_xk[8][nterm][nlev-1]   k_i of (gas, term, layer), layer 0 = top layer;  d_ro[8][nlev-1] molecules/cm2 of the layer
  *   d_tabs[nb][nlev]         TAUABS: cumulative absorption optical depth per level, level 0 = TOA (feeds sosgpu_profile)
@@ -370,6 +371,44 @@ int  sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, i
                              const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
                              void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
                              double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal, int *bad_wl, void *stream);
+
+/* Replaces the calls `CALL COEFF_ABS_CKD` of SOS_ABSPROFILE's gas and layer loops (src/SOS_ABSPROFILE.F:325-353; the routine:
+ * src/SOS_SUB_TRS.F:171-393) for MANY wavelengths in one launch: k_i of every (gas, exponential term) table of every
+ * wavelength interpolated to the layers -- along the H2O concentration (gas 0 only), the pressure, then by SOS_SPLINE /
+ * SOS_SPLINT along the temperature, with the linear fallback for a negative spline value -- statement for statement, so the
+ * doubles are the host routine's.  One wavefront per slot = (wavelength, gas, term); the coefficient tables stay on the device.
+ *   wl[nwl] (HOST)       one entry per wavelength:
+ *       nterm            terms per gas of its output block (1 .. 65535); the wavelength has 8 * nterm slots, slot = gas * nterm + term
+ *       nt, np, nc       lengths of its temperature, pressure and H2O-concentration axes: 2..16, 2..64, 2..16
+ *       pres_off, temp_off, conc_off   where tab_pres[np], tab_temp[nt], tab_conc[nc] (ascending) start in d_axes, in doubles
+ *       prs_off, tmp_off, cl_off       where the layer means prs[nlay] (hPa), tmp[nlay] (K), conc[nlay] (H2O, ppmv * 1e-6) start
+ *                        in d_axes: the UNCLAMPED means of SOS_ABSPROFILE.F:330-337, layer 0 = top layer
+ *       xk_off           where its xk[8][nterm][nlay] starts in d_out, in doubles
+ *   ki[nslots] (HOST)    one DEVICE pointer per slot, wavelength after wavelength (nslots = sum of 8 * nterm): the table
+ *                        [np][nt] of the (gas, term), for gas 0 [nc][np][nt]; NULL = no absorption (a term >= NEXP of the gas,
+ *                        a table that is all zero): the slot's layers are written +0.0
+ *   d_axes[axes_doubles] the axes and layer states, packed;  nlay 1..63 is common to the launch (49 in the reference)
+ *   d_work               DEVICE work area of nwl * sosgpu_ckd_table_entry_bytes() + nslots * 8 bytes (8-byte aligned): table and
+ *                        slot pointers are copied there on `stream` from a pinned block the library recycles
+ *   d_out[out_doubles]   every xk block is written in full (nothing needs clearing); it may be the d_gas buffer of
+ *                        sosgpu_profile_spectrum, the xk_off being that call's, when this call is queued first on the same stream
+ *   d_status[nwl]        int32, cleared by this call on `stream`, then 0 = ok, 1 = SOS_SPLINT met two equal temperature nodes
+ *                        ('ERROR for SPLINT interpolation'), 2 = COEFF_ABS_CKD ERROR_923 (k_i < 0 after the linear fallback);
+ *                        the failing entries of xk are +0.0
+ * Returns SOSGPU_E_ARG for the argument rules (NULL pointers, nterm < 1, nslots, an offset outside d_axes / d_out) and
+ * SOSGPU_E_UNSUPPORTED for an axis length or nlay outside the limits above, with the wavelength's index in *bad_wl (NULL
+ * allowed; -1 = none); nothing is queued then.  No context; asynchronous on `stream`, nothing is waited for; the inputs, the
+ * tables and the work area must stay allocated until the kernel has run. */
+typedef struct sosgpu_ckd_wl {
+    int64_t pres_off, temp_off, conc_off;
+    int64_t prs_off, tmp_off, cl_off;
+    int64_t xk_off;
+    int32_t nterm, nt, np, nc;
+} sosgpu_ckd_wl;
+size_t sosgpu_ckd_table_entry_bytes(void);
+int  sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl *wl, int nslots, const double *const *ki,
+                             const double *d_axes, size_t axes_doubles, int nlay, void *d_work, double *d_out,
+                             size_t out_doubles, int32_t *d_status, int *bad_wl, void *stream);
 
 /* Replaces SOS_MIE + SOS_FPHASE_MIE (src/SOS_MIE.F:205, :801) for a whole grid of size parameters, no MIE cache file:
  *   xmu[2 nbmu + 1]  cosines RMU(-nbmu:nbmu) of the Mie angle set (host); rn, in: refractive index (in <= 0)

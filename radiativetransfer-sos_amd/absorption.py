@@ -16,6 +16,7 @@ bin, used by the single-profile mode -SOS.AbsModeCKD 2 bookkeeping and by tests.
 Data: CKD coefficient files and SO2-NO2 are read from $SOS_ABS_ROOT/fic like the reference does (GETENV, SOS_SUB_TRS.F:616);
 the six predefined atmospheres come from data/afgl_atmospheres.npz (scripts/make_afgl_tables.py).  REAL*4 literals of the
 Fortran are widened exactly as the compiler does (`_F`)."""
+import collections
 import functools
 import os
 import threading
@@ -172,7 +173,9 @@ def _read_ckd_file(path, nabs, nustep, numax_f, numin_f, _size, _mtime):
         ki[iwa, :nmax] = blk.reshape(nmax, nc, npr, nt)
     if nabs != 1:
         ki = ki[:, :, 0]
-    return dict(numax=numax, numin=numin, tab_temp=tab_t, tab_pres=tab_p, tab_conc=tab_c, nexp=nexp, ai=ai, ki=ki)
+    # key: what this parse is cached under -- the device copy of `ki` (ckd_device_file) is kept under the same
+    return dict(numax=numax, numin=numin, tab_temp=tab_t, tab_pres=tab_p, tab_conc=tab_c, nexp=nexp, ai=ai, ki=ki,
+                key=(path, nabs, nustep, numax_f, numin_f, _size, _mtime))
 
 
 def _interpol(y1, y2, x1, x2, x):
@@ -325,9 +328,10 @@ def _atmosphere(psurf, h2o, o3, co2, ch4, absprofil, ficabsprofil, root, _stamp)
 _PREFETCH = threading.local()
 
 
-def prefetch_gas_tables(requests):
+def prefetch_gas_tables(requests, device_tables=()):
     """requests: argument tuples of prepa_absprofile (wa, nustep, psurf, h2o, o3, co2, ch4, absprofil, ficabsprofil).  A
-    request that fails is left to the call that owns it."""
+    request that fails is left to the call that owns it.  device_tables: the requests (same tuples) whose layer tables the
+    device will interpolate (solver.ckd_layer_tables): they are prepared, but left out of layer_tables_many."""
     preps = {}
     root = None
     try:
@@ -342,8 +346,9 @@ def prefetch_gas_tables(requests):
             preps[key] = prepa_absprofile(*r, root=root)
         except (AbsorptionError, OSError, ValueError):
             pass
+    skip = set(tuple(r) for r in device_tables)
     try:
-        layer_tables_many(list(preps.values()))
+        layer_tables_many([p for key, p in preps.items() if key[:-1] not in skip])
     except AbsorptionError:
         pass                                           # (raised again, by its owner, in layer_tables)
     _PREFETCH.preps = preps
@@ -386,11 +391,12 @@ def prepa_absprofile(wa, nustep, psurf, h2o, o3, co2, ch4, absprofil, ficabsprof
     last = gas[-1]
     lamb1 = 1 + int((last["numax"] - nu) / nustep)
     iw = lamb1 - 1
+    # (_ckd_files: the parsed files the interval's tables are views of, for the device-resident copies -- ckd_device_slots)
     return dict(nu=nu, lamb1=lamb1, altabs=altabs, userprofil=user, ro=ro, absprofil=absprofil,
                 nexp=np.array([g["nexp"][iw] for g in gas], dtype=np.int32),
                 kdis_ai=np.stack([g["ai"][iw] for g in gas], axis=1),            # [5][8]
                 ki=[g["ki"][iw] for g in gas], tab_pres=last["tab_pres"], tab_temp=last["tab_temp"],
-                tab_conc=gas[0]["tab_conc"])
+                tab_conc=gas[0]["tab_conc"], _ckd_files=gas)
 
 
 def _spline_rows(x, y, dy1, dyn):
@@ -710,6 +716,96 @@ def layer_tables_many(preps):
                     outs[m][k, term][g.act] = val[q]
         for prep, xk in zip(members, outs):
             prep["_layer_tables"] = (xk, prep["ro"][:, nl - j - 1].copy())
+
+
+# ---- COEFF_ABS_CKD on the device (csrc/ckd.hip, sosgpu_ckd_layer_tables; solver.ckd_layer_tables) ---------------------------
+# The host keeps what the kernel cannot know: the layer means it starts from, which (gas, term) tables absorb at all, and the
+# device copies of the parsed coefficient files.  The host functions above stay as they are: they are its checkers.
+CKD_STATUS_MESSAGES = {1: "ERROR for SPLINT interpolation",
+                       2: "COEFF_ABS_CKD : ERROR_923 : Calculations give ki < 0 : uncorrect value!"}
+# Byte budget of the device-resident coefficient files (least recently used files are dropped beyond it; the newest always
+# stays).  A whole spectrum of the 10 cm-1 tables is 400 files, about 0.5 GB: the default holds it twice.
+CKD_DEVICE_BUDGET = int(os.environ.get("SOS_CKD_DEVICE_BYTES", str(1 << 30)))
+_CKD_DEV = collections.OrderedDict()               # (key of the parsed file, device) -> (device tensor of its ki, bytes)
+_CKD_DEV_LOCK = threading.Lock()
+
+
+def layer_state(prep):
+    """The layer means SOS_ABSPROFILE hands to COEFF_ABS_CKD (SOS_ABSPROFILE.F:330-337), unclamped: (prs, tmp, conc), each
+    [49] with layer 0 the TOP layer -- the first statements of layer_tables_scalar."""
+    u = prep["userprofil"]
+    nl = NLEVEL
+    j = np.arange(1, nl)
+    lo, hi = nl - j - 1, nl - j
+    prs = (u[lo, 1] + u[hi, 1]) / 2.
+    tmp = (u[lo, 2] + u[hi, 2]) / 2.
+    conc = (u[lo, 3] + u[hi, 3]) / 2.
+    conc = conc * 1.e-06
+    return prs, tmp, conc
+
+
+def layer_ro(prep):
+    """RO(gas, layer) as layer_tables returns it next to xk: [8][49], layer 0 the top layer."""
+    nl = NLEVEL
+    j = np.arange(1, nl)
+    return prep["ro"][:, nl - j - 1].copy()
+
+
+def ckd_absorbing(prep):
+    """bool [8][5]: the (gas, term) tables of the interval that are used (term < NEXP) and not all zero -- the pairs of
+    _absorbing_pairs.  Decided once per parsed file (for all its intervals) and kept with it."""
+    iw = prep["lamb1"] - 1
+    out = np.zeros((NBABS, CKD_NAI_MAX), dtype=bool)
+    for k, f in enumerate(prep["_ckd_files"]):
+        flags = f.get("_absorbing")
+        if flags is None:
+            ki = f["ki"]
+            flags = f["_absorbing"] = ki.reshape(ki.shape[0], ki.shape[1], -1).any(axis=2)          # [intervals][5]
+        out[k] = flags[iw] & (np.arange(CKD_NAI_MAX) < prep["nexp"][k])
+    return out
+
+
+def _ckd_upload(ki, device):
+    """One parsed file's coefficients -> one contiguous device tensor (a synchronous copy: complete, usable from any stream)."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(ki, dtype=np.float64)).to(device)
+
+
+def ckd_device_file(f, device):
+    """The device copy of the parsed file f (a dict of _read_ckd_file): uploaded the first time a wavelength of the file is
+    asked for, then kept under the file's own cache key -- path, size and modification time included, so an edited file is
+    uploaded again -- within CKD_DEVICE_BUDGET bytes.  A caller that queues work on the tensor holds it until that work has
+    run (an evicted tensor stays alive as long as somebody does)."""
+    key = (f["key"], str(device))
+    with _CKD_DEV_LOCK:
+        hit = _CKD_DEV.get(key)
+        if hit is not None:
+            _CKD_DEV.move_to_end(key)
+            return hit[0]
+    t = _ckd_upload(f["ki"], device)
+    nbytes = t.numel() * t.element_size()
+    with _CKD_DEV_LOCK:
+        _CKD_DEV[key] = (t, nbytes)
+        while len(_CKD_DEV) > 1 and sum(b for _, b in _CKD_DEV.values()) > CKD_DEVICE_BUDGET:
+            _CKD_DEV.popitem(last=False)
+    return t
+
+
+def drop_ckd_device_tables():
+    with _CKD_DEV_LOCK:
+        _CKD_DEV.clear()
+
+
+def ckd_device_tables(prep, device):
+    """(base address of the interval's [5][NP][NT] block (H2O: [5][NC][NP][NT]) of every gas as a Python int [8], the device
+    tensors holding them)."""
+    iw = prep["lamb1"] - 1
+    ptrs, keep = [], []
+    for f in prep["_ckd_files"]:
+        t = ckd_device_file(f, device)
+        ptrs.append(t.data_ptr() + iw * t.stride(0) * t.element_size())
+        keep.append(t)
+    return ptrs, keep
 
 
 def layer_tables_scalar(prep):

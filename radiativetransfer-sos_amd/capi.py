@@ -22,7 +22,7 @@ EXPORTS = [
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
-    "sosgpu_debug_tables",
+    "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -41,6 +41,13 @@ class ProfileWl(C.Structure):
                 ("a_tronc", C.c_double), ("piz", C.c_double), ("piztr", C.c_double), ("zout", C.c_double),
                 ("xk_off", C.c_int64), ("ro_off", C.c_int64), ("alt_off", C.c_int64),
                 ("nterm", C.c_int32), ("nbins", C.c_int32), ("absprofil", C.c_int32), ("smax", C.c_int32)]
+
+
+class CkdWl(C.Structure):
+    """sosgpu_ckd_wl (include/sosgpu.h): one wavelength of sosgpu_ckd_layer_tables."""
+    _fields_ = [("pres_off", C.c_int64), ("temp_off", C.c_int64), ("conc_off", C.c_int64),
+                ("prs_off", C.c_int64), ("tmp_off", C.c_int64), ("cl_off", C.c_int64), ("xk_off", C.c_int64),
+                ("nterm", C.c_int32), ("nt", C.c_int32), ("np", C.c_int32), ("nc", C.c_int32)]
 
 
 class TablesInfo(C.Structure):
@@ -158,6 +165,10 @@ def lib():
         L.sosgpu_profile_spectrum.restype = i32
         L.sosgpu_profile_spectrum.argtypes = [i32, i32, vp, i32, vp, vp, vp, C.c_size_t, i32, i32, vp, vp, vp, vp, vp, vp, vp,
                                               vp, vp, vp, C.POINTER(i32), vp]
+        L.sosgpu_ckd_table_entry_bytes.restype = C.c_size_t
+        L.sosgpu_ckd_table_entry_bytes.argtypes = []
+        L.sosgpu_ckd_layer_tables.restype = i32
+        L.sosgpu_ckd_layer_tables.argtypes = [i32, i32, vp, i32, vp, vp, C.c_size_t, i32, vp, vp, C.c_size_t, vp, C.POINTER(i32), vp]
         L.sosgpu_os_flops.restype = i32
         L.sosgpu_os_flops.argtypes = [vp, i32, vp, vp, vp, C.POINTER(dbl)]
         L.sosgpu_last_solve_ms.restype = i32

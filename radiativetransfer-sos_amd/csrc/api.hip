@@ -1424,6 +1424,66 @@ extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile
     return SOSGPU_OK;
 }
 
+// COEFF_ABS_CKD of many wavelengths in one launch (ckd.hip): the per-wavelength table and the slot pointers go through one
+// recycled pinned block into the caller's work area, the status words are cleared, the kernel is queued -- all on `stream`.
+extern "C" size_t sosgpu_ckd_table_entry_bytes(void) { return sizeof(CkdWl); }
+
+extern "C" int sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl *wl, int nslots, const double *const *ki,
+                                       const double *d_axes, size_t axes_doubles, int nlay, void *d_work, double *d_out,
+                                       size_t out_doubles, int32_t *d_status, int *bad_wl, void *stream)
+{
+    if (bad_wl) *bad_wl = -1;
+    if (nwl < 1 || !wl || nslots < 1 || !ki || !d_axes || !d_work || !d_out || !d_status) return SOSGPU_E_ARG;
+    if (((uintptr_t)d_work & 7) != 0) return SOSGPU_E_ARG;
+    if (nlay < 1 || nlay > SOS_CKD_NLAY_MAX) return SOSGPU_E_UNSUPPORTED;
+    // --- limits and argument rules per wavelength, before anything is queued
+    std::vector<CkdWl> tab((size_t)nwl);
+    long long slots = 0;
+    int max_slots = 0;
+    const long long ad = (long long)axes_doubles, od = (long long)out_doubles;
+    for (int w = 0; w < nwl; w++) {
+        const sosgpu_ckd_wl &s = wl[w];
+        CkdWl &t = tab[w];
+        if (bad_wl) *bad_wl = w;
+        if (s.nterm < 1 || s.nterm > 65535) return SOSGPU_E_ARG;
+        if (s.nt < 2 || s.nt > SOS_CKD_NT_MAX || s.np < 2 || s.np > SOS_CKD_NP_MAX || s.nc < 2 || s.nc > SOS_CKD_NC_MAX)
+            return SOSGPU_E_UNSUPPORTED;
+        const struct { long long off, len; } in[] = {{s.pres_off, s.np}, {s.temp_off, s.nt}, {s.conc_off, s.nc},
+                                                     {s.prs_off, nlay}, {s.tmp_off, nlay}, {s.cl_off, nlay}};
+        for (const auto &a : in)
+            if (a.off < 0 || a.off > ad || a.len > ad - a.off) return SOSGPU_E_ARG;
+        const long long xn = 8ll * s.nterm * nlay;
+        if (s.xk_off < 0 || s.xk_off > od || xn > od - s.xk_off) return SOSGPU_E_ARG;
+        t.pres_off = s.pres_off; t.temp_off = s.temp_off; t.conc_off = s.conc_off;
+        t.prs_off = s.prs_off; t.tmp_off = s.tmp_off; t.cl_off = s.cl_off;
+        t.xk_off = s.xk_off; t.slot0 = slots;
+        t.nterm = s.nterm; t.nt = s.nt; t.np = s.np; t.nc = s.nc;
+        slots += 8ll * s.nterm;
+        max_slots = std::max(max_slots, 8 * s.nterm);
+    }
+    if (bad_wl) *bad_wl = -1;
+    if (slots != nslots) return SOSGPU_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
+    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t tbytes = (size_t)nwl * sizeof(CkdWl), pbytes = (size_t)nslots * sizeof(double *);
+    size_t slot = 0;
+    if (int rc = stage_take(device, tbytes + pbytes, &slot)) return rc;
+    char *hp = (char *)stage_ptr(slot);
+    memcpy(hp, tab.data(), tbytes);
+    memcpy(hp + tbytes, ki, pbytes);
+    hipError_t ce = hipMemcpyAsync(d_work, hp, tbytes + pbytes, hipMemcpyHostToDevice, st);
+    stage_release(slot, st);
+    HIPCHK(ce);
+    HIPCHK(hipMemsetAsync(d_status, 0, (size_t)nwl * sizeof(int32_t), st));
+    launch_coeff_abs_ckd_table((const CkdWl *)d_work, nwl, max_slots, (const double *const *)((const char *)d_work + tbytes), d_axes,
+                               nlay, d_out, d_status, st);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
 extern "C" int sosgpu_mie(int device, int nbmu, const double *xmu, double rn, double in, int nalpha, const double *alphas,
                           float *d_rec, double *d_g, void *stream)
 {

@@ -105,6 +105,23 @@ void launch_profile_nogas(double tr, double hr, double ta, double ha, int nt, do
 void launch_absprofile(int nb, int nlev, int nterm, const int32_t *d_ik, const double *d_xk, const double *d_ro, double *d_tabs,
                        hipStream_t st);
 
+// COEFF_ABS_CKD of many wavelengths (ckd.hip k_coeff_abs_ckd_table, sosgpu_ckd_layer_tables): one wavefront per slot =
+// (wavelength, gas, term), lane = layer.  One entry per wavelength, uploaded by the entry point; offsets count doubles in
+// the packed axes buffer / the output block; slot0: the wavelength's first slot in the pointer table (8 * nterm slots each).
+#define SOS_CKD_NT_MAX 16         // temperature nodes (9 in the reference's tables)
+#define SOS_CKD_NP_MAX 64         // pressure nodes (31)
+#define SOS_CKD_NC_MAX 16         // H2O concentration nodes (12)
+#define SOS_CKD_NLAY_MAX 63       // layers = lanes (49)
+struct CkdWl {
+    long long pres_off, temp_off, conc_off;      // tab_pres[np], tab_temp[nt], tab_conc[nc]
+    long long prs_off, tmp_off, cl_off;          // layer means prs / tmp / conc [nlay], unclamped, layer 0 = top layer
+    long long xk_off;                            // xk[8][nterm][nlay] of the wavelength in the output block
+    long long slot0;
+    int nterm, nt, np, nc;
+};
+void launch_coeff_abs_ckd_table(const CkdWl *d_tab, int nwl, int max_slots, const double *const *d_ki, const double *d_axes, int nlay,
+                                double *d_out, int32_t *d_status, hipStream_t st);
+
 // Mie records of a size-parameter grid (mie.hip): rec[nalpha][4 + 3 (2 nbmu + 1)] floats, g[nalpha]; returns 0, -2 (HIP) or -3
 // (alpha_max beyond the LDS-resident coefficient arrays)
 size_t mie_scratch_doubles(double alpha_max, int count);

@@ -855,6 +855,15 @@ def _gas_table_request(p):
         return None
 
 
+def _gas_tables_on_device(p):
+    """True when, as far as the validated keyword set p tells, _prepare will defer the profiles of this gas call (the rest of its
+    rule needs the optical thicknesses)."""
+    try:
+        return int(p["iprofil"]) == 1 and str(p["fictrans"]).strip() == "NO_OUTPUT" and int(p["imode_ckd_calcul"]) == 1
+    except Exception:
+        return False
+
+
 def _aerosol_call(p, aer_phase):
     """(p, nb_mie, os_nb) of the SOS_AEROSOLS run _prepare will make at the simulation wavelength for the validated keyword set p,
     or None when that step does not run or its parameters are refused (the real pass reports)."""
@@ -914,7 +923,8 @@ def _profiles_deferrable(tr, hr, ta, ha):
         return False
 
 
-def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False):
+def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False,
+             device_gas_tables=False):
     """Everything of one SOS_PROC call up to the CKD bin loop (SOS_PROC.F:1310-3458): parameter checks, SOS_ANGLES,
     SOS_AEROSOLS, SOS_SURFACE, SOS_PREPA_ABSPROFILE, SOS_PREPA_OS, and the profiles of every bin of the band on the device
     (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Returns a _Plan whose `ctx` the caller closes.
@@ -925,7 +935,9 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     aer_at_wa: the result of SOS_AEROSOLS at the simulation wavelength when sos_spectrum has formed it already (aerosols_many).
     defer_profiles (_spectrum_pass only): a call that qualifies -- -AP.AerProfile.Type 1, no -SOS.Trans, -SOS.AbsModeCKD 1 or
     no gas, band not sharded -- gets no profile launches here: the plan comes back with `bins` None and `profile_request`, the
-    request solver.make_profiles_spectrum takes, and the pass makes the profiles of a whole part in three launches."""
+    request solver.make_profiles_spectrum takes, and the pass makes the profiles of a whole part in three launches.
+    device_gas_tables (with defer_profiles): a deferred gas wavelength hands over its `prep` instead of the layer tables xk --
+    COEFF_ABS_CKD then runs on the device for the whole part (sosgpu_ckd_layer_tables) and absorption.layer_tables not at all."""
     _seg(None)
     missing = [k for k in SOS_PROC_KWARGS if k not in kw]
     if missing:
@@ -1059,7 +1071,12 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
             prep = _abs.prepa_absprofile(p["wa_simu"], float(p["nustep"]), p["psurf"], p["h2o"], p["o3"], p["co2"], p["ch4"],
                                          absprofil, str(p["ficabsprofil"]).strip())
             ik, aik, _ = _abs.bins(prep)
-            xk, ro_lay = _abs.layer_tables(prep)
+            # (a sharded band; more levels than the kernels hold: the error is make_profiles')
+            defer = defer and not (_dist_rank_world()[1] > 1 and shard_bins or len(prep["altabs"]) > 64 or not len(aik))
+            if defer and device_gas_tables and len(prep["altabs"]) == _abs.NLEVEL:
+                xk, ro_lay = None, _abs.layer_ro(prep)                              # xk: made on the device, for the whole part
+            else:
+                xk, ro_lay = _abs.layer_tables(prep)
         except _abs.AbsorptionError as e:
             raise SosProcError(str(e), ier=-1)
     mode_ckd = int(p["imode_ckd_calcul"])
@@ -1130,13 +1147,13 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
         tabs_flux = None                              # TAUABS of the band's last bin (Flux file): host array or [.][nlev] device tensor
         request = None                                # deferred: what solver.make_profiles_spectrum needs of this wavelength
         common = dict(tr=tr, hr=p["hr"], ta=ta, ha=ha, a_tronc=a_tronc, piz=piz, piztr=piztr, zout=zout, smax=ctx.smax)
-        if defer and use_gas and (_dist_rank_world()[1] > 1 and shard_bins or len(prep["altabs"]) > 64 or not len(aik)):
-            defer = False                             # (a sharded band; more levels than the kernels hold: the error is make_profiles')
         if defer and not use_gas:
             request = dict(common, ik=None, absprofil=7)
             bins, aik = None, np.ones(1)
         elif defer:
             request = dict(common, ik=ik, xk=xk, ro=ro_lay, altabs=prep["altabs"], absprofil=absprofil)
+            if xk is None:
+                request["prep"] = prep
             bins = None
         elif not use_gas and iprofil == 1:
             # the single no-gas profile of the wavelength: SOS_PROFILE, the PROFIL-file round trip, the rescale, IBORM and the
@@ -1430,10 +1447,13 @@ def spectrum_costs(kwargs_list):
     return costs
 
 
-def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st):
+def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_gas_tables=False):
     """The shared host work of a spectrum chunk `idx`, queued ahead of its per-wavelength preparation: the size-distribution
     integrals (aerosols.prefetch_size_integrals), the gas tables interpolated to the layers in one pass, and SOS_AEROSOLS at the
-    simulation wavelength of each call.  Returns {index: aerosols at the simulation wavelength} for _prepare(aer_at_wa=...)."""
+    simulation wavelength of each call.  Returns {index: aerosols at the simulation wavelength} for _prepare(aer_at_wa=...).
+    device_gas_tables: the calls whose profiles _prepare can defer (as far as the keywords alone tell: -AP.AerProfile.Type 1,
+    no -SOS.Trans, -SOS.AbsModeCKD 1) get their layer tables from the device, so the one-pass host interpolation leaves them
+    out; a call _prepare then does not defer after all interpolates its own tables there."""
     import torch
     from . import aerosols as _aer
     from . import absorption as _abs
@@ -1447,9 +1467,10 @@ def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st):
         with torch.cuda.stream(aer_st):
             _aer.prefetch_size_integrals(reqs)
     # ... and the gas tables of the chunk's wavelengths, interpolated to the layers in one pass
-    greqs = [r for r in (_gas_table_request(v) for v in valid.values()) if r is not None]
+    greqs = [(r, v) for r, v in ((_gas_table_request(v), v) for v in valid.values()) if r is not None]
     if greqs:
-        _abs.prefetch_gas_tables(greqs)
+        on_device = [r for r, v in greqs if device_gas_tables and _gas_tables_on_device(v)]
+        _abs.prefetch_gas_tables([r for r, _ in greqs], device_tables=on_device)
     # ... and SOS_AEROSOLS at the simulation wavelength of each, the Legendre expansions formed together (the gas tables
     # above were made while the size integrals ran)
     aer_wa = {}
@@ -1538,6 +1559,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                       "the GPU)" % (len(side), fn), RuntimeWarning, stacklevel=3)
     # SOS_SPECTRUM_PROFILES_PER_CALL=1: every wavelength makes its own profile launches, as sos_proc does (A/B timing)
     batch_profiles = not os.environ.get("SOS_SPECTRUM_PROFILES_PER_CALL")
+    # the layer tables of the deferred gas wavelengths (COEFF_ABS_CKD) are interpolated on the device, one launch per part on the
+    # resident coefficient files; SOS_SPECTRUM_HOST_GAS_TABLES=1: on the host, uploaded with the requests (A/B timing).  A band
+    # dealt over several ranks keeps the host tables: bin_costs needs them
+    device_tables = batch_profiles and not os.environ.get("SOS_SPECTRUM_HOST_GAS_TABLES")
     where, err = -1, None                               # the wavelength being worked on (named by a failure)
     # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
     # a growing list of result tuples, and the collections this triggers re-walk the results again and again (SOS_SPECTRUM_KEEP_GC=1
@@ -1558,7 +1583,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 # device, and the launches below wait for all of them
                 for st in side + [aer_st]:
                     st.wait_stream(main_st)
-                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st)
+                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_tables)
+                ckd_checks = []                   # (status tensor of a part's device gas tables, the plans it speaks of)
                 # The chunk goes to the solver in a few parts: the solves of a part run on the device while the host prepares the
                 # next one, so that only the last part's solve is waited for below.
                 solved = []                       # (plans, rec [K][nw][S][3][W], scal [K][nw][10+N], table) device tensors
@@ -1571,7 +1597,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                         where = i
                         with torch.cuda.stream(side[k % len(side)]):
                             pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
-                                          aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles)
+                                          aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles, device_gas_tables=device_tables)
                             pl.writes_files = True
                             pl.index = i
                             plans.append(pl)
@@ -1593,6 +1619,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                             if info.get("bad") is not None:
                                 where = deferred[info["bad"]].index
                             raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
+                        if info.get("ckd_status") is not None:
+                            ckd_checks.append((info["ckd_status"], [deferred[g] for g in info["ckd_index"]]))
                         lv = None if alts is None else deferred[0].ctx.output_levels(info["bins"], alts)
                         for g, pl in enumerate(deferred):
                             # (views of the part's blocks: the plans keep them alive until the chunk's streams are synchronised)
@@ -1642,9 +1670,18 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     tm["solve_launch"] += t0 - t1
                 t2 = time.perf_counter()
                 # --- one copy of all band scalars (waits for the solves), then every azimuth recomposition back to back
-                scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in solved]).cpu().numpy()
+                # (the status words of the device gas tables ride at its end)
+                scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in solved] +
+                                     [s.to(torch.float64) for s, _ in ckd_checks]).cpu().numpy()
                 t3 = time.perf_counter()
                 tm["wait"] += t3 - t2
+                pos = scal_all.size - sum(len(pls) for _, pls in ckd_checks)
+                for _, pls in ckd_checks:
+                    for pl, code in zip(pls, scal_all[pos:pos + len(pls)]):
+                        if code != 0:                           # COEFF_ABS_CKD failed for this wavelength: sos_proc's error for it
+                            where = pl.index
+                            raise SosProcError(_abs.CKD_STATUS_MESSAGES.get(int(code), "COEFF_ABS_CKD failed"), ier=-1)
+                    pos += len(pls)
                 todo, pos = [], 0                               # (plan, slot, record, finish_scalars, segment)
                 for gp, rec, scal, _ in solved:
                     sw = scal.shape[2]
@@ -1711,7 +1748,12 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
       1. the host preparation of every wavelength (parameter checks, angles, aerosol model, gas tables, surface, context), then
          the profiles of ALL CKD bins of a part of the chunk in three launches (sosgpu_profile_spectrum through
          solver.make_profiles_spectrum: no-gas profiles, SOS_ABSPROFILE, SOS_PROFILE, every wavefront taking its wavelength's
-         parameters from a device table), nothing waited for.  Calls with -SOS.Trans, -SOS.AbsModeCKD 2 or an aerosol layer
+         parameters from a device table), nothing waited for.  The gas coefficients of these wavelengths (COEFF_ABS_CKD for
+         every gas, term and layer) are interpolated in one more launch ahead of them, on device-resident copies of the parsed
+         CKD files (sosgpu_ckd_layer_tables); its per-wavelength status comes back with the band scalars of step 3, and a
+         wavelength it flags raises the SosProcError sos_proc raises for that call (SOS_SPECTRUM_HOST_GAS_TABLES=1 in the
+         environment: the tables are interpolated on the host and uploaded, for A/B timing).
+         Calls with -SOS.Trans, -SOS.AbsModeCKD 2 or an aerosol layer
          (-AP.AerProfile.Type 2), and a call whose profile the library refuses (its error is then sos_proc's), make their own
          profile launches (sosgpu_absprofile + sosgpu_profile) as sos_proc does;
       2. ALL bins of ALL wavelengths in one launch of the fused solver per group of wavelengths sharing a kernel variant

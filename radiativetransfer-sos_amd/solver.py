@@ -595,12 +595,109 @@ def solve_spectrum(table, bins, ctx_of_bin, seg, aik, out=None, order="cost"):
     return cx.aggregate(out, aik, seg=seg, scal=bins.get("scal"))
 
 
+CKD_WL_DTYPE = np.dtype([("pres_off", "<i8"), ("temp_off", "<i8"), ("conc_off", "<i8"), ("prs_off", "<i8"), ("tmp_off", "<i8"),
+                         ("cl_off", "<i8"), ("xk_off", "<i8"), ("nterm", "<i4"), ("nt", "<i4"), ("np", "<i4"), ("nc", "<i4")])   # capi.CkdWl
+
+
+def pack_ckd_requests(preps, table_ptr, xk_off=None, base=0):
+    """Host side of ckd_layer_tables (pure numpy): the per-wavelength table, the slot pointers and the packed axes / layer
+    states of a list of absorption.prepa_absprofile dicts.
+      table_ptr(prep, gas)  device address (int) of the interval's coefficient block of that gas, [5][NP][NT] (H2O
+                            [5][NC][NP][NT]) doubles -- absorption.ckd_device_tables on a GPU, anything in a test
+      xk_off                where each wavelength's xk[8][5][nlay] starts in the output block, in doubles (default: one after
+                            the other);  base: where `axes` will start in the device buffer it is uploaded into, in doubles
+    Returns a dict: wl (structured array [nwl], CKD_WL_DTYPE = sosgpu_ckd_wl), slots (uint64 [nwl * 40]: slot gas * 5 + term of
+    each wavelength, 0 = NULL for a term >= NEXP of the gas and for a table that is all zero), axes (float64: every distinct
+    axis and layer state once -- a spectrum shares one atmosphere and a file's intervals share their axes), nlay, nterm,
+    out_doubles (end of the last xk block)."""
+    from . import absorption as _abs
+    nterm, nlay = _abs.CKD_NAI_MAX, _abs.NLEVEL - 1
+    wl = np.zeros(len(preps), dtype=CKD_WL_DTYPE)
+    slots = np.zeros((len(preps), 8, nterm), dtype=np.uint64)
+    parts, where, n = [], {}, 0
+
+    def place(a):
+        nonlocal n
+        hit = where.get(id(a))
+        if hit is None:
+            hit = where[id(a)] = (n, a)                       # (the array is held: its id stays its own)
+            parts.append(np.ascontiguousarray(a, dtype=np.float64).ravel())
+            n += parts[-1].size
+        return base + hit[0]
+
+    states = {}
+    out = 0
+    for w, prep in enumerate(preps):
+        e = wl[w]
+        e["nterm"], e["nt"], e["np"], e["nc"] = nterm, len(prep["tab_temp"]), len(prep["tab_pres"]), len(prep["tab_conc"])
+        e["pres_off"], e["temp_off"], e["conc_off"] = place(prep["tab_pres"]), place(prep["tab_temp"]), place(prep["tab_conc"])
+        st = states.get(id(prep["userprofil"]))
+        if st is None:
+            st = states[id(prep["userprofil"])] = (prep["userprofil"],) + tuple(_abs.layer_state(prep))
+        e["prs_off"], e["tmp_off"], e["cl_off"] = place(st[1]), place(st[2]), place(st[3])
+        e["xk_off"] = out if xk_off is None else int(xk_off[w])
+        out = max(out, int(e["xk_off"]) + 8 * nterm * nlay)
+        absorbing = _abs.ckd_absorbing(prep)
+        for k in range(8):
+            if absorbing[k].any():
+                block = int(table_ptr(prep, k))
+                per = prep["ki"][k][0].size * 8                # bytes of one term's table
+                for term in np.flatnonzero(absorbing[k]):
+                    slots[w, k, term] = block + int(term) * per
+    axes = np.concatenate(parts) if parts else np.zeros(0)
+    return dict(wl=wl, slots=slots.reshape(-1), axes=axes, nlay=nlay, nterm=nterm, out_doubles=out)
+
+
+def _ckd_launch(L, dev, pk, axes_t, axes_doubles, out_t, out_doubles, st, where):
+    """Queue sosgpu_ckd_layer_tables for the packed requests pk on stream handle st; returns (status tensor, work area)."""
+    nwl = len(pk["wl"])
+    work = torch.empty(nwl * int(L.sosgpu_ckd_table_entry_bytes()) + 8 * pk["slots"].size, dtype=torch.uint8, device=dev)
+    status = torch.empty(nwl, dtype=torch.int32, device=dev)
+    bad = C.c_int(-1)
+    rc = L.sosgpu_ckd_layer_tables(dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), int(pk["slots"].size),
+                                   pk["slots"].ctypes.data_as(C.c_void_p), _ptr(axes_t), axes_doubles, pk["nlay"], _ptr(work),
+                                   _ptr(out_t), out_doubles, _ptr(status), C.byref(bad), st)
+    if rc != 0 and bad.value >= 0 and where is not None:
+        where["bad"] = int(bad.value)
+    capi.check(rc, "sosgpu_ckd_layer_tables")
+    return status, work
+
+
+def ckd_layer_tables(preps, device=0, stream=None):
+    """COEFF_ABS_CKD of many wavelengths in ONE launch on device-resident coefficient tables (sosgpu_ckd_layer_tables): what
+    absorption.layer_tables computes for each prep (absorption.prepa_absprofile), bit for bit, without the host interpolation
+    and without an upload of the tables.  One upload (axes and layer states), queued on `stream` (a torch stream; None: the
+    current one), nothing waited for.  Returns (xk, ro, status): xk[g] device tensors [8][5][49] (views of one block), ro[g]
+    host arrays [8][49] as layer_tables returns them, status an int32 device tensor [len(preps)] -- 0 ok, else the key of
+    absorption.CKD_STATUS_MESSAGES for the error the host routine raises for that wavelength (its xk is then not usable)."""
+    from . import absorption as _abs
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    tables = {}
+
+    def table_ptr(prep, k):
+        hit = tables.get(id(prep))
+        if hit is None:
+            hit = tables[id(prep)] = (prep,) + _abs.ckd_device_tables(prep, dev)
+        return hit[1][k]
+
+    pk = pack_ckd_requests(preps, table_ptr)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        axes = _upload(torch.from_numpy(pk["axes"]), dev)
+        out = torch.empty(pk["out_doubles"], dtype=torch.float64, device=dev)
+        status, work = _ckd_launch(capi.lib(), dev, pk, axes, pk["axes"].size, out, pk["out_doubles"], st, None)
+    per = 8 * pk["nterm"] * pk["nlay"]
+    xk = [out[int(o):int(o) + per].view(8, pk["nterm"], pk["nlay"]) for o in pk["wl"]["xk_off"]]
+    status._keep = (axes, work, [t[2] for t in tables.values()])      # alive until the caller lets go of the result
+    return xk, [_abs.layer_ro(p) for p in preps], status
+
+
 PROFILE_WL_DTYPE = np.dtype([("tr", "<f8"), ("hr", "<f8"), ("ta", "<f8"), ("ha", "<f8"), ("a_tronc", "<f8"), ("piz", "<f8"),
                              ("piztr", "<f8"), ("zout", "<f8"), ("xk_off", "<i8"), ("ro_off", "<i8"), ("alt_off", "<i8"),
                              ("nterm", "<i4"), ("nbins", "<i4"), ("absprofil", "<i4"), ("smax", "<i4")])   # capi.ProfileWl
 
 
-def pack_profile_requests(requests):
+def pack_profile_requests(requests, table_ptr=None):
     """Host side of make_profiles_spectrum (pure numpy): the per-wavelength table, the packed gas buffer and the per-bin
     wavelength index of a list of profile requests.  A request is a dict with the arguments of SosContext.absorption_profiles
     and make_profiles of one wavelength -- ik[nb][8], xk[8][nterm][nlev-1], ro[8][nlev-1], altabs[nlev] (ik None: no gas,
@@ -609,8 +706,14 @@ def pack_profile_requests(requests):
       wl          structured array [nwl] (PROFILE_WL_DTYPE = sosgpu_profile_wl); xk_off / ro_off / alt_off count doubles in buf
       buf         ONE float64 array for one upload: the gas tables of every wavelength (xk, ro, altabs, in request order), then
                   ik[nb][8] (int32, rows of no-gas bins zero) at ik_off, then wl_of_bin[nb] (int32) at wob_off
-      gas_doubles, ik_off, wob_off   (in doubles);  nb, nblev (0 without any gas), seg[nwl + 1] (first bin of each request)"""
+      gas_doubles, ik_off, wob_off   (in doubles);  nb, nblev (0 without any gas), seg[nwl + 1] (first bin of each request)
+    A gas request may carry `prep` (absorption.prepa_absprofile's dict) in place of `xk`: its xk[8][5][nlev-1] is then made on
+    the device (sosgpu_ckd_layer_tables, queued ahead of the profile kernels) in a block BEHIND buf -- the device buffer is
+    buf.size + device_doubles long and the request's xk_off points there.  The dict then also holds `ckd`, the
+    pack_ckd_requests of these requests (its axes appended to buf, its xk_off those of wl), and `ckd_index`, their indices in
+    requests; table_ptr: see pack_ckd_requests."""
     nwl = len(requests)
+    dev_w, dev_off = [], 0
     wl = np.zeros(nwl, dtype=PROFILE_WL_DTYPE)
     gas, iks, counts = [], [], []
     nblev, off = 0, 0
@@ -625,9 +728,25 @@ def pack_profile_requests(requests):
             counts.append(1)
             continue
         ik = np.ascontiguousarray(r["ik"], dtype=np.int32)
-        xk, ro = np.ascontiguousarray(r["xk"], dtype=np.float64), np.ascontiguousarray(r["ro"], dtype=np.float64)
+        ro = np.ascontiguousarray(r["ro"], dtype=np.float64)
         alt = np.ascontiguousarray(r["altabs"], dtype=np.float64).ravel()
         nlev = int(alt.size)
+        if r.get("xk") is None and r.get("prep") is not None:
+            if ik.ndim != 2 or ik.shape[1] != 8 or ik.shape[0] < 1 or nlev != 50 or ro.shape != (8, nlev - 1):
+                raise ValueError("request %d: ik must be [nb][8], ro [8][49], altabs [50] with the tables made on the device" % w)
+            if nblev and nlev != nblev:
+                raise ValueError("request %d: every wavelength of a launch must have the same number of absorption levels" % w)
+            nblev = nlev
+            e["nterm"], e["nbins"], e["absprofil"] = 5, ik.shape[0], int(r["absprofil"])
+            e["xk_off"], e["ro_off"], e["alt_off"] = dev_off, off, off + ro.size        # (xk_off: moved behind buf below)
+            dev_off += 8 * 5 * (nlev - 1)
+            off += ro.size + nlev
+            gas += [ro.ravel(), alt]
+            dev_w.append(w)
+            iks.append(ik)
+            counts.append(ik.shape[0])
+            continue
+        xk = np.ascontiguousarray(r["xk"], dtype=np.float64)
         if ik.ndim != 2 or ik.shape[1] != 8 or ik.shape[0] < 1 or xk.ndim != 3 or xk.shape[0] != 8 or xk.shape[1] < 1 or \
                 xk.shape[2] != nlev - 1 or ro.shape != (8, nlev - 1):
             raise ValueError("request %d: ik must be [nb][8], xk [8][nterm][nlev-1], ro [8][nlev-1], altabs [nlev]" % w)
@@ -644,9 +763,22 @@ def pack_profile_requests(requests):
     wob = np.repeat(np.arange(nwl, dtype=np.int32), counts)
     if nb % 2:
         wob = np.concatenate([wob, np.zeros(1, dtype=np.int32)])          # (8-byte units)
-    buf = np.concatenate(gas + [np.concatenate(iks).ravel().view(np.float64), wob.view(np.float64)])
-    return dict(wl=wl, buf=buf, gas_doubles=off, ik_off=off, wob_off=off + 4 * nb, nb=nb, nblev=nblev,
-                seg=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64))
+    tail = [np.concatenate(iks).ravel().view(np.float64), wob.view(np.float64)]
+    out = dict(wl=wl, gas_doubles=off, ik_off=off, wob_off=off + 4 * nb, nb=nb, nblev=nblev,
+               seg=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), ckd=None, ckd_index=dev_w, device_doubles=dev_off)
+    if dev_w:
+        if table_ptr is None:
+            raise ValueError("requests with `prep` need table_ptr (the device addresses of the coefficient tables)")
+        axes_off = off + sum(t.size for t in tail)
+        ckd = pack_ckd_requests([requests[w]["prep"] for w in dev_w], table_ptr, xk_off=wl["xk_off"][dev_w], base=axes_off)
+        total = axes_off + ckd["axes"].size
+        wl["xk_off"][dev_w] += total
+        ckd["wl"]["xk_off"] += total
+        ckd["out_doubles"] = total + dev_off
+        tail.append(ckd["axes"])
+        out["ckd"] = ckd
+    out["buf"] = np.concatenate(gas + tail)
+    return out
 
 
 def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
@@ -657,9 +789,23 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
     nothing waited for.  Returns one `bins` dict per request, as make_profiles returns it for that wavelength alone -- the same
     keys, dtypes and, bit for bit, values; the tensors are views of the shared blocks.
     part: optional dict, filled with `bins` (all bins as one dict, for output_levels), `tabs` (per request: TAUABS[nb][nlev]
-    view, or None without gas), `seg`, and -- when the library refuses a wavelength -- `bad`, its index in requests."""
+    view, or None without gas), `seg`, and -- when the library refuses a wavelength -- `bad`, its index in requests.
+    A gas request with `prep` in place of `xk` (pack_profile_requests) gets its coefficient tables from ONE launch of
+    sosgpu_ckd_layer_tables over all such requests, on the device-resident CKD files, queued on the same stream ahead of the
+    profile kernels and writing straight to the request's xk block: no host interpolation, no upload of xk.  `part` then also
+    holds `ckd_status` (int32 device tensor, one entry per such request: absorption.CKD_STATUS_MESSAGES) and `ckd_index` (their
+    indices in requests); without such requests `ckd_status` is None."""
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    pk = pack_profile_requests(requests)
+    tables = {}
+
+    def table_ptr(prep, k):
+        from . import absorption as _abs
+        hit = tables.get(id(prep))
+        if hit is None:
+            hit = tables[id(prep)] = (prep,) + _abs.ckd_device_tables(prep, dev)
+        return hit[1][k]
+
+    pk = pack_profile_requests(requests, table_ptr)
     nwl, nb, nblev, seg = len(requests), pk["nb"], pk["nblev"], pk["seg"]
     L = capi.lib()
     ng = capi.NOGAS_LEVELS
@@ -668,7 +814,19 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
         part = {}
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        up = _upload(torch.from_numpy(pk["buf"]), dev)
+        ckd, status, work = pk["ckd"], None, None
+        if ckd is None:
+            up = _upload(torch.from_numpy(pk["buf"]), dev)
+        else:
+            # (the xk blocks the device fills stand behind the uploaded part of the one gas buffer)
+            up = torch.empty(pk["buf"].size + pk["device_doubles"], dtype=torch.float64, device=dev)
+            up[:pk["buf"].size].copy_(torch.from_numpy(pk["buf"]).pin_memory(), non_blocking=True)
+            refused = {}
+            try:
+                status, work = _ckd_launch(L, dev, ckd, up, ckd["out_doubles"], up, ckd["out_doubles"], st, refused)
+            finally:
+                if "bad" in refused:
+                    part["bad"] = int(pk["ckd_index"][refused["bad"]])
         # (two cleared blocks for the whole part; the work areas of the launch -- table, no-gas blocks -- ride at the end)
         o_z, o_s, o_zz, o_t = nb * 3 * lp, nb * 4 * lp, nb * (4 * lp + 4), nb * (4 * lp + 5)
         o_ng, o_tab = o_t + nb * nblev, o_t + nb * nblev + nwl * 4 * ng
@@ -681,7 +839,8 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
         ik_t = up[pk["ik_off"]:pk["wob_off"]].view(torch.int32) if nblev else None
         bad = C.c_int(-1)
         rc = L.sosgpu_profile_spectrum(dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), nb, _ptr(up[pk["wob_off"]:]),
-                                       _ptr(ik_t), _ptr(up) if nblev else None, pk["gas_doubles"], nblev, lp,
+                                       _ptr(ik_t), _ptr(up) if nblev else None, pk["gas_doubles"] if ckd is None else up.numel(),
+                                       nblev, lp,
                                        _ptr(fb[o_tab:]), _ptr(fb[o_ng:o_tab]), _ptr(tabs), _ptr(prof), _ptr(nt), _ptr(iborm),
                                        _ptr(zprof), _ptr(jout) if any_out else None, _ptr(zz) if any_out else None, _ptr(scal),
                                        C.byref(bad), st)
@@ -696,7 +855,8 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
                         jout=jout[b0:b1] if lev else None, zz=zz[b0:b1] if lev else None, zprof=zprof[b0:b1], scal=scal[b0:b1]))
         tabs_l.append(tabs[b0:b1] if pk["wl"]["nterm"][w] else None)
     part.update(bins=dict(nb=nb, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=None, zz=None, zprof=zprof, scal=scal),
-                tabs=tabs_l, seg=seg, upload=up)
+                tabs=tabs_l, seg=seg, upload=up, ckd_status=status, ckd_index=pk["ckd_index"],
+                ckd_keep=(work, [t[2] for t in tables.values()]))
     return out
 
 

@@ -421,6 +421,40 @@ int  sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl *wl, int n
 int  sosgpu_mie(int device, int nbmu, const double *xmu, double rn, double in, int nalpha, const double *alphas,
                 float *d_rec, double *d_g, void *stream);
 
+/* sosgpu_mie for `count` (refractive index, size-parameter list, records) jobs at once, ASYNCHRONOUS on `stream`: the
+ * table-driven aerosol models (WMO, Shettle & Fenn) change the index of every component with the wavelength, so a spectrum
+ * needs three or four fresh record sets per wavelength; this queues those of a chunk without a host wait, ahead of the
+ * sosgpu_granu_batch call that reads them on the same stream.  All jobs share the angle set xmu[2 nbmu + 1] (HOST).
+ *   jobs[count] (HOST; the structures and the lists are read before the call returns)
+ *       rn, in           refractive index (in <= 0), as sosgpu_mie
+ *       alphas[nalpha]   HOST, positive and ascending; jobs that pass the same pointer and length share one uploaded copy
+ *       d_rec, d_g       DEVICE outputs of the job, [nalpha][4 + 3 (2 nbmu + 1)] REAL*4 and [nalpha] doubles as sosgpu_mie writes
+ *                        them: the same bits (both entry points run the same device code per size parameter)
+ *   d_work               DEVICE work area of sosgpu_mie_batch_work_bytes(nbmu, count, jobs) bytes, 8-byte aligned: the angle
+ *                        set, the lists and the job table arrive there in ONE copy on `stream` from a pinned block the library
+ *                        recycles; behind them the coefficient scratch of the sizes past alpha = 850, one for the whole batch:
+ *                        min(such items, 2048) slots of 11 (2 A + 24) doubles, A the largest alpha of the batch.  Free again once
+ *                        `stream` has passed the call.
+ *   d_status[count]      int32, cleared by this call on `stream`, then 0 = ok, bit 0 = a size parameter of the job did not fit
+ *                        the coefficient arrays (what sosgpu_mie reports as SOSGPU_E_UNSUPPORTED after its own wait)
+ * The work unit is one (job, size parameter), not one job: the items of all jobs are split by the size of their coefficient
+ * arrays over at most 5 launches (4 LDS classes, 1 scratch form; csrc/mie.hip), whatever `count` is.
+ * Every job is checked on the host first, with sosgpu_mie's rules: SOSGPU_E_ARG for a malformed job (NULL pointer, nalpha < 1,
+ * a list that is not positive and ascending), SOSGPU_E_UNSUPPORTED for 2 alpha + 24 > 10000 (CTE_MIE_DIM) or a work_bytes
+ * below the size above.  One bad job refuses the whole call: nothing is queued, no output and no status is touched.
+ * count = 0: SOSGPU_OK, nothing queued.  No allocation and no wait inside. */
+typedef struct sosgpu_mie_job {
+    double rn, in;
+    const double *alphas;               /* HOST */
+    int32_t nalpha, reserved;
+    float  *d_rec;                      /* DEVICE */
+    double *d_g;                        /* DEVICE */
+} sosgpu_mie_job;
+/* bytes of d_work for these jobs; 0 when a job is malformed or unsupported (sosgpu_mie_batch tells which) */
+size_t sosgpu_mie_batch_work_bytes(int nbmu, int count, const sosgpu_mie_job *jobs);
+int  sosgpu_mie_batch(int device, int nbmu, const double *xmu, int count, const sosgpu_mie_job *jobs, void *d_work,
+                      size_t work_bytes, int32_t *d_status, void *stream);
+
 /* Replaces SOS_GRANU (src/SOS_AEROSOLS.F:4392-4820): the integral of Mie records over a size distribution, on the device -- the
  * records (2 MB per refractive index at 40 Mie angles) never travel to the host.  The reference reads its MIE file record by
  * record and accumulates in file order; the kernel adds in record order too (the sums of the Fortran loop term for term).

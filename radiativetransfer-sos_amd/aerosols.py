@@ -81,26 +81,99 @@ def alpha_grid(alphao, alphaf):
     return np.array(out)
 
 
-# Device-resident Mie records of the last few (refractive index, angle set, size-parameter range) combinations: what the
+# Device-resident Mie records of the last (refractive index, angle set, size-parameter range) combinations: what the
 # reference keeps as MIE cache files named after exactly these quantities (SOS_NOM_FICMIE, SOS_AEROSOLS.F:3128 --
-# "MIE1.450-0.00300-0.0001-00100.00-MU12") and re-reads for every wavelength that shares them.  2 MB each at 40 Mie angles.
-_MIE_CACHE = collections.OrderedDict()
+# "MIE1.450-0.00300-0.0001-00100.00-MU12") and re-reads for every wavelength that shares them.  2 MB each at 40 Mie angles, 7.7 MB
+# for the WMO dust-like component.  The cache holds MIE_DEVICE_BUDGET bytes (256 MiB; SOS_MIE_DEVICE_BYTES overrides it, read at
+# every insertion) and drops the least recently used sets beyond: a table-model spectrum, whose index changes with every
+# wavelength, pins a bounded amount, and the one set a fixed-index spectrum shares is the most recently used and stays (the
+# last set is never dropped).  A caller that queued work on a set holds its tensors until that work has run -- an evicted
+# set lives as long as somebody does (_GranuBatch.keep).
+MIE_DEVICE_BUDGET = 256 << 20
+_MIE_CACHE = collections.OrderedDict()           # key -> _MieEntry
 _MIE_LOCK = threading.Lock()
-_MIE_CACHE_MAX = 12
+_MIE_TOO_LARGE = "size parameter up to %g: more Mie coefficients than the device kernel holds"
 
 
-def _mie_device_records(xmu, rn, in_, alphao, alphaf, device=0):
-    """(rec float32 [na][4 + 3 W], g float64 [na]) device tensors of sosgpu_mie for the grid alpha_grid(alphao, alphaf)."""
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("Mie theory needs a GPU (gfx950); there is no CPU fallback in the product path")
-    xmu = np.ascontiguousarray(xmu, dtype=np.float64)
-    key = (xmu.tobytes(), float(rn), float(in_), float(alphao), float(alphaf), int(device))
+def _mie_budget():
+    return int(os.environ.get("SOS_MIE_DEVICE_BYTES", MIE_DEVICE_BUDGET))
+
+
+class _MieBatchStatus:
+    """d_status of one sosgpu_mie_batch call on its way to pinned host memory, and the event recorded behind that copy."""
+
+    def __init__(self, host, event, stream):
+        self.host, self.event, self.stream = host, event, stream
+
+
+class _MieEntry:
+    """One cached record set.  batch is None for records of the synchronous sosgpu_mie (complete, usable from any stream);
+    otherwise the set was queued by sosgpu_mie_batch: other streams wait for batch.event, and slot is its status word."""
+    __slots__ = ("rec", "g", "alphaf", "batch", "slot", "checked")
+
+    def __init__(self, rec, g, alphaf, batch=None, slot=0):
+        self.rec, self.g, self.alphaf, self.batch, self.slot, self.checked = rec, g, alphaf, batch, slot, batch is None
+
+    @property
+    def nbytes(self):
+        return self.rec.numel() * 4 + self.g.numel() * 8
+
+    def order_after_launch(self):
+        """Make the current stream see the records: it waits (on the device) for the launch when that ran on another stream."""
+        import torch
+        b = self.batch
+        if b is None:
+            return
+        if b.event.query():
+            if self.checked:
+                self.batch = None
+            return
+        cur = torch.cuda.current_stream(self.rec.device)
+        if cur != b.stream:
+            cur.wait_event(b.event)
+
+    def check(self):
+        """The status of the set, once, before its first host-visible use (waits for the launch)."""
+        if self.checked:
+            return
+        self.batch.event.synchronize()
+        self.checked = True
+        if int(self.batch.host[self.slot]) != 0:
+            raise AerosolError(_MIE_TOO_LARGE % self.alphaf)
+
+
+def _mie_key(xmu, rn, in_, alphao, alphaf, device):
+    return (np.ascontiguousarray(xmu, dtype=np.float64).tobytes(), float(rn), float(in_), float(alphao), float(alphaf), int(device))
+
+
+def _mie_cache_put(key, entry):
+    with _MIE_LOCK:
+        _MIE_CACHE[key] = entry
+        budget = _mie_budget()
+        while len(_MIE_CACHE) > 1 and sum(e.nbytes for e in _MIE_CACHE.values()) > budget:
+            _MIE_CACHE.popitem(last=False)
+
+
+def _mie_cache_get(key):
     with _MIE_LOCK:
         hit = _MIE_CACHE.get(key)
         if hit is not None:
             _MIE_CACHE.move_to_end(key)
-            return hit
+        return hit
+
+
+def _mie_entry(xmu, rn, in_, alphao, alphaf, device=0):
+    """The cached record set of the key, made with the synchronous sosgpu_mie when it is missing; ordered before the current
+    stream's later work, its status not yet looked at."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("Mie theory needs a GPU (gfx950); there is no CPU fallback in the product path")
+    xmu = np.ascontiguousarray(xmu, dtype=np.float64)
+    key = _mie_key(xmu, rn, in_, alphao, alphaf, device)
+    hit = _mie_cache_get(key)
+    if hit is not None:
+        hit.order_after_launch()
+        return hit
     al = alpha_grid(alphao, alphaf)
     w = len(xmu)
     dev = torch.device("cuda", device)
@@ -110,19 +183,78 @@ def _mie_device_records(xmu, rn, in_, alphao, alphaf, device=0):
     rc = capi.lib().sosgpu_mie(device, (w - 1) // 2, xmu.ctypes.data_as(C.c_void_p), float(rn), float(in_), len(al),
                                al.ctypes.data_as(C.c_void_p), C.c_void_p(rec.data_ptr()), C.c_void_p(g.data_ptr()), st)
     if rc == -3:
-        raise AerosolError("size parameter up to %g: more Mie coefficients than the device kernel holds" % alphaf)
+        raise AerosolError(_MIE_TOO_LARGE % alphaf)
     capi.check(rc, "sosgpu_mie")               # (synchronous: the records are complete, usable from any stream)
-    with _MIE_LOCK:
-        _MIE_CACHE[key] = (rec, g)
-        while len(_MIE_CACHE) > _MIE_CACHE_MAX:
-            _MIE_CACHE.popitem(last=False)
-    return rec, g
+    e = _MieEntry(rec, g, float(alphaf))
+    _mie_cache_put(key, e)
+    return e
+
+
+def _mie_device_records(xmu, rn, in_, alphao, alphaf, device=0):
+    """(rec float32 [na][4 + 3 W], g float64 [na]) device tensors of sosgpu_mie for the grid alpha_grid(alphao, alphaf).  Records
+    queued by prefetch_mie_records on another stream are ordered before the current stream's later work (wait_event)."""
+    e = _mie_entry(xmu, rn, in_, alphao, alphaf, device)
+    try:
+        e.check()
+    except AerosolError:
+        with _MIE_LOCK:
+            _MIE_CACHE.pop(_mie_key(xmu, rn, in_, alphao, alphaf, device), None)
+        raise
+    return e.rec, e.g
+
+
+def prefetch_mie_records(keys):
+    """Queue the Mie records of the (xmu bytes, rn, in, alphao, alphaf, device) `keys` that the cache lacks on the current HIP
+    stream: one asynchronous sosgpu_mie_batch call per (angle set, device), no host wait.  A key sosgpu_mie would refuse (size
+    parameters past the kernel's dimension) is left out: the call that needs its records reports it.  Returns {key: entry} of
+    the sets it queued (the caller's reference: the cache may drop a set again under a small budget)."""
+    import torch
+    groups = collections.OrderedDict()
+    for k in keys:
+        k = (k[0], float(k[1]), float(k[2]), float(k[3]), float(k[4]), int(k[5]))
+        if _mie_cache_get(k) is None:
+            groups.setdefault((k[0], k[5]), collections.OrderedDict())[k] = None
+    made = {}
+    for (xb, device), ks in groups.items():
+        todo = [(k, alpha_grid(k[3], k[4])) for k in ks]
+        todo = [(k, al) for k, al in todo if 2 * al[-1] + 24 <= 10000]           # CTE_MIE_DIM (sosgpu_mie: rc = -3)
+        if not todo:
+            continue
+        xmu = np.frombuffer(xb, dtype=np.float64)
+        w = len(xmu)
+        dev = torch.device("cuda", device)
+        st = torch.cuda.current_stream(dev)
+        jobs = (capi.MieJob * len(todo))()
+        sets = []
+        for j, (k, al) in enumerate(todo):
+            rec = torch.empty((len(al), 4 + 3 * w), dtype=torch.float32, device=dev)     # (every entry is written)
+            g = torch.empty(len(al), dtype=torch.float64, device=dev)
+            jobs[j] = capi.MieJob(k[1], k[2], al.ctypes.data, len(al), 0, rec.data_ptr(), g.data_ptr())
+            sets.append((rec, g))
+        L = capi.lib()
+        nbytes = L.sosgpu_mie_batch_work_bytes((w - 1) // 2, len(todo), jobs)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)                # (this stream's memory: free behind the call)
+        status = torch.empty(len(todo), dtype=torch.int32, device=dev)
+        rc = L.sosgpu_mie_batch(device, (w - 1) // 2, xmu.ctypes.data_as(C.c_void_p), len(todo), jobs, C.c_void_p(work.data_ptr()),
+                                nbytes, C.c_void_p(status.data_ptr()), C.c_void_p(st.cuda_stream))
+        if rc == -3:
+            raise AerosolError(_MIE_TOO_LARGE % max(k[4] for k, _ in todo))
+        capi.check(rc, "sosgpu_mie_batch")
+        host = torch.empty(len(todo), dtype=torch.int32, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(st)
+        b = _MieBatchStatus(host, ev, st)
+        for j, ((k, _), (rec, g)) in enumerate(zip(todo, sets)):
+            made[k] = _MieEntry(rec, g, k[4], b, j)
+            _mie_cache_put(k, made[k])
+    return made
 
 
 def mie_records(xmu, rn, in_, alphao, alphaf, device=0):
     """The records of the reference's MIE file for (rn, in_) on the grid alpha_grid(alphao, alphaf), on the host (parity
     accessor): dict(alpha, qext, qsca float32 [na]; g float64 [na]; imie, qmie, umie float32 [na][2N+1])."""
-    rec, g = _mie_device_records(xmu, rn, in_, alphao, alphaf, device)
+    rec, g = _mie_device_records(xmu, rn, in_, alphao, alphaf, device)      # (status checked: the launch has been waited for)
     w = len(xmu)
     r = rec.cpu().numpy()
     return dict(alpha=r[:, 0].copy(), qext=r[:, 1].copy(), qsca=r[:, 2].copy(), g=g.cpu().numpy(), imie=r[:, 4:4 + w].copy(),
@@ -146,13 +278,17 @@ def _granu_key(xmu, rn, in_, alphaf, igranu, v1, v2, v3, wa, device):
 class _GranuBatch:
     """The results of one sosgpu_granu_batch call on their way to the host (the first reader waits for the copy)."""
 
-    def __init__(self, host, event, keep):
-        self.host, self.event, self.keep = host, event, keep
+    def __init__(self, host, event, keep, entries=()):
+        self.host, self.event, self.keep, self.entries = host, event, keep, list(entries)
 
     def row(self, i):
         if self.event is not None:
             self.event.synchronize()
             self.event = self.keep = None                  # (device output, work area and the records' references)
+        if self.entries:
+            e, self.entries[i] = self.entries[i], None     # the status of the records this integral read, looked at once
+            if e is not None:
+                e.check()
         return self.host[i]
 
 
@@ -174,6 +310,8 @@ def prefetch_size_integrals(requests, batch=32):
     ready = getattr(_TLS, "ready", None)
     if ready is None:
         ready = _TLS.ready = {}
+    # SOS_SPECTRUM_MIE_PER_CALL=1: one synchronous sosgpu_mie call per refractive index, as before sosgpu_mie_batch (A/B timing)
+    per_call = bool(os.environ.get("SOS_SPECTRUM_MIE_PER_CALL"))
     todo = collections.OrderedDict()
     for k in requests:
         if k not in ready and k[4] in (1, 2):
@@ -185,10 +323,19 @@ def prefetch_size_integrals(requests, batch=32):
         w = len(xmu)
         dev = torch.device("cuda", device)
         for c0 in range(0, len(keys), batch):
-            part, recs = [], []
+            # the records this group lacks: one sosgpu_mie_batch call, queued ahead of the integrals on the same stream
+            mkey = lambda k: (xb, k[1], k[2], float(MIE_ALPHAMIN), k[3], device)
+            made = {} if per_call else prefetch_mie_records([mkey(k) for k in keys[c0:c0 + batch]])
+            part, recs, ents = [], [], []
             for k in keys[c0:c0 + batch]:
                 try:
-                    recs.append(_mie_device_records(xmu, k[1], k[2], MIE_ALPHAMIN, k[3], device)[0])
+                    e = made.get(mkey(k))
+                    if e is None:
+                        if not per_call and _mie_cache_get(mkey(k)) is None:
+                            continue                       # (refused by the host validation)
+                        e = _mie_entry(xmu, k[1], k[2], MIE_ALPHAMIN, k[3], device)
+                    recs.append(e.rec)
+                    ents.append(e)
                     part.append(k)
                 except AerosolError:                       # (the call that owns this integral reports it)
                     pass
@@ -208,7 +355,7 @@ def prefetch_size_integrals(requests, batch=32):
             host.copy_(out, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(st)
-            b = _GranuBatch(host.numpy(), ev, (out, work, recs, host))
+            b = _GranuBatch(host.numpy(), ev, (out, work, recs, host), ents)
             for j, k in enumerate(part):
                 ready[k] = (b, j)
             queued += len(part)

@@ -18,7 +18,7 @@ EXPORTS = [
     "sosgpu_os_flops", "sosgpu_last_solve_ms", "sosgpu_profile", "sosgpu_profile_nogas", "sosgpu_glitter", "sosgpu_mat_fresnel_host", "sosgpu_trphi",
     "sosgpu_debug_phase_buffer", "sosgpu_debug_scratch", "sosgpu_comm_unique_id", "sosgpu_comm_init_rank", "sosgpu_comm_destroy",
     "sosgpu_pack", "sosgpu_unpack", "sosgpu_reduce", "sosgpu_absprofile", "sosgpu_land_surface", "sosgpu_mie", "sosgpu_granu",
-    "sosgpu_granu_batch",
+    "sosgpu_granu_batch", "sosgpu_mie_batch", "sosgpu_mie_batch_work_bytes",
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
@@ -33,6 +33,12 @@ class GranuJob(C.Structure):
     """sosgpu_granu_job (include/sosgpu.h)."""
     _fields_ = [("d_rec", C.c_void_p), ("nalpha", C.c_int32), ("igranu", C.c_int32), ("v1", C.c_double), ("v2", C.c_double),
                 ("v3", C.c_double), ("wa", C.c_double), ("alphaf", C.c_double)]
+
+
+class MieJob(C.Structure):
+    """sosgpu_mie_job (include/sosgpu.h): one refractive index of sosgpu_mie_batch."""
+    _fields_ = [("rn", C.c_double), ("in_", C.c_double), ("alphas", C.c_void_p), ("nalpha", C.c_int32), ("reserved", C.c_int32),
+                ("d_rec", C.c_void_p), ("d_g", C.c_void_p)]
 
 
 class ProfileWl(C.Structure):
@@ -149,6 +155,10 @@ def lib():
         L.sosgpu_granu.argtypes = [i32, i32, i32, vp, i32, dbl, dbl, dbl, dbl, dbl, vp, vp]
         L.sosgpu_granu_batch.restype = i32
         L.sosgpu_granu_batch.argtypes = [i32, i32, i32, C.POINTER(GranuJob), vp, vp, C.c_size_t, vp]
+        L.sosgpu_mie_batch_work_bytes.restype = C.c_size_t
+        L.sosgpu_mie_batch_work_bytes.argtypes = [i32, i32, C.POINTER(MieJob)]
+        L.sosgpu_mie_batch.restype = i32
+        L.sosgpu_mie_batch.argtypes = [i32, i32, vp, i32, C.POINTER(MieJob), vp, C.c_size_t, vp, vp]
         L.sosgpu_reduce.restype = i32
         L.sosgpu_reduce.argtypes = [vp, vp, i32, vp, vp]
         L.sosgpu_ctx_bytes.restype = C.c_size_t

@@ -7,8 +7,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <dlfcn.h>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -1526,6 +1528,118 @@ extern "C" int sosgpu_mie(int device, int nbmu, const double *xmu, double rn, do
     if (rc == -2) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
     HIPCHK(e);
     return err ? SOSGPU_E_UNSUPPORTED : SOSGPU_OK;
+}
+
+// The records of many refractive indices, queued (mie.hip k_mie_batch).  mie_batch_plan checks every job with sosgpu_mie's
+// rules and lays the work area out: xmu | packed lists | job table | first[classes + 1][count + 1] | scratch.
+namespace {
+static_assert(sizeof(MieBatchJob) == 64, "the job table keeps the item offsets behind it 8-byte aligned");
+struct MieBatchPlan {
+    std::vector<MieBatchJob> tab;
+    std::vector<int> first;                       // [MIE_BATCH_CLASSES + 1][count + 1]
+    std::vector<std::pair<const double *, int>> lists;       // the distinct lists, in upload order
+    int nitems[MIE_BATCH_CLASSES + 1];
+    double scr_alpha;
+    size_t al_doubles, head_bytes, scr_doubles;
+};
+
+int mie_batch_plan(int nbmu, int count, const sosgpu_mie_job *jobs, MieBatchPlan &p)
+{
+    if (nbmu < 1 || nbmu > 100 || count < 0 || (count && !jobs)) return SOSGPU_E_ARG;
+    const int NC = MIE_BATCH_CLASSES + 1, W = 2 * nbmu + 1;
+    p.tab.assign((size_t)count, MieBatchJob());
+    p.first.assign((size_t)NC * (count + 1), 0);
+    p.lists.clear();
+    p.scr_alpha = 0.;
+    p.al_doubles = 0;
+    long long n[MIE_BATCH_CLASSES + 1] = {};
+    std::map<std::pair<const double *, int>, long long> seen;
+    int rc = SOSGPU_OK;
+    for (int k = 0; k < count; k++) {
+        const sosgpu_mie_job &j = jobs[k];
+        MieBatchJob &t = p.tab[k];
+        if (!j.alphas || j.nalpha < 1 || !j.d_rec || !j.d_g) return SOSGPU_E_ARG;
+        for (int c = 0; c <= NC; c++) t.bound[c] = j.nalpha;
+        t.bound[0] = 0;
+        for (int i = 0, c = 0; i < j.nalpha; i++) {
+            const double a = j.alphas[i];
+            if (!(a > 0.) || (i && a < j.alphas[i - 1])) return SOSGPU_E_ARG;
+            for (const int ca = mie_batch_class(a); c < ca; c++) t.bound[c + 1] = i;
+        }
+        const double amax = j.alphas[j.nalpha - 1];
+        if (2 * amax + 24 > 10000) rc = SOSGPU_E_UNSUPPORTED;                    // CTE_MIE_DIM (a malformed later job still wins)
+        if (t.bound[NC] > t.bound[NC - 1]) p.scr_alpha = std::max(p.scr_alpha, amax);
+        for (int c = 0; c < NC; c++) {
+            p.first[(size_t)c * (count + 1) + k] = (int)n[c];
+            n[c] += t.bound[c + 1] - t.bound[c];
+            if (n[c] > INT_MAX) rc = SOSGPU_E_UNSUPPORTED;
+        }
+        const auto key = std::make_pair(j.alphas, (int)j.nalpha);
+        auto it = seen.find(key);
+        if (it == seen.end()) {
+            it = seen.emplace(key, (long long)p.al_doubles).first;
+            p.lists.push_back(key);
+            p.al_doubles += (size_t)j.nalpha;
+        }
+        t.al_off = it->second;
+        t.rn = j.rn; t.in = j.in; t.rec = j.d_rec; t.g = j.d_g;
+    }
+    if (rc) return rc;
+    for (int c = 0; c < NC; c++) {
+        p.first[(size_t)c * (count + 1) + count] = (int)n[c];
+        p.nitems[c] = (int)n[c];
+    }
+    p.head_bytes = ((size_t)W + p.al_doubles) * sizeof(double) + (size_t)count * sizeof(MieBatchJob) +
+                   (((size_t)NC * (count + 1) * sizeof(int) + 7) & ~(size_t)7);
+    p.scr_doubles = p.nitems[NC - 1] ? (size_t)mie_batch_slots(p.nitems[NC - 1]) * 11 * (size_t)(int)(2 * p.scr_alpha + 24) : 0;
+    return SOSGPU_OK;
+}
+}  // namespace
+
+extern "C" size_t sosgpu_mie_batch_work_bytes(int nbmu, int count, const sosgpu_mie_job *jobs)
+{
+    MieBatchPlan p;
+    if (mie_batch_plan(nbmu, count, jobs, p) != SOSGPU_OK || !count) return 0;
+    return p.head_bytes + p.scr_doubles * sizeof(double);
+}
+
+extern "C" int sosgpu_mie_batch(int device, int nbmu, const double *xmu, int count, const sosgpu_mie_job *jobs, void *d_work,
+                                size_t work_bytes, int32_t *d_status, void *stream)
+{
+    MieBatchPlan p;
+    if (int rc = mie_batch_plan(nbmu, count, jobs, p)) return rc;
+    if (!count) return SOSGPU_OK;
+    if (!xmu || !d_work || !d_status || ((uintptr_t)d_work & 7) != 0) return SOSGPU_E_ARG;
+    if (work_bytes < p.head_bytes + p.scr_doubles * sizeof(double)) return SOSGPU_E_UNSUPPORTED;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
+    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const int W = 2 * nbmu + 1;
+    // --- angle set, lists, job table and item offsets: one pinned block -> d_work on the caller's stream, nothing waited for
+    size_t slot = 0;
+    if (int rc = stage_take(device, p.head_bytes, &slot)) return rc;
+    char *hp = (char *)stage_ptr(slot);
+    const size_t off_al = (size_t)W * sizeof(double), off_tab = off_al + p.al_doubles * sizeof(double),
+                 off_first = off_tab + (size_t)count * sizeof(MieBatchJob);
+    memcpy(hp, xmu, off_al);
+    size_t o = off_al;
+    for (const auto &l : p.lists) { memcpy(hp + o, l.first, (size_t)l.second * sizeof(double)); o += (size_t)l.second * sizeof(double); }
+    memcpy(hp + off_tab, p.tab.data(), (size_t)count * sizeof(MieBatchJob));
+    memcpy(hp + off_first, p.first.data(), p.first.size() * sizeof(int));
+    const hipError_t ce = hipMemcpyAsync(d_work, hp, p.head_bytes, hipMemcpyHostToDevice, st);
+    stage_release(slot, st);
+    HIPCHK(ce);
+    HIPCHK(hipMemsetAsync(d_status, 0, (size_t)count * sizeof(int32_t), st));
+    char *dw = (char *)d_work;
+    const int rc = launch_mie_batch(nbmu, (const double *)dw, count, (const MieBatchJob *)(dw + off_tab), (const int *)(dw + off_first),
+                                    p.nitems, (const double *)(dw + off_al), p.scr_alpha,
+                                    p.scr_doubles ? (double *)(dw + p.head_bytes) : nullptr, d_status, st);
+    if (rc == -3) return SOSGPU_E_UNSUPPORTED;
+    if (rc == -2) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
 }
 
 extern "C" int sosgpu_granu(int device, int nbmu, int nalpha, const float *d_rec, int igranu, double v1, double v2, double v3,

@@ -133,3 +133,17 @@ void launch_granu_batch(int count, int nbmu, const sosgpu_granu_job *jobs, doubl
                         hipStream_t st);
 int launch_mie(int nalpha, int nbmu, const double *d_xmu, double rn, double in, const double *d_alphas, int n_lds, double alpha_lds,
                double alpha_max, double *d_scratch, float *d_rec, double *d_g, int32_t *d_err, hipStream_t st);
+// ... of many refractive indices as one pool of (job, size parameter) items (mie.hip: the classes and the item mapping).
+// bound[c] .. bound[c + 1]: the size parameters of the job in class c (its list ascends; class MIE_BATCH_CLASSES = scratch form)
+#define MIE_BATCH_CLASSES 4
+struct MieBatchJob {
+    double rn, in;
+    float *rec;
+    double *g;
+    long long al_off;                            // its list in the packed size parameters, in doubles
+    int bound[MIE_BATCH_CLASSES + 2];
+};
+int mie_batch_class(double alpha);
+int mie_batch_slots(long long scratch_items);    // resident workgroups (= scratch slots) of the scratch-form launch
+int launch_mie_batch(int nbmu, const double *d_xmu, int count, const MieBatchJob *d_jobs, const int *d_first, const int *nitems,
+                     const double *d_alphas, double alpha_scr_max, double *d_scratch, int32_t *d_status, hipStream_t st);

@@ -20,14 +20,14 @@
 // GLOBAL = true : they live in a per-workgroup slot of an HBM scratch (the WMO dust-like component needs alpha = 4000,
 //                 SOS.h:122).  The recurrences carry their previous terms in registers, so the serial chain never waits
 //                 for its own stores; the arithmetic and its order are the same in both forms.
-// Workgroup b handles the size parameters first + b, first + b + gridDim.x, ... below `last`.
+// mie_item is one size parameter by one workgroup: the whole of SOS_MIE's loop body and SOS_FPHASE_MIE for it.  Both kernels
+// below (k_mie: one refractive index; k_mie_batch: the items of many) call it, so their records are the same bits.
+// sm: the 11 arrays; r: the record of this alpha; gout: its g; err: the status word bit 0 is set in when nmax is too small.
 template <bool GLOBAL>
-__global__ void k_mie(int nbmu, const double *__restrict__ xmu, double rn, double in, const double *__restrict__ alphas,
-                      int first, int last, int nmax, double *__restrict__ gscratch, float *__restrict__ rec,
-                      double *__restrict__ gout, int32_t *__restrict__ err)
+__device__ __forceinline__ void mie_item(int nbmu, const double *__restrict__ xmu, double rn, double in, double alpha, int nmax,
+                                         double *sm, float *__restrict__ r, double *__restrict__ gout,
+                                         int32_t *__restrict__ err)
 {
-    extern __shared__ double lds[];
-    double *sm = GLOBAL ? gscratch + (size_t)blockIdx.x * 11 * nmax : lds;
     // arrays with Fortran lower bound -1: element i at [i + 1]
     double *cna = sm, *sna = cna + nmax, *rgna = sna + nmax, *igna = rgna + nmax;
     double *rdna = igna + nmax, *rdnb = rdna + nmax, *idnb = rdnb + nmax;
@@ -36,8 +36,7 @@ __global__ void k_mie(int nbmu, const double *__restrict__ xmu, double rn, doubl
     __shared__ double s_q[3];
     const int t = threadIdx.x;
     const int W = 2 * nbmu + 1;
-    for (int a = first + blockIdx.x; a < last; a += gridDim.x) {
-        const double alpha = alphas[a];
+    {
         if (t == 0) {
             int n1 = (int)(alpha + alpha + 20), n2 = (int)(alpha + alpha + 5);
             if (n1 + 3 > nmax) { atomicOr(err, 1); s_n2 = -1; }
@@ -132,8 +131,7 @@ __global__ void k_mie(int nbmu, const double *__restrict__ xmu, double rn, doubl
         __syncthreads();
         const int n2 = s_n2;
         if (n2 >= 0) {
-            float *r = rec + (size_t)a * (4 + 3 * W);
-            if (t == 0) { r[0] = (float)alpha; r[1] = (float)s_q[0]; r[2] = (float)s_q[1]; r[3] = 0.f; gout[a] = s_q[2]; }
+            if (t == 0) { r[0] = (float)alpha; r[1] = (float)s_q[0]; r[2] = (float)s_q[1]; r[3] = 0.f; *gout = s_q[2]; }
             const double coef = 2. / s_q[1] / (alpha * alpha);
             for (int jj = t; jj < W; jj += blockDim.x) {                         // SOS_FPHASE_MIE :873-900
                 const double x = -xmu[jj];
@@ -157,6 +155,19 @@ __global__ void k_mie(int nbmu, const double *__restrict__ xmu, double rn, doubl
         }
         __syncthreads();                                                         // the arrays and s_q are reused by the next alpha
     }
+}
+
+// Workgroup b handles the size parameters first + b, first + b + gridDim.x, ... below `last`.
+template <bool GLOBAL>
+__global__ void k_mie(int nbmu, const double *__restrict__ xmu, double rn, double in, const double *__restrict__ alphas,
+                      int first, int last, int nmax, double *__restrict__ gscratch, float *__restrict__ rec,
+                      double *__restrict__ gout, int32_t *__restrict__ err)
+{
+    extern __shared__ double lds[];
+    double *sm = GLOBAL ? gscratch + (size_t)blockIdx.x * 11 * nmax : lds;
+    const int W = 2 * nbmu + 1;
+    for (int a = first + blockIdx.x; a < last; a += gridDim.x)
+        mie_item<GLOBAL>(nbmu, xmu, rn, in, alphas[a], nmax, sm, rec + (size_t)a * (4 + 3 * W), gout + a, err);
 }
 
 // alphas must ascend (alpha_grid does).  Size parameters whose arrays fit LDS run in the LDS form; the rest in the scratch
@@ -188,6 +199,81 @@ int launch_mie(int nalpha, int nbmu, const double *d_xmu, double rn, double in, 
         const int nmax = mie_nmax(alpha_max);
         const int wg = std::min(nalpha - n_lds, MIE_SLOTS);
         k_mie<true><<<wg, 128, 0, st>>>(nbmu, d_xmu, rn, in, d_alphas, n_lds, nalpha, nmax, d_scratch, d_rec, d_g, d_err);
+    }
+    return 0;
+}
+
+// The records of MANY refractive indices in one pool of work (sosgpu_mie_batch; the table-driven aerosol models of a spectrum
+// change their index with every wavelength).  The unit of work is one ITEM = (job, size parameter), not one job: a 50-term
+// water-soluble grid and an 8000-term dust-like grid fill the card together.  Items map to workgroups as in k_mie, one
+// workgroup per item, and are split over at most MIE_BATCH_CLASSES + 1 launches by the size of their coefficient arrays,
+// whatever the number of jobs:
+//   class 0..3  LDS form, alpha <= 64 | 200 | 420 | 850: dynamic LDS of 11 (2 A + 24) doubles for the class limit A, i.e.
+//               13 | 37 | 76 | 152 KB -- 11, 4, 2 and 1 workgroups per CU.  (One launch sized for alpha = 850 would leave a single
+//               workgroup per CU to the thousands of items below alpha = 1; sosgpu_mie avoids that by sizing the LDS for the
+//               call's own largest alpha, the classes do it for a mixed pool.)  Grid = the items of the class.
+//   class 4     scratch form, alpha > 850: min(items, MIE_SLOTS) resident workgroups stride over the items, each with its own
+//               slot (blockIdx.x) of ONE scratch for the whole batch, 11 (2 A + 24) doubles for the batch's largest alpha A.
+// The ascending list of a job is cut into one contiguous range per class (MieBatchJob::bound); first[c][j] is the number of
+// class-c items of the jobs before j, so workgroup item `it` finds its job by bisection and its alpha by offset.  Items are
+// taken from the top: the longest recurrences (largest alpha of a range) start first, the short ones fill the tail.
+static const double MIE_CLASS_ALPHA[MIE_BATCH_CLASSES] = {64., 200., 420., 850.};
+int mie_batch_class(double alpha)
+{
+    for (int c = 0; c < MIE_BATCH_CLASSES; c++)
+        if (alpha <= MIE_CLASS_ALPHA[c]) return c;
+    return MIE_BATCH_CLASSES;
+}
+int mie_batch_slots(long long scratch_items) { return (int)std::min<long long>(std::max<long long>(scratch_items, 0), MIE_SLOTS); }
+
+template <bool GLOBAL>
+__global__ void k_mie_batch(int nbmu, const double *__restrict__ xmu, const MieBatchJob *__restrict__ jobs,
+                            const int *__restrict__ first, int count, int cls, const double *__restrict__ alphas, int nmax,
+                            double *__restrict__ gscratch, int32_t *__restrict__ status)
+{
+    extern __shared__ double lds[];
+    double *sm = GLOBAL ? gscratch + (size_t)blockIdx.x * 11 * nmax : lds;
+    const int W = 2 * nbmu + 1;
+    const int nitem = first[count];
+    for (int i = blockIdx.x; i < nitem; i += gridDim.x) {
+        const int it = nitem - 1 - i;
+        int lo = 0, hi = count - 1;                  // the last job with first[job] <= it (jobs without items of the class: skipped)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (first[mid] <= it) lo = mid; else hi = mid - 1;
+        }
+        const MieBatchJob &jb = jobs[lo];
+        const int a = jb.bound[cls] + (it - first[lo]);
+        mie_item<GLOBAL>(nbmu, xmu, jb.rn, jb.in, alphas[jb.al_off + a], nmax, sm, jb.rec + (size_t)a * (4 + 3 * W), jb.g + a,
+                         status + lo);
+    }
+}
+
+// nitems[c]: items of class c (host); d_first[(MIE_BATCH_CLASSES + 1)][count + 1]; alpha_scr_max: largest scratch-form alpha.
+int launch_mie_batch(int nbmu, const double *d_xmu, int count, const MieBatchJob *d_jobs, const int *d_first, const int *nitems,
+                     const double *d_alphas, double alpha_scr_max, double *d_scratch, int32_t *d_status, hipStream_t st)
+{
+    bool attr = false;
+    for (int c = 0; c < MIE_BATCH_CLASSES; c++) {
+        if (nitems[c] <= 0) continue;
+        const int nmax = mie_nmax(MIE_CLASS_ALPHA[c]);
+        const size_t lds = (size_t)11 * nmax * sizeof(double);
+        if (!attr) {
+            const int most = 11 * mie_nmax(MIE_CLASS_ALPHA[MIE_BATCH_CLASSES - 1]) * (int)sizeof(double);
+            static_assert(MIE_LDS_BYTES >= 11 * (2 * 850 + 24) * 8, "the last LDS class must fit");
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_mie_batch<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    most) != hipSuccess)
+                return -2;
+            attr = true;
+        }
+        k_mie_batch<false><<<nitems[c], 128, lds, st>>>(nbmu, d_xmu, d_jobs, d_first + (size_t)c * (count + 1), count, c, d_alphas,
+                                                       nmax, nullptr, d_status);
+    }
+    if (nitems[MIE_BATCH_CLASSES] > 0) {
+        if (!d_scratch) return -3;
+        const int c = MIE_BATCH_CLASSES;
+        k_mie_batch<true><<<mie_batch_slots(nitems[c]), 128, 0, st>>>(nbmu, d_xmu, d_jobs, d_first + (size_t)c * (count + 1), count, c,
+                                                                     d_alphas, mie_nmax(alpha_scr_max), d_scratch, d_status);
     }
     return 0;
 }

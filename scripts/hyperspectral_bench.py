@@ -22,56 +22,38 @@ USER = {"-ANG.Thetas": 35.0, "-AP.HR": 8.0, "-AP.AerHS.HA": 2.0, "-AP.SpectralRe
         "-SOS.Flux": "NO_OUTPUT"}
 
 
-def spectrum_kwargs(rs, every=1):
+# --aer-model: the table-driven models change the refractive index of every component with the wavelength (fresh Mie records
+# per wavelength: sosgpu_mie_batch); wmo = WMO continental (dust-like component, alpha = 4000: scratch form), sf = Shettle & Fenn
+# maritime at 70 % humidity.  lnd = the keywords above (one index for the whole spectrum).
+AER_MODELS = {"lnd": {}, "wmo": {"-AER.Model": 1, "-AER.WMO.Model": 1}, "sf": {"-AER.Model": 2, "-AER.SF.Model": 3, "-AER.SF.RH": 70.0}}
+GOLDEN_FIC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "fic")
+
+
+def link_aerosol_tables(root):
+    """The aerosol tables of the WMO / Shettle & Fenn models next to the synthetic CKD tables: $SOS_ABS_ROOT/fic."""
+    os.makedirs(os.path.join(root, "fic"), exist_ok=True)
+    for name in os.listdir(GOLDEN_FIC):
+        if name.startswith(("Data_WMO_", "Data_SF_", "IRefrac_")) and not os.path.exists(os.path.join(root, "fic", name)):
+            os.symlink(os.path.join(GOLDEN_FIC, name), os.path.join(root, "fic", name))
+
+
+def spectrum_kwargs(rs, every=1, aer_model="lnd"):
     kws = []
     for nu in np.arange(27495.0, 2500.0, -10.0)[::every]:
         wa = 1.0e4 / nu
         if wa < 0.3641 or wa > 3.999:
             continue
         u = dict(USER)
+        if aer_model != "lnd":
+            u = {k: v for k, v in u.items() if not k.startswith("-AER.MMD.")}
+            u.update(AER_MODELS[aer_model])
         u["-SOS_Main.Wa"] = float(wa)
         kws.append(rs.sos_proc_kwargs(rs.update_parameters(rs.default_parameters(), u), trace=False))
     return kws
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--every", type=int, default=1, help="take every k-th interval of the spectrum")
-    ap.add_argument("--loop", type=int, default=120, help="wavelengths timed in the plain sos_proc loop / sos_proc_many")
-    ap.add_argument("--profile", action="store_true")
-    ap.add_argument("--chunk", type=int, default=256)
-    ap.add_argument("--streams", type=int, default=16, help="side streams of sos_spectrum (prep_streams)")
-    ap.add_argument("--pool", type=int, default=0, help="also run the spectrum through spectrum_pool with this many host processes")
-    ap.add_argument("--pool-only", action="store_true", help="only the spectrum_pool run: this process never touches the GPU")
-    a = ap.parse_args()
-    if a.pool_only:
-        pkg = importlib.import_module("radiativetransfer-sos_amd")
-        rs, sp = pkg.run_sos, pkg.spectrum_pool
-        root = tempfile.mkdtemp(prefix="synth_fic_")
-        synth_ckd.write_tables(root)
-        os.environ["SOS_ABS_ROOT"] = root
-        kws = spectrum_kwargs(rs, a.every)
-        nb = sum(pkg.absorption.band_bin_count(kw["wa_simu"], 10.0) for kw in kws)
-        with sp.SpectrumPool(processes=a.pool or 4) as pool:
-            pool.run(kws[::8])
-            for _ in range(2):
-                t0 = time.perf_counter()
-                pool.run(kws)
-                dt = time.perf_counter() - t0
-                print("(d) spectrum_pool alone, %d processes: %4d wavelengths (%d bins) in %6.2f s = %7.1f wavelengths/s" % (
-                    a.pool or 4, len(kws), nb, dt, len(kws) / dt), flush=True)
-        return
+def spectrum_vs_loops(a, pkg, rs, kws):
     import torch
-    pkg = importlib.import_module("radiativetransfer-sos_amd")
-    rs = pkg.run_sos
-    root = tempfile.mkdtemp(prefix="synth_fic_")
-    t0 = time.perf_counter()
-    nfile = synth_ckd.write_tables(root)
-    os.environ["SOS_ABS_ROOT"] = root
-    kws = spectrum_kwargs(rs, a.every)
-    nb = sum(pkg.absorption.band_bin_count(kw["wa_simu"], 10.0) for kw in kws)
-    print("spectrum: %d wavelengths, %d CKD bins (tables: %d files written and parsed in %.1f s)" % (
-        len(kws), nb, nfile, time.perf_counter() - t0), flush=True)
     sub = kws[::max(1, len(kws) // a.loop)][:a.loop]
     nbs = sum(pkg.absorption.band_bin_count(kw["wa_simu"], 10.0) for kw in sub)
     rs.sos_proc(**sub[0]); torch.cuda.synchronize()                      # warm-up: library load, surface matrices, caches
@@ -92,6 +74,56 @@ def main():
     same = all(np.array_equal(np.asarray(x), np.asarray(y)) for s1, s2 in zip(seq, spec) for x, y in zip(s1, s2))
     same_many = all(np.array_equal(np.asarray(x), np.asarray(y)) for s1, s2 in zip(seq, many) for x, y in zip(s1, s2))
     print("    outputs identical to the plain loop, bit for bit: sos_spectrum %s, sos_proc_many %s" % (same, same_many), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--every", type=int, default=1, help="take every k-th interval of the spectrum")
+    ap.add_argument("--loop", type=int, default=120, help="wavelengths timed in the plain sos_proc loop / sos_proc_many")
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--chunk", type=int, default=256)
+    ap.add_argument("--streams", type=int, default=16, help="side streams of sos_spectrum (prep_streams)")
+    ap.add_argument("--pool", type=int, default=0, help="also run the spectrum through spectrum_pool with this many host processes")
+    ap.add_argument("--pool-only", action="store_true", help="only the spectrum_pool run: this process never touches the GPU")
+    ap.add_argument("--aer-model", choices=sorted(AER_MODELS), default="lnd", help="aerosol model of the spectrum (wmo / sf: table models)")
+    ap.add_argument("--spectrum-only", action="store_true", help="skip the sos_proc loop and sos_proc_many legs: time sos_spectrum alone")
+    a = ap.parse_args()
+    if a.pool_only:
+        pkg = importlib.import_module("radiativetransfer-sos_amd")
+        rs, sp = pkg.run_sos, pkg.spectrum_pool
+        root = tempfile.mkdtemp(prefix="synth_fic_")
+        synth_ckd.write_tables(root)
+        link_aerosol_tables(root)
+        os.environ["SOS_ABS_ROOT"] = root
+        kws = spectrum_kwargs(rs, a.every, a.aer_model)
+        nb = sum(pkg.absorption.band_bin_count(kw["wa_simu"], 10.0) for kw in kws)
+        with sp.SpectrumPool(processes=a.pool or 4) as pool:
+            pool.run(kws[::8])
+            for _ in range(2):
+                t0 = time.perf_counter()
+                pool.run(kws)
+                dt = time.perf_counter() - t0
+                print("(d) spectrum_pool alone, %d processes: %4d wavelengths (%d bins) in %6.2f s = %7.1f wavelengths/s" % (
+                    a.pool or 4, len(kws), nb, dt, len(kws) / dt), flush=True)
+        return
+    import torch
+    pkg = importlib.import_module("radiativetransfer-sos_amd")
+    rs = pkg.run_sos
+    root = tempfile.mkdtemp(prefix="synth_fic_")
+    t0 = time.perf_counter()
+    nfile = synth_ckd.write_tables(root)
+    link_aerosol_tables(root)
+    os.environ["SOS_ABS_ROOT"] = root
+    kws = spectrum_kwargs(rs, a.every, a.aer_model)
+    nb = sum(pkg.absorption.band_bin_count(kw["wa_simu"], 10.0) for kw in kws)
+    print("spectrum: %d wavelengths, %d CKD bins (tables: %d files written and parsed in %.1f s)" % (
+        len(kws), nb, nfile, time.perf_counter() - t0), flush=True)
+    if a.spectrum_only:
+        print("aerosol model %s, SOS_SPECTRUM_MIE_PER_CALL=%s" % (a.aer_model, os.environ.get("SOS_SPECTRUM_MIE_PER_CALL", "")), flush=True)
+        rs.sos_proc(**kws[0]); torch.cuda.synchronize()                  # warm-up: library load, surface matrices, caches
+        rs.sos_spectrum(kws[:8])
+    else:
+        spectrum_vs_loops(a, pkg, rs, kws)
     if rs.PREPARE_SEGMENTS is not None:
         rs.PREPARE_SEGMENTS.clear()
     tm = {}

@@ -492,6 +492,31 @@ int  sosgpu_debug_phase_buffer(sosgpu_ctx *cx, unsigned long long *d_phase);
 /* Diagnostic accessor: device pointer and size (doubles) of the streamed solver's scratch of this context, and the offset of the
  * order-parallel form's I3 hand-over block [nb][iborm_max+1][threads] inside it after such a solve (0 otherwise). */
 int  sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *doubles, size_t *spec_i3_offset);
+/* Diagnostic: the launch plan sosgpu_os_solve (table = 0) / sosgpu_os_solve_multi (table != 0) and their _levels forms (nz > 0
+ * output slots) would follow for `nb` bins of `lp` padded levels in a context of `n` directions and iborm_max = `smax` -- the
+ * kernel variant, the launch form, the bins per launch and the layout of the context's scratch.  Needs no context and no
+ * device; the environment switches are read exactly as a solve reads them.  `nt_max` is the largest valid NT of the batch,
+ * which a solve fetches from the device when (and only when) `needs_nt` comes back set; otherwise it is ignored.
+ * Offsets and sizes are in doubles from the start of the scratch; the blocks follow each other in the order
+ *   work regions [regions][per_bin] | I3 block [i3_doubles] | queue and flag ints [queue_doubles] | slot state
+ *   [regions][slot_stride] (from a multiple of 8 doubles)
+ * and `need` is the end of the last one (0: the solve uses no scratch).
+ * Errors: SOSGPU_E_ARG, SOSGPU_E_UNSUPPORTED as the solve itself. */
+enum { SOSGPU_FORM_LDS = 0,        /* field resident in LDS, one workgroup per bin */
+       SOSGPU_FORM_STREAM = 1,     /* field streamed from the scratch, one workgroup per bin, `opl` Fourier orders per launch */
+       SOSGPU_FORM_PERSIST = 2,    /* streamed, one persistent launch taking (order, bin) tasks from queues */
+       SOSGPU_FORM_SPEC = 3 };     /* streamed, order-parallel: rounds of `spec_k` orders of every bin */
+typedef struct sosgpu_solve_plan {
+    int32_t nw, rtw, ct, big;      /* kernel variant: waves, row tiles per wave, column tiles, streamed (1) or LDS-resident (0) */
+    int32_t form, opl, spec_k;     /* SOSGPU_FORM_*; orders per launch (STREAM, PERSIST); orders per round (SPEC), else 0 */
+    int32_t needs_nt;              /* the order-parallel form is a candidate: the solve reads the batch's NT back */
+    int32_t per_launch, lpb;       /* bins per sub-launch; level capacity of a work region (multiple of 32) */
+    int32_t threads, q_tail;       /* workgroup size; SosBins::q_tail of the persistent form (-1: the launcher's default) */
+    size_t  lds_bytes;             /* dynamic LDS of the LDS-resident variant */
+    size_t  per_bin, regions;      /* doubles per work region, number of work regions */
+    size_t  off_i3, i3_doubles, off_queue, queue_doubles, off_slots, slot_stride, need;
+} sosgpu_solve_plan;
+int  sosgpu_debug_solve_plan(int n, int smax, int nb, int lp, int nz, int table, int nt_max, sosgpu_solve_plan *plan);
 /* Diagnostic accessor: the per-wavelength tables of a context (built by sosgpu_create, sosgpu_noyaux and
  * sosgpu_set_surface_matrices; csrc/sos_common.h documents every layout) and the numbers that describe them, copied to the
  * HOST.  Read-only: nothing in the context changes.  Like sosgpu_noyaux_fetch it waits for the streams the context's work was

@@ -22,7 +22,7 @@ EXPORTS = [
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
-    "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes",
+    "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes", "sosgpu_debug_solve_plan",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -60,6 +60,17 @@ class TablesInfo(C.Structure):
     """sosgpu_tables_info (include/sosgpu.h): layout numbers and scalars of a context's tables."""
     _fields_ = [(k, C.c_int32) for k in ("n", "w", "kp", "kh", "ks2h", "rtph", "nwgt", "prow", "os_nb", "smax", "n0", "ipolar")] + \
                [(k, C.c_double) for k in ("beta2", "gamma2", "alpha2", "f11sun", "f12sun", "mus", "ro")]
+
+
+class SolvePlan(C.Structure):
+    """sosgpu_solve_plan (include/sosgpu.h): launch form and scratch layout of a solve (sosgpu_debug_solve_plan)."""
+    _fields_ = [(k, C.c_int32) for k in ("nw", "rtw", "ct", "big", "form", "opl", "spec_k", "needs_nt", "per_launch", "lpb",
+                                         "threads", "q_tail")] + \
+               [(k, C.c_size_t) for k in ("lds_bytes", "per_bin", "regions", "off_i3", "i3_doubles", "off_queue", "queue_doubles",
+                                          "off_slots", "slot_stride", "need")]
+
+
+FORM_LDS, FORM_STREAM, FORM_PERSIST, FORM_SPEC = range(4)   # SOSGPU_FORM_*
 
 
 class SosgpuError(RuntimeError):
@@ -195,6 +206,8 @@ def lib():
         L.sosgpu_debug_phase_buffer.argtypes = [vp, vp]
         L.sosgpu_debug_scratch.restype = i32
         L.sosgpu_debug_scratch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.sosgpu_debug_solve_plan.restype = i32
+        L.sosgpu_debug_solve_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(SolvePlan)]
         L.sosgpu_debug_roundtrip.restype = i32
         L.sosgpu_debug_roundtrip.argtypes = [i32, i32, C.c_size_t, vp, vp, vp]
         L.sosgpu_debug_tables.restype = i32

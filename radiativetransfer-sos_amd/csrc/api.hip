@@ -3,6 +3,7 @@
 #include "../../include/sosgpu.h"
 #include "kernels.h"
 #include "sos_common.h"
+#include "solve_plan.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +70,17 @@ extern "C" int sosgpu_device_count(void)
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) { g_last_hip = (int)e; return SOSGPU_E_NODEVICE; }
     return n;
+}
+
+// Entry points that name their device: SOSGPU_E_NODEVICE without a usable GPU, SOSGPU_E_ARG for an index out of range,
+// otherwise `device` becomes the calling thread's current device.  (Runs after the host validation of the arguments.)
+static int use_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
+    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
+    HIPCHK(hipSetDevice(device));
+    return SOSGPU_OK;
 }
 
 // Device memory of the per-wavelength tables and of the entry points' temporaries comes from a process-wide pool of released
@@ -227,10 +239,7 @@ extern "C" int sosgpu_create(sosgpu_ctx **out, int device, const sosgpu_wave *wv
     if (N < 1 || N > 85 || B < 2 || B > 400 || iborm_max < 0 || iborm_max > B) return SOSGPU_E_ARG;
     if (wv->n0 < 1 || wv->n0 > N) return SOSGPU_E_ARG;          // the solar direction must be one of mu[]
     if (wv->igmax < 1) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
 
     sosgpu_ctx *cx = new sosgpu_ctx();
     cx->device = device;
@@ -554,14 +563,44 @@ extern "C" int sosgpu_noyaux_fetch(sosgpu_ctx *cx, int is, double *out)
     return SOSGPU_OK;
 }
 
-// output slots (sosgpu_os_solve_levels): lane-private state per work region, [nz][SOS_LV_N][threads] doubles, placed behind
-// the streamed kernel's regions at a 64-byte boundary
-static size_t lv_stride(int nz, int threads) { return (size_t)nz * SOS_LV_N * threads; }
-static size_t lv_off(size_t doubles) { return (doubles + 7) & ~(size_t)7; }
+// the solver's environment switches, read once per solve (not cached: a process may change them between solves)
+static SolveOverrides read_solve_overrides()
+{
+    SolveOverrides ov;
+    if (const char *e = getenv("SOSGPU_SCRATCH_GIB")) ov.scratch_gib = atol(e);
+    if (const char *e = getenv("SOSGPU_STREAM_SPEC")) ov.spec_off = atoi(e) == 0;
+    if (const char *e = getenv("SOSGPU_STREAM_SPEC_MAXBINS")) { ov.has_spec_maxbins = true; ov.spec_maxbins = atoi(e); }
+    if (const char *e = getenv("SOSGPU_STREAM_SPEC_K")) { ov.has_spec_k = true; ov.spec_k = atoi(e); }
+    if (const char *e = getenv("SOSGPU_STREAM_PERSIST")) ov.persist = atoi(e);
+    if (const char *e = getenv("SOSGPU_STREAM_ORDERS_PER_LAUNCH")) ov.orders_per_launch = atoi(e);
+    if (const char *e = getenv("SOSGPU_STREAM_QTAIL")) ov.q_tail = atoi(e);
+    return ov;
+}
+
+// The context's scratch holds at least `need` doubles afterwards (grow-only; taken from / handed back to the pool above).
+// (The scratch is reused from solve to solve and from context to context without being cleared: the streamed kernel
+//  initialises what it reads; the pad levels and pad columns it stages along with a chunk feed columns / rows of the
+//  contraction that are never stored.)
+static int ensure_scratch(sosgpu_ctx *cx, size_t need)
+{
+    if (need <= cx->scratch_doubles) return SOSGPU_OK;
+    if (cx->scratch) {
+        HIPCHK(sync_ctx_streams(cx));   // an earlier solve of this context may still be using it, on any of its streams
+        pool_give(cx->device, cx->scratch, cx->scratch_doubles);
+    }
+    cx->scratch = nullptr;
+    cx->scratch_doubles = 0;
+    size_t got = 0;
+    cx->scratch = pool_take(cx->device, need, &got);
+    if (!cx->scratch) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
+    cx->scratch_doubles = got;
+    return SOSGPU_OK;
+}
 
 // sosgpu_os_solve (table == null) and sosgpu_os_solve_multi (per-bin contexts from a device table)
 // nz > 0: sosgpu_os_solve_levels / sosgpu_os_solve_multi_levels (d_jout / d_zz / d_rec hold nz slots; a split batch reads
 // slot k of its bins at k nb + b0 -- bn.zbs is the whole batch's bin count)
+// Launch form, bins per launch and every scratch offset come from solve_plan (solve_plan.h).
 static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_ctx_of_bin, const int32_t *d_order, int nb, int lp, const int32_t *d_nt,
                          const int32_t *d_iborm, const double *d_prof, const int32_t *d_jout, const double *d_zz,
                          double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream, int nz = 0)
@@ -573,156 +612,63 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
     if (nb == 0) return SOSGPU_OK;
     HIPCHK(hipSetDevice(cx->device));
     hipStream_t st = (hipStream_t)stream;
-    // variant: field in LDS, or (NT too large) field in a per-bin HBM scratch, launched in sub-batches so that
-    // the scratch stays below its budget
-    int nw, rtw, ct, big;
-    size_t lds;
-    const int nt_max = lp - 1;          // lp - 1 bounds every NT of the batch (the host pads the level axis to lp)
-    int rc = sos_os_variant(cx->d.n, nt_max, &nw, &rtw, &ct, &lds, &big);
+    const SolveShape sh = {cx->d.n, cx->d.smax, nb, lp, nz, table != nullptr};
+    const SolveOverrides ov = read_solve_overrides();
+    int ntm = 1;
+    if (solve_plan_needs_nt(sh, ov)) {
+        std::vector<int32_t> h_nt((size_t)nb);
+        HIPCHK(hipMemcpyAsync(h_nt.data(), d_nt, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int b = 0; b < nb; b++) if (h_nt[b] < lp) ntm = std::max(ntm, (int)h_nt[b]);    // (malformed bins are flagged by the kernel)
+    }
+    SolvePlan pl;
+    int rc = solve_plan(sh, ov, ntm, &pl);
     if (rc) return rc;
-    int per_launch = nb, spec_k = 0;
-    int lpb = sos_round_up(lp, 32);
-    size_t per_bin = big ? sos_stream_scratch_doubles(cx->d.n, lpb) : 0;
-    if (big) {
-        // scratch budget: 64 GiB of the 288 GB (a launch covers ~40 000 bins at 608 levels; SOSGPU_SCRATCH_GIB overrides it)
-        size_t gib = 64;
-        if (const char *e = getenv("SOSGPU_SCRATCH_GIB")) { const long v = atol(e); if (v > 0) gib = (size_t)v; }
-        const size_t cap = (gib << 30) / sizeof(double);
-        // (output slots: a bin's work region also carries the slots' lane-private state)
-        const size_t per_region = per_bin + (nz > 0 ? lv_stride(nz, sos_stream_threads(cx->d.n)) : 0);
-        per_launch = (int)std::min<size_t>((size_t)nb, std::max<size_t>(1, cap / per_region));
-        // Few bins (a band of one wavelength): the order-parallel form -- up to 48 Fourier orders of every bin at a time, each in a
-        // work region of its own, so that the band fills ~1024 workgroup slots (sos_stream.hip; SOSGPU_STREAM_SPEC=0 turns it
-        // off, SOSGPU_STREAM_SPEC_MAXBINS moves the limit).  A single bin takes 11 ms as one workgroup, ~1.5 ms this way.
-        int spec_max = 128;
-        if (const char *e = getenv("SOSGPU_STREAM_SPEC")) { if (atoi(e) == 0) spec_max = 0; }
-        if (const char *e = getenv("SOSGPU_STREAM_SPEC_MAXBINS")) spec_max = atoi(e);
-        if (const char *e = getenv("SOSGPU_STREAM_PERSIST")) { if (atoi(e) != 0) spec_max = 0; }      // explicitly chosen forms win
-        if (const char *e = getenv("SOSGPU_STREAM_ORDERS_PER_LAUNCH")) { if (atoi(e) > 0) spec_max = 0; }
-        const int s1n = cx->d.smax + 1;
-        if (!table && nb <= spec_max && s1n > 1) {
-            // first round: 48 orders (a series typically ends after 25-50 of its up to 81), 24 above 40 bins; later rounds run
-            // half as many.  Measured (profiles/r02_sos_proc_latency.txt): the number of rounds is what costs, not the tasks
-            // beyond the chip's 512 workgroup slots.
-            spec_k = std::min(s1n, nb <= 40 ? 48 : 24);
-            // The work regions are laid out for the batch's own level count, not for the padded row length `lp` of the caller
-            // (608 for profiles made by sosgpu_profile): the few NT come to the host -- one small copy behind the work already
-            // queued on the stream, which this latency-bound form has to wait for anyway.
-            std::vector<int32_t> h_nt((size_t)nb);
-            HIPCHK(hipMemcpyAsync(h_nt.data(), d_nt, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            int ntm = 1;
-            for (int b = 0; b < nb; b++) if (h_nt[b] < lp) ntm = std::max(ntm, (int)h_nt[b]);    // (malformed bins are flagged by the kernel)
-            lpb = std::min(lpb, sos_round_up(ntm + 1, 32));
-            per_bin = sos_stream_scratch_doubles(cx->d.n, lpb);
-            // at most 4 GiB of work regions (128 bins x 24 orders at 600 levels need 4.6): beyond, fewer orders per round
-            const size_t soft = ((size_t)4 << 30) / sizeof(double);
-            const size_t fit = soft / ((size_t)nb * per_bin);
-            if (fit < (size_t)spec_k) spec_k = std::max(std::min(spec_k, 8), (int)fit);
-            if (const char *e = getenv("SOSGPU_STREAM_SPEC_K")) spec_k = std::min(s1n, std::max(1, atoi(e)));   // (tests)
-            if ((size_t)nb * spec_k * per_bin > cap) spec_k = 0;
-            if (!spec_k) { lpb = sos_round_up(lp, 32); per_bin = sos_stream_scratch_doubles(cx->d.n, lpb); }
-        }
-        const size_t regions = spec_k ? (size_t)nb * spec_k : (size_t)per_launch;
-        const size_t i3_doubles = spec_k ? (size_t)nb * s1n * sos_stream_threads(cx->d.n) : 0;
-        // + the task queues and per-bin order flags of the persistent form (ints, behind the bins' scratch)
-        size_t need = per_bin * regions + i3_doubles + (256 + (size_t)per_launch) / 2 + 1;
-        if (nz > 0) need = lv_off(need) + lv_stride(nz, sos_stream_threads(cx->d.n)) * regions;
-        if (need > cx->scratch_doubles) {
-            if (cx->scratch) {
-                HIPCHK(sync_ctx_streams(cx));   // an earlier solve of this context may still be using it, on any of its streams
-                pool_give(cx->device, cx->scratch, cx->scratch_doubles);
-            }
-            cx->scratch = nullptr;
-            cx->scratch_doubles = 0;
-            size_t got = 0;
-            cx->scratch = pool_take(cx->device, need, &got);
-            if (!cx->scratch) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
-            cx->scratch_doubles = got;
-        }
-    }
-    // output slots of the LDS-resident kernel: their lane-private state, one region per bin of a launch, in the scratch
-    if (nz > 0 && !big) {
-        const size_t need = lv_stride(nz, 64 * nw) * (size_t)nb;
-        if (need > cx->scratch_doubles) {
-            if (cx->scratch) {
-                HIPCHK(sync_ctx_streams(cx));
-                pool_give(cx->device, cx->scratch, cx->scratch_doubles);
-            }
-            cx->scratch = nullptr;
-            cx->scratch_doubles = 0;
-            size_t got = 0;
-            cx->scratch = pool_take(cx->device, need, &got);
-            if (!cx->scratch) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
-            cx->scratch_doubles = got;
-        }
-    }
-    // (The scratch is reused from solve to solve and from context to context -- pool above -- without being cleared: the streamed
-    //  kernel initialises what it reads; the pad levels and pad columns it stages along with a chunk feed columns / rows of
-    //  the contraction that are never stored.)
+    if ((rc = ensure_scratch(cx, pl.need))) return rc;
     if (!cx->ev0) { HIPCHK(hipEventCreate(&cx->ev0)); }
     if (!cx->ev1) { HIPCHK(hipEventCreate(&cx->ev1)); }
     HIPCHK(hipEventRecord(cx->ev0, st));
     const int S1 = cx->d.smax + 1, W = cx->d.w;
-    for (int b0 = 0; b0 < nb; b0 += per_launch) {
+    const int nt_max = lp - 1;          // lp - 1 bounds every NT of the batch (the host pads the level axis to lp)
+    for (int b0 = 0; b0 < nb; b0 += pl.per_launch) {
         SosBins bn;
-        bn.nb = std::min(per_launch, nb - b0); bn.lp = lp;
+        bn.nb = std::min(pl.per_launch, nb - b0); bn.lp = lp;
         bn.nt = d_nt + b0; bn.iborm = d_iborm + b0; bn.jout = d_jout ? d_jout + b0 : nullptr;
         bn.prof = d_prof + (size_t)b0 * 3 * lp; bn.zz = d_zz ? d_zz + b0 : nullptr;
         bn.rec = d_rec + (size_t)b0 * S1 * 3 * W; bn.flux = d_flux + (size_t)2 * b0;
         bn.norders = d_norders + b0; bn.iglast = d_iglast + (size_t)b0 * S1;
-        bn.scratch = big ? cx->scratch : nullptr; bn.scr_stride = per_bin; bn.lpb = lpb;
+        bn.scratch = pl.big ? cx->scratch : nullptr; bn.scr_stride = pl.per_bin; bn.lpb = pl.lpb;
         bn.phase = cx->phase ? cx->phase + (size_t)b0 * 8 : nullptr;
         bn.ctxs = table; bn.ctx_of_bin = table ? d_ctx_of_bin + b0 : nullptr;
-        bn.order = (table && per_launch >= nb) ? d_order : nullptr;      // (a split batch keeps its given order)
-        bn.queue = bn.qflag = nullptr; bn.q_tail = -1;
+        bn.order = (table && pl.per_launch >= nb) ? d_order : nullptr;      // (a split batch keeps its given order)
+        bn.queue = bn.qflag = nullptr; bn.q_tail = pl.q_tail;
         bn.spec_k = 0; bn.spec_i3 = nullptr;
-        if (const char *e = getenv("SOSGPU_STREAM_QTAIL")) bn.q_tail = atoi(e);
         bn.s_begin = 0; bn.s_end = S1;
-        bn.nz = nz; bn.zbs = nb; bn.zrs = (size_t)nb * S1 * 3 * W; bn.zst = nullptr; bn.zst_stride = 0;
-        if (nz > 0) {
-            const size_t regions = big ? (spec_k ? (size_t)nb * spec_k : (size_t)per_launch) : (size_t)nb;
-            bn.zst_stride = lv_stride(nz, big ? sos_stream_threads(cx->d.n) : 64 * nw);
-            bn.zst = cx->scratch + (big ? lv_off(per_bin * regions + (spec_k ? (size_t)nb * S1 * sos_stream_threads(cx->d.n) : 0) +
-                                                 (256 + (size_t)per_launch) / 2 + 1) : 0);
-        }
-        if (big && spec_k) {
+        bn.nz = nz; bn.zbs = nb; bn.zrs = (size_t)nb * S1 * 3 * W;
+        bn.zst = nz > 0 ? cx->scratch + pl.off_slots : nullptr; bn.zst_stride = nz > 0 ? pl.slot_stride : 0;
+        if (pl.form == SOSGPU_FORM_SPEC) {
             // order-parallel form: set-up launch, then rounds of (K order tasks per bin, replay of their stop tests)
-            bn.spec_i3 = cx->scratch + per_bin * (size_t)nb * spec_k;
-            cx->dbg_spec_i3 = per_bin * (size_t)nb * spec_k;
-            const int nt_max_r = lpb - 1;              // level capacity of the regions (>= every valid NT of the batch)
-            bn.spec_k = -spec_k; bn.s_begin = 0; bn.s_end = 0;
+            bn.spec_i3 = cx->scratch + pl.off_i3;
+            cx->dbg_spec_i3 = pl.off_i3;
+            const int nt_max_r = pl.lpb - 1;           // level capacity of the regions (>= every valid NT of the batch)
+            bn.spec_k = -pl.spec_k; bn.s_begin = 0; bn.s_end = 0;
             rc = launch_sos_stream(cx->d, bn, nt_max_r, st, &g_last_hip);
-            bn.spec_k = spec_k;
+            bn.spec_k = pl.spec_k;
             // (a series typically ends after 25-50 of its up to 81 orders: 32 + 16 + ... wastes less than all at once, and a
             //  launch whose bins have all stopped costs a few microseconds)
-            for (int s0 = 0, kr = spec_k; s0 < S1 && rc == 0; s0 += kr, kr = std::max(1, spec_k / 2)) {
+            for (int s0 = 0, kr = pl.spec_k; s0 < S1 && rc == 0; s0 += kr, kr = std::max(1, pl.spec_k / 2)) {
                 bn.s_begin = s0; bn.s_end = std::min(S1, s0 + kr);
                 rc = launch_sos_stream(cx->d, bn, nt_max_r, st, &g_last_hip);
                 if (rc == 0) rc = launch_sos_stream_replay(cx->d, bn, bn.s_begin, bn.s_end, st, &g_last_hip);
             }
-        } else if (big) {
-            // The streamed kernel can run `opl` Fourier orders of every bin per launch (order-synchronous launches: every
-            // workgroup then streams the same source operator).  Measured on the realistic mix (profiles/r02_stream_experiments.txt):
-            // 1 order per launch 21.1k bins/s, all orders in one launch 21.9k -- the operator stream is not what binds, so one
-            // launch is the default for large batches; SOSGPU_STREAM_ORDERS_PER_LAUNCH = n selects n orders per launch (tests cover both).
-            int opl = 0;
-            if (const char *e = getenv("SOSGPU_STREAM_ORDERS_PER_LAUNCH")) opl = atoi(e);
-            if (opl <= 0) opl = S1;
-            // SOSGPU_STREAM_PERSIST=1: ONE persistent launch whose workgroups take (Fourier order, bin) tasks from per-XCD queues,
-            // so that the workgroups of an XCD share the source operators of one or two orders in L2 (sos_stream.hip, PERSIST).
-            // Measured on the realistic mix (profiles/r02_stream_experiments.txt): fabric reads 505 -> 317 GB per launch (the
-            // operator misses are gone), 22.2 k against 22.6 k bins/s -- the kernel is not bound by that traffic, so one
-            // workgroup per bin stays the default.  Launches with a context table always use the default form.
-            int persist = 0;
-            if (const char *e = getenv("SOSGPU_STREAM_PERSIST")) persist = atoi(e);
-            if (persist && !table && opl == S1 && nz == 0) {        // (output slots: the plain launch)
-                bn.queue = reinterpret_cast<int *>(cx->scratch + per_bin * per_launch);
+        } else if (pl.big) {
+            if (pl.form == SOSGPU_FORM_PERSIST) {
+                bn.queue = reinterpret_cast<int *>(cx->scratch + pl.off_queue);
                 bn.qflag = bn.queue + 256;
                 HIPCHK(hipMemsetAsync(bn.queue, 0, (256 + (size_t)bn.nb) * sizeof(int), st));
             }
-            for (int s0 = 0; s0 < S1 && rc == 0; s0 += opl) {
-                bn.s_begin = s0; bn.s_end = std::min(S1, s0 + opl);
+            for (int s0 = 0; s0 < S1 && rc == 0; s0 += pl.opl) {
+                bn.s_begin = s0; bn.s_end = std::min(S1, s0 + pl.opl);
                 rc = table ? launch_sos_stream_multi(cx->d, bn, nt_max, st, &g_last_hip)
                            : launch_sos_stream(cx->d, bn, nt_max, st, &g_last_hip);
             }
@@ -1117,10 +1063,7 @@ extern "C" int sosgpu_glitter(int device, int n, const double *mu, const double 
     if (n < 1 || n > 85 || !mu || !chr || !d_rsurf || !d_il || !d_e) return SOSGPU_E_ARG;
     if (os_nb < 0 || os_ns < 2 || os_nm < os_nb + os_ns || os_nm > 2000) return SOSGPU_E_ARG;
     if (mat_reflexion_lds_bytes(os_ns, os_nm) > kLdsMaxBytes) return SOSGPU_E_ARG;    // k_mat_reflexion could not be launched
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     std::vector<double> fcoef((size_t)4 * (os_ns + 1));
     int rc = sosgpu_mat_fresnel_host(n, mu, chr, ind, os_ns, fcoef.data());
     if (rc) return rc;
@@ -1173,10 +1116,7 @@ extern "C" int sosgpu_land_surface(int device, const sosgpu_land *land, int n, c
     if (land->isurf == 6) return SOSGPU_E_UNSUPPORTED;               // Nadal: refused by the reference's SOS_PROC as well
     if (os_nb < 0 || os_ns < 2 || os_nm < os_nb + os_ns || os_nm > 2000) return SOSGPU_E_ARG;
     if (mat_reflexion_lds_bytes(os_ns, os_nm) > kLdsMaxBytes) return SOSGPU_E_ARG;    // k_mat_reflexion could not be launched
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     std::vector<double> fcoef((size_t)4 * (os_ns + 1), 0.);
     if (land->isurf > 3) {
@@ -1276,13 +1216,10 @@ extern "C" int sosgpu_profile(sosgpu_ctx *cx, int nb, double tr, double hr, doub
 extern "C" int sosgpu_profile_nogas(int device, double tr, double hr, double ta, double ha, double *d_nogas, void *stream)
 {
     if (!d_nogas || !(hr > 0.) || !(ha > 0.) || tr < 0. || ta < 0.) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
+    if (const int rc = use_device(device)) return rc;
     double t_first = 0., t_layer = 0.;
     const int nt_ng = profile_nogas_grid(tr, ta, &t_first, &t_layer);
     if (nt_ng < 0) return SOSGPU_E_UNSUPPORTED;
-    HIPCHK(hipSetDevice(device));
     launch_profile_nogas(tr, hr, ta, ha, nt_ng, t_first, t_layer, d_nogas, SOSGPU_NOGAS_LEVELS, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;
@@ -1292,10 +1229,7 @@ extern "C" int sosgpu_absprofile(int device, int nb, int nlev, int nterm, const 
                                  const double *d_ro, double *d_tabs, void *stream)
 {
     if (nb < 1 || nlev < 2 || nlev > SOS_PROF_NBLEV_MAX || nterm < 1 || !d_ik || !d_xk || !d_ro || !d_tabs) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     launch_absprofile(nb, nlev, nterm, d_ik, d_xk, d_ro, d_tabs, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;
@@ -1396,10 +1330,7 @@ extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile
     }
     if (bad_wl) *bad_wl = -1;
     if (bins != nb) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     // --- the table: pinned block -> d_table on the caller's stream, nothing waited for
     const size_t bytes = (size_t)nwl * sizeof(ProfileWl);
@@ -1465,10 +1396,7 @@ extern "C" int sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl 
     }
     if (bad_wl) *bad_wl = -1;
     if (slots != nslots) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t tbytes = (size_t)nwl * sizeof(CkdWl), pbytes = (size_t)nslots * sizeof(double *);
     size_t slot = 0;
@@ -1490,10 +1418,7 @@ extern "C" int sosgpu_mie(int device, int nbmu, const double *xmu, double rn, do
                           float *d_rec, double *d_g, void *stream)
 {
     if (nbmu < 1 || nbmu > 100 || !xmu || nalpha < 1 || !alphas || !d_rec || !d_g) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int W = 2 * nbmu + 1;
     // ascending size parameters (SOS_MIE's grid): those whose 11 arrays of 2 alpha + 24 terms fit LDS form a prefix
@@ -1611,10 +1536,7 @@ extern "C" int sosgpu_mie_batch(int device, int nbmu, const double *xmu, int cou
     if (!count) return SOSGPU_OK;
     if (!xmu || !d_work || !d_status || ((uintptr_t)d_work & 7) != 0) return SOSGPU_E_ARG;
     if (work_bytes < p.head_bytes + p.scr_doubles * sizeof(double)) return SOSGPU_E_UNSUPPORTED;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int W = 2 * nbmu + 1;
     // --- angle set, lists, job table and item offsets: one pinned block -> d_work on the caller's stream, nothing waited for
@@ -1646,10 +1568,7 @@ extern "C" int sosgpu_granu(int device, int nbmu, int nalpha, const float *d_rec
                             double wa, double alphaf, double *out, void *stream)
 {
     if (nbmu < 1 || nbmu > 100 || nalpha < 1 || !d_rec || igranu < 1 || igranu > 2 || !out || !(wa > 0.)) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t nout = (size_t)3 + 3 * (2 * nbmu + 1), nwork = (size_t)3 * nalpha + 1;
     TmpBuf tb(device, (nout + nwork) * sizeof(double));
@@ -1674,10 +1593,7 @@ extern "C" int sosgpu_granu_batch(int device, int nbmu, int count, const sosgpu_
             return SOSGPU_E_ARG;
     }
     if (!count) return SOSGPU_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     launch_granu_batch(count, nbmu, jobs, d_work, work_stride, d_out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;
@@ -1685,6 +1601,13 @@ extern "C" int sosgpu_granu_batch(int device, int nbmu, int count, const sosgpu_
 
 // Diagnostic: the streamed solver's scratch of this context (device pointer, size in doubles) and, after an order-parallel
 // solve, where its I3 hand-over block starts (doubles from the start; 0 when the last solve did not use that form).
+extern "C" int sosgpu_debug_solve_plan(int n, int smax, int nb, int lp, int nz, int table, int nt_max, sosgpu_solve_plan *plan)
+{
+    if (!plan || smax < 0 || nb < 1 || lp < 2 || nz < 0 || nz > SOSGPU_MAX_OUTPUT_LEVELS) return SOSGPU_E_ARG;
+    const SolveShape sh = {n, smax, nb, lp, nz, table != 0};
+    return solve_plan(sh, read_solve_overrides(), nt_max, plan);
+}
+
 extern "C" int sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *doubles, size_t *spec_i3_offset)
 {
     if (!cx || !d_scratch || !doubles || !spec_i3_offset) return SOSGPU_E_ARG;
@@ -1739,10 +1662,7 @@ extern "C" int sosgpu_debug_phase_buffer(sosgpu_ctx *cx, unsigned long long *d_p
 extern "C" int sosgpu_debug_roundtrip(int device, int fmt, size_t n, const double *d_in, double *d_out, void *stream)
 {
     if ((fmt != 0 && fmt != 1) || n < 1 || n > ((size_t)1 << 31) || !d_in || !d_out) return SOSGPU_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SOSGPU_E_NODEVICE;
-    if (device < 0 || device >= ndev) return SOSGPU_E_ARG;
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = use_device(device)) return rc;
     launch_debug_roundtrip(fmt, n, d_in, d_out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;

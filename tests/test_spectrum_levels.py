@@ -105,9 +105,9 @@ def test_concat_levels_orders_and_pads_like_concat_bins(pkg):
         sv.concat_levels([la, sv.host_output_levels(b, alts[:2])])
 
 
-def _scratch_split(n, lp, nb, nz, gib):
-    """Bins per launch of a streamed table launch (os_solve_impl, csrc/api.hip): the SOSGPU_SCRATCH_GIB budget over a work
-    region of stream_scratch_doubles (csrc/sos_stream.hip) plus the slots' lane-private state (lv_stride)."""
+def _scratch_numbers(n, lp, nz):
+    """Doubles of one work region of the streamed kernel at lp padded levels (stream_scratch_doubles, csrc/sos_stream.hip) and
+    of the lane-private state of nz output slots of that region (lv_stride, csrc/solve_plan.h)."""
     kh = vm._round_up(3 * n, 8)
     nw, kht = (8, 16) if kh > 128 else (4, 4) if kh <= 64 else (4, 5 if kh <= 80 else 6 if kh <= 96 else 8)
     khm, cols, vpad = 16 * kht, 32, 8
@@ -116,6 +116,14 @@ def _scratch_split(n, lp, nb, nz, gib):
     d = lpb * fs + (lpb + 1) * ns + 7 * (lpb + vpad) + (lpb // cols) * (2 * khm + 2 * ns) + 2 * 64 * nw + 8
     per_bin = (d + 15) & ~15
     lv = nz * 8 * 64 * nw                                  # [nz][SOS_LV_N][threads]
+    return per_bin, lv
+
+
+def _scratch_split(n, lp, nb, nz, gib):
+    """Bins per launch of a streamed table launch (solve_plan, csrc/solve_plan.h), with and without output slots: the
+    SOSGPU_SCRATCH_GIB budget over a work region plus the slots' lane-private state.  An independent restatement:
+    test_solve_plan.py compares it with what the library reports (sosgpu_debug_solve_plan)."""
+    per_bin, lv = _scratch_numbers(n, lp, nz)
     cap = (gib << 30) // 8
     return min(nb, max(1, cap // (per_bin + lv))), min(nb, max(1, cap // per_bin))
 

@@ -103,6 +103,25 @@ int  sosgpu_set_surface_matrices_async(sosgpu_ctx *cx, const float *d_rsurf, voi
 /* Replaces SOS_NOYAUX (SOS_OS.F:1857-2158) for every Fourier order 0..iborm_max at once; must be called
  * once per context before sosgpu_os_solve.  Fills the context's packed source operators. */
 int  sosgpu_noyaux(sosgpu_ctx *cx, void *stream);
+/* The two calls above for the contexts of a part of a spectrum at once: sosgpu_set_surface_matrices_async followed by
+ * sosgpu_noyaux of every context, in at most FIVE launches whatever nctx is (table forms of the same kernels: a workgroup takes
+ * its context from a device table, and the doubles written are, bit for bit, those of the two calls).
+ *  ctxs[nctx]      HOST array of contexts of one device; they may differ in N, OS_NB, iborm_max, IPOLAR, Fresnel and surface
+ *  d_rsurf[nctx]   HOST array of DEVICE pointers, each laid out as sosgpu_set_surface_matrices takes it; NULL for a context with
+ *                  imat_surf = 0.  The whole argument may be NULL when no context has matrices (the fifth launch, the ground
+ *                  operators, is made only when some entry is non-NULL).  Keep the matrices allocated until `stream` has passed
+ *                  the call.
+ *  d_work          DEVICE area of nctx * (sosgpu_ctx_table_entry_bytes() + 8) bytes, 8-byte aligned, the caller's until `stream`
+ *                  has passed the call: the table of the contexts and the list of matrix pointers arrive there in ONE copy on
+ *                  `stream`, from a pinned block ctxs[0] keeps until it is destroyed (as sosgpu_ctx_table's).
+ * Asynchronous: nothing is waited for and no device memory is allocated.  On return every context is in the host-side state the
+ * two calls leave (its ground operators registered, `stream` noted for sosgpu_destroy); once `stream` has passed the call its
+ * tables are filled.  Call sosgpu_ctx_table AFTER this call, not before: the table copies the ground-operator pointers this
+ * call registers.
+ * Checked before anything is queued or any context is changed, SOSGPU_E_ARG for: NULL ctxs or d_work, a NULL entry of ctxs,
+ * nctx < 0 or nctx > 65535, contexts on different devices, imat_surf = 1 with a NULL matrix pointer, a matrix pointer for a
+ * context with imat_surf = 0, a misaligned d_work.  nctx = 0 returns SOSGPU_OK with nothing queued. */
+int  sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const float *const *d_rsurf, void *d_work, void *stream);
 /* Debug/parity accessor: copies the six kernels of order `is` to host as the reference lays them
  * out, X[(j+N)*W + (k+N)] = X(J,K), in the order BP,GR,GT,ARR,ART,ATT, then XPL,XRL,XTL (W each).
  * Synchronous.  out must hold 6*W*W + 3*W doubles. */

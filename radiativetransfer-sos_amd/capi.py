@@ -23,6 +23,7 @@ EXPORTS = [
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
     "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes", "sosgpu_debug_solve_plan",
+    "sosgpu_noyaux_spectrum",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -128,6 +129,8 @@ def lib():
         L.sosgpu_set_surface_matrices_async.argtypes = [vp, vp, vp]
         L.sosgpu_noyaux.restype = i32
         L.sosgpu_noyaux.argtypes = [vp, vp]
+        L.sosgpu_noyaux_spectrum.restype = i32
+        L.sosgpu_noyaux_spectrum.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), vp, vp]
         L.sosgpu_noyaux_fetch.restype = i32
         L.sosgpu_noyaux_fetch.argtypes = [vp, i32, vp]
         L.sosgpu_os_solve.restype = i32

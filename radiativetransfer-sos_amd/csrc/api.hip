@@ -462,14 +462,16 @@ extern "C" size_t sosgpu_ctx_bytes(const sosgpu_ctx *cx) { return cx ? cx->bytes
 //                     + 2 rho w_j mu_j for c = b = 0 and s = 0 (Lambertian part, SOS_OS.F:1177-1190)
 // with the polarisation cut of SOS_OS.F:928-941 (IPOLAR = 0: only R_11 is kept), plus the solar-beam column
 // rdir[s][c][k] = R_c1(N0, k) of the direct term (SOS_OS.F:984-990).
-__global__ void k_pack_ground(SosDev cx, const float *__restrict__ r, double *__restrict__ gop, double *__restrict__ rdir)
+// (the body of element q of order s, shared by k_pack_ground and the table form k_pack_ground_table: the same bits)
+template <class CX>
+__device__ inline void pack_ground_body(const CX &cx, const int s, const size_t q, const float *__restrict__ r,
+                                        double *__restrict__ gop, double *__restrict__ rdir)
 {
     // no fused multiply-add: the Lambertian term is added to the rounded BRDF term, as the formula above reads (with
     // contraction the sum was one ulp off its plain evaluation in about one entry of eight)
 #pragma clang fp contract(off)
-    const int s = blockIdx.y, N = cx.n;
+    const int N = cx.n;
     const size_t per = (size_t)cx.rtph * cx.ks2h * 128;
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const float *rs = r + (size_t)s * 9 * N * N;
     if (q < per) {
         const int e2 = q & 1, lane = (q >> 1) & 63;
@@ -493,6 +495,23 @@ __global__ void k_pack_ground(SosDev cx, const float *__restrict__ r, double *__
         if (!cx.ipolar && c) x = 0.;
         rdir[(size_t)s * 3 * N + q] = x;
     }
+}
+
+__global__ void k_pack_ground(SosDev cx, const float *__restrict__ r, double *__restrict__ gop, double *__restrict__ rdir)
+{
+    pack_ground_body(cx, blockIdx.y, (size_t)blockIdx.x * blockDim.x + threadIdx.x, r, gop, rdir);
+}
+
+// Table form (sosgpu_noyaux_spectrum): context = blockIdx.z of a device table, its matrices rsurf[blockIdx.z] (null: the
+// context has none, the workgroup leaves), its outputs the entry's own mp_gnd / rdir.  The grid takes the largest context with
+// matrices; a workgroup tests the order against its own context, the body tests the element (q < per, q < 3N).
+__global__ void k_pack_ground_table(const SosDev *tab, const float *const *rsurf)
+{
+    const SosDevK &cx = *(const SosDevK *)(unsigned long long)(tab + blockIdx.z);
+    const float *r = rsurf[blockIdx.z];
+    if (!r || (int)blockIdx.y > cx.smax) return;
+    pack_ground_body(cx, blockIdx.y, (size_t)blockIdx.x * blockDim.x + threadIdx.x, r, const_cast<double *>(cx.mp_gnd),
+                     const_cast<double *>(cx.rdir));
 }
 
 static int set_surface_matrices_impl(sosgpu_ctx *cx, const float *d_rsurf, hipStream_t st)
@@ -543,6 +562,55 @@ extern "C" int sosgpu_noyaux(sosgpu_ctx *cx, void *stream)
     launch_noyaux(cx->d, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     note_stream(cx, (hipStream_t)stream);
+    return SOSGPU_OK;
+}
+
+// sosgpu_set_surface_matrices_async + sosgpu_noyaux of nctx contexts in at most five launches (the table forms of their
+// kernels, noyaux.hip / k_pack_ground_table).  d_work = [SosDev entries | matrix pointers], filled by one copy from a pinned
+// block ctxs[0] keeps until it is destroyed (as sosgpu_ctx_table's).  Everything is checked before a context is touched.
+extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const float *const *d_rsurf, void *d_work, void *stream)
+{
+    if (!ctxs || !d_work || nctx < 0 || nctx > 65535) return SOSGPU_E_ARG;
+    if (nctx == 0) return SOSGPU_OK;
+    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    NoyauxTableGrid g = {0, 0, 0};
+    size_t gnd_elems = 0;                       // ground launch: largest max(per, 3N) and smax over the contexts with matrices
+    int gnd_smax = -1;
+    for (int i = 0; i < nctx; i++) {
+        const sosgpu_ctx *cx = ctxs[i];
+        if (!cx || cx->device != ctxs[0]->device) return SOSGPU_E_ARG;
+        const float *r = d_rsurf ? d_rsurf[i] : nullptr;
+        if ((cx->d.imat_surf != 0) != (r != nullptr)) return SOSGPU_E_ARG;
+        if (r && (!cx->gnd_op || !cx->gnd_dir)) return SOSGPU_E_ARG;
+        const size_t per = (size_t)cx->d.rtph * cx->d.ks2h * 128;
+        g.smax = std::max(g.smax, cx->d.smax); g.kp = std::max(g.kp, cx->d.kp); g.per = std::max(g.per, per);
+        if (r) { gnd_elems = std::max(gnd_elems, std::max(per, (size_t)3 * cx->d.n)); gnd_smax = std::max(gnd_smax, cx->d.smax); }
+    }
+    HIPCHK(hipSetDevice(ctxs[0]->device));
+    const size_t n_tab = (size_t)nctx * sizeof(SosDev), n_all = n_tab + (size_t)nctx * sizeof(const float *);
+    static_assert(sizeof(SosDev) % 8 == 0, "the pointer list follows the entries");
+    char *stage = nullptr;
+    HIPCHK(hipHostMalloc((void **)&stage, n_all, hipHostMallocDefault));
+    ctxs[0]->host_staging.push_back(stage);
+    SosDev *tab = reinterpret_cast<SosDev *>(stage);
+    const float **rs = reinterpret_cast<const float **>(stage + n_tab);
+    for (int i = 0; i < nctx; i++) {
+        sosgpu_ctx *cx = ctxs[i];
+        rs[i] = d_rsurf ? d_rsurf[i] : nullptr;
+        cx->d.mp_gnd = rs[i] ? cx->gnd_op : nullptr;
+        cx->d.rdir = rs[i] ? cx->gnd_dir : nullptr;
+        tab[i] = cx->d;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(d_work, stage, n_all, hipMemcpyHostToDevice, st));
+    const SosDev *d_tab = static_cast<const SosDev *>(d_work);
+    if (gnd_smax >= 0) {
+        dim3 grid((unsigned)((gnd_elems + 255) / 256), (unsigned)gnd_smax + 1, (unsigned)nctx);
+        k_pack_ground_table<<<grid, 256, 0, st>>>(d_tab, reinterpret_cast<const float *const *>(static_cast<char *>(d_work) + n_tab));
+    }
+    launch_noyaux_table(d_tab, nctx, g, st);
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < nctx; i++) note_stream(ctxs[i], st);
     return SOSGPU_OK;
 }
 

@@ -5,6 +5,13 @@
 
 void launch_noyaux(const SosDev &cx, hipStream_t st);
 void launch_noyaux_fetch(const SosDev &cx, int s, double *d_out, hipStream_t st);
+// Table forms (sosgpu_noyaux_spectrum): the same four kernels for the nctx entries of a device table, context = blockIdx.z.
+// The grids take the largest context of the call; every workgroup tests its own context's bounds.
+struct NoyauxTableGrid {
+    int smax, kp;                // largest iborm_max and order-1 stride
+    size_t per;                  // largest rtph * ks2h * 128 (elements of one system per order)
+};
+void launch_noyaux_table(const SosDev *d_tab, int nctx, const NoyauxTableGrid &g, hipStream_t st);
 
 // Fused successive-orders solver.  Returns 0, SOSGPU_E_UNSUPPORTED when (N, max NT) has no variant, or -2 with the HIP
 // error code in *hip_err.

@@ -12,6 +12,12 @@
 // recurrence, one thread per direction, sequential in l (SOS_OS.F:1968-2100).
 // Kernel 2 (k_pack): one thread per packed operator element; the sum over l runs in the reference's
 // order (l ascending) with contraction disabled so the kernels agree with the Fortran to the last bits.
+//
+// Every kernel exists in two forms that call the same __device__ body (gsf_body, pack_body, pack_ray_body, sv_body), so their
+// doubles are the same bits by construction: the by-value form (one context as the kernel argument, sosgpu_noyaux) and the
+// table form k_*_table (sosgpu_noyaux_spectrum: the contexts of a part of a spectrum in ONE launch, blockIdx.z = the context,
+// read from a device table through the constant address space like the solver's SOS_BIND_CTX).  The bodies are templates
+// over the context type for that reason only (SosDev, or SosDev in address space 4).
 #include "sos_common.h"
 #include "kernels.h"
 
@@ -20,10 +26,10 @@
 // ---------------------------------------------------------------------------------------------
 // prt[((s*3 + q)*(B+1) + l)*W + (jj+N)]
 // ---------------------------------------------------------------------------------------------
-__global__ void k_gsf(SosDev cx)
+// s: Fourier order, j: 0..N ; 0 = solar beam slot, RMU(0) = -mus (SOS_OS.F:706-715)
+template <class CX>
+__device__ inline void gsf_body(const CX &cx, const int s, const int j)
 {
-    const int s = blockIdx.x;
-    const int j = threadIdx.x;          // 0..N ; 0 = solar beam slot, RMU(0) = -mus (SOS_OS.F:706-715)
     const int N = cx.n, W = cx.w, B = cx.os_nb;
     if (j > N) return;
     double *P = cx.prt + ((size_t)(s * 3 + 0) * (B + 1)) * W + N;
@@ -90,11 +96,17 @@ __global__ void k_gsf(SosDev cx)
     }
 }
 
+__global__ void k_gsf(SosDev cx)
+{
+    gsf_body(cx, blockIdx.x, threadIdx.x);
+}
+
 // One element of one of the six kernels of SOS_NOYAUX (SOS_OS.F:2134-2143) for order s:
 //   X: 0 BP, 1 GR, 2 GT, 3 ARR, 4 ART, 5 ATT;  a, b in -N..N (0 = solar slot)
 // with the aerosol coefficient arrays alpha..zeta, l = s..B.  (The molecular kernels are single l = 2 terms, SOS_OS.F:2859-2876:
 // k_pack_ray factorises them and k_sv writes them out term by term.)
-__device__ inline double ktab(const SosDev &cx, int s, int X, int a, int b)
+template <class CX>
+__device__ inline double ktab(const CX &cx, int s, int X, int a, int b)
 {
     const int W = cx.w, N = cx.n, B = cx.os_nb;
     const double *P = cx.prt + ((size_t)(s * 3 + 0) * (B + 1)) * W + N;
@@ -122,7 +134,8 @@ __device__ inline double ktab(const SosDev &cx, int s, int X, int a, int b)
 //   Q<-I  plus(GR,j,k)    Q<-Q  plus(ARR,j,k)    Q<-U  -plus(ART,j,k)
 //   U<-I  -minus(GT,j,k)  U<-Q  -plus(ART,k,j)   U<-U  minus(ATT,j,k)
 // times w_j/4 (the reference's Gauss weight and final 1/2, and the 1/2 of the recombination).
-__device__ inline double half_element(const SosDev &cx, int s, int sys, int row, int col)
+template <class CX>
+__device__ inline double half_element(const CX &cx, int s, int sys, int row, int col)
 {
     const int N = cx.n;
     const int ro = cx.rowmap[row], cl = cx.rowmap[col];         // half-system positions -> (component, direction)
@@ -148,7 +161,8 @@ __device__ inline double half_element(const SosDev &cx, int s, int sys, int row,
 }
 
 // Element (row 0..3, half-system position col) of the projection factor V^T of the molecular operator (see k_pack_ray)
-__device__ inline double ray_vt_element(const SosDev &cx, int s, int row, int col)
+template <class CX>
+__device__ inline double ray_vt_element(const CX &cx, int s, int row, int col)
 {
     const int N = cx.n, W = cx.w, B = cx.os_nb;
     const double *P = cx.prt + ((size_t)(s * 3 + 0) * (B + 1) + 2) * W + N;   // l = 2
@@ -166,11 +180,11 @@ __device__ inline double ray_vt_element(const SosDev &cx, int s, int row, int co
     return (ci == 0) ? hw * b0 : 0.;
 }
 
-__global__ void k_pack(SosDev cx)
+// element e of the two packed systems of order s
+template <class CX>
+__device__ inline void pack_body(const CX &cx, const int s, const size_t e)
 {
-    const int s = blockIdx.y;
     const size_t per = (size_t)cx.rtph * cx.ks2h * 128;     // one system
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= 2 * per) return;
     const int sys = e >= per;
     const size_t q = e - (size_t)sys * per;
@@ -188,6 +202,11 @@ __global__ void k_pack(SosDev cx)
     cx.mp_aer[(size_t)s * 2 * per + e] = v;
 }
 
+__global__ void k_pack(SosDev cx)
+{
+    pack_body(cx, blockIdx.y, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // Molecular (Rayleigh) part of the source operator for s <= 2 (SOS_OS.F:2859-2876).  Its kernels are single
 // Legendre terms (l = 2, plus beta0 at s = 0), so in the parity basis the operator is EXACTLY rank <= 4 and acts on
 // one half system only (A for even s, B for odd s; the other half is identically zero):
@@ -199,9 +218,9 @@ __global__ void k_pack(SosDev cx)
 // with P,R,T = P^s_2, R^s_2, T^s_2 at the Gauss nodes.  Packed as MFMA A operands:
 //   vt[(m*64 + lane)*2 + e] = V^T[lane&15][8m + 2(lane>>4) + e]   (projection, K = 3N)
 //   uf[rt*64 + lane]        = U[rt*16 + (lane&15)][lane>>4]       (expansion, K = 4)
-__global__ void k_pack_ray(SosDev cx)
+template <class CX>
+__device__ inline void pack_ray_body(const CX &cx, const int s)      // s: 0..2
 {
-    const int s = blockIdx.x;                 // 0..2
     const int N = cx.n, W = cx.w, B = cx.os_nb;
     const double *P = cx.prt + ((size_t)(s * 3 + 0) * (B + 1) + 2) * W + N;   // l = 2
     const double *R = cx.prt + ((size_t)(s * 3 + 1) * (B + 1) + 2) * W + N;
@@ -229,6 +248,11 @@ __global__ void k_pack_ray(SosDev cx)
     }
 }
 
+__global__ void k_pack_ray(SosDev cx)
+{
+    pack_ray_body(cx, blockIdx.x);
+}
+
 // Order-1 source vectors, one per state row r = (c, +-k):
 //   sv[s][0][r]  aerosol part of SOS_FSOURCE_ORDRE1:  I: BP(0,J), Q: GR(0,J), U: -GT(0,J)   (SOS_OS.F:2557-2559)
 //   sv[s][1][r]  molecular part (s <= 2)
@@ -237,10 +261,9 @@ __global__ void k_pack_ray(SosDev cx)
 //                I: F11sun BP(0,D) + F12sun GR(D,0), Q: F11sun GR(0,D) + F12sun ARR(0,D),
 //                U: F11sun GT(0,D) + F12sun ART(D,0)
 //   sv[s][3][r]  molecular part of the same (s <= 2)
-__global__ void k_sv(SosDev cx)
+template <class CX>
+__device__ inline void sv_body(const CX &cx, const int s, const int r)
 {
-    const int s = blockIdx.x;
-    const int r = threadIdx.x;
     if (r >= cx.kp) return;
     double *o = cx.sv + (size_t)s * 4 * cx.kp;
     double v0 = 0., v1 = 0., v2 = 0., v3 = 0.;
@@ -284,6 +307,45 @@ __global__ void k_sv(SosDev cx)
     o[0 * cx.kp + r] = v0; o[1 * cx.kp + r] = v1; o[2 * cx.kp + r] = v2; o[3 * cx.kp + r] = v3;
 }
 
+__global__ void k_sv(SosDev cx)
+{
+    sv_body(cx, blockIdx.x, threadIdx.x);
+}
+
+// Table forms: the grid is sized by the largest context of the call (launch_noyaux_table), so every workgroup tests the order
+// against ITS context before the body tests the element (j > N, e >= 2 per, r >= kp) -- the tables of a context lie next to
+// those of other contexts in the recycling pool.  The entry is wave-uniform (blockIdx.z) and read through the constant
+// address space: its fields stay scalar loads.
+#define SOS_TABLE_CTX(cx, tab) const SosDevK &cx = *(const SosDevK *)(unsigned long long)((tab) + blockIdx.z)
+
+__global__ void k_gsf_table(const SosDev *tab)
+{
+    SOS_TABLE_CTX(cx, tab);
+    if ((int)blockIdx.x > cx.smax) return;
+    gsf_body(cx, blockIdx.x, threadIdx.x);
+}
+
+__global__ void k_pack_table(const SosDev *tab)
+{
+    SOS_TABLE_CTX(cx, tab);
+    if ((int)blockIdx.y > cx.smax) return;
+    pack_body(cx, blockIdx.y, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ void k_pack_ray_table(const SosDev *tab)
+{
+    SOS_TABLE_CTX(cx, tab);
+    if ((int)blockIdx.x > (cx.smax < 2 ? cx.smax : 2)) return;
+    pack_ray_body(cx, blockIdx.x);
+}
+
+__global__ void k_sv_table(const SosDev *tab)
+{
+    SOS_TABLE_CTX(cx, tab);
+    if ((int)blockIdx.x > cx.smax) return;
+    sv_body(cx, blockIdx.x, threadIdx.x);
+}
+
 // Parity accessor: the six (W x W) kernels of one order laid out as the reference does.
 __global__ void k_noyaux_fetch(SosDev cx, int s, double *out)
 {
@@ -309,6 +371,16 @@ void launch_noyaux(const SosDev &cx, hipStream_t st)
     k_pack<<<g, 256, 0, st>>>(cx);
     k_pack_ray<<<(cx.smax < 2 ? cx.smax + 1 : 3), 256, 0, st>>>(cx);
     k_sv<<<S, sos_round_up(cx.kp, 64), 0, st>>>(cx);
+}
+
+// The four launches of launch_noyaux for the nctx contexts of a device table; g holds the maxima over them.
+void launch_noyaux_table(const SosDev *d_tab, int nctx, const NoyauxTableGrid &g, hipStream_t st)
+{
+    const unsigned S = (unsigned)g.smax + 1, Z = (unsigned)nctx;
+    k_gsf_table<<<dim3(S, 1, Z), 128, 0, st>>>(d_tab);
+    k_pack_table<<<dim3((unsigned)((2 * g.per + 255) / 256), S, Z), 256, 0, st>>>(d_tab);
+    k_pack_ray_table<<<dim3(g.smax < 2 ? g.smax + 1 : 3, 1, Z), 256, 0, st>>>(d_tab);
+    k_sv_table<<<dim3(S, 1, Z), sos_round_up(g.kp, 64), 0, st>>>(d_tab);
 }
 
 void launch_noyaux_fetch(const SosDev &cx, int s, double *d_out, hipStream_t st)

@@ -924,7 +924,7 @@ def _profiles_deferrable(tr, hr, ta, ha):
 
 
 def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False,
-             device_gas_tables=False):
+             device_gas_tables=False, defer_operators=False):
     """Everything of one SOS_PROC call up to the CKD bin loop (SOS_PROC.F:1310-3458): parameter checks, SOS_ANGLES,
     SOS_AEROSOLS, SOS_SURFACE, SOS_PREPA_ABSPROFILE, SOS_PREPA_OS, and the profiles of every bin of the band on the device
     (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Returns a _Plan whose `ctx` the caller closes.
@@ -937,7 +937,10 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     no gas, band not sharded -- gets no profile launches here: the plan comes back with `bins` None and `profile_request`, the
     request solver.make_profiles_spectrum takes, and the pass makes the profiles of a whole part in three launches.
     device_gas_tables (with defer_profiles): a deferred gas wavelength hands over its `prep` instead of the layer tables xk --
-    COEFF_ABS_CKD then runs on the device for the whole part (sosgpu_ckd_layer_tables) and absorption.layer_tables not at all."""
+    COEFF_ABS_CKD then runs on the device for the whole part (sosgpu_ckd_layer_tables) and absorption.layer_tables not at all.
+    defer_operators (_spectrum_pass only): the context comes back unbuilt (SosContext(build=False)) and the pass fills the
+    operator tables of a whole part in one solver.build_operators call -- unless this function uses the operators itself, which
+    only a -SOS.Trans call does (diffuse_transmissions below)."""
     _seg(None)
     missing = [k for k in SOS_PROC_KWARGS if k not in kw]
     if missing:
@@ -1128,9 +1131,11 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
         rsurf = rsurf[:iborm + 1].contiguous()
 
     _seg('surface')
+    want_trans = str(p["fictrans"]).strip() != "NO_OUTPUT"
     ctx = SosContext(mu, ga, n0, alpha, beta, gamma, zeta, iborm_max=iborm, ro=p["rho"], imat_surf=imat,
                      ifresnel=ifresnel, ind_surf=p["surf_ind"] if isurf in (1, 2) or isurf >= 4 else 1.34, ron=MDF_DEFAULT,
-                     ipolar=int(p["ipolar"]), igmax=igmax, rsurf=rsurf, device=device)
+                     ipolar=int(p["ipolar"]), igmax=igmax, rsurf=rsurf, device=device,
+                     build=not (defer_operators and not want_trans))
     _seg('context')
     pl = _Plan()
     pl.p, pl.ctx, pl.device = p, ctx, device
@@ -1140,7 +1145,7 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     pl.tr, pl.ta, pl.ha, pl.use_gas, pl.prep = tr, ta, ha, use_gas, prep
     pl.itrphi, pl.igli, pl.land = itrphi, igli, land
     pl.tdifmug = None
-    pl.want_trans = str(p["fictrans"]).strip() != "NO_OUTPUT"
+    pl.want_trans = want_trans
     try:
         # --- the CKD bin loop (SOS_PROC.F:3459-3594): profiles of every bin on the device
         band_sharded = False                          # True: every rank holds a slice of the band and the partials are all-reduced
@@ -1563,6 +1568,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     # resident coefficient files; SOS_SPECTRUM_HOST_GAS_TABLES=1: on the host, uploaded with the requests (A/B timing).  A band
     # dealt over several ranks keeps the host tables: bin_costs needs them
     device_tables = batch_profiles and not os.environ.get("SOS_SPECTRUM_HOST_GAS_TABLES")
+    # the operator tables of a part's contexts (surface packing + SOS_NOYAUX kernels) are filled by one call on the main stream,
+    # at most five launches for the part; SOS_SPECTRUM_OPERATORS_PER_CALL=1: four or five launches per wavelength on its side
+    # stream, as sos_proc makes them (A/B timing)
+    batch_operators = not os.environ.get("SOS_SPECTRUM_OPERATORS_PER_CALL")
     where, err = -1, None                               # the wavelength being worked on (named by a failure)
     # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
     # a growing list of result tuples, and the collections this triggers re-walk the results again and again (SOS_SPECTRUM_KEEP_GC=1
@@ -1597,7 +1606,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                         where = i
                         with torch.cuda.stream(side[k % len(side)]):
                             pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
-                                          aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles, device_gas_tables=device_tables)
+                                          aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles, device_gas_tables=device_tables,
+                                          defer_operators=batch_operators)
                             pl.writes_files = True
                             pl.index = i
                             plans.append(pl)
@@ -1631,6 +1641,12 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                                                  tauout=lv["tauout"][:, b0:b1])
                     for st in side:
                         main_st.wait_stream(st)
+                    # the operators of the part's unbuilt contexts, grouped and single alike (after the wait: the surface
+                    # matrices come from the side streams)
+                    unbuilt = [pl for pl in part if not pl.ctx._built]
+                    if unbuilt:
+                        where = unbuilt[0].index
+                        solver.build_operators([pl.ctx for pl in unbuilt])
                     t1 = time.perf_counter()
                     tm["prepare"] += t1 - t0
                     # --- groups of wavelengths one launch can cover
@@ -1783,7 +1799,10 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     there.  The profile kernels (level placement of the no-gas profile and of every bin: bisections, a serial chain of about
     3 ms on one wavefront per bin) are not among them any more: they run once per part for all its bins, on the stream of the
     solves.  SOS_SPECTRUM_PROFILES_PER_CALL=1 (environment, for A/B timing) sends every call through the per-wavelength
-    profile launches on its side stream again."""
+    profile launches on its side stream again.  The source operators are not among them either: the contexts are created unbuilt
+    and solver.build_operators fills the operator tables of a part in at most five launches on the stream of the solves
+    (sosgpu_noyaux_spectrum), after the side streams -- which produce the surface matrices -- have been waited for; a -SOS.Trans
+    call builds its own, and SOS_SPECTRUM_OPERATORS_PER_CALL=1 gives every call its four or five launches on its side stream."""
     return _spectrum_pass("sos_spectrum", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts)
 
 

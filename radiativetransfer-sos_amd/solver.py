@@ -133,10 +133,12 @@ def host_output_levels(bins, altitudes):
 class SosContext:
     """Everything SOS_OS needs that does not depend on the CKD bin (angles, phase-matrix expansion,
     surface), resident on one GPU, with the Fourier kernels of every order precomputed
-    (sosgpu_noyaux, replaces SOS_NOYAUX SOS_OS.F:1857)."""
+    (sosgpu_noyaux, replaces SOS_NOYAUX SOS_OS.F:1857).
+    build=False: the constructor stops after sosgpu_create -- the surface matrices are kept, nothing is queued -- and
+    build_operators() fills the operator tables of many such contexts in one call; solving before that is an error."""
 
     def __init__(self, mu, ga, n0, alpha, beta, gamma, zeta, *, iborm_max=None, ro=0.0, imat_surf=0,
-                 ifresnel=0, ind_surf=1.34, ron=MDF_DEFAULT, ipolar=1, igmax=100, rsurf=None, device=0):
+                 ifresnel=0, ind_surf=1.34, ron=MDF_DEFAULT, ipolar=1, igmax=100, rsurf=None, device=0, build=True):
         if not torch.cuda.is_available():
             raise RuntimeError("SosContext needs a GPU (gfx950); there is no CPU fallback in the product path")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -165,6 +167,8 @@ class SosContext:
                    "sosgpu_create")
         SEG and SEG("context: sosgpu_create")
         self._rsurf = None
+        self._built = False
+        self._operator_work = None        # build_operators: the device work area of the call, kept by its first context
         if int(imat_surf) == 1:
             if rsurf is None:
                 raise ValueError("imat_surf=1 needs rsurf[smax+1][9][N][N] (float32)")
@@ -174,18 +178,25 @@ class SosContext:
                 r = torch.from_numpy(np.ascontiguousarray(rsurf, dtype=np.float32)).to(self.device)
             if tuple(r.shape) != (self.smax + 1, 9, self.n, self.n):
                 raise ValueError("rsurf shape %s != %s" % (tuple(r.shape), (self.smax + 1, 9, self.n, self.n)))
-            self._rsurf = r               # kept alive: the packing below is only queued
-            capi.check(L.sosgpu_set_surface_matrices_async(self._h, _ptr(r), self._stream()),
-                       "sosgpu_set_surface_matrices_async")
-            SEG and SEG("context: surface matrices")
-        self.noyaux()
-        SEG and SEG("context: sosgpu_noyaux")
+            self._rsurf = r               # kept alive: the packing (below, or build_operators') is only queued
+            if build:
+                capi.check(L.sosgpu_set_surface_matrices_async(self._h, _ptr(r), self._stream()),
+                           "sosgpu_set_surface_matrices_async")
+                SEG and SEG("context: surface matrices")
+        if build:
+            self.noyaux()
+            SEG and SEG("context: sosgpu_noyaux")
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def noyaux(self):
         capi.check(capi.lib().sosgpu_noyaux(self._h, self._stream()), "sosgpu_noyaux")
+        self._built = True
+
+    def _need_operators(self):
+        if not self._built:
+            raise RuntimeError("this context was created with build=False: call solver.build_operators first")
 
     def noyaux_fetch(self, is_):
         """Kernels of Fourier order is_ in the reference layout (parity accessor)."""
@@ -360,6 +371,7 @@ class SosContext:
     def solve_levels(self, bins, levels, out=None):
         """One solve for the K output levels of output_levels (sosgpu_os_solve_levels).  Returns dict(rec[K][nb][smax+1][3][W],
         norders, iglast, flux): rec[k] equals the rec of solve() with that altitude's jout / zz, bit for bit."""
+        self._need_operators()
         nz, nb = levels["nz"], bins["nb"]
         if out is None:
             out = self.alloc_outputs(nb)
@@ -426,6 +438,7 @@ class SosContext:
 
     def solve(self, bins, out=None):
         """Run the fused SOS_OS kernel on a batch of bins already resident in HBM (upload_bins)."""
+        self._need_operators()
         if out is None:
             out = self.alloc_outputs(bins["nb"])
         capi.check(capi.lib().sosgpu_os_solve(self._h, bins["nb"], bins["lp"], _ptr(bins["nt"]), _ptr(bins["iborm"]),
@@ -519,12 +532,37 @@ class SosContext:
             capi.lib().sosgpu_destroy(self._h)            # waits for the streams this context's work was queued on
             self._h = C.c_void_p()
             self._rsurf = None
+            self._operator_work = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+def build_operators(ctxs):
+    """The operator tables of the contexts created with build=False, in ONE sosgpu_noyaux_spectrum call on the current stream:
+    at most five launches for all of them (the table forms of the kernels of sosgpu_set_surface_matrices_async and
+    sosgpu_noyaux; the same bits).  The contexts live on one device and may differ in every size; their surface matrices must
+    be complete on, or ordered before, the current stream.  Contexts that are built already are left alone.  Nothing is
+    waited for: the work area of the call is one tensor the first context keeps until it is closed."""
+    todo = [cx for cx in ctxs if not cx._built]
+    if not todo:
+        return 0
+    L = capi.lib()
+    n = len(todo)
+    first = todo[0]
+    work = torch.empty(n * (int(L.sosgpu_ctx_table_entry_bytes()) + 8), dtype=torch.uint8, device=first.device)
+    hs = (C.c_void_p * n)(*[cx._h for cx in todo])
+    rs = None
+    if any(cx._rsurf is not None for cx in todo):
+        rs = (C.c_void_p * n)(*[None if cx._rsurf is None else cx._rsurf.data_ptr() for cx in todo])
+    capi.check(L.sosgpu_noyaux_spectrum(hs, n, rs, _ptr(work), first._stream()), "sosgpu_noyaux_spectrum")
+    first._operator_work = work
+    for cx in todo:
+        cx._built = True
+    return n
 
 
 def release_scratch():
@@ -543,6 +581,8 @@ class ContextTable:
         if not self.ctxs:
             raise ValueError("ContextTable needs at least one context")
         self.device = self.ctxs[0].device
+        for cx in self.ctxs:
+            cx._need_operators()              # (the table copies the ground-operator pointers the build registers)
         L = capi.lib()
         n = len(self.ctxs)
         self.table = torch.empty(n * int(L.sosgpu_ctx_table_entry_bytes()), dtype=torch.uint8, device=self.device)

@@ -37,6 +37,7 @@
  *   sosgpu_glitter     <- SOS_GLITTER (+SOS_GSF, SOS_MAT_FRESNEL, SOS_MAT_REFLEXION, SOS_MISE_FORMAT)
  *                                                 src/SOS_GLITTER.F:229, src/SOS_SURFACE.F:1235,1708,2307
  *   sosgpu_trphi       <- SOS_TRPHI               src/SOS_TRPHI.F:749
+ *   sosgpu_trphi_spectrum     the same for the wavelengths and output altitudes of a part of a spectrum: one launch
  *
  * Index conventions (identical to oracle/sos_oracle.h): N = NBMU positive directions, mu[0..N-1] =
  * RMU(1..N) descending; direction jj in -N..N lives at offset jj+N of width W = 2N+1 (slot jj=0 is
@@ -284,6 +285,33 @@ typedef struct sosgpu_land {
 } sosgpu_land;
 int  sosgpu_trphi(sosgpu_ctx *cx, int nf, const double *d_rec, double tau, double tauout, int nphi,
                   const double *d_phi, int igli, double wind, const sosgpu_land *land, double *d_out, void *stream);
+
+/* sosgpu_trphi for many (context, record, azimuth list) jobs -- the wavelengths and output altitudes of a part of a spectrum -- in
+ * ONE launch: one workgroup per (job, azimuth) pair, each finding its job in a device array of job entries.  Block j of d_out holds,
+ * bit for bit, what sosgpu_trphi writes for job j's arguments.
+ *  jobs[njobs]     HOST array; jobs may share a context, a record pointer and an azimuth range
+ *  d_phi[nphi_total]  DEVICE azimuths (radians) of the whole call; job j reads d_phi[phi_off .. phi_off + nphi)
+ *  d_out           DEVICE, the blocks [nphi_j][7][W_j] of the jobs back to back, in job order
+ *  d_work          DEVICE area of sosgpu_trphi_spectrum_work_bytes(njobs) bytes, 8-byte aligned, the caller's until `stream` has
+ *                  passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block jobs[0].cx keeps until
+ *                  it is destroyed (as sosgpu_noyaux_spectrum's).
+ * Asynchronous: one launch, nothing is waited for and no device memory is allocated; `stream` is noted for sosgpu_destroy on
+ * every context of the call.  Records, azimuths and contexts must stay alive until `stream` has passed the call.
+ * Checked before anything is queued, SOSGPU_E_ARG for: NULL jobs, d_phi, d_out or d_work, njobs < 0 or njobs > 65535, a NULL cx
+ * or d_rec, nf < 1 or nf > iborm_max + 1 of the job's context, nphi < 1, phi_off < 0 or phi_off + nphi > nphi_total, contexts
+ * on different devices, a land->isurf outside 3..7, a misaligned d_work; SOSGPU_E_UNSUPPORTED for isurf = 6, as sosgpu_trphi.
+ * njobs = 0 returns SOSGPU_OK with nothing queued. */
+typedef struct sosgpu_trphi_job {
+    sosgpu_ctx *cx;            /* context of the wavelength (HOST handle) */
+    const double *d_rec;       /* [>= nf][3][W] aggregated records (DEVICE) */
+    int32_t nf, igli;
+    int32_t phi_off, nphi;     /* this job's azimuths: d_phi[phi_off .. phi_off + nphi) */
+    double tau, tauout, wind;
+    const sosgpu_land *land;   /* HOST pointer or NULL, as sosgpu_trphi takes it */
+} sosgpu_trphi_job;
+size_t sosgpu_trphi_spectrum_work_bytes(int njobs);
+int  sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, const double *d_phi, int nphi_total,
+                           double *d_out, void *d_work, void *stream);
 
 /* Replaces SOS_ROUJEAN (src/SOS_ROUJEAN.F:212), SOS_SURFACE_BPDF (src/SOS_SURFACE_BPDF.F:219) and SOS_BPDF_AJOUT_BRDF
  * (src/SOS_SURFACE.F:2503) for -SURF.Type 3..7, no temporary files: Fourier reflection matrices of the land surface,

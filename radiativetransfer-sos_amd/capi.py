@@ -23,7 +23,7 @@ EXPORTS = [
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
     "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes", "sosgpu_debug_solve_plan",
-    "sosgpu_noyaux_spectrum",
+    "sosgpu_noyaux_spectrum", "sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -93,6 +93,13 @@ class Land(C.Structure):
     """struct sosgpu_land"""
     _fields_ = [("isurf", C.c_int32), ("reserved", C.c_int32), ("k0", C.c_double), ("k1", C.c_double), ("k2", C.c_double),
                 ("alpha", C.c_double), ("beta", C.c_double), ("coef_c", C.c_double)]
+
+
+class TrphiJob(C.Structure):
+    """sosgpu_trphi_job (include/sosgpu.h): one recomposition of sosgpu_trphi_spectrum."""
+    _fields_ = [("cx", C.c_void_p), ("d_rec", C.c_void_p), ("nf", C.c_int32), ("igli", C.c_int32),
+                ("phi_off", C.c_int32), ("nphi", C.c_int32), ("tau", C.c_double), ("tauout", C.c_double), ("wind", C.c_double),
+                ("land", C.POINTER(Land))]
 
 
 _lib = None
@@ -203,6 +210,10 @@ def lib():
         L.sosgpu_mat_fresnel_host.argtypes = [i32, vp, vp, dbl, i32, vp]
         L.sosgpu_trphi.restype = i32
         L.sosgpu_trphi.argtypes = [vp, i32, vp, dbl, dbl, i32, vp, i32, dbl, C.POINTER(Land), vp, vp]
+        L.sosgpu_trphi_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_trphi_spectrum_work_bytes.argtypes = [i32]
+        L.sosgpu_trphi_spectrum.restype = i32
+        L.sosgpu_trphi_spectrum.argtypes = [C.POINTER(TrphiJob), i32, vp, i32, vp, vp, vp]
         L.sosgpu_land_surface.restype = i32
         L.sosgpu_land_surface.argtypes = [i32, C.POINTER(Land), i32, vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_int32), vp]
         L.sosgpu_debug_phase_buffer.restype = i32

@@ -1174,6 +1174,64 @@ extern "C" int sosgpu_trphi(sosgpu_ctx *cx, int nf, const double *d_rec, double 
     launch_trphi(cx->d, nf, d_rec, tau, tauout, nphi, d_phi, igli, sigma2_of_wind(wind), cx->ind_surf, land_terms(land), d_out,
                  (hipStream_t)stream);
     HIPCHK(hipGetLastError());
+    note_stream(cx, (hipStream_t)stream);       // the kernel reads the context's mu: sosgpu_destroy waits for this stream
+    return SOSGPU_OK;
+}
+
+extern "C" size_t sosgpu_trphi_spectrum_work_bytes(int njobs)
+{
+    return njobs > 0 ? (size_t)njobs * sizeof(TrphiJobDev) : 0;
+}
+
+// sosgpu_trphi of njobs (context, record, azimuth range) jobs in ONE launch (k_trphi_table).  d_work = the job entries, filled
+// by one copy from a pinned block jobs[0].cx keeps until it is destroyed (as sosgpu_noyaux_spectrum's).  Everything is checked
+// before anything is queued.
+extern "C" int sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, const double *d_phi, int nphi_total,
+                                     double *d_out, void *d_work, void *stream)
+{
+    if (!jobs || !d_phi || !d_out || !d_work || njobs < 0 || njobs > 65535) return SOSGPU_E_ARG;
+    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    if (njobs == 0) return SOSGPU_OK;
+    static_assert(sizeof(TrphiJobDev) % 8 == 0, "entries of pointers and doubles");
+    long long nblocks = 0;
+    int w_max = 0;
+    bool nadal = false;
+    for (int i = 0; i < njobs; i++) {
+        const sosgpu_trphi_job &j = jobs[i];
+        if (!j.cx || !j.d_rec || j.cx->device != jobs[0].cx->device) return SOSGPU_E_ARG;
+        if (j.nf < 1 || j.nf > j.cx->d.smax + 1) return SOSGPU_E_ARG;
+        if (j.nphi < 1 || j.phi_off < 0 || (long long)j.phi_off + j.nphi > (long long)nphi_total) return SOSGPU_E_ARG;
+        if (j.land && (j.land->isurf < 3 || j.land->isurf > 7)) return SOSGPU_E_ARG;
+        nadal = nadal || (j.land && j.land->isurf == 6);
+        nblocks += j.nphi;
+        w_max = std::max(w_max, j.cx->d.w);
+    }
+    if (nblocks > 0x7fffffffLL) return SOSGPU_E_ARG;                 // (one grid dimension, first_block an int32)
+    if (nadal) return SOSGPU_E_UNSUPPORTED;                          // Nadal: refused by the reference's SOS_PROC as well
+    HIPCHK(hipSetDevice(jobs[0].cx->device));
+    const size_t bytes = (size_t)njobs * sizeof(TrphiJobDev);
+    TrphiJobDev *tab = nullptr;
+    HIPCHK(hipHostMalloc((void **)&tab, bytes, hipHostMallocDefault));
+    jobs[0].cx->host_staging.push_back(tab);
+    int first = 0;
+    double *out = d_out;
+    for (int i = 0; i < njobs; i++) {
+        const sosgpu_trphi_job &j = jobs[i];
+        const SosDev &d = j.cx->d;
+        TrphiJobDev &e = tab[i];
+        e.n = d.n; e.w = d.w; e.n0 = d.n0; e.ipolar = d.ipolar; e.ifresnel = d.ifresnel;
+        e.nf = j.nf; e.igli = j.igli; e.first_block = first;
+        e.mu = d.mu; e.rec = j.d_rec; e.phis = d_phi + j.phi_off; e.out = out;
+        e.ind_surf = j.cx->ind_surf; e.sigma2 = sigma2_of_wind(j.wind); e.tau = j.tau; e.tauout = j.tauout;
+        e.land = land_terms(j.land);
+        first += j.nphi;
+        out += (size_t)j.nphi * 7 * d.w;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(d_work, tab, bytes, hipMemcpyHostToDevice, st));
+    launch_trphi_table(static_cast<const TrphiJobDev *>(d_work), njobs, (int)nblocks, w_max, st);
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < njobs; i++) note_stream(jobs[i].cx, st);
     return SOSGPU_OK;
 }
 

@@ -59,6 +59,18 @@ struct LandTerms {            // direct surface terms of the land models in SOS_
 void launch_trphi(const SosDev &cx, int nf, const double *d_rec, double tau, double tauout, int nphi,
                   const double *d_phi, int igli, double sigma2, double ind_surf, const LandTerms &land, double *d_out,
                   hipStream_t st);
+// Table form (sosgpu_trphi_spectrum): launch_trphi's arguments per job, in a device array.  One launch of nblocks = sum of the
+// jobs' azimuth counts; first_block is their running sum (ascending, 0 for the first job), w_max the largest W of the jobs.
+struct TrphiJobDev {
+    int n, w, n0, ipolar, ifresnel;      // of the job's context, with mu
+    int nf, igli;
+    int first_block;
+    const double *mu, *rec, *phis;       // phis: the job's own azimuths
+    double *out;                         // [nphi][7][W] of the job
+    double ind_surf, sigma2, tau, tauout;
+    LandTerms land;
+};
+void launch_trphi_table(const TrphiJobDev *d_jobs, int njobs, int nblocks, int w_max, hipStream_t st);
 
 #define SOS_PROF_NBLEV_MAX 64     // levels of the absorption profile held in LDS (CTE_ABS_NBLEV = 50 in the reference)
 // Per-bin profile discretisation (profile.hip).  *_ng: the no-gas profile of the wavelength (host-computed, device copy).

@@ -4,7 +4,7 @@
 // SOS_REFLEX (:1433), SOS_MATRIC (:1505) and SOS_POLAR (:1843), for a whole list of azimuths in one
 // launch (the reference re-opens and re-reads the result file once per azimuth, SOS_TRPHI.F:558-613).
 // One workgroup per azimuth, one thread per direction jj in -N..N; the Fourier sum runs in the
-// reference's order (s ascending).  HBM-streaming bound but tiny: F*3*(2N+1)*8 bytes per azimuth, L2 hits.
+// reference's order (s ascending).  k_trphi_table: the same for the jobs of a device table (a part of a spectrum) in one launch.  HBM-streaming bound but tiny: F*3*(2N+1)*8 bytes per azimuth, L2 hits.
 // The direct surface term covers the Cox-Munk glint (:946-1001), the flat-sea sun glint (:1008-1039) and the land models:
 // Roujean (:1047-1076) and Rondeaux / Breon / Maignan (:1084-1136); Nadal (:1145-1200) is refused upstream by SOS_PROC.
 #include "sos_common.h"
@@ -32,12 +32,18 @@ __device__ inline void reflex(double cosdif, double ind, double &r11, double &r1
     r33 = rr * rl;
 }
 
+// Azimuth iphi of one recomposition, thread t = direction; the body shared by k_trphi and the table form k_trphi_table.
+// cx: the fields of the wavelength context the recomposition reads (both kernels hand them over as wave-uniform values).
 // out[iphi][q][W], q = 0 XIT, 1 XQT, 2 XUT, 3 ANGDIFF, 4 XAN (polarisation angle), 5 TPOL, 6 LPOL
-__global__ void k_trphi(SosDev cx, int nf, const double *__restrict__ rec, double tau, double tauout,
-                        const double *__restrict__ phis, int igli, double sigma2, double ind_surf, LandTerms land,
-                        double *__restrict__ out)
+struct TrphiCtx {
+    int n, w, n0, ipolar, ifresnel;
+    const double *mu;
+};
+
+__device__ __forceinline__ void trphi_body(const TrphiCtx &cx, const int iphi, int nf, const double *__restrict__ rec, double tau,
+                                           double tauout, const double *__restrict__ phis, int igli, double sigma2,
+                                           double ind_surf, const LandTerms &land, double *__restrict__ out)
 {
-    const int iphi = blockIdx.x;
     const int N = cx.n, W = cx.w;
     const int t = threadIdx.x;
     if (t >= W) return;
@@ -149,6 +155,43 @@ __global__ void k_trphi(SosDev cx, int nf, const double *__restrict__ rec, doubl
     tpol = (xit != 0.0) ? 100. * lpol / xit : VALEUR_INDEF;
     o[0 * W + t] = xit; o[1 * W + t] = xqt; o[2 * W + t] = xut; o[3 * W + t] = angdiff;
     o[4 * W + t] = xan; o[5 * W + t] = tpol; o[6 * W + t] = lpol;
+}
+
+__global__ void k_trphi(SosDev cx, int nf, const double *__restrict__ rec, double tau, double tauout,
+                        const double *__restrict__ phis, int igli, double sigma2, double ind_surf, LandTerms land,
+                        double *__restrict__ out)
+{
+    const TrphiCtx c = {cx.n, cx.w, cx.n0, cx.ipolar, cx.ifresnel, cx.mu};
+    trphi_body(c, blockIdx.x, nf, rec, tau, tauout, phis, igli, sigma2, ind_surf, land, out);
+}
+
+// Table form (sosgpu_trphi_spectrum): one workgroup per (job, azimuth) pair, flat in blockIdx.x.  Job j owns the workgroups
+// first_block[j] .. first_block[j] + nphi_j - 1 (ascending, jobs[0].first_block = 0); the workgroup finds its job by bisection
+// of that prefix -- on blockIdx.x and scalar loads only, so the search and every field of the entry stay on the scalar side --
+// and runs the body with the entry's values where k_trphi has its kernel arguments.  The block takes the widest job of the
+// call; threads past the job's own W leave in the body.
+__global__ void k_trphi_table(const TrphiJobDev *jobs, int njobs)
+{
+    typedef const __attribute__((address_space(4))) TrphiJobDev JobK;
+    JobK *tab = (JobK *)(unsigned long long)jobs;
+    const int b = blockIdx.x;
+    int lo = 0, hi = njobs - 1;                    // the last job with first_block <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].first_block <= b) lo = mid; else hi = mid - 1;
+    }
+    JobK &jb = tab[__builtin_amdgcn_readfirstlane(lo)];
+    const TrphiCtx c = {jb.n, jb.w, jb.n0, jb.ipolar, jb.ifresnel, jb.mu};
+    LandTerms land;
+    land.iroujean = jb.land.iroujean; land.irondeaux = jb.land.irondeaux; land.ibreon = jb.land.ibreon;
+    land.imaignan = jb.land.imaignan;
+    land.k0 = jb.land.k0; land.k1 = jb.land.k1; land.k2 = jb.land.k2; land.coef_c = jb.land.coef_c;
+    trphi_body(c, b - jb.first_block, jb.nf, jb.rec, jb.tau, jb.tauout, jb.phis, jb.igli, jb.sigma2, jb.ind_surf, land, jb.out);
+}
+
+void launch_trphi_table(const TrphiJobDev *d_jobs, int njobs, int nblocks, int w_max, hipStream_t st)
+{
+    k_trphi_table<<<nblocks, sos_round_up(w_max, 64), 0, st>>>(d_jobs, njobs);
 }
 
 void launch_trphi(const SosDev &cx, int nf, const double *d_rec, double tau, double tauout, int nphi,

@@ -1235,6 +1235,24 @@ def _trphi_launch(pl, rec0, nf, tau, tauout):
     return pl.ctx.trphi(rec0, nf, tau, tauout, phis, igli=pl.igli, wind=pl.p["wind"] if pl.igli else 0.0, land=pl.land)
 
 
+def _trphi_launch_many(jobs):
+    """_trphi_launch for the jobs [(pl, rec0, nf, tau, tauout)] of a chunk or of the altitudes of a band: ONE launch
+    (solver.trphi_many, sosgpu_trphi_spectrum) for all of them.  Returns the flat device tensor of the results and the shapes
+    [nphi][7][W] of its blocks, in job order (no synchronisation).  SOS_SPECTRUM_TRPHI_PER_CALL=1 (environment, for A/B timing):
+    one sosgpu_trphi launch per job, concatenated."""
+    import torch
+    from . import solver
+    if os.environ.get("SOS_SPECTRUM_TRPHI_PER_CALL"):
+        outs = [_trphi_launch(pl, rec0, nf, tau, tauout) for pl, rec0, nf, tau, tauout in jobs]
+        return torch.cat([o.reshape(-1) for o in outs]), [tuple(o.shape) for o in outs]
+    items = []
+    for pl, rec0, nf, tau, tauout in jobs:
+        phis, pl.rows, pl.phi_fin = _trphi_azimuths(pl.itrphi, pl.p["phios"], pl.p["pas_phi"])
+        items.append((pl.ctx, rec0, nf, tau, tauout, phis, pl.igli, pl.p["wind"] if pl.igli else 0.0, pl.land))
+    flat, views = solver.trphi_many(items)
+    return flat, [tuple(v.shape) for v in views]
+
+
 def _finish(pl, out, rec0, fin, g=0, block=None):
     """The tail of SOS_PROC (SOS_PROC.F:3755-3874) on the host: the (361,81) tables from sosgpu_trphi's output `out` (host
     array), fluxes, result files (rank 0 only), the 23-tuple.  rec0: aggregated records [S][3][W] of this wavelength
@@ -1329,9 +1347,17 @@ def _band_call(fn, kw, aer_phase, device, alts=None):
                 rec, fin = pl.ctx.solve_band_levels(pl.bins, levels, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
         except SosBinError as e:
             raise SosProcError(str(e), ier=-1)
-        outs = [_trphi_launch(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]), float(fin["tauout"][k]))
-                for k in range(len(rec))]
-        return [_finish(pl, outs[k].cpu().numpy(), rec[k], fin, k) for k in range(len(rec))]
+        if alts is None:                           # sos_proc: the single call
+            outs = [_trphi_launch(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]), float(fin["tauout"][k]))
+                    .cpu().numpy() for k in range(len(rec))]
+        else:                                      # the K altitudes in one launch, one download
+            flat, shapes = _trphi_launch_many([(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]),
+                                                float(fin["tauout"][k])) for k in range(len(rec))])
+            flat, outs, pos = flat.cpu().numpy(), [], 0
+            for shp in shapes:
+                outs.append(flat[pos:pos + int(np.prod(shp))].reshape(shp))
+                pos += outs[-1].size
+        return [_finish(pl, outs[k], rec[k], fin, k) for k in range(len(rec))]
     finally:
         pl.ctx.close()
 
@@ -1711,20 +1737,22 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                             raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
                                                "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
                         todo += [(pl, k, recs[k][g], fins[k], g) for k in range(nz)]
-                outs = [_trphi_launch(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
-                        for pl, _, r, f, g in todo]
-                flat = torch.cat([o.reshape(-1) for o in outs]).cpu().numpy()
+                # one launch for every (wavelength, altitude) of the chunk, its flat result downloaded as it is
+                flat, shapes = _trphi_launch_many([(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
+                                                   for pl, _, r, f, g in todo])
+                flat = flat.cpu().numpy()
                 t4 = time.perf_counter()
                 tm["trphi"] += t4 - t3
                 pos = 0
-                blocks = _zero_pages((len(outs), 2, 7, 361, 81))  # the result tables of the chunk's wavelengths (views of it)
-                for j, ((pl, k, r, f, g), o) in enumerate(zip(todo, outs)):
+                blocks = _zero_pages((len(todo), 2, 7, 361, 81))  # the result tables of the chunk's wavelengths (views of it)
+                for j, ((pl, k, r, f, g), shp) in enumerate(zip(todo, shapes)):
                     where = pl.index
                     if results[pl.index] is None:
                         results[pl.index] = [None] * nz
-                    results[pl.index][k] = _finish(pl, flat[pos:pos + o.numel()].reshape(o.shape), r, f, g, blocks[j])
+                    cnt = shp[0] * shp[1] * shp[2]
+                    results[pl.index][k] = _finish(pl, flat[pos:pos + cnt].reshape(shp), r, f, g, blocks[j])
                     nrows[pl.index] = len(pl.rows)
-                    pos += o.numel()
+                    pos += cnt
                 tm["finish"] += time.perf_counter() - t4
             finally:
                 _aer.drop_prefetched_size_integrals()
@@ -1776,8 +1804,9 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
          (direction count, highest Fourier order, surface-matrix flag, level capacity, output level): a device table of the
          wavelength contexts, every bin carrying the index of its own (sosgpu_ctx_table + sosgpu_os_solve_multi), and one
          segmented SOS_AGGREGATE;
-      3. one device-to-host copy of the band scalars, the azimuth recompositions (sosgpu_trphi) of every wavelength queued
-         back to back, one copy of their results, and the 23-tuples on the host.
+      3. one device-to-host copy of the band scalars, the azimuth recompositions of every wavelength of the chunk in ONE launch
+         (sosgpu_trphi_spectrum through solver.trphi_many; SOS_SPECTRUM_TRPHI_PER_CALL=1 in the environment: one sosgpu_trphi
+         launch per wavelength, for A/B timing), one copy of their results, and the 23-tuples on the host.
 
     Outputs are those of `[sos_proc(**kw) for kw in kwargs_list]`, bit for bit (the table form of the kernels computes the same
     instruction sequence per bin; bands up to 128 bins are aggregated in the reference's serial bin order in both).

@@ -541,6 +541,52 @@ class SosContext:
             pass
 
 
+def trphi_many(items):
+    """SosContext.trphi for many jobs in ONE sosgpu_trphi_spectrum call (one launch) on the current stream.  items: a list of
+    (ctx, rec, nf, tau, tauout, phis_rad, igli, wind, land), each as SosContext.trphi takes them; the contexts live on one device.
+    Returns (flat, views): one flat device tensor holding the results back to back and its per-item views [nphi][7][W] -- the
+    bits SosContext.trphi gives for each item.  Every distinct azimuth list is uploaded once (and kept, _const_dev_f64).
+    Nothing is waited for."""
+    if not items:
+        return None, []
+    L = capi.lib()
+    d = items[0][0].device
+    lists, offs, total = {}, [], 0                  # distinct azimuth lists -> offset in the call's azimuth array
+    for it in items:
+        a = np.atleast_1d(np.asarray(it[5], dtype=np.float64))
+        key = a.tobytes()
+        if key not in lists:
+            lists[key] = (total, a)
+            total += a.size
+        offs.append((lists[key][0], a.size))
+    if len(lists) == 1:
+        phis = _const_dev_f64(next(iter(lists.values()))[1], d)
+    else:
+        phis = torch.cat([_const_dev_f64(a, d) for _, a in lists.values()])
+    n = len(items)
+    jobs = (capi.TrphiJob * n)()
+    recs, shapes, count = [], [], 0
+    for j, ((cx, rec, nf, tau, tauout, _, igli, wind, land), (off, nphi)) in zip(jobs, zip(items, offs)):
+        rec = rec.to(device=d, dtype=torch.float64).contiguous()
+        recs.append(rec)
+        j.cx, j.d_rec, j.nf, j.igli, j.phi_off, j.nphi = cx._h.value, rec.data_ptr(), int(nf), int(igli), off, nphi
+        j.tau, j.tauout, j.wind = float(tau), float(tauout), float(wind)
+        if land is not None:
+            j.land = C.pointer(land)
+        shapes.append((nphi, 7, cx.w))
+        count += nphi * 7 * cx.w
+    flat = torch.empty(count, dtype=torch.float64, device=d)
+    work = torch.empty(int(L.sosgpu_trphi_spectrum_work_bytes(n)), dtype=torch.uint8, device=d)
+    capi.check(L.sosgpu_trphi_spectrum(jobs, n, _ptr(phis), int(phis.numel()), _ptr(flat), _ptr(work), items[0][0]._stream()),
+               "sosgpu_trphi_spectrum")
+    views, pos = [], 0
+    for shp in shapes:
+        m = shp[0] * shp[1] * shp[2]
+        views.append(flat[pos:pos + m].view(shp))
+        pos += m
+    return flat, views
+
+
 def build_operators(ctxs):
     """The operator tables of the contexts created with build=False, in ONE sosgpu_noyaux_spectrum call on the current stream:
     at most five launches for all of them (the table forms of the kernels of sosgpu_set_surface_matrices_async and

@@ -38,6 +38,8 @@
  *                                                 src/SOS_GLITTER.F:229, src/SOS_SURFACE.F:1235,1708,2307
  *   sosgpu_trphi       <- SOS_TRPHI               src/SOS_TRPHI.F:749
  *   sosgpu_trphi_spectrum     the same for the wavelengths and output altitudes of a part of a spectrum: one launch
+ *   sosgpu_level_flux  <- EMOINS / EPLUS of SOS_OS  src/SOS_OS.F:1447-1456, at the output altitude of an aggregated record
+ *   sosgpu_level_flux_spectrum   the same for the wavelengths and output altitudes of a part of a spectrum: one launch
  *
  * Index conventions (identical to oracle/sos_oracle.h): N = NBMU positive directions, mu[0..N-1] =
  * RMU(1..N) descending; direction jj in -N..N lives at offset jj+N of width W = 2N+1 (slot jj=0 is
@@ -312,6 +314,30 @@ typedef struct sosgpu_trphi_job {
 size_t sosgpu_trphi_spectrum_work_bytes(int njobs);
 int  sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, const double *d_phi, int nphi_total,
                            double *d_out, void *d_work, void *stream);
+
+/* Diffuse fluxes of an aggregated record at its output altitude: d_out[0] = E-(z), d_out[1] = E+(z), the Gauss quadrature the
+ * reference applies to the order-0 intensity at the ground and at the top of the atmosphere (EMOINS / EPLUS, SOS_OS.F:1447-1456):
+ *   e = sum_{j=1..N} mu_j ga_j I(-+j)   (- : E-, + : E+; j ascending, products formed as (mu ga) I),   E = -e * 2 / TAB,
+ * TAB = -mu[n0-1].  d_rec: DEVICE, the aggregated records of one output slot (sosgpu_aggregate); only its order-0 intensity row
+ * d_rec[0][0][W] is read.  For the standard output (altitude -1) E- is the ground value and E+ the top-of-atmosphere value.
+ * Asynchronous on `stream` (one launch), noted for sosgpu_destroy.  SOSGPU_E_ARG for a NULL cx, d_rec or d_out. */
+int  sosgpu_level_flux(sosgpu_ctx *cx, const double *d_rec, double *d_out /*[2]*/, void *stream);
+
+/* sosgpu_level_flux for many (context, record) jobs -- the wavelengths and output altitudes of a part of a spectrum -- in ONE
+ * launch: one thread per (job, hemisphere).  d_out[j][0..1] holds, bit for bit, what sosgpu_level_flux writes for job j.
+ *  jobs[njobs]     HOST array; jobs may share a context and a record pointer
+ *  d_out[njobs][2] DEVICE
+ *  d_work          DEVICE area of sosgpu_level_flux_spectrum_work_bytes(njobs) bytes, 8-byte aligned, the caller's until `stream`
+ *                  has passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block jobs[0].cx keeps
+ *                  until it is destroyed (as sosgpu_trphi_spectrum's).
+ * Asynchronous: one launch, nothing is waited for and no device memory is allocated; `stream` is noted for sosgpu_destroy on
+ * every context of the call (the kernel reads their mu and ga).  Records and contexts must stay alive until `stream` has passed
+ * the call.  Checked before anything is queued, SOSGPU_E_ARG for: NULL jobs, d_out or d_work, njobs < 0 (or > 2^30 - 1), a NULL
+ * cx or d_rec, contexts on different devices, a misaligned d_work.  njobs = 0 returns SOSGPU_OK with nothing queued. */
+typedef struct sosgpu_flux_job { sosgpu_ctx *cx; const double *d_rec; } sosgpu_flux_job;
+size_t sosgpu_level_flux_spectrum_work_bytes(int njobs);
+int  sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out /*[njobs][2]*/,
+                                void *d_work, void *stream);
 
 /* Replaces SOS_ROUJEAN (src/SOS_ROUJEAN.F:212), SOS_SURFACE_BPDF (src/SOS_SURFACE_BPDF.F:219) and SOS_BPDF_AJOUT_BRDF
  * (src/SOS_SURFACE.F:2503) for -SURF.Type 3..7, no temporary files: Fourier reflection matrices of the land surface,

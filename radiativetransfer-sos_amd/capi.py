@@ -24,6 +24,7 @@ EXPORTS = [
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
     "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes", "sosgpu_debug_solve_plan",
     "sosgpu_noyaux_spectrum", "sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes",
+    "sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -100,6 +101,11 @@ class TrphiJob(C.Structure):
     _fields_ = [("cx", C.c_void_p), ("d_rec", C.c_void_p), ("nf", C.c_int32), ("igli", C.c_int32),
                 ("phi_off", C.c_int32), ("nphi", C.c_int32), ("tau", C.c_double), ("tauout", C.c_double), ("wind", C.c_double),
                 ("land", C.POINTER(Land))]
+
+
+class FluxJob(C.Structure):
+    """sosgpu_flux_job (include/sosgpu.h): one (context, record) pair of sosgpu_level_flux_spectrum."""
+    _fields_ = [("cx", C.c_void_p), ("d_rec", C.c_void_p)]
 
 
 _lib = None
@@ -214,6 +220,12 @@ def lib():
         L.sosgpu_trphi_spectrum_work_bytes.argtypes = [i32]
         L.sosgpu_trphi_spectrum.restype = i32
         L.sosgpu_trphi_spectrum.argtypes = [C.POINTER(TrphiJob), i32, vp, i32, vp, vp, vp]
+        L.sosgpu_level_flux.restype = i32
+        L.sosgpu_level_flux.argtypes = [vp, vp, vp, vp]
+        L.sosgpu_level_flux_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_level_flux_spectrum_work_bytes.argtypes = [i32]
+        L.sosgpu_level_flux_spectrum.restype = i32
+        L.sosgpu_level_flux_spectrum.argtypes = [C.POINTER(FluxJob), i32, vp, vp, vp]
         L.sosgpu_land_surface.restype = i32
         L.sosgpu_land_surface.argtypes = [i32, C.POINTER(Land), i32, vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_int32), vp]
         L.sosgpu_debug_phase_buffer.restype = i32

@@ -1235,6 +1235,52 @@ extern "C" int sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, co
     return SOSGPU_OK;
 }
 
+extern "C" int sosgpu_level_flux(sosgpu_ctx *cx, const double *d_rec, double *d_out, void *stream)
+{
+    if (!cx || !d_rec || !d_out) return SOSGPU_E_ARG;
+    HIPCHK(hipSetDevice(cx->device));
+    launch_level_flux(cx->d, d_rec, d_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    note_stream(cx, (hipStream_t)stream);       // the kernel reads the context's mu and ga: sosgpu_destroy waits for this stream
+    return SOSGPU_OK;
+}
+
+extern "C" size_t sosgpu_level_flux_spectrum_work_bytes(int njobs)
+{
+    return njobs > 0 ? (size_t)njobs * sizeof(FluxJobDev) : 0;
+}
+
+// sosgpu_level_flux of njobs (context, record) jobs in ONE launch (k_level_flux_table).  d_work = the job entries, filled by one
+// copy from a pinned block jobs[0].cx keeps until it is destroyed (as sosgpu_trphi_spectrum's).  Everything is checked before
+// anything is queued.
+extern "C" int sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out, void *d_work, void *stream)
+{
+    if (!jobs || !d_out || !d_work || njobs < 0 || njobs > 0x3fffffff) return SOSGPU_E_ARG;    // (2 njobs threads, an int32)
+    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    if (njobs == 0) return SOSGPU_OK;
+    static_assert(sizeof(FluxJobDev) % 8 == 0, "entries of pointers");
+    for (int i = 0; i < njobs; i++)
+        if (!jobs[i].cx || !jobs[i].d_rec) return SOSGPU_E_ARG;
+    for (int i = 1; i < njobs; i++)
+        if (jobs[i].cx->device != jobs[0].cx->device) return SOSGPU_E_ARG;
+    HIPCHK(hipSetDevice(jobs[0].cx->device));
+    const size_t bytes = (size_t)njobs * sizeof(FluxJobDev);
+    FluxJobDev *tab = nullptr;
+    HIPCHK(hipHostMalloc((void **)&tab, bytes, hipHostMallocDefault));
+    jobs[0].cx->host_staging.push_back(tab);
+    for (int i = 0; i < njobs; i++) {
+        const SosDev &d = jobs[i].cx->d;
+        FluxJobDev &e = tab[i];
+        e.n = d.n; e.n0 = d.n0; e.mu = d.mu; e.ga = d.ga; e.rec = jobs[i].d_rec; e.out = d_out + 2 * (size_t)i;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(d_work, tab, bytes, hipMemcpyHostToDevice, st));
+    launch_level_flux_table(static_cast<const FluxJobDev *>(d_work), njobs, st);
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < njobs; i++) note_stream(jobs[i].cx, st);
+    return SOSGPU_OK;
+}
+
 extern "C" int sosgpu_land_surface(int device, const sosgpu_land *land, int n, const double *mu, const double *chr, double ind,
                                    int os_nb, int os_ns, int os_nm, float *d_rsurf, int32_t *ier_out, void *stream)
 {

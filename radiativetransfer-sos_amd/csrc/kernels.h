@@ -72,6 +72,18 @@ struct TrphiJobDev {
 };
 void launch_trphi_table(const TrphiJobDev *d_jobs, int njobs, int nblocks, int w_max, hipStream_t st);
 
+// Diffuse fluxes of an aggregated record at its output altitude (flux.hip): d_out[0] = E-, d_out[1] = E+ from the order-0
+// intensity row d_rec[0][0][W] and the context's mu, ga, n0
+void launch_level_flux(const SosDev &cx, const double *d_rec, double *d_out, hipStream_t st);
+// Table form (sosgpu_level_flux_spectrum): launch_level_flux's arguments per job, in a device array; one launch of
+// ceil(2 njobs / 64) workgroups, thread = (job, hemisphere)
+struct FluxJobDev {
+    int n, n0;                           // of the job's context, with mu and ga
+    const double *mu, *ga, *rec;
+    double *out;                         // [2] of the job
+};
+void launch_level_flux_table(const FluxJobDev *d_jobs, int njobs, hipStream_t st);
+
 #define SOS_PROF_NBLEV_MAX 64     // levels of the absorption profile held in LDS (CTE_ABS_NBLEV = 50 in the reference)
 // Per-bin profile discretisation (profile.hip).  *_ng: the no-gas profile of the wavelength (host-computed, device copy).
 struct ProfileArgs {

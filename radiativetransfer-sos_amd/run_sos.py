@@ -110,6 +110,10 @@ OUTPUT_NAMES = ["nblum", "ind_angout", "phi", "vza", "sca_ang_up", "i_up", "q_up
                 "flux_dir_down", "flux_diff_down", "flux_tot_down", "flux_diff_up", "coef_tronca"]
 
 
+# columns of the per-altitude flux rows of sos_proc_levels / sos_spectrum_levels with fluxes=True (_level_flux_row)
+LEVEL_FLUX_NAMES = ["flux_dir_down_tronc", "flux_diff_down_tronc", "flux_tot_down", "flux_diff_up", "flux_net"]
+
+
 class SosProcError(RuntimeError):
     """Raised where the reference prints a message and returns IER=1 (SOS_PROC.F:3895-4896)."""
 
@@ -1253,6 +1257,19 @@ def _trphi_launch_many(jobs):
     return flat, [tuple(v.shape) for v in views]
 
 
+def _level_flux_row(pl, alt, fin, g, e):
+    """One row of LEVEL_FLUX_NAMES for output altitude `alt` (km, -1 = the standard output) of plan pl: e = (E-, E+) of
+    sosgpu_level_flux for that altitude's aggregated record, fin / g its finish_scalars dictionary and segment.  The direct term
+    is formed as _finish forms tdir_tronc: exp(-tau / cos(theta_s)) of the truncated optical depth down to the altitude (the
+    whole column for -1, where the down-going columns refer to the ground and the up-going one to the top of the atmosphere)."""
+    cs = math.cos(math.pi * pl.p["tetas"] / 180.0)
+    tau = float(fin["ttot_tronc"][g]) if alt == -1.0 else float(fin["tauout"][g])
+    tdir = math.exp(-tau / cs)
+    em, ep = float(e[0]), float(e[1])
+    tot = em + tdir
+    return (tdir, em, tot, ep, tot - ep)
+
+
 def _finish(pl, out, rec0, fin, g=0, block=None):
     """The tail of SOS_PROC (SOS_PROC.F:3755-3874) on the host: the (361,81) tables from sosgpu_trphi's output `out` (host
     array), fluxes, result files (rank 0 only), the 23-tuple.  rec0: aggregated records [S][3][W] of this wavelength
@@ -1313,10 +1330,11 @@ def sos_proc(aer_phase=None, device=0, **kw):
     return _band_call("sos_proc", kw, aer_phase, device)[0]
 
 
-def _band_call(fn, kw, aer_phase, device, alts=None):
+def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False):
     """One band for sos_proc (alts None: solve_band, the kernels without output slots) or sos_proc_levels (alts: the K
     altitudes, solve_band_levels): prepare, let the ranks agree on an error flag, solve, SOS_TRPHI and _finish per output.
-    Returns the list of 23-tuples (one without alts)."""
+    Returns the list of 23-tuples (one without alts); with fluxes (alts only) the pair (that list, flux rows [K][5])."""
+    from . import solver
     from .solver import SosBinError
     pl, levels, err = None, None, None
     try:
@@ -1351,22 +1369,30 @@ def _band_call(fn, kw, aer_phase, device, alts=None):
             outs = [_trphi_launch(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]), float(fin["tauout"][k]))
                     .cpu().numpy() for k in range(len(rec))]
         else:                                      # the K altitudes in one launch, one download
+            if fluxes:                             # (one more launch for the K flux pairs, on the reduced records)
+                flux_dev = solver.level_flux_many([(pl.ctx, rec[k]) for k in range(len(rec))])
             flat, shapes = _trphi_launch_many([(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]),
                                                 float(fin["tauout"][k])) for k in range(len(rec))])
             flat, outs, pos = flat.cpu().numpy(), [], 0
             for shp in shapes:
                 outs.append(flat[pos:pos + int(np.prod(shp))].reshape(shp))
                 pos += outs[-1].size
-        return [_finish(pl, outs[k], rec[k], fin, k) for k in range(len(rec))]
+        tuples = [_finish(pl, outs[k], rec[k], fin, k) for k in range(len(rec))]
+        if not fluxes:
+            return tuples
+        e = flux_dev.cpu().numpy()                 # (complete: it was queued ahead of the recompositions just downloaded)
+        return tuples, np.array([_level_flux_row(pl, alts[k], fin, k, e[k]) for k in range(len(rec))], dtype=np.float64)
     finally:
         pl.ctx.close()
 
 
-def _levels_arguments(fn, altitudes, kwargs_list):
+def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False):
     """The argument rules of the output-slot entry points, checked before any device work: 1 to 16 altitudes, each passing the
     -SOS.OutputAlt rule (SosProcError 2611), and calls with zout = -1 and no -SOS_Main.ResRoot (ValueError).  Returns the
-    altitudes as floats."""
+    altitudes as floats.  fluxes: the entry point's flag, a bool (ValueError)."""
     from . import capi
+    if not isinstance(fluxes, (bool, np.bool_)):
+        raise ValueError("%s: fluxes must be True or False, got %r" % (fn, fluxes))
     alts = [float(z) for z in altitudes]
     if not 1 <= len(alts) <= capi.MAX_OUTPUT_LEVELS:
         raise ValueError("%s: 1 to %d altitudes, got %d" % (fn, capi.MAX_OUTPUT_LEVELS, len(alts)))
@@ -1384,7 +1410,7 @@ def _levels_arguments(fn, altitudes, kwargs_list):
     return alts
 
 
-def sos_proc_levels(altitudes, aer_phase=None, device=0, **kw):
+def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, **kw):
     """sos_proc for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output) at once: ONE
     profile, context and solve, whose K output slots capture the field at each altitude (sosgpu_os_solve_levels), then
     one aggregate and SOS_TRPHI per altitude.  Returns a list of K 23-tuples in the order of `altitudes`; element k equals
@@ -1392,8 +1418,23 @@ def sos_proc_levels(altitudes, aer_phase=None, device=0, **kw):
     1 <= K <= 16, duplicates allowed; each altitude must pass the -SOS.OutputAlt rule (SosProcError 2611, raised before any
     device work).  kw is sos_proc's keyword set with zout = -1 (another zout: ValueError) and no -SOS_Main.ResRoot (result
     files stay sos_proc's: ValueError).  Under torch.distributed the call is a collective as sos_proc is: the bins are
-    sharded and one all-reduce covers the K record sets."""
-    return _band_call("sos_proc_levels", kw, aer_phase, device, _levels_arguments("sos_proc_levels", altitudes, [kw]))
+    sharded and one all-reduce covers the K record sets.
+
+    fluxes=True (a bool, ValueError otherwise, before any device work): returns (tuples, flux) with flux a numpy array [K][5],
+    the irradiances at each altitude z in units of the incident solar irradiance on a horizontal plane, columns
+    LEVEL_FLUX_NAMES: flux_dir_down_tronc = exp(-tauout / cos(theta_s)) of the truncated optical depth down to z;
+    flux_diff_down_tronc = E-(z) and flux_diff_up = E+(z), the reference's EMOINS / EPLUS quadrature (SOS_OS.F:1447-1456) of
+    the order-0 intensity captured at z (sosgpu_level_flux_spectrum: the K pairs in one launch on the aggregated -- under
+    torch.distributed reduced -- records, every rank computing them); flux_tot_down, the sum of the first two, which does not
+    depend on the truncation; flux_net = flux_tot_down - flux_diff_up.  For altitude -1 the down-going columns refer to the
+    ground (direct term exp(-ttot_tronc / cos(theta_s))) and flux_diff_up to the top of the atmosphere: the row restates
+    elements 20 and 21 of that altitude's 23-tuple (to rounding; with surface matrices, -SURF.Type 1 and 3..7, flux_diff_up
+    agrees with element 21 to some 1e-9 only, as the reference's EPLUS and its own record do).  The split of the down-going flux into TRUE direct and TRUE diffuse parts at
+    an interior altitude (elements 18 and 19 of the tuple, given at the ground only) needs the untruncated optical depth down
+    to z, which the profile stage does not export: not provided.  With the default the return value, the launches and the
+    bits are unchanged."""
+    alts = _levels_arguments("sos_proc_levels", altitudes, [kw], fluxes)
+    return _band_call("sos_proc_levels", kw, aer_phase, device, alts, bool(fluxes))
 
 
 def sos_proc_many(kwargs_list, n_workers=8, device=0):
@@ -1437,15 +1478,24 @@ def _expand_outputs(c, block=None):
     return tuple(out)
 
 
-def _gather_results(results, mine, nrows, world, nz=None):
+def _gather_results(results, mine, nrows, world, nz=None, flux=None):
     """Every rank receives the 23-tuples of the wavelengths the other ranks computed (all_gather_object of the compacted
     tuples; the only exchange of a wavelength-partitioned spectrum).  nz: every result is a list of nz 23-tuples (output
-    altitudes) instead of one tuple."""
+    altitudes) instead of one tuple.  flux: the per-wavelength flux rows of sos_spectrum_levels(fluxes=True), which travel with
+    the compact tuples and are filled in the same way."""
     import torch.distributed as dist
     per = 1 if nz is None else nz
     part = [(i, [_compact_outputs(t, nrows[i]) for t in ([results[i]] if nz is None else results[i])]) for i in mine]
+    if flux is not None:
+        part = [(i, (cs, flux[i])) for i, cs in part]
     parts = [None] * world
     dist.all_gather_object(parts, part)
+    if flux is not None:
+        for pr in parts:
+            for i, (_, fx) in pr:
+                if flux[i] is None:
+                    flux[i] = fx
+        parts = [[(i, cs) for i, (cs, _) in pr] for pr in parts]
     todo = [(i, cs) for pr in parts for i, cs in pr if results[i] is None]
     blocks = _zero_pages((len(todo) * per, len(_TABLE_NAMES), 361, 81)) if todo else None
     for j, (i, cs) in enumerate(todo):
@@ -1528,7 +1578,7 @@ def _first_failed_index(index, device):
     return int(t.item())
 
 
-def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None):
+def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
     launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop."""
@@ -1544,7 +1594,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if len(aer_phases) != nwl:
         raise ValueError("aer_phases must be parallel to kwargs_list")
     if nwl == 0:
-        return []
+        return ([], []) if fluxes else []
     capi.lib()
     dev = torch.device("cuda", device)
     # solve_spectrum / solve_spectrum_levels are looked up when called: the tests count launches by replacing them
@@ -1575,9 +1625,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     else:
         mine = list(range(nwl))
     results = [None] * nwl                              # K 23-tuples per wavelength
+    flux_rows = [None] * nwl if fluxes else None        # fluxes: the [K][5] flux rows per wavelength
     debug = bool(os.environ.get("SOS_SPECTRUM_DEBUG"))
     nrows = {}
-    tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0)
+    tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0, fluxes=0.0)
     main_st = torch.cuda.current_stream(dev)
     side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(prep_streams)))]
     aer_st = torch.cuda.Stream(device=dev)
@@ -1710,6 +1761,14 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                         solved.append(([pl], rec, scal, None))
                     t0 = time.perf_counter()
                     tm["solve_launch"] += t0 - t1
+                flux_dev = None
+                if fluxes:
+                    # the flux pairs of every (wavelength, altitude) of the chunk: one launch behind the aggregates, in the order
+                    # of `todo` below; the result comes down with the recompositions'
+                    tf = time.perf_counter()
+                    flux_dev = solver.level_flux_many([(pl.ctx, rec[k][g]) for gp, rec, _, _ in solved
+                                                       for g, pl in enumerate(gp) for k in range(nz)])
+                    tm["fluxes"] += time.perf_counter() - tf
                 t2 = time.perf_counter()
                 # --- one copy of all band scalars (waits for the solves), then every azimuth recomposition back to back
                 # (the status words of the device gas tables ride at its end)
@@ -1743,6 +1802,15 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 flat = flat.cpu().numpy()
                 t4 = time.perf_counter()
                 tm["trphi"] += t4 - t3
+                if fluxes:
+                    e = flux_dev.cpu().numpy()                  # (complete: queued ahead of the recompositions just downloaded)
+                    for j, (pl, k, r, f, g) in enumerate(todo):
+                        if flux_rows[pl.index] is None:
+                            flux_rows[pl.index] = np.empty((nz, len(LEVEL_FLUX_NAMES)))
+                        flux_rows[pl.index][k] = _level_flux_row(pl, alts[k], f, g, e[j])
+                    t5 = time.perf_counter()
+                    tm["fluxes"] += t5 - t4
+                    t4 = t5
                 pos = 0
                 blocks = _zero_pages((len(todo), 2, 7, 361, 81))  # the result tables of the chunk's wavelengths (views of it)
                 for j, ((pl, k, r, f, g), shp) in enumerate(zip(todo, shapes)):
@@ -1781,8 +1849,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if alts is None:
         results = [None if r is None else r[0] for r in results]
     if world > 1 and gather:
-        _gather_results(results, mine, nrows, world, None if alts is None else nz)
-    return results
+        _gather_results(results, mine, nrows, world, None if alts is None else nz, flux_rows)
+    return (results, flux_rows) if fluxes else results
 
 
 def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16, parts=4):
@@ -1836,7 +1904,7 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
 
 
 def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16,
-                        parts=4):
+                        parts=4, fluxes=False):
     """sos_spectrum for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output): every wavelength is
     prepared once, ALL bins of a group of wavelengths go through ONE launch of the fused solver per kernel variant with K output
     slots each (sosgpu_os_solve_multi_levels), then K segmented aggregates (each altitude with its own TAUOUT) and K azimuth
@@ -1854,10 +1922,19 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
     to the ranks by cost (spectrum_costs), without an all-reduce; the ranks then agree on failures (one integer all-reduce),
     so that a call failing on one rank makes EVERY rank raise SosProcError naming that wavelength instead of leaving the
     others waiting in the gather (all_gather_object of the compacted tuples, K per wavelength).  gather=False leaves None in
-    the slots of other ranks."""
-    alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list)
+    the slots of other ranks.
+
+    fluxes=True (a bool, ValueError otherwise, before any device work): returns (spec, flux) with spec the list above and
+    flux[i] the numpy array [K][5] of call i, the irradiances at each altitude as sos_proc_levels(..., fluxes=True) describes
+    them (columns LEVEL_FLUX_NAMES; the true direct / diffuse split at an interior altitude is not provided).  The flux pairs
+    of ALL (wavelength, altitude) jobs of a chunk are computed by one launch (sosgpu_level_flux_spectrum through
+    solver.level_flux_many) queued behind the chunk's aggregates, and come down after the recompositions without a wait of
+    their own; `timings` gains the host phase "fluxes".  With gather=True the rows travel with the compacted tuples, so
+    every rank returns the same arrays; gather=False leaves None in the slots of other ranks.  With the default the return
+    value, the launches and the bits are unchanged."""
+    alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes)
     return _spectrum_pass("sos_spectrum_levels", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
-                          alts)
+                          alts, bool(fluxes))
 
 
 def write_trans_file(path, tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):

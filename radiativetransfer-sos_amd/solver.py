@@ -527,6 +527,16 @@ class SosContext:
                                            _ptr(phis), int(igli), float(wind), lp, _ptr(out), self._stream()), "sosgpu_trphi")
         return out
 
+    def level_flux(self, rec):
+        """Diffuse fluxes at the output altitude of an aggregated record (sosgpu_level_flux): rec is a device tensor
+        [>=1][3][W] (one output slot of aggregate / aggregate_levels); only its order-0 intensity row is read.  Returns a device
+        tensor [2]: E-(z), E+(z) (for the standard output: E- at the ground, E+ at the top of the atmosphere).  Nothing is
+        waited for."""
+        row = _flux_row(rec, self.device, self.w)
+        out = torch.empty(2, dtype=torch.float64, device=self.device)
+        capi.check(capi.lib().sosgpu_level_flux(self._h, _ptr(row), _ptr(out), self._stream()), "sosgpu_level_flux")
+        return out
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             capi.lib().sosgpu_destroy(self._h)            # waits for the streams this context's work was queued on
@@ -585,6 +595,36 @@ def trphi_many(items):
         views.append(flat[pos:pos + m].view(shp))
         pos += m
     return flat, views
+
+
+def _flux_row(rec, device, w):
+    """The order-0 intensity row rec[0][0][W] of a record tensor, contiguous on `device` (a view wherever the record allows)."""
+    row = rec[0, 0]
+    if row.shape != (w,):
+        raise ValueError("a record is [orders][3][W] with W = %d, got %s" % (w, tuple(rec.shape)))
+    return row.to(device=device, dtype=torch.float64).contiguous()
+
+
+def level_flux_many(items):
+    """SosContext.level_flux for many jobs in ONE sosgpu_level_flux_spectrum call (one launch) on the current stream.  items: a
+    list of (ctx, rec), each as SosContext.level_flux takes them; the contexts live on one device; jobs may share a context or a
+    record.  Returns a device tensor [njobs][2] (E-, E+ per job) -- the bits SosContext.level_flux gives for each item.  Nothing
+    is waited for."""
+    n = len(items)
+    if n == 0:
+        return None
+    L = capi.lib()
+    d = items[0][0].device
+    jobs = (capi.FluxJob * n)()
+    rows = []
+    for j, (cx, rec) in zip(jobs, items):
+        row = _flux_row(rec, d, cx.w)
+        rows.append(row)
+        j.cx, j.d_rec = cx._h.value, row.data_ptr()
+    out = torch.empty((n, 2), dtype=torch.float64, device=d)
+    work = torch.empty(int(L.sosgpu_level_flux_spectrum_work_bytes(n)), dtype=torch.uint8, device=d)
+    capi.check(L.sosgpu_level_flux_spectrum(jobs, n, _ptr(out), _ptr(work), items[0][0]._stream()), "sosgpu_level_flux_spectrum")
+    return out
 
 
 def build_operators(ctxs):

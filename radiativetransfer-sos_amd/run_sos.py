@@ -1429,7 +1429,9 @@ def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, **kw):
     depend on the truncation; flux_net = flux_tot_down - flux_diff_up.  For altitude -1 the down-going columns refer to the
     ground (direct term exp(-ttot_tronc / cos(theta_s))) and flux_diff_up to the top of the atmosphere: the row restates
     elements 20 and 21 of that altitude's 23-tuple (to rounding; with surface matrices, -SURF.Type 1 and 3..7, flux_diff_up
-    agrees with element 21 to some 1e-9 only, as the reference's EPLUS and its own record do).  The split of the down-going flux into TRUE direct and TRUE diffuse parts at
+    agrees with element 21 to some 1e-9 only, as the reference's EPLUS and its own record do); its flux_net, ground minus top,
+    is the net flux of no altitude (the net flux at the ground takes flux_diff_up of the 0 km row, that at the top flux_tot_down
+    of the 120 km row).  The split of the down-going flux into TRUE direct and TRUE diffuse parts at
     an interior altitude (elements 18 and 19 of the tuple, given at the ground only) needs the untruncated optical depth down
     to z, which the profile stage does not export: not provided.  With the default the return value, the launches and the
     bits are unchanged."""

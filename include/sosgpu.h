@@ -21,6 +21,9 @@
  *   - sosgpu_destroy waits for the streams the context's own work was queued on, nothing else.
  * Device memory of contexts and of temporaries is recycled through a process-wide pool (hipFree would synchronise the
  * device); sosgpu_trim() returns it.
+ * The table of every table-form entry point (sosgpu_ctx_table, the *_spectrum, *_tables and *_batch calls) travels to the caller's
+ * work area from a pinned block the library recycles: nothing is waited for and no context owns it, so any context of such a
+ * call may be destroyed as soon as the call has returned (sosgpu_destroy waits for the context's streams, as ever).
  *
  * Each entry point replaces one routine of the reference per-wavelength pipeline that
  * binding/run_sos.py reaches through sos.sos_proc (binding/run_sos.py:640, SOS_PROC.F:415):
@@ -116,7 +119,7 @@ int  sosgpu_noyaux(sosgpu_ctx *cx, void *stream);
  *                  the call.
  *  d_work          DEVICE area of nctx * (sosgpu_ctx_table_entry_bytes() + 8) bytes, 8-byte aligned, the caller's until `stream`
  *                  has passed the call: the table of the contexts and the list of matrix pointers arrive there in ONE copy on
- *                  `stream`, from a pinned block ctxs[0] keeps until it is destroyed (as sosgpu_ctx_table's).
+ *                  `stream`, from a pinned block the library recycles.
  * Asynchronous: nothing is waited for and no device memory is allocated.  On return every context is in the host-side state the
  * two calls leave (its ground operators registered, `stream` noted for sosgpu_destroy); once `stream` has passed the call its
  * tables are filled.  Call sosgpu_ctx_table AFTER this call, not before: the table copies the ground-operator pointers this
@@ -179,7 +182,8 @@ int  sosgpu_output_levels(sosgpu_ctx *cx, int nb, int lp, const double *d_prof, 
 
 /* The scratch of the streamed solver (level grids beyond 64 levels) is kept by the library when a context is destroyed and
  * handed to the next context that needs one (at most 8 buffers and 8 GiB per process): a context per wavelength would
- * otherwise pay a 60-1000 MB hipMalloc per call.  sosgpu_trim() returns that memory to the device. */
+ * otherwise pay a 60-1000 MB hipMalloc per call.  sosgpu_trim() returns that memory to the device, and frees the pinned
+ * staging blocks whose copies have passed. */
 int  sosgpu_trim(void);
 
 /* Many wavelengths in ONE launch (hyperspectral runs, BASELINE config 5: each wavelength has only 5-100 CKD bins, a fraction
@@ -187,7 +191,7 @@ int  sosgpu_trim(void);
  * bin loops SOS_PROC.F:3459-3594 of nctx wavelengths are concatenated and every bin carries the index of its wavelength.
  *   sosgpu_ctx_table   copies the device-side description of nctx contexts (sosgpu_ctx_table_entry_bytes() each) into the
  *                      caller's device buffer d_table, ordered on `stream` (nothing is waited for: the copy comes from a pinned
- *                      block ctxs[0] keeps until it is destroyed).  All contexts must live on one device and agree in
+ *                      block the library recycles).  All contexts must live on one device and agree in
  *                      N, iborm_max and IMAT_SURF (E_ARG otherwise).  The table refers to the contexts' operator tables: it
  *                      stays valid until one of them is destroyed or has sosgpu_set_surface_matrices called again -- a
  *                      destroyed context's memory is recycled at once, so wait for the launches that use the table first.
@@ -295,8 +299,8 @@ int  sosgpu_trphi(sosgpu_ctx *cx, int nf, const double *d_rec, double tau, doubl
  *  d_phi[nphi_total]  DEVICE azimuths (radians) of the whole call; job j reads d_phi[phi_off .. phi_off + nphi)
  *  d_out           DEVICE, the blocks [nphi_j][7][W_j] of the jobs back to back, in job order
  *  d_work          DEVICE area of sosgpu_trphi_spectrum_work_bytes(njobs) bytes, 8-byte aligned, the caller's until `stream` has
- *                  passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block jobs[0].cx keeps until
- *                  it is destroyed (as sosgpu_noyaux_spectrum's).
+ *                  passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block the library
+ *                  recycles.
  * Asynchronous: one launch, nothing is waited for and no device memory is allocated; `stream` is noted for sosgpu_destroy on
  * every context of the call.  Records, azimuths and contexts must stay alive until `stream` has passed the call.
  * Checked before anything is queued, SOSGPU_E_ARG for: NULL jobs, d_phi, d_out or d_work, njobs < 0 or njobs > 65535, a NULL cx
@@ -328,8 +332,8 @@ int  sosgpu_level_flux(sosgpu_ctx *cx, const double *d_rec, double *d_out /*[2]*
  *  jobs[njobs]     HOST array; jobs may share a context and a record pointer
  *  d_out[njobs][2] DEVICE
  *  d_work          DEVICE area of sosgpu_level_flux_spectrum_work_bytes(njobs) bytes, 8-byte aligned, the caller's until `stream`
- *                  has passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block jobs[0].cx keeps
- *                  until it is destroyed (as sosgpu_trphi_spectrum's).
+ *                  has passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block the library
+ *                  recycles.
  * Asynchronous: one launch, nothing is waited for and no device memory is allocated; `stream` is noted for sosgpu_destroy on
  * every context of the call (the kernel reads their mu and ga).  Records and contexts must stay alive until `stream` has passed
  * the call.  Checked before anything is queued, SOSGPU_E_ARG for: NULL jobs, d_out or d_work, njobs < 0 (or > 2^30 - 1), a NULL
@@ -565,6 +569,9 @@ int  sosgpu_debug_phase_buffer(sosgpu_ctx *cx, unsigned long long *d_phase);
 /* Diagnostic accessor: device pointer and size (doubles) of the streamed solver's scratch of this context, and the offset of the
  * order-parallel form's I3 hand-over block [nb][iborm_max+1][threads] inside it after such a solve (0 otherwise). */
 int  sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *doubles, size_t *spec_i3_offset);
+/* Diagnostic: how many pinned staging blocks the library holds for `device` (*total), and how many of them the next
+ * table-form call could take now (*idle: in no call's hands, the event behind its last copy passed). */
+int  sosgpu_debug_stage_blocks(int device, int *total, int *idle);
 /* Diagnostic: the launch plan sosgpu_os_solve (table = 0) / sosgpu_os_solve_multi (table != 0) and their _levels forms (nz > 0
  * output slots) would follow for `nb` bins of `lp` padded levels in a context of `n` directions and iborm_max = `smax` -- the
  * kernel variant, the launch form, the bins per launch and the layout of the context's scratch.  Needs no context and no

@@ -24,7 +24,7 @@ EXPORTS = [
     "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
     "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes", "sosgpu_debug_solve_plan",
     "sosgpu_noyaux_spectrum", "sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes",
-    "sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes",
+    "sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes", "sosgpu_debug_stage_blocks",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -232,6 +232,8 @@ def lib():
         L.sosgpu_debug_phase_buffer.argtypes = [vp, vp]
         L.sosgpu_debug_scratch.restype = i32
         L.sosgpu_debug_scratch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.sosgpu_debug_stage_blocks.restype = i32
+        L.sosgpu_debug_stage_blocks.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
         L.sosgpu_debug_solve_plan.restype = i32
         L.sosgpu_debug_solve_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(SolvePlan)]
         L.sosgpu_debug_roundtrip.restype = i32

@@ -35,7 +35,6 @@ struct sosgpu_ctx {
     bool timed;
     hipStream_t last_stream;
     std::vector<hipStream_t> used_streams;   // every stream a solve / table build of this context was queued on
-    std::vector<void *> host_staging;        // pinned host blocks of queued copies (sosgpu_ctx_table), freed by sosgpu_destroy
     int nt_max_hint;
     double ind_surf;
     unsigned long long *phase;   // diagnostic phase-cycle buffer (sosgpu_debug_phase_buffer), else null
@@ -427,6 +426,63 @@ void pool_give(int dev, double *p, size_t n)
 }
 }   // namespace
 
+// The per-wavelength or per-job table of every table-form entry point travels to the caller's work area from a pinned block
+// the library recycles (per device): a block is free again when the event recorded behind its copy has passed.  Nothing is
+// waited for and no context owns a block; sosgpu_trim frees those that have passed.
+namespace {
+struct StageBlock { void *p; size_t bytes; hipEvent_t ev; int device; };
+std::mutex g_stage_mutex;
+std::vector<StageBlock> g_stage;     // the blocks in no call's hands
+
+bool stage_passed(const StageBlock &b)      // (a never-recorded event queries as complete)
+{
+    if (hipEventQuery(b.ev) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// One table on its way: takes the first block of the device that is large enough and has passed out of g_stage, else makes
+// one (16 KiB at least); the caller fills host() in place and send()s it.  A block that is never sent goes back as it came.
+class Staged {
+    StageBlock b = {};
+    const size_t n;
+    int take(int device)
+    {
+        {
+            std::lock_guard<std::mutex> lk(g_stage_mutex);
+            for (auto it = g_stage.begin(); it != g_stage.end(); ++it)
+                if (it->device == device && it->bytes >= n && stage_passed(*it)) { b = *it; g_stage.erase(it); return SOSGPU_OK; }
+        }
+        b.bytes = std::max(n, (size_t)16384); b.device = device;
+        HIPCHK(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+        const hipError_t e = hipHostMalloc(&b.p, b.bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { b.p = nullptr; (void)hipEventDestroy(b.ev); HIPCHK(e); }
+        return SOSGPU_OK;
+    }
+    void give()
+    {
+        if (!b.p) return;
+        std::lock_guard<std::mutex> lk(g_stage_mutex);
+        g_stage.push_back(b);
+        b.p = nullptr;
+    }
+public:
+    const int rc;                    // SOSGPU_OK, or why there is no block (g_last_hip set)
+    Staged(int device, size_t bytes) : n(bytes), rc(take(device)) {}
+    ~Staged() { give(); }
+    Staged(const Staged &) = delete;
+    void *host() const { return b.p; }
+    // queues the copy of the table to d_dst on st and records the event that frees the block behind it; the copy's status
+    hipError_t send(void *d_dst, hipStream_t st)
+    {
+        const hipError_t e = hipMemcpyAsync(d_dst, b.p, n, hipMemcpyHostToDevice, st);
+        (void)hipEventRecord(b.ev, st);
+        give();
+        return e;
+    }
+};
+}   // namespace
+
 extern "C" int sosgpu_trim(void)
 {
     std::vector<ScratchBuf> all;
@@ -436,6 +492,11 @@ extern "C" int sosgpu_trim(void)
     }
     for (const ScratchBuf &b : all) { (void)hipSetDevice(b.dev); (void)hipFree(b.p); }
     mem_trim();
+    std::lock_guard<std::mutex> lk(g_stage_mutex);
+    for (size_t i = g_stage.size(); i-- > 0;) {
+        const StageBlock b = g_stage[i];
+        if (stage_passed(b)) { (void)hipHostFree(b.p); (void)hipEventDestroy(b.ev); g_stage.erase(g_stage.begin() + i); }
+    }
     return SOSGPU_OK;
 }
 
@@ -445,7 +506,6 @@ extern "C" int sosgpu_destroy(sosgpu_ctx *cx)
     // teardown: nothing useful can be done with a failing free, errors are deliberately dropped
     (void)hipSetDevice(cx->device);
     (void)sync_ctx_streams(cx);        // solves / table builds of this context may still be running, on any of its streams
-    for (void *h : cx->host_staging) (void)hipHostFree(h);
     for (size_t i = 0; i < cx->allocs.size(); i++) mem_give(cx->device, cx->allocs[i], cx->alloc_cls[i]);
     if (cx->scratch) pool_give(cx->device, cx->scratch, cx->scratch_doubles);
     if (cx->ev0) (void)hipEventDestroy(cx->ev0);
@@ -566,8 +626,8 @@ extern "C" int sosgpu_noyaux(sosgpu_ctx *cx, void *stream)
 }
 
 // sosgpu_set_surface_matrices_async + sosgpu_noyaux of nctx contexts in at most five launches (the table forms of their
-// kernels, noyaux.hip / k_pack_ground_table).  d_work = [SosDev entries | matrix pointers], filled by one copy from a pinned
-// block ctxs[0] keeps until it is destroyed (as sosgpu_ctx_table's).  Everything is checked before a context is touched.
+// kernels, noyaux.hip / k_pack_ground_table).  d_work = [SosDev entries | matrix pointers], filled by one copy from a recycled
+// pinned block (Staged).  Everything is checked before a context is touched.
 extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const float *const *d_rsurf, void *d_work, void *stream)
 {
     if (!ctxs || !d_work || nctx < 0 || nctx > 65535) return SOSGPU_E_ARG;
@@ -589,9 +649,9 @@ extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const f
     HIPCHK(hipSetDevice(ctxs[0]->device));
     const size_t n_tab = (size_t)nctx * sizeof(SosDev), n_all = n_tab + (size_t)nctx * sizeof(const float *);
     static_assert(sizeof(SosDev) % 8 == 0, "the pointer list follows the entries");
-    char *stage = nullptr;
-    HIPCHK(hipHostMalloc((void **)&stage, n_all, hipHostMallocDefault));
-    ctxs[0]->host_staging.push_back(stage);
+    Staged s(ctxs[0]->device, n_all);
+    if (s.rc) return s.rc;
+    char *stage = static_cast<char *>(s.host());
     SosDev *tab = reinterpret_cast<SosDev *>(stage);
     const float **rs = reinterpret_cast<const float **>(stage + n_tab);
     for (int i = 0; i < nctx; i++) {
@@ -602,7 +662,7 @@ extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const f
         tab[i] = cx->d;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(d_work, stage, n_all, hipMemcpyHostToDevice, st));
+    HIPCHK(s.send(d_work, st));
     const SosDev *d_tab = static_cast<const SosDev *>(d_work);
     if (gnd_smax >= 0) {
         dim3 grid((unsigned)((gnd_elems + 255) / 256), (unsigned)gnd_smax + 1, (unsigned)nctx);
@@ -791,13 +851,6 @@ extern "C" int sosgpu_ctx_table(sosgpu_ctx *const *ctxs, int nctx, void *d_table
 {
     if (!ctxs || nctx < 1 || !d_table || !ctxs[0]) return SOSGPU_E_ARG;
     const SosDev &a = ctxs[0]->d;
-    // The table is copied on the caller's stream -- d_table is the caller's memory and may still be read by work queued there
-    // (a buffer the caller's allocator has just recycled) -- from a pinned staging block the first context keeps until it is
-    // destroyed, so nothing is waited for.
-    HIPCHK(hipSetDevice(ctxs[0]->device));
-    SosDev *tab = nullptr;
-    HIPCHK(hipHostMalloc((void **)&tab, (size_t)nctx * sizeof(SosDev), hipHostMallocDefault));
-    ctxs[0]->host_staging.push_back(tab);
     for (int i = 0; i < nctx; i++) {
         if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device) return SOSGPU_E_ARG;
         const SosDev &d = ctxs[i]->d;
@@ -806,9 +859,14 @@ extern "C" int sosgpu_ctx_table(sosgpu_ctx *const *ctxs, int nctx, void *d_table
             (d.imat_surf != 0) != (a.imat_surf != 0))
             return SOSGPU_E_ARG;
         if (d.imat_surf && !d.mp_gnd) return SOSGPU_E_ARG;
-        tab[i] = d;
     }
-    HIPCHK(hipMemcpyAsync(d_table, tab, (size_t)nctx * sizeof(SosDev), hipMemcpyHostToDevice, (hipStream_t)stream));
+    // copied on the caller's stream (d_table may be a buffer the caller's allocator has just recycled, still read by work queued there)
+    HIPCHK(hipSetDevice(ctxs[0]->device));
+    Staged s(ctxs[0]->device, (size_t)nctx * sizeof(SosDev));
+    if (s.rc) return s.rc;
+    SosDev *tab = static_cast<SosDev *>(s.host());
+    for (int i = 0; i < nctx; i++) tab[i] = ctxs[i]->d;
+    HIPCHK(s.send(d_table, (hipStream_t)stream));
     note_stream(ctxs[0], (hipStream_t)stream);
     return SOSGPU_OK;
 }
@@ -1184,8 +1242,7 @@ extern "C" size_t sosgpu_trphi_spectrum_work_bytes(int njobs)
 }
 
 // sosgpu_trphi of njobs (context, record, azimuth range) jobs in ONE launch (k_trphi_table).  d_work = the job entries, filled
-// by one copy from a pinned block jobs[0].cx keeps until it is destroyed (as sosgpu_noyaux_spectrum's).  Everything is checked
-// before anything is queued.
+// by one copy from a recycled pinned block (Staged).  Everything is checked before anything is queued.
 extern "C" int sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, const double *d_phi, int nphi_total,
                                      double *d_out, void *d_work, void *stream)
 {
@@ -1209,10 +1266,9 @@ extern "C" int sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, co
     if (nblocks > 0x7fffffffLL) return SOSGPU_E_ARG;                 // (one grid dimension, first_block an int32)
     if (nadal) return SOSGPU_E_UNSUPPORTED;                          // Nadal: refused by the reference's SOS_PROC as well
     HIPCHK(hipSetDevice(jobs[0].cx->device));
-    const size_t bytes = (size_t)njobs * sizeof(TrphiJobDev);
-    TrphiJobDev *tab = nullptr;
-    HIPCHK(hipHostMalloc((void **)&tab, bytes, hipHostMallocDefault));
-    jobs[0].cx->host_staging.push_back(tab);
+    Staged s(jobs[0].cx->device, (size_t)njobs * sizeof(TrphiJobDev));
+    if (s.rc) return s.rc;
+    TrphiJobDev *tab = static_cast<TrphiJobDev *>(s.host());
     int first = 0;
     double *out = d_out;
     for (int i = 0; i < njobs; i++) {
@@ -1228,7 +1284,7 @@ extern "C" int sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, co
         out += (size_t)j.nphi * 7 * d.w;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(d_work, tab, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(s.send(d_work, st));
     launch_trphi_table(static_cast<const TrphiJobDev *>(d_work), njobs, (int)nblocks, w_max, st);
     HIPCHK(hipGetLastError());
     for (int i = 0; i < njobs; i++) note_stream(jobs[i].cx, st);
@@ -1251,8 +1307,7 @@ extern "C" size_t sosgpu_level_flux_spectrum_work_bytes(int njobs)
 }
 
 // sosgpu_level_flux of njobs (context, record) jobs in ONE launch (k_level_flux_table).  d_work = the job entries, filled by one
-// copy from a pinned block jobs[0].cx keeps until it is destroyed (as sosgpu_trphi_spectrum's).  Everything is checked before
-// anything is queued.
+// copy from a recycled pinned block (Staged).  Everything is checked before anything is queued.
 extern "C" int sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out, void *d_work, void *stream)
 {
     if (!jobs || !d_out || !d_work || njobs < 0 || njobs > 0x3fffffff) return SOSGPU_E_ARG;    // (2 njobs threads, an int32)
@@ -1264,17 +1319,16 @@ extern "C" int sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs
     for (int i = 1; i < njobs; i++)
         if (jobs[i].cx->device != jobs[0].cx->device) return SOSGPU_E_ARG;
     HIPCHK(hipSetDevice(jobs[0].cx->device));
-    const size_t bytes = (size_t)njobs * sizeof(FluxJobDev);
-    FluxJobDev *tab = nullptr;
-    HIPCHK(hipHostMalloc((void **)&tab, bytes, hipHostMallocDefault));
-    jobs[0].cx->host_staging.push_back(tab);
+    Staged s(jobs[0].cx->device, (size_t)njobs * sizeof(FluxJobDev));
+    if (s.rc) return s.rc;
+    FluxJobDev *tab = static_cast<FluxJobDev *>(s.host());
     for (int i = 0; i < njobs; i++) {
         const SosDev &d = jobs[i].cx->d;
         FluxJobDev &e = tab[i];
         e.n = d.n; e.n0 = d.n0; e.mu = d.mu; e.ga = d.ga; e.rec = jobs[i].d_rec; e.out = d_out + 2 * (size_t)i;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(d_work, tab, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(s.send(d_work, st));
     launch_level_flux_table(static_cast<const FluxJobDev *>(d_work), njobs, st);
     HIPCHK(hipGetLastError());
     for (int i = 0; i < njobs; i++) note_stream(jobs[i].cx, st);
@@ -1410,48 +1464,6 @@ extern "C" int sosgpu_absprofile(int device, int nb, int nlev, int nterm, const 
 // ---------------------------------------------------------------------------------------------
 // The profile stage of many wavelengths as three launches (profile.hip, the *_table kernels).
 // ---------------------------------------------------------------------------------------------
-namespace {
-// Pinned staging blocks of the per-wavelength table: the entry point has no context to keep one (sosgpu_ctx_table), so the
-// library recycles them -- a block is free again when the event recorded behind its copy has passed.  Never waited for.
-struct StageBlock { void *p; size_t bytes; hipEvent_t ev; int device; bool busy; };
-std::mutex g_stage_mutex;
-std::vector<StageBlock> g_stage;
-
-int stage_take(int device, size_t bytes, size_t *slot)
-{
-    std::lock_guard<std::mutex> lk(g_stage_mutex);
-    for (size_t i = 0; i < g_stage.size(); i++) {
-        StageBlock &s = g_stage[i];
-        if (s.busy || s.device != device || s.bytes < bytes) continue;
-        if (hipEventQuery(s.ev) != hipSuccess) { (void)hipGetLastError(); continue; }       // its copy has not passed yet
-        s.busy = true;
-        *slot = i;
-        return SOSGPU_OK;
-    }
-    StageBlock s;
-    s.bytes = std::max(bytes, (size_t)16384); s.device = device; s.busy = true; s.p = nullptr;
-    HIPCHK(hipHostMalloc(&s.p, s.bytes, hipHostMallocDefault));
-    if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(s.p); return SOSGPU_E_HIP; }
-    g_stage.push_back(s);
-    *slot = g_stage.size() - 1;
-    return SOSGPU_OK;
-}
-
-void *stage_ptr(size_t slot)
-{
-    std::lock_guard<std::mutex> lk(g_stage_mutex);
-    return g_stage[slot].p;
-}
-
-// the copy from the block is queued on st (or was not): record the event that frees it
-void stage_release(size_t slot, hipStream_t st)
-{
-    std::lock_guard<std::mutex> lk(g_stage_mutex);
-    (void)hipEventRecord(g_stage[slot].ev, st);
-    g_stage[slot].busy = false;
-}
-}  // namespace
-
 extern "C" size_t sosgpu_profile_table_entry_bytes(void) { return sizeof(ProfileWl); }
 
 extern "C" int sosgpu_profile_nogas_levels(double tr, double ta)
@@ -1505,13 +1517,10 @@ extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile
     if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     // --- the table: pinned block -> d_table on the caller's stream, nothing waited for
-    const size_t bytes = (size_t)nwl * sizeof(ProfileWl);
-    size_t slot = 0;
-    if (int rc = stage_take(device, bytes, &slot)) return rc;
-    memcpy(stage_ptr(slot), tab.data(), bytes);
-    const hipError_t ce = hipMemcpyAsync(d_table, stage_ptr(slot), bytes, hipMemcpyHostToDevice, st);
-    stage_release(slot, st);
-    HIPCHK(ce);
+    Staged s(device, (size_t)nwl * sizeof(ProfileWl));
+    if (s.rc) return s.rc;
+    memcpy(s.host(), tab.data(), (size_t)nwl * sizeof(ProfileWl));
+    HIPCHK(s.send(d_table, st));
     const ProfileWl *d_tab = (const ProfileWl *)d_table;
     const int NG = SOSGPU_NOGAS_LEVELS;
     launch_profile_nogas_table(d_tab, nwl, d_nogas, NG, st);
@@ -1571,14 +1580,12 @@ extern "C" int sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl 
     if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t tbytes = (size_t)nwl * sizeof(CkdWl), pbytes = (size_t)nslots * sizeof(double *);
-    size_t slot = 0;
-    if (int rc = stage_take(device, tbytes + pbytes, &slot)) return rc;
-    char *hp = (char *)stage_ptr(slot);
+    Staged s(device, tbytes + pbytes);
+    if (s.rc) return s.rc;
+    char *hp = (char *)s.host();
     memcpy(hp, tab.data(), tbytes);
     memcpy(hp + tbytes, ki, pbytes);
-    hipError_t ce = hipMemcpyAsync(d_work, hp, tbytes + pbytes, hipMemcpyHostToDevice, st);
-    stage_release(slot, st);
-    HIPCHK(ce);
+    HIPCHK(s.send(d_work, st));
     HIPCHK(hipMemsetAsync(d_status, 0, (size_t)nwl * sizeof(int32_t), st));
     launch_coeff_abs_ckd_table((const CkdWl *)d_work, nwl, max_slots, (const double *const *)((const char *)d_work + tbytes), d_axes,
                                nlay, d_out, d_status, st);
@@ -1712,9 +1719,9 @@ extern "C" int sosgpu_mie_batch(int device, int nbmu, const double *xmu, int cou
     hipStream_t st = (hipStream_t)stream;
     const int W = 2 * nbmu + 1;
     // --- angle set, lists, job table and item offsets: one pinned block -> d_work on the caller's stream, nothing waited for
-    size_t slot = 0;
-    if (int rc = stage_take(device, p.head_bytes, &slot)) return rc;
-    char *hp = (char *)stage_ptr(slot);
+    Staged s(device, p.head_bytes);
+    if (s.rc) return s.rc;
+    char *hp = (char *)s.host();
     const size_t off_al = (size_t)W * sizeof(double), off_tab = off_al + p.al_doubles * sizeof(double),
                  off_first = off_tab + (size_t)count * sizeof(MieBatchJob);
     memcpy(hp, xmu, off_al);
@@ -1722,9 +1729,7 @@ extern "C" int sosgpu_mie_batch(int device, int nbmu, const double *xmu, int cou
     for (const auto &l : p.lists) { memcpy(hp + o, l.first, (size_t)l.second * sizeof(double)); o += (size_t)l.second * sizeof(double); }
     memcpy(hp + off_tab, p.tab.data(), (size_t)count * sizeof(MieBatchJob));
     memcpy(hp + off_first, p.first.data(), p.first.size() * sizeof(int));
-    const hipError_t ce = hipMemcpyAsync(d_work, hp, p.head_bytes, hipMemcpyHostToDevice, st);
-    stage_release(slot, st);
-    HIPCHK(ce);
+    HIPCHK(s.send(d_work, st));
     HIPCHK(hipMemsetAsync(d_status, 0, (size_t)count * sizeof(int32_t), st));
     char *dw = (char *)d_work;
     const int rc = launch_mie_batch(nbmu, (const double *)dw, count, (const MieBatchJob *)(dw + off_tab), (const int *)(dw + off_first),
@@ -1786,6 +1791,17 @@ extern "C" int sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *
     *d_scratch = cx->scratch;
     *doubles = cx->scratch_doubles;
     *spec_i3_offset = cx->dbg_spec_i3;
+    return SOSGPU_OK;
+}
+
+// Diagnostic: the pinned staging blocks the library holds for `device`, and how many of them a table could take now.
+extern "C" int sosgpu_debug_stage_blocks(int device, int *total, int *idle)
+{
+    if (!total || !idle) return SOSGPU_E_ARG;
+    std::lock_guard<std::mutex> lk(g_stage_mutex);
+    *total = *idle = 0;
+    for (const StageBlock &b : g_stage)
+        if (b.device == device) { *total += 1; *idle += stage_passed(b); }
     return SOSGPU_OK;
 }
 

@@ -168,7 +168,6 @@ class SosContext:
         SEG and SEG("context: sosgpu_create")
         self._rsurf = None
         self._built = False
-        self._operator_work = None        # build_operators: the device work area of the call, kept by its first context
         if int(imat_surf) == 1:
             if rsurf is None:
                 raise ValueError("imat_surf=1 needs rsurf[smax+1][9][N][N] (float32)")
@@ -542,7 +541,6 @@ class SosContext:
             capi.lib().sosgpu_destroy(self._h)            # waits for the streams this context's work was queued on
             self._h = C.c_void_p()
             self._rsurf = None
-            self._operator_work = None
 
     def __del__(self):
         try:
@@ -632,7 +630,7 @@ def build_operators(ctxs):
     at most five launches for all of them (the table forms of the kernels of sosgpu_set_surface_matrices_async and
     sosgpu_noyaux; the same bits).  The contexts live on one device and may differ in every size; their surface matrices must
     be complete on, or ordered before, the current stream.  Contexts that are built already are left alone.  Nothing is
-    waited for: the work area of the call is one tensor the first context keeps until it is closed."""
+    waited for."""
     todo = [cx for cx in ctxs if not cx._built]
     if not todo:
         return 0
@@ -645,15 +643,14 @@ def build_operators(ctxs):
     if any(cx._rsurf is not None for cx in todo):
         rs = (C.c_void_p * n)(*[None if cx._rsurf is None else cx._rsurf.data_ptr() for cx in todo])
     capi.check(L.sosgpu_noyaux_spectrum(hs, n, rs, _ptr(work), first._stream()), "sosgpu_noyaux_spectrum")
-    first._operator_work = work
     for cx in todo:
         cx._built = True
     return n
 
 
 def release_scratch():
-    """Return the scratch buffers the library keeps from destroyed contexts (streamed solver; at most 8 GiB) to the device
-    (sosgpu_trim)."""
+    """Return the scratch buffers the library keeps from destroyed contexts (streamed solver; at most 8 GiB) to the device,
+    and free the pinned staging blocks of the table-form calls whose copies have passed (sosgpu_trim)."""
     capi.check(capi.lib().sosgpu_trim(), "sosgpu_trim")
 
 

@@ -179,6 +179,14 @@ int  sosgpu_os_solve_levels(sosgpu_ctx *cx, int nb, int lp, const int32_t *d_nt,
  * One small kernel on `stream`. */
 int  sosgpu_output_levels(sosgpu_ctx *cx, int nb, int lp, const double *d_prof, const double *d_zprof, const int32_t *d_nt,
                           int nz, const double *zout, int32_t *d_jout, double *d_zz, double *d_tauout, void *stream);
+/* The optical depth alone, on any cumulative-depth row of the bins: the statements of sosgpu_output_levels for the level, the
+ * weight and (1 - zz) H(j-1) + zz H(j) (same roundings, same -1 rule H(0), a flagged bin gets 0), with
+ *  d_h, h_stride     the row of bin b starts at d_h + b * h_stride (doubles): lp for the d_hvrai of sosgpu_profile_true,
+ *                    3 lp for the H row of d_prof -- where d_tau is sosgpu_output_levels' d_tauout bit for bit
+ *  d_tau[nz][nb]     device output
+ * No context is needed.  nb = 0 queues nothing.  One small kernel on `stream`. */
+int  sosgpu_output_depths(int device, int nb, int lp, const double *d_h, size_t h_stride, const double *d_zprof,
+                          const int32_t *d_nt, int nz, const double *zout, double *d_tau, void *stream);
 
 /* The scratch of the streamed solver (level grids beyond 64 levels) is kept by the library when a context is destroyed and
  * handed to the next context that needs one (at most 8 buffers and 8 GiB per process): a context per wavelength would
@@ -230,7 +238,8 @@ int  sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table, const int
  *  d_out_scal[nseg][SOSGPU_SCAL_BASE + N]:
  *      [0..2] sum aik*{TDIFMUS, EMOINS, EPLUS}     [3..5] sum aik*exp(-{TTOT_TRONC, TTOT_VRAI, TAUOUT})
  *      [6]    sum aik        [7] max norders       [8] -(min norders): > 0 when a bin of the segment failed
- *      [9]    0              [10..10+N) sum aik*TDIFMUG(j)     (SOS_AGGREGATE.F:452-459)
+ *      [9]    0 (sosgpu_level_transmission, queued behind this call, puts sum aik*exp(-tau_vrai(z)) of an output slot here)
+ *      [10..10+N) sum aik*TDIFMUG(j)     (SOS_AGGREGATE.F:452-459)
  *   Across GPUs elements 7 and 8 combine with MAX, all others (and d_out_rec) with SUM; the -ln of the three
  *   transmissions (SOS_AGGREGATE.F:467-488) is applied afterwards (sosgpu_reduce does all of this).
  */
@@ -238,6 +247,17 @@ int  sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table, const int
 int  sosgpu_aggregate(sosgpu_ctx *cx, int nb, int nseg, const int32_t *d_seg, const double *d_aik,
                       const double *d_rec, const int32_t *d_norders, const double *d_flux, const double *d_scal,
                       const double *d_tdifmug, double *d_out_rec, double *d_out_scal, void *stream);
+/* Band transmission of a per-slot optical depth (the untruncated depth down to an output altitude, sosgpu_output_depths on
+ * d_hvrai): for slot k = 0..nz-1 and segment g, sum_b aik[b] exp(-d_tau[k][b]) over the bins of the segment, written into
+ * element [9] of the scalar block at d_out_scal + k * slot_stride + g * block_width (doubles; block_width =
+ * SOSGPU_SCAL_BASE + N of the blocks sosgpu_aggregate wrote, slot_stride >= nseg * block_width when nz > 1).  Bins with
+ * norders < 0 are skipped, and the sum has sosgpu_aggregate's shape (per-thread striding, fixed tree): a slot whose depth is
+ * TTOT_VRAI gets the bits of element [4].  Queue it on the stream of the slots' sosgpu_aggregate calls, behind them (they
+ * write 0 there); the element then sums across GPUs like its neighbours.  One launch for all slots and segments; nb = 0
+ * queues nothing.  No context is needed. */
+int  sosgpu_level_transmission(int device, int nb, int nseg, const int32_t *d_seg, const double *d_aik, const int32_t *d_norders,
+                               int nz, const double *d_tau, double *d_out_scal, size_t slot_stride, int block_width,
+                               void *stream);
 
 /* Cross-GPU step of SOS_AGGREGATE for callers without torch.distributed (C / Fortran hosts): one RCCL
  * all-reduce (ncclDouble, ncclSum) over xGMI of the packed buffer d_buf[nseg][(iborm_max+1)*3*W + SOSGPU_SCAL_BASE + N]
@@ -388,6 +408,15 @@ int  sosgpu_profile(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, dou
                     double a_tronc, double piz, double piztr, double zout, int lp,
                     double *d_prof, int32_t *d_nt, int32_t *d_iborm, double *d_zprof,
                     int32_t *d_jout, double *d_zz, double *d_scal, const double *d_nogas, void *stream);
+/* sosgpu_profile with one more output: d_hvrai[nb][lp] (device, NULL = sosgpu_profile), the cumulative optical depth H of
+ * every level as the PROFIL file gives it, BEFORE the truncation rescale of SOS.F:521-543 -- the untruncated depth, of which
+ * d_scal keeps the last entry only (d_hvrai[b][nt] = TTOT_VRAI); zeros above nt, and the row of a flagged bin (nt = -1) is
+ * left as passed.  Every other output has the bits of sosgpu_profile. */
+int  sosgpu_profile_true(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, double ha, int absprofil,
+                         int nblev, const double *d_altabs, const double *d_tabs,
+                         double a_tronc, double piz, double piztr, double zout, int lp,
+                         double *d_prof, int32_t *d_nt, int32_t *d_iborm, double *d_zprof,
+                         int32_t *d_jout, double *d_zz, double *d_scal, const double *d_nogas, double *d_hvrai, void *stream);
 
 /* Head start for sosgpu_profile (optional).  The level placement of a wavelength's no-gas profile is a serial chain of about a
  * millisecond on one wavefront and needs (tr, hr, ta, ha) only: a driver can queue it here as soon as it knows them -- before it
@@ -448,6 +477,12 @@ int  sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, i
                              const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
                              void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
                              double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal, int *bad_wl, void *stream);
+/* ... with d_hvrai[nb][lp] for the concatenated bins, as sosgpu_profile_true (NULL = sosgpu_profile_spectrum) */
+int  sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
+                                  const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
+                                  void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
+                                  double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal, int *bad_wl, double *d_hvrai,
+                                  void *stream);
 
 /* Replaces the calls `CALL COEFF_ABS_CKD` of SOS_ABSPROFILE's gas and layer loops (src/SOS_ABSPROFILE.F:325-353; the routine:
  * src/SOS_SUB_TRS.F:171-393) for MANY wavelengths in one launch: k_i of every (gas, exponential term) table of every

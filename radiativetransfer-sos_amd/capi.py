@@ -25,6 +25,7 @@ EXPORTS = [
     "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes", "sosgpu_debug_solve_plan",
     "sosgpu_noyaux_spectrum", "sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes",
     "sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes", "sosgpu_debug_stage_blocks",
+    "sosgpu_profile_true", "sosgpu_profile_spectrum_true", "sosgpu_output_depths", "sosgpu_level_transmission",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -152,6 +153,10 @@ def lib():
         L.sosgpu_os_solve_levels.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.sosgpu_output_levels.restype = i32
         L.sosgpu_output_levels.argtypes = [vp, i32, i32, vp, vp, vp, i32, C.POINTER(dbl), vp, vp, vp, vp]
+        L.sosgpu_output_depths.restype = i32
+        L.sosgpu_output_depths.argtypes = [i32, i32, i32, vp, C.c_size_t, vp, vp, i32, C.POINTER(dbl), vp, vp]
+        L.sosgpu_level_transmission.restype = i32
+        L.sosgpu_level_transmission.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, C.c_size_t, i32, vp]
         L.sosgpu_trim.restype = i32
         L.sosgpu_trim.argtypes = []
         L.sosgpu_ctx_table_entry_bytes.restype = C.c_size_t
@@ -193,6 +198,8 @@ def lib():
         L.sosgpu_profile.restype = i32
         L.sosgpu_profile.argtypes = [vp, i32, dbl, dbl, dbl, dbl, i32, i32, vp, vp, dbl, dbl, dbl, dbl, i32,
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sosgpu_profile_true.restype = i32
+        L.sosgpu_profile_true.argtypes = L.sosgpu_profile.argtypes[:-1] + [vp, vp]
         L.sosgpu_profile_nogas.restype = i32
         L.sosgpu_profile_nogas.argtypes = [i32, dbl, dbl, dbl, dbl, vp, vp]
         L.sosgpu_profile_table_entry_bytes.restype = C.c_size_t
@@ -202,6 +209,8 @@ def lib():
         L.sosgpu_profile_spectrum.restype = i32
         L.sosgpu_profile_spectrum.argtypes = [i32, i32, vp, i32, vp, vp, vp, C.c_size_t, i32, i32, vp, vp, vp, vp, vp, vp, vp,
                                               vp, vp, vp, C.POINTER(i32), vp]
+        L.sosgpu_profile_spectrum_true.restype = i32
+        L.sosgpu_profile_spectrum_true.argtypes = L.sosgpu_profile_spectrum.argtypes[:-1] + [vp, vp]
         L.sosgpu_ckd_table_entry_bytes.restype = C.c_size_t
         L.sosgpu_ckd_table_entry_bytes.argtypes = []
         L.sosgpu_ckd_layer_tables.restype = i32

@@ -63,6 +63,21 @@ __global__ void k_aggregate_final(int nel, int nchunk, const double *partial, do
 // then sum aik*TDIFMUG(j), j = 1..N (SOS_AGGREGATE.F:452-459; zero when no per-bin TDIFMUG is given).
 // Elements 7 and 8 combine across ranks with MAX, everything else with SUM.
 #define SCB 10
+// The two pieces k_aggregate_scal and k_level_transmission share, so that equal depths give equal bits: the term of a bin in a
+// band transmission, and the fixed-shape tree over the 256 per-thread partials (columns in MAXMASK combine with MAX).
+__device__ __forceinline__ double transmission_term(double w, double tau) { return w * exp(-tau); }
+
+template <int NC, unsigned MAXMASK>
+__device__ __forceinline__ void tree256(double (*sm)[NC], const int t)
+{
+    for (int st = 128; st > 0; st >>= 1) {
+        if (t < st)
+            for (int i = 0; i < NC; i++)
+                sm[t][i] = ((MAXMASK >> i) & 1u) ? fmax(sm[t][i], sm[t + st][i]) : sm[t][i] + sm[t + st][i];
+        __syncthreads();
+    }
+}
+
 __global__ void k_aggregate_scal(int n, const int32_t *seg, const double *aik, const int32_t *norders,
                                  const double *flux, const double *scal, const double *tdifmug, double *out)
 {
@@ -83,19 +98,14 @@ __global__ void k_aggregate_scal(int n, const int32_t *seg, const double *aik, c
         a[0] = a[0] + w * scal[4 * b + 0];
         a[1] = a[1] + w * flux[2 * b + 0];
         a[2] = a[2] + w * flux[2 * b + 1];
-        a[3] = a[3] + w * exp(-scal[4 * b + 1]);
-        a[4] = a[4] + w * exp(-scal[4 * b + 2]);
-        a[5] = a[5] + w * exp(-scal[4 * b + 3]);
+        a[3] = a[3] + transmission_term(w, scal[4 * b + 1]);
+        a[4] = a[4] + transmission_term(w, scal[4 * b + 2]);
+        a[5] = a[5] + transmission_term(w, scal[4 * b + 3]);
         a[6] = a[6] + w;
     }
     for (int i = 0; i < SCB; i++) sm[t][i] = a[i];
     __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (t < st)
-            for (int i = 0; i < SCB; i++)
-                sm[t][i] = (i == 7 || i == 8) ? fmax(sm[t][i], sm[t + st][i]) : sm[t][i] + sm[t + st][i];
-        __syncthreads();
-    }
+    tree256<SCB, (1u << 7) | (1u << 8)>(sm, t);
     const int sw = SCB + n;
     if (t < SCB) out[(size_t)sw * g + t] = sm[0][t];
     // TDIFMUG(j): one thread per direction, bins in serial order (SOS_AGGREGATE.F:455-458)
@@ -106,6 +116,33 @@ __global__ void k_aggregate_scal(int n, const int32_t *seg, const double *aik, c
                 if (norders[b] >= 0) acc = acc + aik[b] * tdifmug[(size_t)b * n + j];
         out[(size_t)sw * g + SCB + j] = acc;
     }
+}
+
+// Band transmission of a per-slot depth (sosgpu_level_transmission): workgroup (g, k) forms sum aik(b) exp(-tau[k][b]) over the
+// bins of segment g -- k_aggregate_scal's striding, term and tree, so a slot whose depth is TTOT_VRAI repeats element [4] bit
+// for bit -- and stores it into element [9] of slot k's block of the segment, which k_aggregate_scal left 0.
+__global__ __launch_bounds__(256) void k_level_transmission(int nb, const int32_t *seg, const double *aik, const int32_t *norders,
+                                                            const double *tau, double *out, size_t slot_stride, int sw)
+{
+    __shared__ double sm[256][1];
+    const int g = blockIdx.x, k = blockIdx.y, t = threadIdx.x;
+    const int b0 = seg[g], b1 = seg[g + 1];
+    const double *tk = tau + (size_t)k * nb;
+    double a = 0.;
+    for (int b = b0 + t; b < b1; b += 256) {
+        if (norders[b] < 0) continue;               // failed bin: no contribution, as in k_aggregate_scal
+        a = a + transmission_term(aik[b], tk[b]);
+    }
+    sm[t][0] = a;
+    __syncthreads();
+    tree256<1, 0u>(sm, t);
+    if (t == 0) out[(size_t)k * slot_stride + (size_t)sw * g + 9] = sm[0][0];
+}
+
+void launch_level_transmission(int nb, int nseg, const int32_t *d_seg, const double *d_aik, const int32_t *d_norders, int nz,
+                               const double *d_tau, double *d_out_scal, size_t slot_stride, int block_width, hipStream_t st)
+{
+    k_level_transmission<<<dim3(nseg, nz), 256, 0, st>>>(nb, d_seg, d_aik, d_norders, d_tau, d_out_scal, slot_stride, block_width);
 }
 
 void launch_aggregate(const SosDev &cx, int nseg, const int32_t *d_seg, const double *d_aik,

@@ -845,6 +845,22 @@ extern "C" int sosgpu_output_levels(sosgpu_ctx *cx, int nb, int lp, const double
     return SOSGPU_OK;
 }
 
+extern "C" int sosgpu_output_depths(int device, int nb, int lp, const double *d_h, size_t h_stride, const double *d_zprof,
+                                    const int32_t *d_nt, int nz, const double *zout, double *d_tau, void *stream)
+{
+    if (nb < 0 || lp < 2 || !d_h || h_stride < (size_t)lp || !d_zprof || !d_nt || !zout || !d_tau) return SOSGPU_E_ARG;
+    if (nz < 1 || nz > SOSGPU_MAX_OUTPUT_LEVELS) return SOSGPU_E_ARG;
+    if (nb == 0) return SOSGPU_OK;
+    if (const int rc = use_device(device)) return rc;
+    OutputDepthArgs a;
+    a.nb = nb; a.lp = lp; a.nz = nz; a.h_stride = h_stride;
+    for (int k = 0; k < SOSGPU_MAX_OUTPUT_LEVELS; k++) a.zout[k] = k < nz ? zout[k] : -1.0;
+    a.h = d_h; a.zprof = d_zprof; a.nt = d_nt; a.tau = d_tau;
+    launch_output_depths(a, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
 extern "C" size_t sosgpu_ctx_table_entry_bytes(void) { return sizeof(SosDev); }
 
 extern "C" int sosgpu_ctx_table(sosgpu_ctx *const *ctxs, int nctx, void *d_table, void *stream)
@@ -966,6 +982,22 @@ extern "C" int sosgpu_aggregate(sosgpu_ctx *cx, int nb, int nseg, const int32_t 
                      nb_single, cx->agg_partial, max_chunks);
     HIPCHK(hipGetLastError());
     note_stream(cx, st);
+    return SOSGPU_OK;
+}
+
+extern "C" int sosgpu_level_transmission(int device, int nb, int nseg, const int32_t *d_seg, const double *d_aik,
+                                         const int32_t *d_norders, int nz, const double *d_tau, double *d_out_scal,
+                                         size_t slot_stride, int block_width, void *stream)
+{
+    if (nb < 0 || nseg < 1 || nseg > 65535 || !d_seg || !d_aik || !d_norders || !d_tau || !d_out_scal) return SOSGPU_E_ARG;
+    if (nz < 1 || nz > SOSGPU_MAX_OUTPUT_LEVELS || block_width < SOSGPU_SCAL_BASE) return SOSGPU_E_ARG;
+    if (nz > 1 && slot_stride < (size_t)nseg * (size_t)block_width) return SOSGPU_E_ARG;      // slots would overlap
+    if (nb == 0) return SOSGPU_OK;          // empty shard of a band: sosgpu_aggregate's 0 is the neutral element
+    if (nseg > nb) return SOSGPU_E_ARG;
+    if (const int rc = use_device(device)) return rc;
+    launch_level_transmission(nb, nseg, d_seg, d_aik, d_norders, nz, d_tau, d_out_scal, slot_stride, block_width,
+                              (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return SOSGPU_OK;
 }
 
@@ -1398,11 +1430,12 @@ int profile_nogas_grid(double tr, double ta, double *t_first, double *t_layer)
 }
 }  // namespace
 
-extern "C" int sosgpu_profile(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, double ha, int absprofil,
-                              int nblev, const double *d_altabs, const double *d_tabs,
-                              double a_tronc, double piz, double piztr, double zout, int lp,
-                              double *d_prof, int32_t *d_nt, int32_t *d_iborm, double *d_zprof,
-                              int32_t *d_jout, double *d_zz, double *d_scal, const double *d_nogas, void *stream)
+extern "C" int sosgpu_profile_true(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, double ha, int absprofil,
+                                   int nblev, const double *d_altabs, const double *d_tabs,
+                                   double a_tronc, double piz, double piztr, double zout, int lp,
+                                   double *d_prof, int32_t *d_nt, int32_t *d_iborm, double *d_zprof,
+                                   int32_t *d_jout, double *d_zz, double *d_scal, const double *d_nogas, double *d_hvrai,
+                                   void *stream)
 {
     if (!cx || nb < 1 || lp < 2 || !d_prof || !d_nt || !d_iborm || !d_zprof || !d_scal) return SOSGPU_E_ARG;
     if ((d_jout == nullptr) != (d_zz == nullptr)) return SOSGPU_E_ARG;
@@ -1433,10 +1466,21 @@ extern "C" int sosgpu_profile(sosgpu_ctx *cx, int nb, double tr, double hr, doub
     a.altabs = d_altabs; a.tabs = d_tabs;
     a.z_ng = ngp; a.h_ng = ngp + NG; a.pca_ng = ngp + 2 * NG; a.pcm_ng = ngp + 3 * NG;
     a.prof = d_prof; a.zprof = d_zprof; a.zz = d_zz; a.scal = d_scal; a.nt = d_nt; a.iborm = d_iborm; a.jout = d_jout;
+    a.hvrai = d_hvrai;
     launch_profile(a, st);
     HIPCHK(hipGetLastError());
     note_stream(cx, st);
     return SOSGPU_OK;
+}
+
+extern "C" int sosgpu_profile(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, double ha, int absprofil,
+                              int nblev, const double *d_altabs, const double *d_tabs,
+                              double a_tronc, double piz, double piztr, double zout, int lp,
+                              double *d_prof, int32_t *d_nt, int32_t *d_iborm, double *d_zprof,
+                              int32_t *d_jout, double *d_zz, double *d_scal, const double *d_nogas, void *stream)
+{
+    return sosgpu_profile_true(cx, nb, tr, hr, ta, ha, absprofil, nblev, d_altabs, d_tabs, a_tronc, piz, piztr, zout, lp, d_prof,
+                               d_nt, d_iborm, d_zprof, d_jout, d_zz, d_scal, d_nogas, nullptr, stream);
 }
 
 extern "C" int sosgpu_profile_nogas(int device, double tr, double hr, double ta, double ha, double *d_nogas, void *stream)
@@ -1473,11 +1517,11 @@ extern "C" int sosgpu_profile_nogas_levels(double tr, double ta)
     return profile_nogas_grid(tr, ta, &t_first, &t_layer);
 }
 
-extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
-                                       const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
-                                       void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt,
-                                       int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
-                                       int *bad_wl, void *stream)
+extern "C" int sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
+                                            const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
+                                            void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt,
+                                            int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
+                                            int *bad_wl, double *d_hvrai, void *stream)
 {
     if (bad_wl) *bad_wl = -1;
     if (nwl < 1 || !wl || nb < 1 || lp < 2 || !d_wl_of_bin || !d_table || !d_nogas) return SOSGPU_E_ARG;
@@ -1533,9 +1577,20 @@ extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile
     q.nb = nb; q.nwl = nwl; q.lp = lp; q.nblev = any_gas ? nblev : 0; q.ngl = NG;
     q.tab = d_tab; q.wl_of_bin = d_wl_of_bin; q.gas = d_gas; q.tabs = any_gas ? d_tabs : nullptr; q.nogas = d_nogas;
     q.prof = d_prof; q.zprof = d_zprof; q.zz = d_zz; q.scal = d_scal; q.nt = d_nt; q.iborm = d_iborm; q.jout = d_jout;
+    q.hvrai = d_hvrai;
     launch_profile_table(q, st);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;
+}
+
+extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
+                                       const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
+                                       void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt,
+                                       int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
+                                       int *bad_wl, void *stream)
+{
+    return sosgpu_profile_spectrum_true(device, nwl, wl, nb, d_wl_of_bin, d_ik, d_gas, gas_doubles, nblev, lp, d_table, d_nogas,
+                                        d_tabs, d_prof, d_nt, d_iborm, d_zprof, d_jout, d_zz, d_scal, bad_wl, nullptr, stream);
 }
 
 // COEFF_ABS_CKD of many wavelengths in one launch (ckd.hip): the per-wavelength table and the slot pointers go through one

@@ -34,6 +34,9 @@ void launch_aggregate(const SosDev &cx, int nseg, const int32_t *d_seg, const do
                       const double *d_rec, const int32_t *d_norders, const double *d_flux, const double *d_scal,
                       const double *d_tdifmug, double *d_out_rec, double *d_out_scal, hipStream_t st, int nb_single,
                       double *d_partial, int max_chunks);
+// element [9] of the scalar blocks of nz slots: sum aik * exp(-tau[k][b]) over the bins of every segment (k_level_transmission)
+void launch_level_transmission(int nb, int nseg, const int32_t *d_seg, const double *d_aik, const int32_t *d_norders, int nz,
+                               const double *d_tau, double *d_out_scal, size_t slot_stride, int block_width, hipStream_t st);
 
 void launch_glitter(int n, const double *d_mu, double sig, int os_nb, int os_ns, int os_nm, const double *d_fcoef,
                     int32_t *d_il, double *d_e, float *d_rsurf, hipStream_t st);
@@ -93,6 +96,7 @@ struct ProfileArgs {
     const double *z_ng, *h_ng, *pca_ng, *pcm_ng;  // [nt_ng+1]
     double *prof, *zprof, *zz, *scal;
     int32_t *nt, *iborm, *jout;
+    double *hvrai;                               // [nb][lp] or null: H before the truncation rescale (the untruncated depth)
 };
 void launch_profile(const ProfileArgs &a, hipStream_t st);
 // Table forms of the three profile kernels (sosgpu_profile_spectrum): the bins of MANY wavelengths in one launch per kernel.
@@ -111,6 +115,7 @@ struct ProfileTableArgs {
     const double *gas, *tabs, *nogas;            // packed gas buffer, tabs[nb][nblev] (or null), nogas[nwl][4][ngl]
     double *prof, *zprof, *zz, *scal;
     int32_t *nt, *iborm, *jout;
+    double *hvrai;                               // [nb][lp] or null, as ProfileArgs
 };
 void launch_profile_nogas_table(const ProfileWl *d_tab, int nwl, double *d_ng, int ngl, hipStream_t st);
 void launch_absprofile_table(const ProfileWl *d_tab, int nwl, const int32_t *d_wl_of_bin, int nb, int nlev, const int32_t *d_ik,
@@ -126,6 +131,16 @@ struct OutputLevelArgs {
     double *zz, *tauout;
 };
 void launch_output_levels(const OutputLevelArgs &a, hipStream_t st);
+// the depth of nz altitudes alone, on a depth row of any stride (k_output_depths): tau[nz][nb] from h[b * h_stride + level]
+struct OutputDepthArgs {
+    int nb, lp, nz;
+    size_t h_stride;
+    double zout[SOSGPU_MAX_OUTPUT_LEVELS];
+    const double *h, *zprof;
+    const int32_t *nt;
+    double *tau;
+};
+void launch_output_depths(const OutputDepthArgs &a, hipStream_t st);
 // diagnostic: out[i] = the E15.8 (fmt 0) or F10.5 (fmt 1) round trip of in[i] as k_profile applies it
 void launch_debug_roundtrip(int fmt, size_t n, const double *d_in, double *d_out, hipStream_t st);
 // the no-gas profile of the wavelength into d_ng = z | h | pca | pcm, `ng` doubles each (nt + 1 <= ng used)

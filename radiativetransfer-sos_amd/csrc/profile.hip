@@ -343,7 +343,7 @@ void launch_profile_nogas(double tr, double hr, double ta, double ha, int nt, do
 // One thread per bin, `bpw` bins per wavefront.  The work of a bin is a long serial chain (latency-bound) and very ragged
 // (NT 100...600, bisection depth varies), so a wavefront is deliberately left mostly EMPTY: with few bins per wave the
 // batch spreads over all 1024 SIMDs and a wave only waits for the slowest of its few bins.
-// prof[b][3][lp] <- H, XDEL, YDEL (after the rescale), zprof[b][lp], nt, iborm, jout, zz,
+// prof[b][3][lp] <- H, XDEL, YDEL (after the rescale), zprof[b][lp], nt, iborm, jout, zz, hvrai[b][lp] <- H before the rescale (if asked for),
 // scal[b][4] = {0, TTOT_TRONC, TTOT_VRAI, TAUOUT}; nt[b] = -1 flags a profile that does not fit (IER of the reference).
 // WAVE = true (the form launched): ONE WAVEFRONT per bin.  All 64 lanes run the bin's level loop in lockstep on the same
 // values (stores of one instruction go to one address) and share the work where the time is: SOS_DISC (disc_wave).  A single
@@ -358,6 +358,7 @@ __device__ __forceinline__ void profile_bin_body(const ProfileArgs &a, const int
     const double tr = a.tr, hr = a.hr, ta = a.ta, ha = a.ha;
     double *H = a.prof + (size_t)b * 3 * a.lp, *XD = H + a.lp, *YD = XD + a.lp;
     double *Z = a.zprof + (size_t)b * a.lp;
+    double *HV = a.hvrai ? a.hvrai + (size_t)b * a.lp : nullptr;     // untruncated depth row of the bin (or none)
     // the bin's absorption profile is read thousands of times: keep it (and the altitude grid) in LDS
     GasProf g;
     g.n = a.nblev; g.alt = s_alt; g.tab = nullptr;
@@ -493,6 +494,8 @@ __device__ __forceinline__ void profile_bin_body(const ProfileArgs &a, const int
     const int i0 = WAVE ? (int)(threadIdx.x & 63) : 0, di = WAVE ? 64 : 1;
     if (WAVE) __syncthreads();
     for (int i = i0; i <= nt; i += di) { Z[i] = rt_f10_5(Z[i]); H[i] = rt_e15_8(H[i]); XD[i] = rt_e15_8(XD[i]); YD[i] = rt_e15_8(YD[i]); }
+    // H as the reference reads it back, before the rescale below overwrites it: the untruncated cumulative depth (HV[nt] = TTOT_VRAI)
+    if (HV) for (int i = i0; i <= nt; i += di) HV[i] = H[i];
     if (WAVE) __syncthreads();
     const double ttot_vrai = H[nt];
     // truncation rescale (SOS.F:521-543) and IBORM (:549-550)
@@ -517,6 +520,7 @@ __device__ __forceinline__ void profile_bin_body(const ProfileArgs &a, const int
     for (int i = i0; i <= nt; i += di) { XD[i] = XD[i] * a.piztr; if (XD[i] != 0.) lta = false; }
     if (WAVE) lta = !__any(!lta);
     for (int i = nt + 1 + i0; i < a.lp; i += di) { H[i] = 0.; XD[i] = 0.; YD[i] = 0.; Z[i] = 0.; }
+    if (HV) for (int i = nt + 1 + i0; i < a.lp; i += di) HV[i] = 0.;
     if (WAVE) __syncthreads();
     a.nt[b] = nt;
     a.iborm[b] = lta ? min(2, a.smax) : a.smax;
@@ -568,7 +572,7 @@ __global__ __launch_bounds__(64) void k_profile_table(ProfileTableArgs q)
     a.tr = t.tr; a.hr = t.hr; a.ta = t.ta; a.ha = t.ha; a.a_tronc = t.a_tronc; a.piz = t.piz; a.piztr = t.piztr; a.zout = t.zout;
     a.altabs = gas ? q.gas + t.alt_off : nullptr; a.tabs = gas ? q.tabs : nullptr;
     a.z_ng = ngp; a.h_ng = ngp + q.ngl; a.pca_ng = ngp + 2 * q.ngl; a.pcm_ng = ngp + 3 * q.ngl;
-    a.prof = q.prof; a.zprof = q.zprof; a.scal = q.scal; a.nt = q.nt; a.iborm = q.iborm;
+    a.prof = q.prof; a.zprof = q.zprof; a.scal = q.scal; a.nt = q.nt; a.iborm = q.iborm; a.hvrai = q.hvrai;
     const bool lev = t.zout != -1.0 && q.jout;
     a.jout = lev ? q.jout : nullptr; a.zz = lev ? q.zz : nullptr;
     __shared__ double s_alt[SOS_PROF_NBLEV_MAX];
@@ -676,17 +680,12 @@ void launch_absprofile(int nb, int nlev, int nterm, const int32_t *d_ik, const d
 // (slot, bin).  zout = -1: the standard output (level 0, TAUOUT = H(0)); a flagged bin (NT < 1): 0, 0 and TAUOUT = 0, as
 // k_profile leaves it.  (fp contract is off for this file: the same roundings as k_profile.)
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_output_levels(OutputLevelArgs a)
+// (the statements of one (altitude, bin), shared by k_output_levels and k_output_depths: H is any cumulative-depth row on Z)
+__device__ __forceinline__ double output_level(const double *Z, const double *H, int nt, int lp, double zout, int &j, double &zz)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.nz * a.nb) return;
-    const int k = i / a.nb, b = i - k * a.nb;
-    const int nt = a.nt[b];
-    const double zout = a.zout[k];
-    const double *Z = a.zprof + (size_t)b * a.lp, *H = a.prof + (size_t)b * 3 * a.lp;
-    int j = 0;
-    double zz = 0., tauout = 0.;
-    if (nt >= 1 && nt < a.lp) {
+    double tauout = 0.;
+    j = 0; zz = 0.;
+    if (nt >= 1 && nt < lp) {
         tauout = H[0];
         if (zout != -1.0) {
             j = 1;
@@ -695,7 +694,30 @@ __global__ __launch_bounds__(256) void k_output_levels(OutputLevelArgs a)
             tauout = (1 - zz) * H[j - 1] + zz * H[j];
         }
     }
+    return tauout;
+}
+
+__global__ __launch_bounds__(256) void k_output_levels(OutputLevelArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nz * a.nb) return;
+    const int k = i / a.nb, b = i - k * a.nb;
+    int j;
+    double zz;
+    const double tauout = output_level(a.zprof + (size_t)b * a.lp, a.prof + (size_t)b * 3 * a.lp, a.nt[b], a.lp, a.zout[k], j, zz);
     a.jout[i] = j; a.zz[i] = zz; a.tauout[i] = tauout;
+}
+
+// The depth alone, on a depth row of any stride (sosgpu_output_depths): h_stride = lp for the untruncated rows k_profile
+// exports (hvrai), 3 lp for the H row of prof -- where it returns k_output_levels' tauout bit for bit.
+__global__ __launch_bounds__(256) void k_output_depths(OutputDepthArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nz * a.nb) return;
+    const int k = i / a.nb, b = i - k * a.nb;
+    int j;
+    double zz;
+    a.tau[i] = output_level(a.zprof + (size_t)b * a.lp, a.h + (size_t)b * a.h_stride, a.nt[b], a.lp, a.zout[k], j, zz);
 }
 
 // Diagnostic (sosgpu_debug_roundtrip): the register form of the PROFIL file's decimal round trip over an array, one thread per
@@ -716,4 +738,10 @@ void launch_output_levels(const OutputLevelArgs &a, hipStream_t st)
 {
     const int n = a.nz * a.nb;
     k_output_levels<<<(n + 255) / 256, 256, 0, st>>>(a);
+}
+
+void launch_output_depths(const OutputDepthArgs &a, hipStream_t st)
+{
+    const int n = a.nz * a.nb;
+    k_output_depths<<<(n + 255) / 256, 256, 0, st>>>(a);
 }

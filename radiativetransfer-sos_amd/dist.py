@@ -86,9 +86,11 @@ def all_reduce_partial(buf, n_scal, group=None):
 def finish_scalars(scal):
     """scal [nseg][10+N] (summed over all bins/ranks) -> dict of per-segment results as SOS_AGGREGATE leaves
     them: TDIFMUS, EMOINS, EPLUS, TTOT_TRONC, TTOT_VRAI, TAUOUT (-ln applied, SOS_AGGREGATE.F:467-488), sum(AIK),
-    n_orders, min_orders (< 0: a bin failed, the reference's IER = -1), TDIFMUG[N]."""
+    n_orders, min_orders (< 0: a bin failed, the reference's IER = -1), TDIFMUG[N]; tauvrai_out = -ln of element 9, the
+    untruncated optical depth down to the slot's output altitude where sosgpu_level_transmission wrote it (inf where not)."""
     s = scal.detach().cpu().numpy() if isinstance(scal, torch.Tensor) else np.asarray(scal)
     with np.errstate(divide="ignore"):
         return dict(tdifmus=s[:, 0], emoins=s[:, 1], eplus=s[:, 2], ttot_tronc=-np.log(s[:, 3]),
                     ttot_vrai=-np.log(s[:, 4]), tauout=-np.log(s[:, 5]), sum_aik=s[:, 6],
-                    n_orders=s[:, 7].astype(np.int32), min_orders=(-s[:, 8]).astype(np.int64), tdifmug=s[:, 10:])
+                    n_orders=s[:, 7].astype(np.int32), min_orders=(-s[:, 8]).astype(np.int64), tdifmug=s[:, 10:],
+                    tauvrai_out=-np.log(s[:, 9]))

@@ -112,6 +112,8 @@ OUTPUT_NAMES = ["nblum", "ind_angout", "phi", "vza", "sca_ang_up", "i_up", "q_up
 
 # columns of the per-altitude flux rows of sos_proc_levels / sos_spectrum_levels with fluxes=True (_level_flux_row)
 LEVEL_FLUX_NAMES = ["flux_dir_down_tronc", "flux_diff_down_tronc", "flux_tot_down", "flux_diff_up", "flux_net"]
+# ... with split=True: the down-going flux split into the true direct beam and the true diffuse light at the altitude
+LEVEL_FLUX_SPLIT_NAMES = LEVEL_FLUX_NAMES + ["flux_dir_down", "flux_diff_down"]
 
 
 class SosProcError(RuntimeError):
@@ -928,7 +930,7 @@ def _profiles_deferrable(tr, hr, ta, ha):
 
 
 def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False,
-             device_gas_tables=False, defer_operators=False):
+             device_gas_tables=False, defer_operators=False, true_depth=False):
     """Everything of one SOS_PROC call up to the CKD bin loop (SOS_PROC.F:1310-3458): parameter checks, SOS_ANGLES,
     SOS_AEROSOLS, SOS_SURFACE, SOS_PREPA_ABSPROFILE, SOS_PREPA_OS, and the profiles of every bin of the band on the device
     (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Returns a _Plan whose `ctx` the caller closes.
@@ -942,6 +944,8 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     request solver.make_profiles_spectrum takes, and the pass makes the profiles of a whole part in three launches.
     device_gas_tables (with defer_profiles): a deferred gas wavelength hands over its `prep` instead of the layer tables xk --
     COEFF_ABS_CKD then runs on the device for the whole part (sosgpu_ckd_layer_tables) and absorption.layer_tables not at all.
+    true_depth (the levels calls with split=True): the bins also carry `hvrai`, the cumulative optical depth of every level
+    before the truncation rescale (SosContext.make_profiles(true_depth=True); the aerosol-layer profile uploads its own).
     defer_operators (_spectrum_pass only): the context comes back unbuilt (SosContext(build=False)) and the pass fills the
     operator tables of a whole part in one solver.build_operators call -- unless this function uses the operators itself, which
     only a -SOS.Trans call does (diffuse_transmissions below)."""
@@ -1156,6 +1160,7 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
         tabs_flux = None                              # TAUABS of the band's last bin (Flux file): host array or [.][nlev] device tensor
         request = None                                # deferred: what solver.make_profiles_spectrum needs of this wavelength
         common = dict(tr=tr, hr=p["hr"], ta=ta, ha=ha, a_tronc=a_tronc, piz=piz, piztr=piztr, zout=zout, smax=ctx.smax)
+        true_kw = dict(true_depth=True) if true_depth else {}      # (split=False: the calls as they were)
         if defer and not use_gas:
             request = dict(common, ik=None, absprofil=7)
             bins, aik = None, np.ones(1)
@@ -1170,16 +1175,17 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
             # of tests/test_profile.py)
             try:
                 bins = ctx.make_profiles(1, tr, p["hr"], ta, ha, None, None, a_tronc=a_tronc, piz=piz, piztr=piztr, zout=zout,
-                                         absprofil=7, nogas=nogas)
+                                         absprofil=7, nogas=nogas, **true_kw)
             except Exception as e:
                 raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
             aik = np.ones(1)
         elif not use_gas:
             h, xdel, ydel, zprof = profile_layer(tr, p["hr"], ta, float(p["zmin"]), float(p["zmax"]))
             ttot_vrai = h[-1]
+            h_kw = dict(hvrai=np.array(h, dtype=np.float64)[None]) if true_depth else {}   # H before the rescale
             h, xdel, ydel, ib = rescale_profile(h, xdel, ydel, a_tronc, piz, piztr, os_nb)   # SOS.F:523-550
             bins = ctx.upload_bins(h[None], xdel[None], ydel[None], iborm=np.array([min(ib, iborm)], dtype=np.int32),
-                                   zout=zout, zprof=zprof[None])
+                                   zout=zout, zprof=zprof[None], **h_kw)
             if zout == -1.0:
                 tauout = h[0]                                                        # SOS.F:567-568
             else:
@@ -1212,7 +1218,7 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
             try:
                 if len(aik):
                     bins = ctx.make_profiles(len(aik), tr, p["hr"], ta, ha, prep["altabs"], tabs, a_tronc=a_tronc, piz=piz,
-                                             piztr=piztr, zout=zout, absprofil=absprofil, nogas=nogas)
+                                             piztr=piztr, zout=zout, absprofil=absprofil, nogas=nogas, **true_kw)
                 else:
                     bins = dict(nb=0, scal=None)
             except Exception as e:
@@ -1268,6 +1274,18 @@ def _level_flux_row(pl, alt, fin, g, e):
     em, ep = float(e[0]), float(e[1])
     tot = em + tdir
     return (tdir, em, tot, ep, tot - ep)
+
+
+def _level_flux_split_row(pl, alt, fin, g, e):
+    """One row of LEVEL_FLUX_SPLIT_NAMES: _level_flux_row's five columns, then the split of the down-going flux as _finish
+    forms it at the ground (SOS_PROC.F:3831-3837), at the altitude: flux_dir_down = exp(-tau_vrai / cos(theta_s)) of the
+    UNTRUNCATED optical depth down to the altitude (fin["tauvrai_out"]; the whole column, fin["ttot_vrai"], for -1) and
+    flux_diff_down = E- + tdir_tronc - flux_dir_down.  The two sum to flux_tot_down to within two roundings of it."""
+    row = _level_flux_row(pl, alt, fin, g, e)
+    cs = math.cos(math.pi * pl.p["tetas"] / 180.0)
+    tau = float(fin["ttot_vrai"][g]) if alt == -1.0 else float(fin["tauvrai_out"][g])
+    tdir_vrai = math.exp(-tau / cs)
+    return row + (tdir_vrai, float(e[0]) + row[0] - tdir_vrai)
 
 
 def _finish(pl, out, rec0, fin, g=0, block=None):
@@ -1330,15 +1348,16 @@ def sos_proc(aer_phase=None, device=0, **kw):
     return _band_call("sos_proc", kw, aer_phase, device)[0]
 
 
-def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False):
+def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False, split=False):
     """One band for sos_proc (alts None: solve_band, the kernels without output slots) or sos_proc_levels (alts: the K
     altitudes, solve_band_levels): prepare, let the ranks agree on an error flag, solve, SOS_TRPHI and _finish per output.
-    Returns the list of 23-tuples (one without alts); with fluxes (alts only) the pair (that list, flux rows [K][5])."""
+    Returns the list of 23-tuples (one without alts); with fluxes (alts only) the pair (that list, flux rows [K][5], or
+    [K][7] with split: the bins then carry the untruncated depth rows and the aggregates their band transmission)."""
     from . import solver
     from .solver import SosBinError
     pl, levels, err = None, None, None
     try:
-        pl = _prepare(kw, aer_phase, device, shard_bins=True)
+        pl = _prepare(kw, aer_phase, device, shard_bins=True, **(dict(true_depth=True) if split else {}))
         if alts is not None:
             try:
                 levels = pl.ctx.output_levels(pl.bins, alts)
@@ -1381,18 +1400,23 @@ def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False):
         if not fluxes:
             return tuples
         e = flux_dev.cpu().numpy()                 # (complete: it was queued ahead of the recompositions just downloaded)
-        return tuples, np.array([_level_flux_row(pl, alts[k], fin, k, e[k]) for k in range(len(rec))], dtype=np.float64)
+        row = _level_flux_split_row if split else _level_flux_row
+        return tuples, np.array([row(pl, alts[k], fin, k, e[k]) for k in range(len(rec))], dtype=np.float64)
     finally:
         pl.ctx.close()
 
 
-def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False):
+def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False, split=False):
     """The argument rules of the output-slot entry points, checked before any device work: 1 to 16 altitudes, each passing the
     -SOS.OutputAlt rule (SosProcError 2611), and calls with zout = -1 and no -SOS_Main.ResRoot (ValueError).  Returns the
-    altitudes as floats.  fluxes: the entry point's flag, a bool (ValueError)."""
+    altitudes as floats.  fluxes, split: the entry point's flags, bools, split only with fluxes (ValueError)."""
     from . import capi
     if not isinstance(fluxes, (bool, np.bool_)):
         raise ValueError("%s: fluxes must be True or False, got %r" % (fn, fluxes))
+    if not isinstance(split, (bool, np.bool_)):
+        raise ValueError("%s: split must be True or False, got %r" % (fn, split))
+    if split and not fluxes:
+        raise ValueError("%s: split=True adds columns to the flux rows: it needs fluxes=True" % fn)
     alts = [float(z) for z in altitudes]
     if not 1 <= len(alts) <= capi.MAX_OUTPUT_LEVELS:
         raise ValueError("%s: 1 to %d altitudes, got %d" % (fn, capi.MAX_OUTPUT_LEVELS, len(alts)))
@@ -1410,7 +1434,7 @@ def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False):
     return alts
 
 
-def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, **kw):
+def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, split=False, **kw):
     """sos_proc for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output) at once: ONE
     profile, context and solve, whose K output slots capture the field at each altitude (sosgpu_os_solve_levels), then
     one aggregate and SOS_TRPHI per altitude.  Returns a list of K 23-tuples in the order of `altitudes`; element k equals
@@ -1431,12 +1455,24 @@ def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, **kw):
     elements 20 and 21 of that altitude's 23-tuple (to rounding; with surface matrices, -SURF.Type 1 and 3..7, flux_diff_up
     agrees with element 21 to some 1e-9 only, as the reference's EPLUS and its own record do); its flux_net, ground minus top,
     is the net flux of no altitude (the net flux at the ground takes flux_diff_up of the 0 km row, that at the top flux_tot_down
-    of the 120 km row).  The split of the down-going flux into TRUE direct and TRUE diffuse parts at
-    an interior altitude (elements 18 and 19 of the tuple, given at the ground only) needs the untruncated optical depth down
-    to z, which the profile stage does not export: not provided.  With the default the return value, the launches and the
-    bits are unchanged."""
-    alts = _levels_arguments("sos_proc_levels", altitudes, [kw], fluxes)
-    return _band_call("sos_proc_levels", kw, aer_phase, device, alts, bool(fluxes))
+    of the 120 km row).  With the default the return value, the launches and the bits are unchanged.
+
+    split=True (a bool, and only with fluxes=True: ValueError otherwise, before any device work): flux is [K][7], columns
+    LEVEL_FLUX_SPLIT_NAMES -- the five above, unchanged, then the split of the down-going flux into the TRUE direct beam and the
+    TRUE diffuse light at z, which elements 18 and 19 of the tuple give at the ground only (SOS_PROC.F:3831-3837):
+    flux_dir_down = exp(-tau_vrai(z) / cos(theta_s)) and flux_diff_down = E-(z) + flux_dir_down_tronc - flux_dir_down, with
+    tau_vrai(z) the UNTRUNCATED optical depth down to z (the whole column for -1: that row restates elements 18 and 19).  The
+    profile stage exports the depth of every level before the truncation rescale (sosgpu_profile_true), the depth at z is
+    taken from it as TAUOUT is from the rescaled one (sosgpu_output_depths), and the band value -ln sum aik exp(-tau_vrai)
+    comes from one more launch behind the aggregates (sosgpu_level_transmission), inside the existing all-reduce and download.
+    Convention: the depth at z is the reference's own LINEAR interpolation between the two profile levels that bracket z,
+    the one it uses for TAUOUT and for the field.  In a strongly absorbing CKD bin (gas depth above 1.5) everything below
+    the limit altitude is ONE layer, and the interpolated depth there is far from the analytic one (up to 1.3 in optical
+    depth in such a bin of the O2 A band): that is the reference's resolution at such altitudes, kept so that
+    flux_dir_down + flux_diff_down equals flux_tot_down.  Without forward-peak truncation (a_tronc = 0) flux_dir_down equals
+    flux_dir_down_tronc."""
+    alts = _levels_arguments("sos_proc_levels", altitudes, [kw], fluxes, split)
+    return _band_call("sos_proc_levels", kw, aer_phase, device, alts, bool(fluxes), bool(split))
 
 
 def sos_proc_many(kwargs_list, n_workers=8, device=0):
@@ -1580,10 +1616,12 @@ def _first_failed_index(index, device):
     return int(t.item())
 
 
-def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False):
+def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False,
+                   split=False):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
-    launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop."""
+    launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop.
+    split (with fluxes): the bins carry the untruncated depth rows, the levels `tauvrai`, and the flux rows two more columns."""
     import time
     import torch
     from . import capi, solver
@@ -1621,6 +1659,9 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
         def solve_single(pl):
             out = pl.ctx.solve_levels(pl.bins, pl.levels) if pl.bins["nb"] else None
             return pl.ctx.aggregate_levels(out, pl.levels, pl.aik, scal=pl.bins.get("scal"), tdifmug=pl.tdifmug)
+    true_kw = dict(true_depth=True) if split else {}    # (split=False: the calls as they were)
+    flux_row, flux_names = (_level_flux_split_row, LEVEL_FLUX_SPLIT_NAMES) if split else (_level_flux_row, LEVEL_FLUX_NAMES)
+    level_keys = ("jout", "zz", "tauout") + (("tauvrai",) if split else ())
     rank, world = _dist_rank_world()
     if world > 1:
         mine = [int(i) for i in _dist.balanced_shards(spectrum_costs(kwargs_list), world)[rank]]
@@ -1686,7 +1727,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                         with torch.cuda.stream(side[k % len(side)]):
                             pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
                                           aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles, device_gas_tables=device_tables,
-                                          defer_operators=batch_operators)
+                                          defer_operators=batch_operators, **true_kw)
                             pl.writes_files = True
                             pl.index = i
                             plans.append(pl)
@@ -1703,7 +1744,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                         where = deferred[0].index
                         info = {}
                         try:
-                            made = solver.make_profiles_spectrum([pl.profile_request for pl in deferred], dev, part=info)
+                            made = solver.make_profiles_spectrum([pl.profile_request for pl in deferred], dev, part=info,
+                                                                 **true_kw)
                         except Exception as e:
                             if info.get("bad") is not None:
                                 where = deferred[info["bad"]].index
@@ -1716,8 +1758,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                             pl.bins, pl.tabs_flux, pl.profile_part = made[g], info["tabs"][g], info
                             if lv is not None:
                                 b0, b1 = int(info["seg"][g]), int(info["seg"][g + 1])
-                                pl.levels = dict(nz=lv["nz"], jout=lv["jout"][:, b0:b1], zz=lv["zz"][:, b0:b1],
-                                                 tauout=lv["tauout"][:, b0:b1])
+                                pl.levels = dict(nz=lv["nz"], **{k: lv[k][:, b0:b1] for k in level_keys})
                     for st in side:
                         main_st.wait_stream(st)
                     # the operators of the part's unbuilt contexts, grouped and single alike (after the wait: the surface
@@ -1758,7 +1799,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     for pl in single:
                         where = pl.index
                         if alts is not None and pl.levels["jout"] is not None and not pl.levels["jout"].is_contiguous():
-                            pl.levels = dict(pl.levels, **{k: pl.levels[k].contiguous() for k in ("jout", "zz", "tauout")})
+                            pl.levels = dict(pl.levels, **{k: pl.levels[k].contiguous() for k in level_keys})
                         rec, scal = solve_single(pl)
                         solved.append(([pl], rec, scal, None))
                     t0 = time.perf_counter()
@@ -1808,8 +1849,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     e = flux_dev.cpu().numpy()                  # (complete: queued ahead of the recompositions just downloaded)
                     for j, (pl, k, r, f, g) in enumerate(todo):
                         if flux_rows[pl.index] is None:
-                            flux_rows[pl.index] = np.empty((nz, len(LEVEL_FLUX_NAMES)))
-                        flux_rows[pl.index][k] = _level_flux_row(pl, alts[k], f, g, e[j])
+                            flux_rows[pl.index] = np.empty((nz, len(flux_names)))
+                        flux_rows[pl.index][k] = flux_row(pl, alts[k], f, g, e[j])
                     t5 = time.perf_counter()
                     tm["fluxes"] += t5 - t4
                     t4 = t5
@@ -1906,7 +1947,7 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
 
 
 def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16,
-                        parts=4, fluxes=False):
+                        parts=4, fluxes=False, split=False):
     """sos_spectrum for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output): every wavelength is
     prepared once, ALL bins of a group of wavelengths go through ONE launch of the fused solver per kernel variant with K output
     slots each (sosgpu_os_solve_multi_levels), then K segmented aggregates (each altitude with its own TAUOUT) and K azimuth
@@ -1928,15 +1969,23 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
 
     fluxes=True (a bool, ValueError otherwise, before any device work): returns (spec, flux) with spec the list above and
     flux[i] the numpy array [K][5] of call i, the irradiances at each altitude as sos_proc_levels(..., fluxes=True) describes
-    them (columns LEVEL_FLUX_NAMES; the true direct / diffuse split at an interior altitude is not provided).  The flux pairs
+    them (columns LEVEL_FLUX_NAMES).  The flux pairs
     of ALL (wavelength, altitude) jobs of a chunk are computed by one launch (sosgpu_level_flux_spectrum through
     solver.level_flux_many) queued behind the chunk's aggregates, and come down after the recompositions without a wait of
     their own; `timings` gains the host phase "fluxes".  With gather=True the rows travel with the compacted tuples, so
     every rank returns the same arrays; gather=False leaves None in the slots of other ranks.  With the default the return
-    value, the launches and the bits are unchanged."""
-    alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes)
+    value, the launches and the bits are unchanged.
+
+    split=True (a bool, and only with fluxes=True: ValueError otherwise, before any device work): flux[i] is [K][7], columns
+    LEVEL_FLUX_SPLIT_NAMES, the true direct / diffuse split of the down-going flux at each altitude as
+    sos_proc_levels(..., fluxes=True, split=True) describes it, with its convention (the reference's linear interpolation of
+    the untruncated depth between the two levels that bracket z); the rows equal that call's bit for bit.  The profile
+    launches of a part export the untruncated depth rows (sosgpu_profile_spectrum_true), one sosgpu_output_depths launch per
+    part or wavelength gives the depths at the altitudes, and ONE sosgpu_level_transmission launch per solved group (or single
+    wavelength) -- not one per altitude -- puts their band transmissions into the scalar blocks that are downloaded anyway."""
+    alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes, split)
     return _spectrum_pass("sos_spectrum_levels", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
-                          alts, bool(fluxes))
+                          alts, bool(fluxes), bool(split))
 
 
 def write_trans_file(path, tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):

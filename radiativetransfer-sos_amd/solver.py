@@ -114,7 +114,7 @@ def output_levels_host(zprof, altitudes):
 def host_output_levels(bins, altitudes):
     """The `levels` of SosContext.output_levels for bins of upload_bins (host level altitudes zprof_host, or none: standard
     output only), on the device of bins["prof"]: output_levels_host, TAUOUT from the uploaded H as run_sos computes it for
-    one altitude (SOS.F:567-581)."""
+    one altitude (SOS.F:567-581).  Bins uploaded with hvrai (the untruncated H) also get `tauvrai`, by the same statements."""
     alts = [float(z) for z in altitudes]
     nz, nb, d = len(alts), bins["nb"], bins["prof"].device
     if bins.get("zprof_host") is None and any(z != -1.0 for z in alts):
@@ -127,7 +127,16 @@ def host_output_levels(bins, altitudes):
         for b in range(nb):
             j, zzv = int(jh[k, b]), float(zh[k, b])
             th[k, b] = h[b, 0] if alts[k] == -1.0 else (1 - zzv) * h[b, j - 1] + zzv * h[b, j]
-    return dict(nz=nz, jout=_dev_i32(jh, d), zz=_dev_f64(zh, d), tauout=_dev_f64(th, d))
+    levels = dict(nz=nz, jout=_dev_i32(jh, d), zz=_dev_f64(zh, d), tauout=_dev_f64(th, d))
+    if bins.get("hvrai") is not None:
+        hv = bins["hvrai"].cpu().numpy()
+        tv = np.zeros((nz, nb))
+        for k in range(nz):
+            for b in range(nb):
+                j, zzv = int(jh[k, b]), float(zh[k, b])
+                tv[k, b] = hv[b, 0] if alts[k] == -1.0 else (1 - zzv) * hv[b, j - 1] + zzv * hv[b, j]
+        levels["tauvrai"] = _dev_f64(tv, d)
+    return levels
 
 
 class SosContext:
@@ -228,13 +237,15 @@ class SosContext:
         t.update({k: v for k, v in a.items() if v is not None})
         return t
 
-    def upload_bins(self, h, xdel, ydel, nt=None, iborm=None, zout=-1.0, zprof=None, order=None):
+    def upload_bins(self, h, xdel, ydel, nt=None, iborm=None, zout=-1.0, zprof=None, order=None, hvrai=None):
         """Pack per-bin profiles (after the SOS.F rescale) into the device layout of sosgpu_os_solve.
         h/xdel/ydel: [nb][L] arrays (ragged bins: pass nt[nb] and pad).
         order="cost": bins are permuted by decreasing total optical depth before upload (the returned dict holds
         `perm`, with result[i] belonging to input bin perm[i]).  Bins of similar cost then run side by side, drift
         less across Fourier orders and keep re-reading the same source operators from L2 (scheduling only: every
-        bin's result is unchanged)."""
+        bin's result is unchanged).
+        hvrai: optional [nb][L], the cumulative optical depth BEFORE the truncation rescale (the untruncated depth): uploaded
+        as bins["hvrai"][nb][lp], from which output_levels forms the true depth down to each altitude (`tauvrai`)."""
         h = np.atleast_2d(np.asarray(h, dtype=np.float64))
         xdel = np.atleast_2d(np.asarray(xdel, dtype=np.float64))
         ydel = np.atleast_2d(np.asarray(ydel, dtype=np.float64))
@@ -244,6 +255,8 @@ class SosContext:
         if order == "cost":
             perm = np.argsort(-h[np.arange(nb), nt], kind="stable")
             h, xdel, ydel, nt = h[perm], xdel[perm], ydel[perm], nt[perm]
+            if hvrai is not None:
+                hvrai = np.atleast_2d(np.asarray(hvrai, dtype=np.float64))[perm]
             if iborm is not None and np.ndim(iborm):
                 iborm = np.asarray(iborm)[perm]
             if zprof is not None:
@@ -259,9 +272,17 @@ class SosContext:
         if zout != -1.0:
             jout, zz = (x[0] for x in output_levels_host(zprof, [zout]))
         d = self.device
-        return dict(nb=nb, lp=lp, perm=perm, nt=_dev_i32(nt, d), iborm=_dev_i32(iborm, d), prof=_dev_f64(prof, d),
-                    jout=None if jout is None else _dev_i32(jout, d), zz=None if zz is None else _dev_f64(zz, d),
-                    zprof_host=None if zprof is None else np.atleast_2d(np.asarray(zprof, dtype=np.float64)))
+        out = dict(nb=nb, lp=lp, perm=perm, nt=_dev_i32(nt, d), iborm=_dev_i32(iborm, d), prof=_dev_f64(prof, d),
+                   jout=None if jout is None else _dev_i32(jout, d), zz=None if zz is None else _dev_f64(zz, d),
+                   zprof_host=None if zprof is None else np.atleast_2d(np.asarray(zprof, dtype=np.float64)))
+        if hvrai is not None:
+            hv = np.atleast_2d(np.asarray(hvrai, dtype=np.float64))
+            if hv.shape != h.shape:
+                raise ValueError("hvrai must have the shape of h")
+            hp = np.zeros((nb, lp))
+            hp[:, :lmax] = hv
+            out["hvrai"] = _dev_f64(hp, d)
+        return out
 
     def absorption_profiles(self, ik, xk, ro):
         """SOS_ABSPROFILE (SOS_ABSPROFILE.F:325-371) of every CKD bin on the device (sosgpu_absprofile): ik[nb][8] 1-based
@@ -290,13 +311,16 @@ class SosContext:
         return tabs
 
     def make_profiles(self, nb, tr, hr, ta, ha, altabs=None, tabs=None, *, a_tronc=0.0, piz=1.0, piztr=1.0, zout=-1.0,
-                      lp=608, absprofil=1, nogas=None):
+                      lp=608, absprofil=1, nogas=None, true_depth=False):
         """SOS_PROFILE (IPROFIL=1) + SOS_DISC + the SOS.F rescale for nb CKD bins ON THE DEVICE (sosgpu_profile):
         tabs[nb][nblev] is each bin's cumulative gas absorption optical depth on the descending altitude grid
         altabs[nblev] (None: no gas).  Returns the same dict upload_bins returns (ready for solve()), plus `zprof` and
         the per-bin scalars `scal` [nb][4] = {0, TTOT_TRONC, TTOT_VRAI, TAUOUT} that aggregate() takes.
         Bins whose profile needs more than CTE_OS_NT levels come back with nt = -1 (the reference's IER = -1).
-        nogas: the block nogas_profile(tr, hr, ta, ha) queued earlier on this stream (head start), or None."""
+        nogas: the block nogas_profile(tr, hr, ta, ha) queued earlier on this stream (head start), or None.
+        true_depth=True (sosgpu_profile_true): the dict also holds `hvrai` [nb][lp], the cumulative optical depth of every
+        level before the truncation rescale -- the untruncated depth, hvrai[b][nt] = TTOT_VRAI -- from which output_levels
+        forms `tauvrai`; everything else keeps its bits."""
         d = self.device
         t_alt = t_tab = None
         nblev = 0
@@ -308,7 +332,7 @@ class SosContext:
             if t_tab.shape != (nb, nblev):
                 raise ValueError("tabs must be [nb][len(altabs)]")
         # (two cleared blocks instead of seven: a band has 1-125 bins, each fill is a launch)
-        fb = torch.zeros(nb * (4 * lp + 5), dtype=torch.float64, device=d)
+        fb = torch.zeros(nb * (4 * lp + 5) + (nb * lp if true_depth else 0), dtype=torch.float64, device=d)
         ib = torch.zeros(3 * nb, dtype=torch.int32, device=d)
         prof = fb[:nb * 3 * lp].view(nb, 3, lp)
         zprof = fb[nb * 3 * lp:nb * 4 * lp].view(nb, lp)
@@ -317,12 +341,16 @@ class SosContext:
         jout = zz = None
         if zout != -1.0:
             jout = ib[2 * nb:]
-            zz = fb[nb * (4 * lp + 4):]
-        capi.check(capi.lib().sosgpu_profile(self._h, nb, tr, hr, ta, ha, int(absprofil), nblev, _ptr(t_alt), _ptr(t_tab),
-                                             a_tronc, piz, piztr, zout, lp, _ptr(prof), _ptr(nt), _ptr(iborm),
-                                             _ptr(zprof), _ptr(jout), _ptr(zz), _ptr(scal), _ptr(nogas), self._stream()),
-                   "sosgpu_profile")
-        return dict(nb=nb, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=jout, zz=zz, zprof=zprof, scal=scal)
+            zz = fb[nb * (4 * lp + 4):nb * (4 * lp + 5)]
+        args = (self._h, nb, tr, hr, ta, ha, int(absprofil), nblev, _ptr(t_alt), _ptr(t_tab), a_tronc, piz, piztr, zout, lp,
+                _ptr(prof), _ptr(nt), _ptr(iborm), _ptr(zprof), _ptr(jout), _ptr(zz), _ptr(scal), _ptr(nogas))
+        bins = dict(nb=nb, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=jout, zz=zz, zprof=zprof, scal=scal)
+        if true_depth:
+            bins["hvrai"] = fb[nb * (4 * lp + 5):].view(nb, lp)
+            capi.check(capi.lib().sosgpu_profile_true(*args, _ptr(bins["hvrai"]), self._stream()), "sosgpu_profile_true")
+        else:
+            capi.check(capi.lib().sosgpu_profile(*args, self._stream()), "sosgpu_profile")
+        return bins
 
     def solve_band(self, bins, aik, seg=None, group=None, tdifmug=None, reduce=True):
         """The whole per-wavelength bin loop of SOS_PROC (SOS_PROC.F:3459-3594) for bins already on the device
@@ -350,7 +378,10 @@ class SosContext:
         pair, weight and TAUOUT a single-altitude profile gives for each.  Bins of make_profiles: sosgpu_output_levels on the
         device; bins of upload_bins with zprof (the aerosol-layer profile): output_levels_host, TAUOUT from the uploaded H
         as run_sos computes it for one altitude (SOS.F:567-581).  Returns dict(nz, jout[K][nb], zz[K][nb], tauout[K][nb])
-        of device tensors, the `levels` solve_levels takes (no tensors for an empty batch: a rank without bins)."""
+        of device tensors, the `levels` solve_levels takes (no tensors for an empty batch: a rank without bins).
+        Bins that carry `hvrai` (make_profiles(true_depth=True), upload_bins(hvrai=...)) also get `tauvrai`[K][nb], the
+        UNTRUNCATED optical depth down to each altitude: the same level pair and weight applied to hvrai
+        (sosgpu_output_depths), i.e. the reference's linear interpolation between the two levels that bracket z."""
         alts = [float(z) for z in altitudes]
         nz, nb, d = len(alts), bins["nb"], self.device
         if not 1 <= nz <= capi.MAX_OUTPUT_LEVELS:
@@ -364,7 +395,13 @@ class SosContext:
             capi.check(capi.lib().sosgpu_output_levels(self._h, nb, bins["lp"], _ptr(bins["prof"]), _ptr(bins["zprof"]),
                                                        _ptr(bins["nt"]), nz, (C.c_double * nz)(*alts), _ptr(jout), _ptr(zz),
                                                        _ptr(tauout), self._stream()), "sosgpu_output_levels")
-            return dict(nz=nz, jout=jout, zz=zz, tauout=tauout)
+            levels = dict(nz=nz, jout=jout, zz=zz, tauout=tauout)
+            if bins.get("hvrai") is not None:
+                levels["tauvrai"] = torch.empty((nz, nb), dtype=torch.float64, device=d)
+                capi.check(capi.lib().sosgpu_output_depths(d.index or 0, nb, bins["lp"], _ptr(bins["hvrai"]), bins["lp"],
+                                                           _ptr(bins["zprof"]), _ptr(bins["nt"]), nz, (C.c_double * nz)(*alts),
+                                                           _ptr(levels["tauvrai"]), self._stream()), "sosgpu_output_depths")
+            return levels
         return host_output_levels(bins, alts)
 
     def solve_levels(self, bins, levels, out=None):
@@ -499,11 +536,18 @@ class SosContext:
         """aggregate for the K output slots of solve_levels / solve_spectrum_levels: slot k's records out["rec"][k] with that
         altitude's TAUOUT (levels["tauout"][k]) in column 3 of a copy of the per-bin scalars `scal` (zeros when there are
         none); out = None gives the neutral element K times (a rank without bins).  Returns (rec[K][nseg][smax+1][3][W],
-        scal[K][nseg][10+N]) on device; no synchronisation."""
+        scal[K][nseg][10+N]) on device; no synchronisation.
+        levels with `tauvrai` (output_levels of bins that carry hvrai): one more launch behind the K aggregates
+        (sosgpu_level_transmission) puts sum aik exp(-tauvrai[k]) of every slot and segment into element 9 of its scalar
+        block, where it rides the all-reduce and the download of its neighbours (dist.finish_scalars: tauvrai_out)."""
+        true_depth = out is not None and levels.get("tauvrai") is not None
         if out is None:
             parts = [self.aggregate(None, aik) for _ in range(levels["nz"])]
         else:
             nb, d = out["rec"].shape[1], self.device
+            if true_depth:                                  # (the launch below takes the tensors the aggregates take)
+                aik = _dev_f64(aik, d)
+                seg = None if seg is None else _dev_i32(seg, d)
             base = None if scal is None else _dev_f64(scal, d)
             parts = []
             for k in range(levels["nz"]):
@@ -511,7 +555,14 @@ class SosContext:
                 sc[:, 3] = levels["tauout"][k]
                 parts.append(self.aggregate(dict(rec=out["rec"][k], norders=out["norders"], flux=out["flux"]), aik, seg=seg,
                                             scal=sc, tdifmug=tdifmug))
-        return torch.stack([r for r, _ in parts]), torch.stack([s for _, s in parts])
+        o_rec, o_scal = torch.stack([r for r, _ in parts]), torch.stack([s for _, s in parts])
+        if true_depth:
+            seg_t = self._seg_cache[nb] if seg is None else seg
+            nz, nseg, sw = o_scal.shape
+            capi.check(capi.lib().sosgpu_level_transmission(d.index or 0, nb, nseg, _ptr(seg_t), _ptr(aik), _ptr(out["norders"]),
+                                                            nz, _ptr(levels["tauvrai"]), _ptr(o_scal), nseg * sw, sw,
+                                                            self._stream()), "sosgpu_level_transmission")
+        return o_rec, o_scal
 
     def trphi(self, rec, nf, tau, tauout, phis_rad, igli=0, wind=0.0, land=None):
         """SOS_TRPHI + SOS_POLAR for a list of azimuths (radians).  rec: device tensor [>=nf][3][W]
@@ -693,6 +744,9 @@ def concat_bins(bins_list):
                jout=cat("jout") if all(zo) else None, zz=cat("zz") if all(zo) else None)
     if all(b.get("scal") is not None for b in bins_list):
         out["scal"] = cat("scal")
+    if all(b.get("hvrai") is not None for b in bins_list):
+        out["hvrai"] = torch.cat([torch.nn.functional.pad(b["hvrai"], (0, lp - b["lp"])) if b["lp"] < lp else b["hvrai"]
+                                  for b in bins_list]).contiguous()
     cob = _dev_i32(np.repeat(np.arange(len(bins_list), dtype=np.int32), counts), d)
     seg = _dev_i32(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), d)
     return out, cob, seg
@@ -904,7 +958,7 @@ def pack_profile_requests(requests, table_ptr=None):
     return out
 
 
-def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
+def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None, true_depth=False):
     """The profile stage of MANY wavelengths in three launches (sosgpu_profile_spectrum: no-gas profiles, SOS_ABSPROFILE and
     SOS_PROFILE of every bin of every wavelength, each wavefront taking its wavelength's parameters from a device table)
     instead of three per wavelength.  requests: see pack_profile_requests.  One upload (its buf), one cleared output allocation
@@ -917,7 +971,9 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
     sosgpu_ckd_layer_tables over all such requests, on the device-resident CKD files, queued on the same stream ahead of the
     profile kernels and writing straight to the request's xk block: no host interpolation, no upload of xk.  `part` then also
     holds `ckd_status` (int32 device tensor, one entry per such request: absorption.CKD_STATUS_MESSAGES) and `ckd_index` (their
-    indices in requests); without such requests `ckd_status` is None."""
+    indices in requests); without such requests `ckd_status` is None.
+    true_depth=True (sosgpu_profile_spectrum_true): every dict, and part["bins"], also holds `hvrai` (the untruncated depth
+    rows, as SosContext.make_profiles(true_depth=True) returns them), inside the same cleared block."""
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     tables = {}
 
@@ -953,7 +1009,9 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
         # (two cleared blocks for the whole part; the work areas of the launch -- table, no-gas blocks -- ride at the end)
         o_z, o_s, o_zz, o_t = nb * 3 * lp, nb * 4 * lp, nb * (4 * lp + 4), nb * (4 * lp + 5)
         o_ng, o_tab = o_t + nb * nblev, o_t + nb * nblev + nwl * 4 * ng
-        fb = torch.zeros(o_tab + tab_d, dtype=torch.float64, device=dev)
+        o_hv = o_tab + tab_d
+        fb = torch.zeros(o_hv + (nb * lp if true_depth else 0), dtype=torch.float64, device=dev)
+        hvrai = fb[o_hv:].view(nb, lp) if true_depth else None
         ib = torch.zeros(3 * nb, dtype=torch.int32, device=dev)
         prof, zprof, scal = fb[:o_z].view(nb, 3, lp), fb[o_z:o_s].view(nb, lp), fb[o_s:o_zz].view(nb, 4)
         zz, tabs = fb[o_zz:o_t], (fb[o_t:o_ng].view(nb, nblev) if nblev else None)
@@ -961,25 +1019,28 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None):
         any_out = bool((pk["wl"]["zout"] != -1.0).any())
         ik_t = up[pk["ik_off"]:pk["wob_off"]].view(torch.int32) if nblev else None
         bad = C.c_int(-1)
-        rc = L.sosgpu_profile_spectrum(dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), nb, _ptr(up[pk["wob_off"]:]),
-                                       _ptr(ik_t), _ptr(up) if nblev else None, pk["gas_doubles"] if ckd is None else up.numel(),
-                                       nblev, lp,
-                                       _ptr(fb[o_tab:]), _ptr(fb[o_ng:o_tab]), _ptr(tabs), _ptr(prof), _ptr(nt), _ptr(iborm),
-                                       _ptr(zprof), _ptr(jout) if any_out else None, _ptr(zz) if any_out else None, _ptr(scal),
-                                       C.byref(bad), st)
+        args = (dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), nb, _ptr(up[pk["wob_off"]:]),
+                _ptr(ik_t), _ptr(up) if nblev else None, pk["gas_doubles"] if ckd is None else up.numel(), nblev, lp,
+                _ptr(fb[o_tab:o_hv]), _ptr(fb[o_ng:o_tab]), _ptr(tabs), _ptr(prof), _ptr(nt), _ptr(iborm),
+                _ptr(zprof), _ptr(jout) if any_out else None, _ptr(zz) if any_out else None, _ptr(scal), C.byref(bad))
+        rc = L.sosgpu_profile_spectrum_true(*args, _ptr(hvrai), st) if true_depth else L.sosgpu_profile_spectrum(*args, st)
     if rc != 0 and bad.value >= 0:
         part["bad"] = int(bad.value)
-    capi.check(rc, "sosgpu_profile_spectrum")
+    capi.check(rc, "sosgpu_profile_spectrum_true" if true_depth else "sosgpu_profile_spectrum")
     out, tabs_l = [], []
     for w in range(nwl):
         b0, b1 = int(seg[w]), int(seg[w + 1])
         lev = float(pk["wl"]["zout"][w]) != -1.0
         out.append(dict(nb=b1 - b0, lp=lp, perm=None, nt=nt[b0:b1], iborm=iborm[b0:b1], prof=prof[b0:b1],
                         jout=jout[b0:b1] if lev else None, zz=zz[b0:b1] if lev else None, zprof=zprof[b0:b1], scal=scal[b0:b1]))
+        if true_depth:
+            out[-1]["hvrai"] = hvrai[b0:b1]
         tabs_l.append(tabs[b0:b1] if pk["wl"]["nterm"][w] else None)
     part.update(bins=dict(nb=nb, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=None, zz=None, zprof=zprof, scal=scal),
                 tabs=tabs_l, seg=seg, upload=up, ckd_status=status, ckd_index=pk["ckd_index"],
                 ckd_keep=(work, [t[2] for t in tables.values()]))
+    if true_depth:
+        part["bins"]["hvrai"] = hvrai
     return out
 
 
@@ -995,7 +1056,10 @@ def concat_levels(levels_list):
     if not parts:
         return dict(nz=nz, jout=None, zz=None, tauout=None)
     cat = lambda k: torch.cat([lv[k] for lv in parts], dim=1).contiguous()
-    return dict(nz=nz, jout=cat("jout"), zz=cat("zz"), tauout=cat("tauout"))
+    levels = dict(nz=nz, jout=cat("jout"), zz=cat("zz"), tauout=cat("tauout"))
+    if all(lv.get("tauvrai") is not None for lv in parts):
+        levels["tauvrai"] = cat("tauvrai")
+    return levels
 
 
 def _spectrum_order(cx, bins, order):

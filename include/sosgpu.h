@@ -363,6 +363,40 @@ size_t sosgpu_level_flux_spectrum_work_bytes(int njobs);
 int  sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out /*[njobs][2]*/,
                                 void *d_work, void *stream);
 
+/* Sensor channels of a spectrum: response-weighted sums of recomposition blocks over the wavelengths, on the device.
+ * A call adds the terms of nchan channels onto an accumulator that lives for the whole spectrum:
+ *   d_acc[c][k][iphi][q][t] += sum_m wgt[m] * block(job[m], k)[iphi][q][t],   q = 0, 1, 2 (XIT, XQT, XUT),
+ * over the terms m = first[c] .. first[c+1]-1 of channel c in term order, every step formed as a = a + w * x (one multiply,
+ * one add, no FMA): a host loop in term order reproduces the sum bit for bit, and successive calls on one accumulator give
+ * the bits of one call with the concatenated term lists.  Rows 3..6 of a block are never read.  A channel without a term
+ * in the call leaves its part of d_acc untouched.
+ *  d_blocks        DEVICE, [njobs][nslots][nphi][7][W]: the blocks of the call back to back, job j, slot k at
+ *                  d_blocks + (j * nslots + k) * nphi * 7 * W -- what sosgpu_trphi_spectrum writes for the jobs of a part of
+ *                  a spectrum with nslots output altitudes each, all of one azimuth list and direction count
+ *  first[nchan+1]  HOST, non-decreasing from first[0] = 0; first[nchan] = the number of terms of the call
+ *  job[], wgt[]    HOST, first[nchan] entries each: block index 0..njobs-1 and finite weight of every term
+ *  d_acc           DEVICE, [nchan][nslots][nphi][3][W]; the caller zeroes it before the first call of a spectrum
+ *  d_work          DEVICE area of work_bytes >= sosgpu_channel_accumulate_work_bytes(nchan, first[nchan]) bytes, 8-byte
+ *                  aligned, the caller's until `stream` has passed the call: the term table arrives there in ONE copy on
+ *                  `stream`, from a pinned block the library recycles.
+ * Asynchronous: one launch, nothing is waited for, no device memory is allocated and no context is needed.
+ * Checked before anything is queued, SOSGPU_E_ARG for: njobs, nslots, nphi, w or nchan < 1 (or nslots, nchan > 65535,
+ * nphi * 7 * w > 2^31 - 1), a NULL pointer, first[0] != 0 or a decreasing first, a job outside 0..njobs-1, a weight that is
+ * not finite, a misaligned d_work, work_bytes too small.  A call without a term returns SOSGPU_OK with nothing queued. */
+size_t sosgpu_channel_accumulate_work_bytes(int nchan, int nterms);
+int  sosgpu_channel_accumulate(int device, const double *d_blocks, int njobs, int nslots, int nphi, int w, int nchan,
+                               const int32_t *first, const int32_t *job, const double *wgt, double *d_acc, void *d_work,
+                               size_t work_bytes, void *stream);
+/* The channel radiances from the sums: d_out[nchan][nslots][nphi][7][W] in the row order of sosgpu_trphi.  Rows 0..2: d_acc
+ * behind the reference's output thresholds (XIT <= 1e-99 -> 0; |XQT|, |XUT| < 1e-15 -> 0, SOS_TRPHI.F:1212-1218); row 3
+ * (ANGDIFF): copied from d_angdiff_block[nphi][7][W], any block of the spectrum (the scattering angle depends on the
+ * directions and the azimuth only); rows 4..6: SOS_POLAR of rows 0..2, the statements sosgpu_trphi executes; direction 0
+ * (t = N, W = 2N + 1) is zero in every row.  Asynchronous: one launch on `stream`, no device memory allocated, no context
+ * needed.  SOSGPU_E_ARG, before anything is queued, for a NULL pointer, nchan, nslots, nphi < 1, an even w or w < 3, and the
+ * size limits of sosgpu_channel_accumulate. */
+int  sosgpu_channel_finish(int device, const double *d_acc, const double *d_angdiff_block, int nchan, int nslots, int nphi,
+                           int w, double *d_out, void *stream);
+
 /* Replaces SOS_ROUJEAN (src/SOS_ROUJEAN.F:212), SOS_SURFACE_BPDF (src/SOS_SURFACE_BPDF.F:219) and SOS_BPDF_AJOUT_BRDF
  * (src/SOS_SURFACE.F:2503) for -SURF.Type 3..7, no temporary files: Fourier reflection matrices of the land surface,
  *  d_rsurf[os_nb+1][9][N][N]  REAL*4, reference surface-file record order (feed to sosgpu_set_surface_matrices).

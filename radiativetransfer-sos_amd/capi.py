@@ -26,6 +26,7 @@ EXPORTS = [
     "sosgpu_noyaux_spectrum", "sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes",
     "sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes", "sosgpu_debug_stage_blocks",
     "sosgpu_profile_true", "sosgpu_profile_spectrum_true", "sosgpu_output_depths", "sosgpu_level_transmission",
+    "sosgpu_channel_accumulate", "sosgpu_channel_accumulate_work_bytes", "sosgpu_channel_finish",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -235,6 +236,12 @@ def lib():
         L.sosgpu_level_flux_spectrum_work_bytes.argtypes = [i32]
         L.sosgpu_level_flux_spectrum.restype = i32
         L.sosgpu_level_flux_spectrum.argtypes = [C.POINTER(FluxJob), i32, vp, vp, vp]
+        L.sosgpu_channel_accumulate_work_bytes.restype = C.c_size_t
+        L.sosgpu_channel_accumulate_work_bytes.argtypes = [i32, i32]
+        L.sosgpu_channel_accumulate.restype = i32
+        L.sosgpu_channel_accumulate.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp]
+        L.sosgpu_channel_finish.restype = i32
+        L.sosgpu_channel_finish.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.sosgpu_land_surface.restype = i32
         L.sosgpu_land_surface.argtypes = [i32, C.POINTER(Land), i32, vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_int32), vp]
         L.sosgpu_debug_phase_buffer.restype = i32

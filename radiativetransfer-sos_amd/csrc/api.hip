@@ -1367,6 +1367,66 @@ extern "C" int sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs
     return SOSGPU_OK;
 }
 
+static bool channel_shape_ok(int nchan, int nslots, int nphi, int w)
+{
+    if (nchan < 1 || nchan > 65535 || nslots < 1 || nslots > 65535 || nphi < 1 || w < 1) return false;   // (grid y and z)
+    return (long long)nphi * 7 * w <= 0x7fffffffLL;                                                    // (element index an int32)
+}
+
+// the term table in the work area: wgt[nterms] | first[nchan + 1] | job[nterms], rounded up to 8 bytes
+extern "C" size_t sosgpu_channel_accumulate_work_bytes(int nchan, int nterms)
+{
+    if (nchan < 1 || nterms < 0) return 0;
+    const size_t n = (size_t)nterms * (sizeof(double) + sizeof(int32_t)) + ((size_t)nchan + 1) * sizeof(int32_t);
+    return (n + 7) & ~(size_t)7;
+}
+
+// The terms of nchan channels onto the accumulator in ONE launch (k_channel_accumulate).  d_work = the term table, filled by one
+// copy from a recycled pinned block (Staged).  Everything is checked before anything is queued.
+extern "C" int sosgpu_channel_accumulate(int device, const double *d_blocks, int njobs, int nslots, int nphi, int w, int nchan,
+                                         const int32_t *first, const int32_t *job, const double *wgt, double *d_acc,
+                                         void *d_work, size_t work_bytes, void *stream)
+{
+    if (!d_blocks || !first || !job || !wgt || !d_acc || !d_work || njobs < 1) return SOSGPU_E_ARG;
+    if (!channel_shape_ok(nchan, nslots, nphi, w)) return SOSGPU_E_ARG;
+    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    if (first[0] != 0) return SOSGPU_E_ARG;
+    for (int c = 0; c < nchan; c++)
+        if (first[c + 1] < first[c]) return SOSGPU_E_ARG;
+    const int nterms = first[nchan];
+    for (int m = 0; m < nterms; m++)
+        if (job[m] < 0 || job[m] >= njobs || !std::isfinite(wgt[m])) return SOSGPU_E_ARG;
+    const size_t bytes = sosgpu_channel_accumulate_work_bytes(nchan, nterms);
+    if (work_bytes < bytes) return SOSGPU_E_ARG;
+    if (nterms == 0) return SOSGPU_OK;
+    if (const int rc = use_device(device)) return rc;
+    Staged s(device, bytes);
+    if (s.rc) return s.rc;
+    char *hp = static_cast<char *>(s.host());
+    const size_t off_first = (size_t)nterms * sizeof(double), off_job = off_first + ((size_t)nchan + 1) * sizeof(int32_t);
+    memcpy(hp, wgt, off_first);
+    memcpy(hp + off_first, first, off_job - off_first);
+    memcpy(hp + off_job, job, (size_t)nterms * sizeof(int32_t));
+    if (bytes > off_job + (size_t)nterms * sizeof(int32_t)) memset(hp + off_job + (size_t)nterms * sizeof(int32_t), 0, 4);
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(s.send(d_work, st));
+    const char *dp = static_cast<const char *>(d_work);
+    launch_channel_accumulate(d_blocks, nslots, nphi, w, nchan, reinterpret_cast<const int32_t *>(dp + off_first),
+                              reinterpret_cast<const int32_t *>(dp + off_job), reinterpret_cast<const double *>(dp), d_acc, st);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
+extern "C" int sosgpu_channel_finish(int device, const double *d_acc, const double *d_angdiff_block, int nchan, int nslots,
+                                     int nphi, int w, double *d_out, void *stream)
+{
+    if (!d_acc || !d_angdiff_block || !d_out || !channel_shape_ok(nchan, nslots, nphi, w) || w < 3 || !(w & 1)) return SOSGPU_E_ARG;
+    if (const int rc = use_device(device)) return rc;
+    launch_channel_finish(d_acc, d_angdiff_block, nchan, nslots, nphi, w, d_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
 extern "C" int sosgpu_land_surface(int device, const sosgpu_land *land, int n, const double *mu, const double *chr, double ind,
                                    int os_nb, int os_ns, int os_nm, float *d_rsurf, int32_t *ier_out, void *stream)
 {

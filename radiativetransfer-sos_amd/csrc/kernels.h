@@ -87,6 +87,15 @@ struct FluxJobDev {
 };
 void launch_level_flux_table(const FluxJobDev *d_jobs, int njobs, hipStream_t st);
 
+// Sensor channels of a spectrum (channels.hip).  launch_channel_accumulate: acc[nchan][nslots][nphi][3][W] += the terms
+// first[c] .. first[c + 1] - 1 of every channel c, term m = wgt[m] x rows 0..2 of block (job[m], slot) of d_blocks
+// [njobs][nslots][nphi][7][W]; one launch of (ceil(nphi 3 W / 256), nslots, nchan) workgroups, first / job / wgt on the device.
+void launch_channel_accumulate(const double *d_blocks, int nslots, int nphi, int w, int nchan, const int32_t *d_first,
+                               const int32_t *d_job, const double *d_wgt, double *d_acc, hipStream_t st);
+// out[nchan][nslots][nphi][7][W] of the sums: thresholds, ANGDIFF from d_angdiff_block[nphi][7][W], SOS_POLAR
+void launch_channel_finish(const double *d_acc, const double *d_angdiff_block, int nchan, int nslots, int nphi, int w,
+                           double *d_out, hipStream_t st);
+
 #define SOS_PROF_NBLEV_MAX 64     // levels of the absorption profile held in LDS (CTE_ABS_NBLEV = 50 in the reference)
 // Per-bin profile discretisation (profile.hip).  *_ng: the no-gas profile of the wavelength (host-computed, device copy).
 struct ProfileArgs {

@@ -12,12 +12,11 @@
 
 #pragma clang fp contract(off)
 #include "land_models.h"
+#include "sos_polar.h"
 
 #define SEUIL_Z ((double)0.0001f)      // SOS.h:407 (REAL*4 literal)
 #define SEUIL_X ((double)0.00001f)     // SOS.h:413
-#define THRESHOLD_Q_U_NULL 1.e-15      // SOS.h:418
 #define SOLAR_DISC_SOLID_ANGLE 6.8e-05 // SOS.h:426
-#define VALEUR_INDEF (-999.)
 
 __device__ inline void reflex(double cosdif, double ind, double &r11, double &r12, double &r33)
 {   // SOS_TRPHI.F:1461-1470
@@ -136,23 +135,9 @@ __device__ __forceinline__ void trphi_body(const TrphiCtx &cx, const int iphi, i
             if (cx.ipolar == 1) xqt = xqt + r12 * coef_sun * atj;
         }
     }
-    if (xit <= 1.e-99) xit = 0.0;                   // SOS_TRPHI.F:1212-1218
-    if (fabs(xqt) < THRESHOLD_Q_U_NULL) xqt = 0.0;
-    if (fabs(xut) < THRESHOLD_Q_U_NULL) xut = 0.0;
-    // SOS_POLAR :1865-1903
+    sos_trphi_thresholds(xit, xqt, xut);            // SOS_TRPHI.F:1212-1218
     double xan, tpol, lpol;
-    if (xqt != 0.) {
-        const double xt = xut / xqt;
-        if (xqt > 0.) xan = 90. * atan(xt) / pi;
-        else if (xut > 0.) xan = 90. + 90. * atan(xt) / pi;
-        else xan = -90. + 90. * atan(xt) / pi;
-    } else {
-        if (xut > 0.) xan = 45.;
-        else if (xut < 0) xan = -45.;
-        else xan = VALEUR_INDEF;
-    }
-    lpol = sqrt(xqt * xqt + xut * xut);
-    tpol = (xit != 0.0) ? 100. * lpol / xit : VALEUR_INDEF;
+    sos_polar(xit, xqt, xut, xan, tpol, lpol);      // SOS_POLAR :1865-1903
     o[0 * W + t] = xit; o[1 * W + t] = xqt; o[2 * W + t] = xut; o[3 * W + t] = angdiff;
     o[4 * W + t] = xan; o[5 * W + t] = tpol; o[6 * W + t] = lpol;
 }

@@ -1288,6 +1288,19 @@ def _level_flux_split_row(pl, alt, fin, g, e):
     return row + (tdir_vrai, float(e[0]) + row[0] - tdir_vrai)
 
 
+def _finish_scalars(pl, fin, g=0):
+    """Elements 18..22 of the 23-tuple of plan pl (SOS_PROC.F:3831-3837): flux_dir_down, flux_diff_down, flux_tot_down,
+    flux_diff_up and coef_tronca, from the finish_scalars dictionary `fin` and the wavelength's segment g in it."""
+    cs = math.cos(math.pi * pl.p["tetas"] / 180.0)
+    tau_agg, ttot_vrai_agg = float(fin["ttot_tronc"][g]), float(fin["ttot_vrai"][g])
+    emoins, eplus = float(fin["emoins"][g]), float(fin["eplus"][g])
+    tdir_tronc = math.exp(-tau_agg / cs)                                          # SOS_PROC.F:3831-3837
+    tdir_vrai = math.exp(-ttot_vrai_agg / cs)
+    flux_diff_down = emoins + tdir_tronc - tdir_vrai
+    flux_down = emoins + tdir_tronc
+    return tdir_vrai, flux_diff_down, flux_down, eplus, pl.a_tronc if pl.coef_tronca_out is None else pl.coef_tronca_out
+
+
 def _finish(pl, out, rec0, fin, g=0, block=None):
     """The tail of SOS_PROC (SOS_PROC.F:3755-3874) on the host: the (361,81) tables from sosgpu_trphi's output `out` (host
     array), fluxes, result files (rank 0 only), the 23-tuple.  rec0: aggregated records [S][3][W] of this wavelength
@@ -1296,7 +1309,6 @@ def _finish(pl, out, rec0, fin, g=0, block=None):
     nf = int(fin["n_orders"][g])
     tau_agg, ttot_vrai_agg = float(fin["ttot_tronc"][g]), float(fin["ttot_vrai"][g])
     phi_fin, theta_fin, up, dn = _trphi_pack(n, mu, out, pl.rows, pl.phi_fin, block)
-    emoins, eplus = float(fin["emoins"][g]), float(fin["eplus"][g])
     from . import absorption as _abs
     resbin = str(p["ficsos_res_bin"]).strip()
     resroot = str(p["resroot"]).strip() if getattr(pl, "writes_files", _dist_rank_world()[0] == 0) else ""
@@ -1315,11 +1327,7 @@ def _finish(pl, out, rec0, fin, g=0, block=None):
             write_aerosols_file(os.path.join(resroot, "SOS", str(p["ficgranu"]).strip()),
                                 dict(alpha=z, beta=z, gamma=z, zeta=z, a_tronc=0.0, piztr=0.0, piz=0.0))
         write_result_bin(os.path.join(resroot, "SOS", resbin), rec0[:nf].cpu().numpy())
-    cs = math.cos(math.pi * p["tetas"] / 180.0)
-    tdir_tronc = math.exp(-tau_agg / cs)                                          # SOS_PROC.F:3831-3837
-    tdir_vrai = math.exp(-ttot_vrai_agg / cs)
-    flux_diff_down = emoins + tdir_tronc - tdir_vrai
-    flux_down = emoins + tdir_tronc
+    tdir_vrai, flux_diff_down, flux_down, eplus, coef_tronca = _finish_scalars(pl, fin, g)
     if resroot and pl.want_trans:
         write_trans_file(os.path.join(resroot, "SOS", str(p["fictrans"]).strip()), p["tetas"], mu, tau_agg, ttot_vrai_agg,
                          float(fin["tdifmus"][g]), fin["tdifmug"][g])
@@ -1334,7 +1342,7 @@ def _finish(pl, out, rec0, fin, g=0, block=None):
     return (n, ind_angout, phi_fin, theta_fin,
             up["sca"], up["i"], up["q"], up["u"], up["ang"], up["rate"], up["lpol"],
             dn["sca"], dn["i"], dn["q"], dn["u"], dn["ang"], dn["rate"], dn["lpol"],
-            tdir_vrai, flux_diff_down, flux_down, eplus, pl.a_tronc if pl.coef_tronca_out is None else pl.coef_tronca_out)
+            tdir_vrai, flux_diff_down, flux_down, eplus, coef_tronca)
 
 
 def sos_proc(aer_phase=None, device=0, **kw):
@@ -1617,11 +1625,15 @@ def _first_failed_index(index, device):
 
 
 def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False,
-                   split=False):
+                   split=False, chan=None):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
     launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop.
-    split (with fluxes): the bins carry the untruncated depth rows, the levels `tauvrai`, and the flux rows two more columns."""
+    split (with fluxes): the bins carry the untruncated depth rows, the levels `tauvrai`, and the flux rows two more columns.
+    chan (sos_spectrum_channels: the weights [C][calls] of the sensor channels, None: the pass as it was): the recomposition
+    blocks of a chunk stay on the device and are added, weight by weight, onto one accumulator [C][K][nphi][3][W] that lives
+    for the pass (solver.channel_accumulate, one call per chunk); no table is built and no 23-tuple formed per wavelength.
+    Returns what _channel_results makes of the accumulator and of the per-call scalars."""
     import time
     import torch
     from . import capi, solver
@@ -1664,14 +1676,24 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     level_keys = ("jout", "zz", "tauout") + (("tauvrai",) if split else ())
     rank, world = _dist_rank_world()
     if world > 1:
-        mine = [int(i) for i in _dist.balanced_shards(spectrum_costs(kwargs_list), world)[rank]]
+        shards = _dist.balanced_shards(spectrum_costs(kwargs_list), world)
+        mine = [int(i) for i in shards[rank]]
     else:
+        shards = [range(nwl)]
         mine = list(range(nwl))
+    if chan is not None:
+        mine = sorted(mine)                             # a rank adds its calls in ascending call index
+        lead = rank == min(r for r in range(world) if len(shards[r]))    # the rank whose ANGDIFF rows the all-reduce carries
+        n_chan = chan.shape[0]
+        acc = ang_rows = None                           # the accumulator and the ANGDIFF rows [nphi][W] of one block
+        call_scal = {}                                  # call -> [K][5 (+ flux columns)]: elements 18..22 (and the flux row)
     results = [None] * nwl                              # K 23-tuples per wavelength
     flux_rows = [None] * nwl if fluxes else None        # fluxes: the [K][5] flux rows per wavelength
     debug = bool(os.environ.get("SOS_SPECTRUM_DEBUG"))
     nrows = {}
     tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0, fluxes=0.0)
+    if chan is not None:
+        tm["channels"] = 0.0
     main_st = torch.cuda.current_stream(dev)
     side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(prep_streams)))]
     aer_st = torch.cuda.Stream(device=dev)
@@ -1842,7 +1864,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 # one launch for every (wavelength, altitude) of the chunk, its flat result downloaded as it is
                 flat, shapes = _trphi_launch_many([(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
                                                    for pl, _, r, f, g in todo])
-                flat = flat.cpu().numpy()
+                if chan is None:
+                    flat = flat.cpu().numpy()
                 t4 = time.perf_counter()
                 tm["trphi"] += t4 - t3
                 if fluxes:
@@ -1854,6 +1877,34 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     t5 = time.perf_counter()
                     tm["fluxes"] += t5 - t4
                     t4 = t5
+                if chan is not None:
+                    # the chunk's blocks stay on the device: one launch adds them onto the accumulator.  todo holds the K slots
+                    # of a call side by side, in group order: block (j, k) of call todo[j K].  A channel names its calls of the
+                    # chunk in ascending call index, whatever that order is.
+                    where = idx[0]
+                    if len(set(shapes)) != 1:
+                        raise ValueError("%s: the calls do not share one block shape [nphi][7][W]: %s" % (fn, sorted(set(shapes))))
+                    nphi, _, w = shapes[0]
+                    if acc is None:
+                        acc = torch.zeros((n_chan, nz, nphi, 3, w), dtype=torch.float64, device=dev)
+                        ang_rows = flat[:nphi * 7 * w].view(nphi, 7, w)[:, 3, :].clone()
+                    job_of = {todo[j * nz][0].index: j for j in range(len(todo) // nz)}
+                    calls = sorted(job_of)
+                    first, job, wgt = [0], [], []
+                    for c in range(n_chan):
+                        for i in calls:
+                            if chan[c, i] != 0.0:
+                                job.append(job_of[i])
+                                wgt.append(chan[c, i])
+                        first.append(len(job))
+                    solver.channel_accumulate(flat, len(calls), nz, nphi, w, first, job, wgt, acc)
+                    for pl, k, r, f, g in todo:
+                        row = _finish_scalars(pl, f, g)
+                        if fluxes:
+                            row = row + tuple(flux_rows[pl.index][k])
+                        call_scal.setdefault(pl.index, [None] * nz)[k] = row
+                    tm["channels"] += time.perf_counter() - t4
+                    continue
                 pos = 0
                 blocks = _zero_pages((len(todo), 2, 7, 361, 81))  # the result tables of the chunk's wavelengths (views of it)
                 for j, ((pl, k, r, f, g), shp) in enumerate(zip(todo, shapes)):
@@ -1889,11 +1940,170 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
         raise err
     if timings is not None:
         timings.update(tm)
+    if chan is not None:
+        return _channel_results(kwargs_list[0], chan, mine, acc, ang_rows, call_scal, alts, len(flux_names) if fluxes else 0,
+                                dev, world, lead)
     if alts is None:
         results = [None if r is None else r[0] for r in results]
     if world > 1 and gather:
         _gather_results(results, mine, nrows, world, None if alts is None else nz, flux_rows)
     return (results, flux_rows) if fluxes else results
+
+
+def _channel_results(kw, chan, mine, acc, ang_rows, call_scal, alts, nflux, dev, world, lead):
+    """The tail of a channel pass: the host sums of the per-call scalars (ascending call index, a = a + w * x), under
+    torch.distributed ONE all-reduce (SUM) of the accumulator -- the ANGDIFF rows of the lead rank ride behind it, the other
+    ranks add zeros there -- and one of the packed scalar sums, then one sosgpu_channel_finish launch, one download and the
+    tables per (channel, altitude).  kw: any call of the list (the geometry is common).  Returns the tuples [C] (alts None)
+    or [C][K], with nflux > 0 the pair (tuples, flux rows [C] of [K][nflux])."""
+    import torch
+    from . import solver
+    p = dict(kw)
+    validate_parameters(p)
+    nb_lum = CTE_DEFAULT_NBMU_LUM if p["nbmu_gauss_lum"] == _I else int(p["nbmu_gauss_lum"])
+    mu, _, _, ind_ang = angles(nb_lum, p["tetas"], p["ficangles_user_lum"])
+    n = len(mu)
+    w = 2 * n + 1
+    _, rows, phi_fin = _trphi_azimuths(p["itrphi"], p["phios"], p["pas_phi"])
+    nphi, nz, n_chan = len(rows), 1 if alts is None else len(alts), chan.shape[0]
+    sums = np.zeros((n_chan, nz, 5 + nflux))
+    vals = {i: np.array(call_scal[i], dtype=np.float64) for i in mine}
+    own = np.array(mine, dtype=np.int64)                # (ascending)
+    for c in range(n_chan):
+        a = sums[c]
+        for i in own[chan[c, own] != 0.0]:
+            a = a + chan[c, i] * vals[int(i)]
+        sums[c] = a
+    if acc is None:                                     # a rank without a call
+        acc = torch.zeros((n_chan, nz, nphi, 3, w), dtype=torch.float64, device=dev)
+        ang_rows = torch.zeros((nphi, w), dtype=torch.float64, device=dev)
+    if tuple(acc.shape) != (n_chan, nz, nphi, 3, w):
+        raise ValueError("the blocks of the pass are %s, the common geometry says %s" % (tuple(acc.shape[2:]), (nphi, 3, w)))
+    if world > 1:
+        import torch.distributed as dist
+        on_gpu = dist.get_backend() == "nccl"
+        buf = torch.cat([acc.reshape(-1), ang_rows.reshape(-1) if lead else torch.zeros_like(ang_rows).reshape(-1)])
+        st = torch.from_numpy(sums.reshape(-1).copy())
+        if on_gpu:
+            st = st.to(dev)
+        else:
+            buf = buf.cpu()
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        dist.all_reduce(st, op=dist.ReduceOp.SUM)
+        buf = buf.to(dev)
+        acc, ang_rows = buf[:acc.numel()].view(acc.shape), buf[acc.numel():].view(nphi, w)
+        sums = st.cpu().numpy().reshape(sums.shape)
+    block = torch.zeros((nphi, 7, w), dtype=torch.float64, device=dev)
+    block[:, 3, :] = ang_rows
+    out = solver.channel_finish(acc.contiguous(), block).cpu().numpy()
+    ind_angout = np.zeros(81, dtype=np.int32)
+    ind_angout[:n] = ind_ang
+    tuples = []
+    for c in range(n_chan):
+        per = []
+        for k in range(nz):
+            ph, th, up, dn = _trphi_pack(n, mu, out[c, k], rows, phi_fin.copy())
+            per.append((n, ind_angout.copy(), ph, th,
+                        up["sca"], up["i"], up["q"], up["u"], up["ang"], up["rate"], up["lpol"],
+                        dn["sca"], dn["i"], dn["q"], dn["u"], dn["ang"], dn["rate"], dn["lpol"]) +
+                       tuple(float(x) for x in sums[c, k, :5]))
+        tuples.append(per[0] if alts is None else per)
+    if not nflux:
+        return tuples
+    return tuples, [sums[c, :, 5:].copy() for c in range(n_chan)]
+
+
+_CHANNEL_SHARED = ("nbmu_gauss_lum", "tetas", "ficangles_user_lum", "itrphi", "phios", "pas_phi", "ipolar")
+
+
+def _channel_arguments(fn, kwargs_list, weights, normalize, altitudes, fluxes, split):
+    """The argument rules of sos_spectrum_channels, checked before any device work (ValueError naming the first offending
+    channel or call).  Returns (the weights [C][calls] as they are applied, the altitudes as floats or None)."""
+    nwl = len(kwargs_list)
+    try:
+        wts = np.array(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: weights must be a [C][%d] array of numbers" % (fn, nwl))
+    if wts.ndim != 2 or wts.shape[0] < 1 or wts.shape[1] != nwl:
+        raise ValueError("%s: weights must be [C][%d] (one row per channel, one column per call), got %s"
+                         % (fn, nwl, tuple(wts.shape)))
+    if not isinstance(normalize, (bool, np.bool_)):
+        raise ValueError("%s: normalize must be True or False, got %r" % (fn, normalize))
+    bad = np.argwhere(~np.isfinite(wts))
+    if len(bad):
+        raise ValueError("%s: the weight of channel %d for call %d is not finite" % (fn, bad[0][0], bad[0][1]))
+    for c in range(wts.shape[0]):
+        if not np.any(wts[c] != 0.0):
+            raise ValueError("%s: channel %d has no non-zero weight" % (fn, c))
+    if normalize:
+        for c in range(wts.shape[0]):
+            total = np.cumsum(wts[c])[-1]               # the left-to-right sum
+            if total == 0.0 or not np.isfinite(total):
+                raise ValueError("%s: the weights of channel %d sum to %r: they cannot be normalised" % (fn, c, float(total)))
+            wts[c] = wts[c] / total
+    defaults = {k: v for _, k, v in PARAMS}
+    shared = _CHANNEL_SHARED + (("zout",) if altitudes is None else ())
+    names = {k: d for d, k, _ in PARAMS}
+    for i, kw in enumerate(kwargs_list):
+        for k in shared:
+            if kw.get(k, defaults[k]) != kwargs_list[0].get(k, defaults[k]):
+                raise ValueError("%s: call %d differs from call 0 in %s (%r against %r): the calls of a channel share their "
+                                 "directions, azimuths and output altitude" % (fn, i, names[k], kw.get(k, defaults[k]),
+                                                                               kwargs_list[0].get(k, defaults[k])))
+    for i, kw in enumerate(kwargs_list):
+        if str(kw.get("resroot", "")).strip():
+            raise ValueError("%s writes no result files: -SOS_Main.ResRoot of call %d must be empty (use sos_spectrum)" % (fn, i))
+    if altitudes is None:
+        if fluxes or split:
+            raise ValueError("%s: fluxes and split belong to the altitudes of a levels call: give `altitudes`" % fn)
+        return wts, None
+    return wts, _levels_arguments(fn, altitudes, kwargs_list, fluxes, split)
+
+
+def sos_spectrum_channels(kwargs_list, weights, normalize=True, altitudes=None, fluxes=False, split=False, aer_phases=None,
+                          device=0, chunk=256, timings=None, prep_streams=16, parts=4):
+    """The radiances of C sensor channels from a spectrum of sos_proc calls: the spectrum of sos_spectrum (or, with
+    `altitudes`, of sos_spectrum_levels) weighted by each channel's spectral response and summed over the calls ON THE DEVICE,
+    so that no per-wavelength block is downloaded, no per-wavelength table built and no per-wavelength 23-tuple formed.
+
+      chan = sos_spectrum_channels(kwargs_list, weights)                         # C 23-tuples in the OUTPUT_NAMES layout
+      chan = sos_spectrum_channels(kwargs_list, weights, altitudes=[-1, 0., 3.]) # chan[c][k]: channel c at altitude k
+      chan, flux = sos_spectrum_channels(kwargs_list, weights, altitudes=[...], fluxes=True)   # flux[c]: [K][5] ([K][7]: split)
+
+    weights: [C][len(kwargs_list)] numbers; weights[c][i] multiplies call i in channel c (the response times the solar
+    irradiance, say).  A zero entry means the call is not in the channel: it becomes no term.  normalize=True divides each row
+    by its left-to-right sum (np.cumsum(row)[-1]) first; normalize=False applies the weights as given.
+
+    The pass is that of sos_spectrum / sos_spectrum_levels up to the azimuth recompositions of a chunk (one
+    sosgpu_trphi_spectrum launch).  Behind it ONE sosgpu_channel_accumulate launch per chunk adds the chunk's blocks onto an
+    accumulator [C][K][nphi][3][W] that lives for the pass: acc = acc + w * x for the I, Q, U rows, one multiply and one add
+    per term, a channel's calls in ASCENDING CALL INDEX whatever `chunk` and `parts` are -- the sums equal, bit for bit, a host
+    loop of that form over the tuples of sos_spectrum.  After the last chunk one sosgpu_channel_finish launch applies the
+    reference's output thresholds (SOS_TRPHI.F:1212-1218) and SOS_POLAR to the sums, one download brings
+    [C][K][nphi][7][W] to the host and the tables are packed per (channel, altitude).
+
+    Returned tuples: elements 0..3 (directions, azimuths) are the calls' common geometry; the tables i, q, u (up and down) are
+    the thresholded sums; sca_ang is any call's; pol_ang, pol_rate and l_pol are SOS_POLAR OF THE SUMS (not sums of the calls'
+    values); elements 18..21 (flux_dir_down, flux_diff_down, flux_tot_down, flux_diff_up) and 22 (coef_tronca) are the weighted
+    sums of the per-call values, formed on the host in ascending call index with the same a = a + w * x.  With fluxes=True the
+    per-call flux rows of sos_spectrum_levels are summed in the same way.
+
+    Checked before any device work, ValueError naming the first offending channel or call: the shape of `weights`, non-finite
+    entries, a row without a non-zero entry, a row that sums to 0 under normalize=True, calls that differ in what shapes a
+    block (-ANG.Rad.NbGauss, -ANG.Thetas, -ANG.Rad.UserAngFile, -SOS.View, -SOS.View.Phi, -SOS.View.Dphi, -SOS.Ipolar, and
+    -SOS.OutputAlt when `altitudes` is None), a non-empty -SOS_Main.ResRoot (no per-wavelength files are written), and the
+    rules of sos_spectrum_levels for altitudes, fluxes and split (fluxes and split need `altitudes`).  A call that fails raises
+    what sos_spectrum raises for it.
+    aer_phases, device, chunk, timings, prep_streams, parts: as sos_spectrum; `timings` gains the host phase "channels" (the
+    accumulate call and the per-call scalars) and its "finish" stays 0.
+
+    With torch.distributed initialised the wavelengths are dealt to the ranks as in sos_spectrum; every rank accumulates its
+    own calls; after the pass's failure agreement ONE all-reduce (SUM) of the accumulator and one of the packed scalar sums
+    follow, then every rank finishes and returns the same objects.  The order of the sum across ranks differs from one
+    process's, so the result equals a single process's to rounding, not to the bit."""
+    wts, alts = _channel_arguments("sos_spectrum_channels", kwargs_list, weights, normalize, altitudes, fluxes, split)
+    return _spectrum_pass("sos_spectrum_channels", kwargs_list, aer_phases, device, True, chunk, timings, prep_streams, parts,
+                          alts, bool(fluxes), bool(split), chan=wts)
 
 
 def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16, parts=4):

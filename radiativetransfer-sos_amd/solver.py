@@ -676,6 +676,52 @@ def level_flux_many(items):
     return out
 
 
+def channel_accumulate(flat, njobs, K, nphi, W, first, job, wgt, acc):
+    """The terms of C sensor channels onto the accumulator of a spectrum, in ONE sosgpu_channel_accumulate call (one launch) on
+    the current stream: acc[c][k][iphi][q][t] += sum_m wgt[m] * block(job[m], k)[iphi][q][t] for q = 0, 1, 2 over the terms
+    m = first[c] .. first[c+1]-1, in term order, each step a = a + w * x (one multiply, one add).  flat: device tensor of
+    njobs * K blocks [nphi][7][W] back to back (job j, slot k at (j K + k) nphi 7 W) -- what trphi_many returns for the jobs of a
+    part of a levels pass; first [C+1], job and wgt [first[C]]: host arrays; acc: contiguous float64 device tensor
+    [C][K][nphi][3][W], updated in place.  Nothing is waited for."""
+    first = np.ascontiguousarray(first, dtype=np.int32)
+    job = np.ascontiguousarray(job, dtype=np.int32)
+    wgt = np.ascontiguousarray(wgt, dtype=np.float64)
+    nchan = first.size - 1
+    if nchan < 1 or job.shape != wgt.shape or job.ndim != 1 or job.size != int(first[-1]):
+        raise ValueError("first is [C+1] with first[C] = len(job) = len(wgt)")
+    if flat.dtype != torch.float64 or not flat.is_contiguous() or flat.numel() < njobs * K * nphi * 7 * W:
+        raise ValueError("flat holds njobs * K contiguous float64 blocks [nphi][7][W]")
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.device != flat.device or acc.numel() != nchan * K * nphi * 3 * W:
+        raise ValueError("acc is a contiguous float64 tensor [C][K][nphi][3][W] on the device of the blocks")
+    L = capi.lib()
+    d = flat.device
+    nbytes = int(L.sosgpu_channel_accumulate_work_bytes(nchan, job.size))
+    work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=d)
+    ip = lambda a: a.ctypes.data_as(C.c_void_p)
+    capi.check(L.sosgpu_channel_accumulate(d.index or 0, _ptr(flat), int(njobs), int(K), int(nphi), int(W), nchan, ip(first),
+                                           ip(job), ip(wgt), _ptr(acc), _ptr(work), nbytes,
+                                           C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "sosgpu_channel_accumulate")
+    return acc
+
+
+def channel_finish(acc, angdiff_block):
+    """The channel radiances from the accumulator of channel_accumulate, in ONE sosgpu_channel_finish call (one launch) on the
+    current stream: acc [C][K][nphi][3][W] -> a new device tensor [C][K][nphi][7][W] in SosContext.trphi's row order (the sums
+    behind the reference's output thresholds, ANGDIFF from angdiff_block -- any block [nphi][7][W] of the spectrum --, SOS_POLAR
+    of the sums, direction 0 zero).  Nothing is waited for."""
+    if acc.dim() != 5 or acc.shape[3] != 3 or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise ValueError("acc is a contiguous float64 tensor [C][K][nphi][3][W]")
+    nchan, K, nphi, _, W = acc.shape
+    d = acc.device
+    blk = angdiff_block.to(device=d, dtype=torch.float64).contiguous()
+    if blk.numel() != nphi * 7 * W:
+        raise ValueError("angdiff_block is one block [nphi][7][W] of the spectrum")
+    out = torch.empty((nchan, K, nphi, 7, W), dtype=torch.float64, device=d)
+    capi.check(capi.lib().sosgpu_channel_finish(d.index or 0, _ptr(acc), _ptr(blk), nchan, K, nphi, W, _ptr(out),
+                                                C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "sosgpu_channel_finish")
+    return out
+
+
 def build_operators(ctxs):
     """The operator tables of the contexts created with build=False, in ONE sosgpu_noyaux_spectrum call on the current stream:
     at most five launches for all of them (the table forms of the kernels of sosgpu_set_surface_matrices_async and

@@ -226,6 +226,38 @@ int  sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table, const int
                                   const int32_t *d_jout, const double *d_zz, double *d_rec, int32_t *d_norders,
                                   int32_t *d_iglast, double *d_flux, void *stream);
 
+/* Diffuse transmissions of the -SOS.Trans option (SOS.F:600-635) for the bins of MANY wavelengths in one solve.  The reference
+ * runs SOS_OS once per direction J with N0 = J, Fourier order 0 only, RHO = 0 and no surface, and keeps EMOINS: TDIFMUG(J).  Here
+ * every (context, direction) pair becomes a child entry of a device context table -- the context's own order-0 operators, which
+ * never touch the solar slot, with n0 = J, mus = mu[J-1], a black ground and order-1 vectors of its own, formed on the device by
+ * the statements of sosgpu_noyaux -- and every (bin, direction) pair an item of one order-0 multi-wavelength solve:
+ *   d_tdifmug[b][J-1] = the d_flux[.][0] of sosgpu_os_solve for a context created with n0 = J, iborm_max = 0, ro = 0,
+ *                       imat_surf = ifresnel = 0 and d_iborm = 0, bit for bit; 0 for a malformed bin (NT < 1, NT >= lp).
+ *  ctxs[nctx]        HOST array of contexts of one device whose operators have been queued (sosgpu_noyaux or
+ *                    sosgpu_noyaux_spectrum, on `stream` or complete); they must agree in N and may differ in OS_NB,
+ *                    iborm_max, IPOLAR, surface and Fresnel flags, none of which a child inherits
+ *  d_ctx_of_bin[nb]  index into ctxs of every bin (int32), or NULL with nctx = 1; a bin whose index is out of range is
+ *                    treated as malformed
+ *  d_nt[nb], d_prof[nb][3][lp]   as sosgpu_os_solve takes them
+ *  d_work            DEVICE area of work_bytes >= sosgpu_trans_spectrum_work_bytes(ctxs, nctx, nb, lp) bytes, 8-byte aligned, the
+ *                    caller's until `stream` has passed the call: the context table arrives there in ONE copy on `stream` from a
+ *                    pinned block the library recycles, followed by the child table, the children's vectors and the items'
+ *                    arrays (the profile rows are replicated per direction: 24 N lp bytes per bin)
+ * Asynchronous: nothing is waited for and no device memory is allocated -- except for level grids beyond the LDS-resident
+ * solver (lp > 64), whose streamed-field scratch comes from where sosgpu_os_solve_multi takes it (ctxs[0], at most 4 GiB at a
+ * time).  Launches: two for the child table, one for the items, the solve, one gather -- whatever N, nctx and nb are; the new
+ * kernels index children and items by blockIdx.x, so nctx N and nb N are bounded by 2^31 - 1 only (SOSGPU_E_ARG beyond), and
+ * the solve is split only where 4 GiB of scratch do not hold all items.  `stream` is noted for sosgpu_destroy on every context.
+ * Checked before anything is queued or a staging block is taken, SOSGPU_E_ARG for: NULL ctxs, d_nt, d_prof, d_tdifmug or
+ * d_work, a NULL context or one whose operators were never queued, contexts on different devices or with different N,
+ * nctx < 1, nb < 0, lp < 2, d_ctx_of_bin = NULL with nctx > 1, work_bytes too small, a misaligned d_work; SOSGPU_E_UNSUPPORTED
+ * when (N, lp) has no solver variant.  nb = 0 returns SOSGPU_OK with nothing queued.  sosgpu_trans_spectrum_work_bytes returns 0
+ * for arguments the call would refuse. */
+size_t sosgpu_trans_spectrum_work_bytes(sosgpu_ctx *const *ctxs, int nctx, int nb, int lp);
+int    sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp,
+                             const int32_t *d_nt, const double *d_prof,
+                             double *d_tdifmug /*[nb][N]*/, void *d_work, size_t work_bytes, void *stream);
+
 /* Replaces SOS_AGGREGATE (SOS_AGGREGATE.F:372-488) for nseg independent wavelengths/bands at once:
  * segment g covers bins seg[g]..seg[g+1]-1 of d_rec; seg[0] = 0, seg[nseg] = nb.  One big band (nseg = 1,
  * nb > 128) is reduced in chunks of 64 bins (deterministic; the strict serial bin order of the reference is kept for

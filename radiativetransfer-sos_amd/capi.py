@@ -27,6 +27,7 @@ EXPORTS = [
     "sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes", "sosgpu_debug_stage_blocks",
     "sosgpu_profile_true", "sosgpu_profile_spectrum_true", "sosgpu_output_depths", "sosgpu_level_transmission",
     "sosgpu_channel_accumulate", "sosgpu_channel_accumulate_work_bytes", "sosgpu_channel_finish",
+    "sosgpu_trans_spectrum", "sosgpu_trans_spectrum_work_bytes",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -248,6 +249,10 @@ def lib():
         L.sosgpu_debug_phase_buffer.argtypes = [vp, vp]
         L.sosgpu_debug_scratch.restype = i32
         L.sosgpu_debug_scratch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.sosgpu_trans_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_trans_spectrum_work_bytes.argtypes = [C.POINTER(vp), i32, i32, i32]
+        L.sosgpu_trans_spectrum.restype = i32
+        L.sosgpu_trans_spectrum.argtypes = [C.POINTER(vp), i32, vp, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
         L.sosgpu_debug_stage_blocks.restype = i32
         L.sosgpu_debug_stage_blocks.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
         L.sosgpu_debug_solve_plan.restype = i32

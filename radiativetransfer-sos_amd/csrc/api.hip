@@ -33,6 +33,7 @@ struct sosgpu_ctx {
     size_t bytes;
     hipEvent_t ev0, ev1;
     bool timed;
+    bool built;             // sosgpu_noyaux / sosgpu_noyaux_spectrum has been queued: the operator tables are (being) filled
     hipStream_t last_stream;
     std::vector<hipStream_t> used_streams;   // every stream a solve / table build of this context was queued on
     int nt_max_hint;
@@ -244,6 +245,7 @@ extern "C" int sosgpu_create(sosgpu_ctx **out, int device, const sosgpu_wave *wv
     cx->device = device;
     cx->bytes = 0;
     cx->timed = false;
+    cx->built = false;
     cx->last_stream = nullptr;
     cx->ind_surf = wv->ind_surf;
     cx->scratch = nullptr;
@@ -622,6 +624,7 @@ extern "C" int sosgpu_noyaux(sosgpu_ctx *cx, void *stream)
     launch_noyaux(cx->d, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     note_stream(cx, (hipStream_t)stream);
+    cx->built = true;
     return SOSGPU_OK;
 }
 
@@ -670,7 +673,7 @@ extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const f
     }
     launch_noyaux_table(d_tab, nctx, g, st);
     HIPCHK(hipGetLastError());
-    for (int i = 0; i < nctx; i++) note_stream(ctxs[i], st);
+    for (int i = 0; i < nctx; i++) { note_stream(ctxs[i], st); ctxs[i]->built = true; }
     return SOSGPU_OK;
 }
 
@@ -731,17 +734,22 @@ static int ensure_scratch(sosgpu_ctx *cx, size_t need)
 // Launch form, bins per launch and every scratch offset come from solve_plan (solve_plan.h).
 static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_ctx_of_bin, const int32_t *d_order, int nb, int lp, const int32_t *d_nt,
                          const int32_t *d_iborm, const double *d_prof, const int32_t *d_jout, const double *d_zz,
-                         double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream, int nz = 0)
+                         double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream, int nz = 0,
+                         const SosDev *as = nullptr, long scratch_gib = 0)
 {
     if (!cx || nb < 0 || lp < 2 || !d_nt || !d_iborm || !d_prof || !d_rec || !d_norders || !d_iglast || !d_flux)
         return SOSGPU_E_ARG;
     if ((d_jout == nullptr) != (d_zz == nullptr)) return SOSGPU_E_ARG;
-    if (cx->d.imat_surf && !cx->d.mp_gnd) return SOSGPU_E_ARG;
+    // `as`: what the entries of `table` have in common where that is not cx's own description (sosgpu_trans_spectrum: order 0
+    // only, no surface); it selects the variant and the record layout, cx still lends its scratch, events and stream list
+    const SosDev &dv = as ? *as : cx->d;
+    if (dv.imat_surf && !dv.mp_gnd) return SOSGPU_E_ARG;
     if (nb == 0) return SOSGPU_OK;
     HIPCHK(hipSetDevice(cx->device));
     hipStream_t st = (hipStream_t)stream;
-    const SolveShape sh = {cx->d.n, cx->d.smax, nb, lp, nz, table != nullptr};
-    const SolveOverrides ov = read_solve_overrides();
+    const SolveShape sh = {dv.n, dv.smax, nb, lp, nz, table != nullptr};
+    SolveOverrides ov = read_solve_overrides();
+    if (ov.scratch_gib <= 0) ov.scratch_gib = scratch_gib;      // (0: the plan's default budget)
     int ntm = 1;
     if (solve_plan_needs_nt(sh, ov)) {
         std::vector<int32_t> h_nt((size_t)nb);
@@ -756,7 +764,7 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
     if (!cx->ev0) { HIPCHK(hipEventCreate(&cx->ev0)); }
     if (!cx->ev1) { HIPCHK(hipEventCreate(&cx->ev1)); }
     HIPCHK(hipEventRecord(cx->ev0, st));
-    const int S1 = cx->d.smax + 1, W = cx->d.w;
+    const int S1 = dv.smax + 1, W = dv.w;
     const int nt_max = lp - 1;          // lp - 1 bounds every NT of the batch (the host pads the level axis to lp)
     for (int b0 = 0; b0 < nb; b0 += pl.per_launch) {
         SosBins bn;
@@ -780,14 +788,14 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
             cx->dbg_spec_i3 = pl.off_i3;
             const int nt_max_r = pl.lpb - 1;           // level capacity of the regions (>= every valid NT of the batch)
             bn.spec_k = -pl.spec_k; bn.s_begin = 0; bn.s_end = 0;
-            rc = launch_sos_stream(cx->d, bn, nt_max_r, st, &g_last_hip);
+            rc = launch_sos_stream(dv, bn, nt_max_r, st, &g_last_hip);
             bn.spec_k = pl.spec_k;
             // (a series typically ends after 25-50 of its up to 81 orders: 32 + 16 + ... wastes less than all at once, and a
             //  launch whose bins have all stopped costs a few microseconds)
             for (int s0 = 0, kr = pl.spec_k; s0 < S1 && rc == 0; s0 += kr, kr = std::max(1, pl.spec_k / 2)) {
                 bn.s_begin = s0; bn.s_end = std::min(S1, s0 + kr);
-                rc = launch_sos_stream(cx->d, bn, nt_max_r, st, &g_last_hip);
-                if (rc == 0) rc = launch_sos_stream_replay(cx->d, bn, bn.s_begin, bn.s_end, st, &g_last_hip);
+                rc = launch_sos_stream(dv, bn, nt_max_r, st, &g_last_hip);
+                if (rc == 0) rc = launch_sos_stream_replay(dv, bn, bn.s_begin, bn.s_end, st, &g_last_hip);
             }
         } else if (pl.big) {
             if (pl.form == SOSGPU_FORM_PERSIST) {
@@ -797,11 +805,11 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
             }
             for (int s0 = 0; s0 < S1 && rc == 0; s0 += pl.opl) {
                 bn.s_begin = s0; bn.s_end = std::min(S1, s0 + pl.opl);
-                rc = table ? launch_sos_stream_multi(cx->d, bn, nt_max, st, &g_last_hip)
-                           : launch_sos_stream(cx->d, bn, nt_max, st, &g_last_hip);
+                rc = table ? launch_sos_stream_multi(dv, bn, nt_max, st, &g_last_hip)
+                           : launch_sos_stream(dv, bn, nt_max, st, &g_last_hip);
             }
-        } else rc = table ? launch_sos_os_multi(cx->d, bn, nt_max, st, &g_last_hip)
-                          : launch_sos_os(cx->d, bn, nt_max, st, &g_last_hip);
+        } else rc = table ? launch_sos_os_multi(dv, bn, nt_max, st, &g_last_hip)
+                          : launch_sos_os(dv, bn, nt_max, st, &g_last_hip);
         if (rc == -2) return SOSGPU_E_HIP;
         if (rc) return rc;
     }
@@ -907,6 +915,108 @@ extern "C" int sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table,
     if (nz < 1 || nz > SOSGPU_MAX_OUTPUT_LEVELS || !d_jout || !d_zz) return SOSGPU_E_ARG;
     return os_solve_impl(cx, static_cast<const SosDev *>(d_table), d_ctx_of_bin, d_order, nb, lp, d_nt, d_iborm, d_prof, d_jout,
                          d_zz, d_rec, d_norders, d_iglast, d_flux, stream, nz);
+}
+
+// Diffuse transmissions of -SOS.Trans for the bins of many wavelengths (SOS.F:600-635): every (context, direction) pair becomes
+// a child entry of a context table in the work area, every (bin, direction) pair an item of ONE order-0 multi-wavelength solve
+// (trans.hip).  Work area, from its first 256-byte boundary, every block at a multiple of 256 bytes:
+//   parents [nctx] SosDev | children [nctx N] SosDev | sv [nctx N][4][kp] | ctx_of_item, nt, iborm, norders, iglast [nb N] int32
+//   | flux [nb N][2] | rec [nb N][3][W] | prof [nb N][3][lp]
+namespace {
+struct TransLayout { size_t parents, children, sv, ctx_of_item, nt, iborm, norders, iglast, flux, rec, prof, total; };
+
+bool trans_layout(int n, int kp, int nctx, int nb, int lp, TransLayout *out)
+{
+    if (n < 1 || nctx < 1 || nb < 0 || lp < 2) return false;
+    const size_t nchild = (size_t)nctx * n, nitems = (size_t)nb * n;
+    // children and items are counted in int by the kernels and the solver; the item kernel has one thread per profile element
+    if (nchild > (size_t)INT_MAX || nitems > (size_t)INT_MAX || nitems * 3 * lp / 256 >= (size_t)INT_MAX) return false;
+    size_t o = 0;
+    auto take = [&o](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+    TransLayout L;
+    L.parents = take((size_t)nctx * sizeof(SosDev));
+    L.children = take(nchild * sizeof(SosDev));
+    L.sv = take(nchild * 4 * kp * sizeof(double));
+    L.ctx_of_item = take(nitems * sizeof(int32_t));
+    L.nt = take(nitems * sizeof(int32_t));
+    L.iborm = take(nitems * sizeof(int32_t));
+    L.norders = take(nitems * sizeof(int32_t));
+    L.iglast = take(nitems * sizeof(int32_t));
+    L.flux = take(nitems * 2 * sizeof(double));
+    L.rec = take(nitems * 3 * (2 * (size_t)n + 1) * sizeof(double));
+    L.prof = take(nitems * 3 * lp * sizeof(double));
+    L.total = o + 256;                                      // (the caller's area need only be 8-byte aligned)
+    *out = L;
+    return true;
+}
+
+// the contexts of a call: all there, built, on one device, one N
+bool trans_ctxs_ok(sosgpu_ctx *const *ctxs, int nctx)
+{
+    if (!ctxs || nctx < 1) return false;
+    for (int i = 0; i < nctx; i++)
+        if (!ctxs[i] || !ctxs[i]->built || ctxs[i]->device != ctxs[0]->device || ctxs[i]->d.n != ctxs[0]->d.n) return false;
+    return true;
+}
+}   // namespace
+
+extern "C" size_t sosgpu_trans_spectrum_work_bytes(sosgpu_ctx *const *ctxs, int nctx, int nb, int lp)
+{
+    TransLayout L;
+    if (!trans_ctxs_ok(ctxs, nctx) || !trans_layout(ctxs[0]->d.n, ctxs[0]->d.kp, nctx, nb, lp, &L)) return 0;
+    return L.total;
+}
+
+extern "C" int sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp,
+                                     const int32_t *d_nt, const double *d_prof, double *d_tdifmug, void *d_work,
+                                     size_t work_bytes, void *stream)
+{
+    if (!d_nt || !d_prof || !d_tdifmug || !d_work || nb < 0 || lp < 2) return SOSGPU_E_ARG;
+    if (!trans_ctxs_ok(ctxs, nctx) || (!d_ctx_of_bin && nctx > 1)) return SOSGPU_E_ARG;
+    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    const SosDev &p0 = ctxs[0]->d;
+    TransLayout L;
+    if (!trans_layout(p0.n, p0.kp, nctx, nb, lp, &L) || work_bytes < L.total) return SOSGPU_E_ARG;
+    if (const int rc = sos_os_variant(p0.n, lp - 1, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (nb == 0) return SOSGPU_OK;
+    const int device = ctxs[0]->device;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    char *base = reinterpret_cast<char *>(((unsigned long long)d_work + 255) & ~255ull);
+    SosDev *d_parents = reinterpret_cast<SosDev *>(base + L.parents), *d_children = reinterpret_cast<SosDev *>(base + L.children);
+    int os_nb_max = 0;
+    {
+        Staged s(device, (size_t)nctx * sizeof(SosDev));
+        if (s.rc) return s.rc;
+        SosDev *tab = static_cast<SosDev *>(s.host());
+        for (int i = 0; i < nctx; i++) { tab[i] = ctxs[i]->d; os_nb_max = std::max(os_nb_max, ctxs[i]->d.os_nb); }
+        HIPCHK(s.send(d_parents, st));
+    }
+    const int nchild = nctx * p0.n, nitems = nb * p0.n;
+    launch_trans_table(d_parents, nchild, p0.n, d_children, reinterpret_cast<double *>(base + L.sv), os_nb_max, st);
+    TransItems it;
+    it.nb = nb; it.n = p0.n; it.lp = lp; it.nctx = nctx;
+    it.ctx_of_bin = d_ctx_of_bin; it.nt = d_nt; it.prof = d_prof;
+    it.ctx_of_item = reinterpret_cast<int32_t *>(base + L.ctx_of_item);
+    it.nt_item = reinterpret_cast<int32_t *>(base + L.nt);
+    it.iborm_item = reinterpret_cast<int32_t *>(base + L.iborm);
+    it.prof_item = reinterpret_cast<double *>(base + L.prof);
+    it.flux = reinterpret_cast<double *>(base + L.flux);
+    launch_trans_items(it, st);
+    HIPCHK(hipGetLastError());
+    // what the children have in common: order 0 only, a black ground without matrices (variant and record layout of the solve)
+    SosDev as = p0;
+    as.smax = 0; as.imat_surf = 0; as.ifresnel = 0; as.ro = 0.; as.mp_gnd = nullptr; as.rdir = nullptr;
+    // 4 GiB of streamed-field scratch at a time: a few thousand items, several times what the chip hosts at once
+    const int rc = os_solve_impl(ctxs[0], d_children, it.ctx_of_item, nullptr, nitems, lp, it.nt_item, it.iborm_item, it.prof_item,
+                                 nullptr, nullptr, reinterpret_cast<double *>(base + L.rec),
+                                 reinterpret_cast<int32_t *>(base + L.norders), reinterpret_cast<int32_t *>(base + L.iglast),
+                                 it.flux, stream, 0, &as, 4);
+    for (int i = 0; i < nctx; i++) note_stream(ctxs[i], st);       // (the kernels queued so far read their tables)
+    if (rc) return rc;
+    launch_trans_gather((size_t)nitems, it.flux, d_tdifmug, st);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
 }
 
 extern "C" int sosgpu_last_solve_ms(sosgpu_ctx *cx, float *ms)

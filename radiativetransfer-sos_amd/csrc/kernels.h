@@ -30,6 +30,23 @@ int sos_stream_threads(int n);
 int launch_sos_os_multi(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err);
 int launch_sos_stream_multi(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err);
 
+// The stage around the solver for the diffuse transmissions of -SOS.Trans (trans.hip, sosgpu_trans_spectrum).
+// launch_trans_table: the nchild = nctx * n child entries (incidence J = 1..n of every parent, n common to the parents) and
+// their order-1 vectors d_sv[nchild][4][kp]; two launches.  os_nb_max: the largest OS_NB of the parents (LDS of the second).
+inline size_t trans_sv_lds_bytes(int os_nb) { return (size_t)8 * (os_nb + 1) * sizeof(double); }
+void launch_trans_table(const SosDev *d_parents, int nchild, int n, SosDev *d_children, double *d_sv, int os_nb_max, hipStream_t st);
+// the arrays the multi solver takes for the nb * n items (bin b, incidence J) -> item b * n + J - 1; one launch
+struct TransItems {
+    int nb, n, lp, nctx;
+    const int32_t *ctx_of_bin, *nt;              // [nb]; ctx_of_bin null: context 0
+    const double *prof;                          // [nb][3][lp]
+    int32_t *ctx_of_item, *nt_item, *iborm_item; // [nb n]
+    double *prof_item, *flux;                    // [nb n][3][lp], [nb n][2] (cleared)
+};
+void launch_trans_items(const TransItems &a, hipStream_t st);
+// tdifmug[i] = EMOINS of item i; one launch
+void launch_trans_gather(size_t nitems, const double *d_flux, double *d_tdifmug, hipStream_t st);
+
 void launch_aggregate(const SosDev &cx, int nseg, const int32_t *d_seg, const double *d_aik,
                       const double *d_rec, const int32_t *d_norders, const double *d_flux, const double *d_scal,
                       const double *d_tdifmug, double *d_out_rec, double *d_out_scal, hipStream_t st, int nb_single,

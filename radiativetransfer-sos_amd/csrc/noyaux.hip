@@ -20,6 +20,7 @@
 // over the context type for that reason only (SosDev, or SosDev in address space 4).
 #include "sos_common.h"
 #include "kernels.h"
+#include "noyaux_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -45,9 +46,8 @@ __device__ inline void gsf_body(const CX &cx, const int s, const int j)
     int lstart;
     // sg: parity factor IG of the mirror relation at the current l (SOS_OS.F:2064-2099)
     if (s == 0) {                        // SOS_OS.F:1970-1991
-        const double x26 = 2. * sqrt(6.0);
-        const double p2 = (3. * c * c - 1.) * 0.5;
-        const double r2 = 3. * (1. - c * c) / x26;
+        double p2, r2;
+        gsf_start0(c, p2, r2);
         P[0 * W + j] = 1.; P[1 * W + j] = c; P[2 * W + j] = p2; R[2 * W + j] = r2;
         if (j) { P[0 * W - j] = 1.; P[1 * W - j] = -c; P[2 * W - j] = p2; R[2 * W - j] = r2; }
         pl = p2; plm = c; rl = r2; rlm = 0.; tl = 0.; tlm = 0.;
@@ -79,15 +79,8 @@ __device__ inline void gsf_body(const CX &cx, const int s, const int j)
     }
     int sg = (s == 1) ? 1 : -1;
     for (int l = lstart; l <= B - 1; l++) {   // SOS_OS.F:2067-2100
-        const double a = (2 * l + 1.) / sqrt((l + s + 1.0) * (l - s + 1.));
-        const double b = sqrt((double)((l + s) * (l - s))) / (2. * l + 1.);
-        const double d = (l + 1.) * (2 * l + 1.) / sqrt((l + 3.0) * (l - 1.) * (l + s + 1.) * (l - s + 1.));
-        const double e = sqrt((l + 2.0) * (l - 2.) * (l + s) * (l - s)) / (l * (2. * l + 1.));
-        // F = 2.*IS/(L*(L+1.)) is evaluated in REAL*4 by the reference (SOS_OS.F:2079)
-        const double f = (double)((2.f * (float)s) / ((float)l * ((float)l + 1.f)));
-        const double pn = a * (c * pl - b * plm);
-        const double rn = d * (c * rl - f * tl - e * rlm);
-        const double tn = d * (c * tl - f * rl - e * tlm);
+        double pn, rn, tn;
+        gsf_step(gsf_coef(s, l), c, pl, plm, rl, rlm, tl, tlm, pn, rn, tn);
         const size_t o = (size_t)(l + 1) * W;
         P[o + j] = pn; R[o + j] = rn; T[o + j] = tn;
         if (j) { P[o - j] = sg * pn; R[o - j] = sg * rn; T[o - j] = -sg * tn; }
@@ -108,24 +101,7 @@ __global__ void k_gsf(SosDev cx)
 template <class CX>
 __device__ inline double ktab(const CX &cx, int s, int X, int a, int b)
 {
-    const int W = cx.w, N = cx.n, B = cx.os_nb;
-    const double *P = cx.prt + ((size_t)(s * 3 + 0) * (B + 1)) * W + N;
-    const double *R = cx.prt + ((size_t)(s * 3 + 1) * (B + 1)) * W + N;
-    const double *T = cx.prt + ((size_t)(s * 3 + 2) * (B + 1)) * W + N;
-    const double *AL = cx.coef, *BE = cx.coef + (B + 1), *GA = cx.coef + 2 * (B + 1), *ZE = cx.coef + 3 * (B + 1);
-    double sum = 0.;
-    for (int l = s; l <= B; l++) {
-        const size_t o = (size_t)l * W;
-        switch (X) {
-        case 0: sum = sum + BE[l] * P[o + a] * P[o + b]; break;
-        case 1: sum = sum + GA[l] * P[o + a] * R[o + b]; break;
-        case 2: sum = sum + GA[l] * P[o + a] * T[o + b]; break;
-        case 3: { double r1 = T[o + a] * T[o + b], r2 = R[o + a] * R[o + b]; sum = sum + ZE[l] * r1 + AL[l] * r2; } break;
-        case 4: sum = sum + AL[l] * R[o + b] * T[o + a] + ZE[l] * R[o + a] * T[o + b]; break;
-        default: { double r1 = T[o + a] * T[o + b], r2 = R[o + a] * R[o + b]; sum = sum + AL[l] * r1 + ZE[l] * r2; } break;
-        }
-    }
-    return sum;
+    return ktab_sum(prt_table(cx, s), cx.coef, s, cx.os_nb, X, a, b);
 }
 
 // Half-system operator element (parity decomposition, sos_common.h).  sg = +1 for system A, -1 for B;
@@ -266,45 +242,10 @@ __device__ inline void sv_body(const CX &cx, const int s, const int r)
 {
     if (r >= cx.kp) return;
     double *o = cx.sv + (size_t)s * 4 * cx.kp;
-    double v0 = 0., v1 = 0., v2 = 0., v3 = 0.;
-    if (r < cx.r6) {
-        const int N = cx.n, W = cx.w, B = cx.os_nb;
-        const int c = r / (2 * N), d = r % (2 * N);
-        const int J = d < N ? d + 1 : -(d - N + 1);
-        const int D = -J;
-        const double f11 = cx.f11sun, f12 = cx.f12sun;
-        // molecular parts: single l = 2 terms, multiplied in the order the reference writes each of them (SOS_OS.F:2533-2545,
-        // 3237-3252 -- GR(D,0) is written differently for the two signs of D), so that they are its values to the last bit
-        const bool ray = s <= 2;
-        const double *P2 = cx.prt + ((size_t)(s * 3 + 0) * (B + 1) + 2) * W + N;
-        const double *R2 = cx.prt + ((size_t)(s * 3 + 1) * (B + 1) + 2) * W + N;
-        const double *T2 = cx.prt + ((size_t)(s * 3 + 2) * (B + 1) + 2) * W + N;
-        const double b0 = (s == 0) ? 1. : 0., b2 = cx.beta2, g2 = cx.gamma2, a2 = cx.alpha2;
-        const double spl = P2[0], srl = R2[0];
-        if (c == 0) {
-            v0 = ktab(cx, s, 0, 0, J);
-            v2 = f11 * ktab(cx, s, 0, 0, D) + f12 * ktab(cx, s, 1, D, 0);
-            if (ray) {
-                v1 = b0 + b2 * P2[J] * spl;
-                v3 = f11 * (b0 + b2 * P2[D] * spl) + f12 * (D < 0 ? g2 * srl * P2[D] : srl * P2[D] * g2);
-            }
-        } else if (c == 1) {
-            v0 = ktab(cx, s, 1, 0, J);
-            v2 = f11 * ktab(cx, s, 1, 0, D) + f12 * ktab(cx, s, 3, 0, D);
-            if (ray) {
-                v1 = g2 * R2[J] * spl;
-                v3 = f11 * (R2[D] * spl * g2) + f12 * (a2 * srl * R2[D]);
-            }
-        } else {
-            v0 = -ktab(cx, s, 2, 0, J);
-            v2 = f11 * ktab(cx, s, 2, 0, D) + f12 * ktab(cx, s, 4, D, 0);
-            if (ray) {
-                v1 = -(g2 * T2[J] * spl);
-                v3 = f11 * (g2 * spl * T2[D]) + f12 * (a2 * T2[D] * srl);
-            }
-        }
-    }
-    o[0 * cx.kp + r] = v0; o[1 * cx.kp + r] = v1; o[2 * cx.kp + r] = v2; o[3 * cx.kp + r] = v3;
+    double v[4] = {0., 0., 0., 0.};
+    if (r < cx.r6)
+        sv_rows(prt_table(cx, s), cx.coef, s, cx.os_nb, cx.n, r, cx.f11sun, cx.f12sun, cx.beta2, cx.gamma2, cx.alpha2, v);
+    o[0 * cx.kp + r] = v[0]; o[1 * cx.kp + r] = v[1]; o[2 * cx.kp + r] = v[2]; o[3 * cx.kp + r] = v[3];
 }
 
 __global__ void k_sv(SosDev cx)

@@ -1154,6 +1154,9 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     pl.itrphi, pl.igli, pl.land = itrphi, igli, land
     pl.tdifmug = None
     pl.want_trans = want_trans
+    # (_spectrum_pass with trans: the plan's rows of the part's diffuse_transmissions_many; a scalar block that came from the host)
+    pl.trans_rows = None
+    pl.host_scal = False
     try:
         # --- the CKD bin loop (SOS_PROC.F:3459-3594): profiles of every bin on the device
         band_sharded = False                          # True: every rank holds a slice of the band and the partials are all-reduced
@@ -1524,24 +1527,27 @@ def _expand_outputs(c, block=None):
     return tuple(out)
 
 
-def _gather_results(results, mine, nrows, world, nz=None, flux=None):
+def _gather_results(results, mine, nrows, world, nz=None, flux=None, trans=None):
     """Every rank receives the 23-tuples of the wavelengths the other ranks computed (all_gather_object of the compacted
     tuples; the only exchange of a wavelength-partitioned spectrum).  nz: every result is a list of nz 23-tuples (output
     altitudes) instead of one tuple.  flux: the per-wavelength flux rows of sos_spectrum_levels(fluxes=True), which travel with
-    the compact tuples and are filled in the same way."""
+    the compact tuples and are filled in the same way.  trans: the per-wavelength transmission entries
+    (transmissions=True), which travel and are filled like the flux rows."""
     import torch.distributed as dist
     per = 1 if nz is None else nz
     part = [(i, [_compact_outputs(t, nrows[i]) for t in ([results[i]] if nz is None else results[i])]) for i in mine]
-    if flux is not None:
-        part = [(i, (cs, flux[i])) for i, cs in part]
+    extras = [x for x in (flux, trans) if x is not None]
+    if extras:
+        part = [(i, (cs,) + tuple(x[i] for x in extras)) for i, cs in part]
     parts = [None] * world
     dist.all_gather_object(parts, part)
-    if flux is not None:
+    if extras:
         for pr in parts:
-            for i, (_, fx) in pr:
-                if flux[i] is None:
-                    flux[i] = fx
-        parts = [[(i, cs) for i, (cs, _) in pr] for pr in parts]
+            for i, row in pr:
+                for x, v in zip(extras, row[1:]):
+                    if x[i] is None:
+                        x[i] = v
+        parts = [[(i, row[0]) for i, row in pr] for pr in parts]
     todo = [(i, cs) for pr in parts for i, cs in pr if results[i] is None]
     blocks = _zero_pages((len(todo) * per, len(_TABLE_NAMES), 361, 81)) if todo else None
     for j, (i, cs) in enumerate(todo):
@@ -1625,7 +1631,7 @@ def _first_failed_index(index, device):
 
 
 def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False,
-                   split=False, chan=None):
+                   split=False, chan=None, trans=False):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
     launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop.
@@ -1633,7 +1639,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     chan (sos_spectrum_channels: the weights [C][calls] of the sensor channels, None: the pass as it was): the recomposition
     blocks of a chunk stay on the device and are added, weight by weight, onto one accumulator [C][K][nphi][3][W] that lives
     for the pass (solver.channel_accumulate, one call per chunk); no table is built and no 23-tuple formed per wavelength.
-    Returns what _channel_results makes of the accumulator and of the per-call scalars."""
+    Returns what _channel_results makes of the accumulator and of the per-call scalars.
+    trans (transmissions=True of the two entry points): after a part's operators are queued, ONE
+    solver.diffuse_transmissions_many call per group of equal direction count gives the diffuse transmissions of every bin of
+    the part; they ride the groups' and the singles' aggregates, and the pass also returns one trans_entry per call."""
     import time
     import torch
     from . import capi, solver
@@ -1646,31 +1655,39 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if len(aer_phases) != nwl:
         raise ValueError("aer_phases must be parallel to kwargs_list")
     if nwl == 0:
-        return ([], []) if fluxes else []
+        return tuple([] for _ in range(1 + bool(fluxes) + bool(trans))) if fluxes or trans else []
     capi.lib()
     dev = torch.device("cuda", device)
+    # the per-bin diffuse transmissions of a plan: its own loop's (a -SOS.Trans call), or its rows of the part's
+    # diffuse_transmissions_many (trans); the keyword is passed only with trans, so that the calls are as they were without it
+    def single_trans(pl):
+        return pl.tdifmug if pl.tdifmug is not None else pl.trans_rows
+
+    def group_trans(gp):
+        return dict(tdifmug=torch.cat([pl.trans_rows for pl in gp])) if trans else {}
+
     # solve_spectrum / solve_spectrum_levels are looked up when called: the tests count launches by replacing them
     if alts is None:
         nz, per_chunk = 1, max(1, int(chunk))
 
         def solve_group(table, gp, bins, cob, seg, aik):
-            rec, scal = solver.solve_spectrum(table, bins, cob, seg, aik, order=None)
+            rec, scal = solver.solve_spectrum(table, bins, cob, seg, aik, order=None, **group_trans(gp))
             return rec[None], scal[None]
 
         def solve_single(pl):
             out = pl.ctx.solve(pl.bins, pl.ctx.alloc_outputs(pl.bins["nb"], zero=False))
-            rec, scal = pl.ctx.aggregate(out, pl.aik, scal=pl.bins.get("scal"), tdifmug=pl.tdifmug)
+            rec, scal = pl.ctx.aggregate(out, pl.aik, scal=pl.bins.get("scal"), tdifmug=single_trans(pl))
             return rec[None], scal[None]
     else:
         nz, per_chunk = len(alts), max(1, int(chunk) // len(alts))      # the record-memory rule of sos_spectrum_levels
 
         def solve_group(table, gp, bins, cob, seg, aik):
             return solver.solve_spectrum_levels(table, bins, cob, seg, aik, solver.concat_levels([pl.levels for pl in gp]),
-                                                order=None)
+                                                order=None, **group_trans(gp))
 
         def solve_single(pl):
             out = pl.ctx.solve_levels(pl.bins, pl.levels) if pl.bins["nb"] else None
-            return pl.ctx.aggregate_levels(out, pl.levels, pl.aik, scal=pl.bins.get("scal"), tdifmug=pl.tdifmug)
+            return pl.ctx.aggregate_levels(out, pl.levels, pl.aik, scal=pl.bins.get("scal"), tdifmug=single_trans(pl))
     true_kw = dict(true_depth=True) if split else {}    # (split=False: the calls as they were)
     flux_row, flux_names = (_level_flux_split_row, LEVEL_FLUX_SPLIT_NAMES) if split else (_level_flux_row, LEVEL_FLUX_NAMES)
     level_keys = ("jout", "zz", "tauout") + (("tauvrai",) if split else ())
@@ -1689,6 +1706,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
         call_scal = {}                                  # call -> [K][5 (+ flux columns)]: elements 18..22 (and the flux row)
     results = [None] * nwl                              # K 23-tuples per wavelength
     flux_rows = [None] * nwl if fluxes else None        # fluxes: the [K][5] flux rows per wavelength
+    trans_out = [None] * nwl if trans else None         # trans: the trans_entry of every wavelength
     debug = bool(os.environ.get("SOS_SPECTRUM_DEBUG"))
     nrows = {}
     tm = dict(prepare=0.0, solve_launch=0.0, wait=0.0, trphi=0.0, finish=0.0, fluxes=0.0)
@@ -1789,6 +1807,27 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     if unbuilt:
                         where = unbuilt[0].index
                         solver.build_operators([pl.ctx for pl in unbuilt])
+                    if trans:
+                        # the diffuse transmissions of every bin of the part: one call per direction count, whatever the calls
+                        # are (it reads the contexts' order-0 operators, queued above or by the side streams waited for)
+                        by_n = collections.OrderedDict()
+                        for pl in part:
+                            if pl.bins["nb"]:
+                                by_n.setdefault(pl.n, []).append(pl)
+                        for gp in by_n.values():
+                            where = gp[0].index
+                            tbins, tcob = solver.concat_profiles([pl.bins for pl in gp])
+                            tdifmus, tdifmug = solver.diffuse_transmissions_many([pl.ctx for pl in gp], tbins, tcob)
+                            b0 = 0
+                            for pl in gp:
+                                b1 = b0 + pl.bins["nb"]
+                                pl.trans_rows = tdifmug[b0:b1]
+                                sc = pl.bins["scal"]                 # TDIFMUS into column 0, as _prepare does for -SOS.Trans
+                                if not isinstance(sc, torch.Tensor):
+                                    pl.host_scal = True              # (a host profile: the call stays with the singles)
+                                    sc = pl.bins["scal"] = solver._dev_f64(np.asarray(sc), dev)
+                                sc[:, 0] = tdifmus[b0:b1]
+                                b0 = b1
                     t1 = time.perf_counter()
                     tm["prepare"] += t1 - t0
                     # --- groups of wavelengths one launch can cover
@@ -1796,7 +1835,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     single = []
                     for pl in part:
                         b = pl.bins
-                        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor):
+                        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor) or pl.host_scal:
                             single.append(pl)
                             continue
                         # (the last entry is False throughout with output slots: their calls have zout = -1)
@@ -1861,6 +1900,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                             raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
                                                "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
                         todo += [(pl, k, recs[k][g], fins[k], g) for k in range(nz)]
+                        if trans:                               # (the same values in every slot: they ignore the altitude)
+                            trans_out[pl.index] = trans_entry(pl.p["tetas"], pl.mu, float(fins[0]["ttot_tronc"][g]),
+                                                              float(fins[0]["ttot_vrai"][g]), float(fins[0]["tdifmus"][g]),
+                                                              np.array(fins[0]["tdifmug"][g], dtype=np.float64))
                 # one launch for every (wavelength, altitude) of the chunk, its flat result downloaded as it is
                 flat, shapes = _trphi_launch_many([(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
                                                    for pl, _, r, f, g in todo])
@@ -1946,8 +1989,9 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if alts is None:
         results = [None if r is None else r[0] for r in results]
     if world > 1 and gather:
-        _gather_results(results, mine, nrows, world, None if alts is None else nz, flux_rows)
-    return (results, flux_rows) if fluxes else results
+        _gather_results(results, mine, nrows, world, None if alts is None else nz, flux_rows, trans_out)
+    ret = (results,) + ((flux_rows,) if fluxes else ()) + ((trans_out,) if trans else ())
+    return ret if len(ret) > 1 else results
 
 
 def _channel_results(kw, chan, mine, acc, ang_rows, call_scal, alts, nflux, dev, world, lead):
@@ -2106,7 +2150,21 @@ def sos_spectrum_channels(kwargs_list, weights, normalize=True, altitudes=None, 
                           alts, bool(fluxes), bool(split), chan=wts)
 
 
-def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16, parts=4):
+def _transmissions_argument(fn, kwargs_list, transmissions):
+    """The rule of transmissions=True, checked before any library call: a bool, and no call may ask for the -SOS.Trans file
+    (that option keeps its own path: one order-0 context per direction)."""
+    if not isinstance(transmissions, (bool, np.bool_)):
+        raise ValueError("%s: transmissions must be True or False, got %r" % (fn, transmissions))
+    if transmissions:
+        for i, kw in enumerate(kwargs_list):
+            if str(kw.get("fictrans", "NO_OUTPUT")).strip() != "NO_OUTPUT":
+                raise ValueError("%s: transmissions=True returns the diffuse transmissions as arrays; call %d asks for the "
+                                 "-SOS.Trans file %r (leave it at NO_OUTPUT, or drop the keyword)" % (fn, i, kw["fictrans"]))
+    return bool(transmissions)
+
+
+def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16, parts=4,
+                 transmissions=False):
     """A spectrum of sos_proc calls -- one per wavelength, as the reference issues them one after the other
     (binding/run_sos.py:640-695; the bin loop of each is SOS_PROC.F:3459-3594) -- as ONE pass over the GPU:
 
@@ -2152,12 +2210,22 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     profile launches on its side stream again.  The source operators are not among them either: the contexts are created unbuilt
     and solver.build_operators fills the operator tables of a part in at most five launches on the stream of the solves
     (sosgpu_noyaux_spectrum), after the side streams -- which produce the surface matrices -- have been waited for; a -SOS.Trans
-    call builds its own, and SOS_SPECTRUM_OPERATORS_PER_CALL=1 gives every call its four or five launches on its side stream."""
-    return _spectrum_pass("sos_spectrum", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts)
+    call builds its own, and SOS_SPECTRUM_OPERATORS_PER_CALL=1 gives every call its four or five launches on its side stream.
+
+    transmissions=True (a bool; every call with -SOS.Trans at NO_OUTPUT: ValueError naming the call otherwise, before any
+    library call): returns (tuples, trans) with trans[i] the trans_entry of call i -- the diffuse transmittances TOA -> surface
+    and surface -> TOA for every direction that the -SOS.Trans file prints, as arrays in full precision.  The transmissions of
+    ALL bins of a part come from ONE order-0 solve per direction count (solver.diffuse_transmissions_many,
+    sosgpu_trans_spectrum: no context per direction), whatever mix of grouped, single, no-gas, -SOS.AbsModeCKD 2 and aerosol-layer
+    calls the part holds, and ride the aggregates that run anyway; the 23-tuples keep their bits.  With gather=True the
+    entries travel with the compacted tuples.  With the default the return value, the launches and the bits are unchanged."""
+    trans = _transmissions_argument("sos_spectrum", kwargs_list, transmissions)
+    return _spectrum_pass("sos_spectrum", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
+                          trans=trans)
 
 
 def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16,
-                        parts=4, fluxes=False, split=False):
+                        parts=4, fluxes=False, split=False, transmissions=False):
     """sos_spectrum for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output): every wavelength is
     prepared once, ALL bins of a group of wavelengths go through ONE launch of the fused solver per kernel variant with K output
     slots each (sosgpu_os_solve_multi_levels), then K segmented aggregates (each altitude with its own TAUOUT) and K azimuth
@@ -2192,27 +2260,51 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
     the untruncated depth between the two levels that bracket z); the rows equal that call's bit for bit.  The profile
     launches of a part export the untruncated depth rows (sosgpu_profile_spectrum_true), one sosgpu_output_depths launch per
     part or wavelength gives the depths at the altitudes, and ONE sosgpu_level_transmission launch per solved group (or single
-    wavelength) -- not one per altitude -- puts their band transmissions into the scalar blocks that are downloaded anyway."""
+    wavelength) -- not one per altitude -- puts their band transmissions into the scalar blocks that are downloaded anyway.
+
+    transmissions=True: as sos_spectrum describes it; trans (one trans_entry per call: the values do not depend on the output
+    altitude) is appended behind spec, and behind flux with fluxes=True."""
+    trans = _transmissions_argument("sos_spectrum_levels", kwargs_list, transmissions)
     alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes, split)
     return _spectrum_pass("sos_spectrum_levels", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
-                          alts, bool(fluxes), bool(split))
+                          alts, bool(fluxes), bool(split), trans=trans)
+
+
+def trans_quantities(tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):
+    """The three quantities of the -SOS.Trans file (SOS_PROC.F:3785-3822) from the aggregated values: the direct transmission
+    for the true optical depth, and the diffuse transmissions TOA -> surface and surface -> TOA (one per direction) brought
+    back to the true atmosphere by + exp(-tau_tr/mu) - exp(-tau/mu).  Returns (t_dir_down, t_dif_down, t_dif_up[N])."""
+    cs = math.cos(math.pi * tetas / 180.0)
+    t_dir_down = math.exp(-ttot_vrai / cs)
+    t_dif_down = tdifmus + math.exp(-ttot_tronc / cs) - math.exp(-ttot_vrai / cs)
+    t_dif_up = np.empty(len(mu))
+    for j in range(len(mu)):
+        t_dif_up[j] = tdifmug[j] + math.exp(-ttot_tronc / mu[j]) - math.exp(-ttot_vrai / mu[j])
+    return t_dir_down, t_dif_down, t_dif_up
+
+
+def trans_entry(tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):
+    """trans[i] of sos_spectrum(..., transmissions=True): the angles, the aggregated values write_trans_file receives and the
+    three quantities it prints (trans_quantities), in full precision."""
+    t_dir_down, t_dif_down, t_dif_up = trans_quantities(tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug)
+    return dict(thetas=float(tetas), thetav=np.array([math.degrees(math.acos(m)) for m in mu]),
+                ttot_tronc=ttot_tronc, ttot_vrai=ttot_vrai, tdifmus=tdifmus, tdifmug=tdifmug,
+                t_dir_down=t_dir_down, t_dif_down=t_dif_down, t_dif_up=t_dif_up)
 
 
 def write_trans_file(path, tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):
-    """-SOS.Trans file (SOS_PROC.F:3785-3822, formats 1005, 1006, 1010, 2010): direct transmission for the true optical
-    depth, diffuse transmissions brought back to the true atmosphere by + exp(-tau_tr/mu) - exp(-tau/mu)."""
-    cs = math.cos(math.pi * tetas / 180.0)
+    """-SOS.Trans file (SOS_PROC.F:3785-3822, formats 1005, 1006, 1010, 2010): the quantities of trans_quantities."""
+    t_dir_down, t_dif_down, t_dif_up = trans_quantities(tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug)
     with open(path, "w") as f:
         f.write("Solar Zenith Angle : %7.3f\n" % tetas)
-        f.write("Direct transmission TOA -> surface : %8.4f\n" % math.exp(-ttot_vrai / cs))
+        f.write("Direct transmission TOA -> surface : %8.4f\n" % t_dir_down)
         f.write("  \n")
         f.write(" Diffuse transmittance : TOA -> surface\n")
-        f.write("    thetas = %6.3f   td(thetas) = %7.4f\n" % (tetas, tdifmus + math.exp(-ttot_tronc / cs) - math.exp(-ttot_vrai / cs)))
+        f.write("    thetas = %6.3f   td(thetas) = %7.4f\n" % (tetas, t_dif_down))
         f.write("  \n")
         f.write(" Diffuse transmittance : surface -> TOA\n")
         for j in range(len(mu)):
-            td = tdifmug[j] + math.exp(-ttot_tronc / mu[j]) - math.exp(-ttot_vrai / mu[j])
-            f.write("    thetav = %6.3f   td(thetav) = %7.4f\n" % (math.degrees(math.acos(mu[j])), td))
+            f.write("    thetav = %6.3f   td(thetav) = %7.4f\n" % (math.degrees(math.acos(mu[j])), t_dif_up[j]))
 
 
 def write_flux_file(path, tetas, tdir_vrai, flux_diff_down, flux_down, eplus, zalt, tr, hr, ta, ha, tauabs):

@@ -745,6 +745,37 @@ def build_operators(ctxs):
     return n
 
 
+def diffuse_transmissions_many(ctxs, bins, ctx_of_bin=None):
+    """SosContext.diffuse_transmissions for the bins of MANY contexts in one call (sosgpu_trans_spectrum): every (bin,
+    direction) pair is an item of ONE order-0 solve, every (context, direction) pair an entry of a device table that shares
+    the context's order-0 operators -- no context per direction, nothing waited for.  ctxs: built contexts of one device that
+    agree in N (OS_NB, polarisation, surface may differ); bins: their concatenated bins (concat_bins, or the bins of the one
+    context); ctx_of_bin[nb]: int32 index into ctxs of every bin (None with one context).  Returns (tdifmus[nb],
+    tdifmug[nb][N]) device tensors with the bits of the per-direction loop; tdifmus[b] is column n0 - 1 of the bin's context.
+    The work area comes from torch's allocator and is dropped at return (the allocator keeps it for the stream)."""
+    ctxs = list(ctxs)
+    if not ctxs:
+        raise ValueError("diffuse_transmissions_many needs at least one context")
+    for cx in ctxs:
+        cx._need_operators()
+    first = ctxs[0]
+    d, n, nb = first.device, first.n, int(bins["nb"])
+    if ctx_of_bin is None and len(ctxs) > 1:
+        raise ValueError("ctx_of_bin is required with more than one context")
+    cob = None if ctx_of_bin is None else _dev_i32(ctx_of_bin, d)
+    L = capi.lib()
+    hs = (C.c_void_p * len(ctxs))(*[cx._h for cx in ctxs])
+    tdifmug = torch.empty((nb, n), dtype=torch.float64, device=d)
+    need = int(L.sosgpu_trans_spectrum_work_bytes(hs, len(ctxs), nb, bins["lp"]))
+    work = torch.empty(max(need, 8), dtype=torch.uint8, device=d)
+    capi.check(L.sosgpu_trans_spectrum(hs, len(ctxs), _ptr(cob), nb, bins["lp"], _ptr(bins["nt"]), _ptr(bins["prof"]),
+                                       _ptr(tdifmug), _ptr(work), need, first._stream()), "sosgpu_trans_spectrum")
+    if len({cx.n0 for cx in ctxs}) == 1:
+        return tdifmug[:, first.n0 - 1].clone(), tdifmug
+    n0 = _dev_i32(np.array([cx.n0 - 1 for cx in ctxs], dtype=np.int32), d).long()
+    return tdifmug.gather(1, n0[cob.long()][:, None])[:, 0].contiguous(), tdifmug
+
+
 def release_scratch():
     """Return the scratch buffers the library keeps from destroyed contexts (streamed solver; at most 8 GiB) to the device,
     and free the pinned staging blocks of the table-form calls whose copies have passed (sosgpu_trim)."""
@@ -798,10 +829,25 @@ def concat_bins(bins_list):
     return out, cob, seg
 
 
-def solve_spectrum(table, bins, ctx_of_bin, seg, aik, out=None, order="cost"):
+def concat_profiles(bins_list):
+    """The level profiles alone of per-wavelength bin dicts, concatenated as concat_bins does it (level axis padded to the
+    largest lp) -- what diffuse_transmissions_many reads, whatever output levels the dicts carry.  Returns (dict(nb, lp, nt,
+    prof), ctx_of_bin int32 device tensor); one dict is passed through as it is, with ctx_of_bin None."""
+    if len(bins_list) == 1:
+        return bins_list[0], None
+    d = bins_list[0]["prof"].device
+    lp = max(b["lp"] for b in bins_list)
+    prof = [b["prof"] if b["lp"] == lp else torch.nn.functional.pad(b["prof"], (0, lp - b["lp"])) for b in bins_list]
+    counts = [b["nb"] for b in bins_list]
+    cob = _dev_i32(np.repeat(np.arange(len(bins_list), dtype=np.int32), counts), d)
+    return dict(nb=int(sum(counts)), lp=lp, nt=torch.cat([b["nt"] for b in bins_list]), prof=torch.cat(prof).contiguous()), cob
+
+
+def solve_spectrum(table, bins, ctx_of_bin, seg, aik, out=None, order="cost", tdifmug=None):
     """The bin loops of MANY wavelengths (one SOS_PROC call each in the reference, binding/run_sos.py:640) as ONE launch of the
     fused solver plus one segmented SOS_AGGREGATE: bin b runs with the operators of table.ctxs[ctx_of_bin[b]], segment g of
     `seg` is wavelength g.  bins / ctx_of_bin / seg from concat_bins; aik[nb] device tensor in the same order.
+    tdifmug: optional per-bin [nb][N] diffuse transmissions (diffuse_transmissions_many), aggregated per segment.
     Returns (rec[nwavelengths][smax+1][3][W], scal[nwavelengths][10+N]) like SosContext.aggregate; no synchronisation."""
     cx = table.ctxs[0]
     if out is None:
@@ -815,7 +861,7 @@ def solve_spectrum(table, bins, ctx_of_bin, seg, aik, out=None, order="cost"):
                                                 _ptr(bins["nt"]), _ptr(bins["iborm"]), _ptr(bins["prof"]),
                                                 _ptr(bins["jout"]), _ptr(bins["zz"]), _ptr(out["rec"]), _ptr(out["norders"]),
                                                 _ptr(out["iglast"]), _ptr(out["flux"]), cx._stream()), "sosgpu_os_solve_multi")
-    return cx.aggregate(out, aik, seg=seg, scal=bins.get("scal"))
+    return cx.aggregate(out, aik, seg=seg, scal=bins.get("scal"), tdifmug=tdifmug)
 
 
 CKD_WL_DTYPE = np.dtype([("pres_off", "<i8"), ("temp_off", "<i8"), ("conc_off", "<i8"), ("prs_off", "<i8"), ("tmp_off", "<i8"),
@@ -1120,13 +1166,14 @@ def _spectrum_order(cx, bins, order):
     return None
 
 
-def solve_spectrum_levels(table, bins, ctx_of_bin, seg, aik, levels, out=None, order="cost"):
+def solve_spectrum_levels(table, bins, ctx_of_bin, seg, aik, levels, out=None, order="cost", tdifmug=None):
     """solve_spectrum for K output altitudes: ONE launch of the fused solver over the bins of many wavelengths, every bin with
     K output slots (sosgpu_os_solve_multi_levels), then one segmented SOS_AGGREGATE per altitude with that altitude's TAUOUT in
     scal[:, 3] (SosContext.aggregate_levels).  bins / ctx_of_bin / seg from concat_bins, levels from concat_levels,
     aik[nb] device tensor in the same order; order as in solve_spectrum.  Returns (rec[K][nwavelengths][smax+1][3][W],
     scal[K][nwavelengths][10+N]) device tensors; no synchronisation.  Slot k of wavelength g equals solve_spectrum's record of
-    g with that altitude's profile, bit for bit."""
+    g with that altitude's profile, bit for bit.  tdifmug: optional per-bin [nb][N] diffuse transmissions, aggregated per
+    segment into every altitude's scalar block."""
     cx = table.ctxs[0]
     nz, nb = levels["nz"], bins["nb"]
     if out is None:
@@ -1138,7 +1185,7 @@ def solve_spectrum_levels(table, bins, ctx_of_bin, seg, aik, levels, out=None, o
                                                        _ptr(levels["jout"]), _ptr(levels["zz"]), _ptr(out["rec"]),
                                                        _ptr(out["norders"]), _ptr(out["iglast"]), _ptr(out["flux"]),
                                                        cx._stream()), "sosgpu_os_solve_multi_levels")
-    return cx.aggregate_levels(out, levels, aik, seg=seg, scal=bins.get("scal"))
+    return cx.aggregate_levels(out, levels, aik, seg=seg, scal=bins.get("scal"), tdifmug=tdifmug)
 
 
 def solve_many(items, n_streams=16):

@@ -39,6 +39,7 @@
  *   sosgpu_aggregate   <- SOS_AGGREGATE           src/SOS_AGGREGATE.F:172
  *   sosgpu_glitter     <- SOS_GLITTER (+SOS_GSF, SOS_MAT_FRESNEL, SOS_MAT_REFLEXION, SOS_MISE_FORMAT)
  *                                                 src/SOS_GLITTER.F:229, src/SOS_SURFACE.F:1235,1708,2307
+ *   sosgpu_surface_batch      sea and land surface matrices of a part of a spectrum: one asynchronous call
  *   sosgpu_trphi       <- SOS_TRPHI               src/SOS_TRPHI.F:749
  *   sosgpu_trphi_spectrum     the same for the wavelengths and output altitudes of a part of a spectrum: one launch
  *   sosgpu_level_flux  <- EMOINS / EPLUS of SOS_OS  src/SOS_OS.F:1447-1456, at the output altitude of an aggregated record
@@ -437,6 +438,41 @@ int  sosgpu_channel_finish(int device, const double *d_acc, const double *d_angd
  * OS_NM are those of sosgpu_glitter. */
 int  sosgpu_land_surface(int device, const sosgpu_land *land, int n, const double *mu, const double *chr, double ind,
                          int os_nb, int os_ns, int os_nm, float *d_rsurf, int32_t *ier_out, void *stream);
+
+/* sosgpu_glitter / sosgpu_land_surface for many jobs on one angle set -- the wavelengths of a part of a spectrum, whose water
+ * index or Roujean coefficients change with the wavelength -- in ONE asynchronous call.  Block j holds, bit for bit, the
+ * d_rsurf sosgpu_glitter (isurf 1) or sosgpu_land_surface (isurf 3, 4, 5, 7) writes for job j's parameters.
+ * What the jobs have in common is computed once; the distinct parameter sets are found by exact equality of the doubles:
+ *   one Cox-Munk azimuth analysis per distinct wind, one Maignan analysis per distinct coef_c, one constant analysis each for
+ *   Rondeaux-Herman and Breon; one SOS_MAT_REFLEXION result per distinct (analysis, ind), COEF = 1/sigma^2 for the sea and 1
+ *   for land; one sosgpu_mat_fresnel_host per distinct ind (on the host, inside the call); one Roujean analysis per distinct
+ *   (k0, k1, k2); one kernel that writes every job's block and status.
+ *  mu[n], chr[n]   HOST, as sosgpu_glitter
+ *  jobs[njobs]     HOST array; jobs may repeat one another (their blocks are then equal) but not share a d_rsurf
+ *  d_status[njobs] DEVICE, written on `stream` for every job: 0, or -1 when the Roujean function goes negative for the job's
+ *                  coefficients (the reference's IER = -1, SOS_ROUJEAN.F:548).  A flagged job disturbs no other job; the
+ *                  content of its block is unspecified.
+ *  d_work          DEVICE area of work_bytes >= sosgpu_surface_batch_work_bytes(...) bytes, 8-byte aligned, the caller's until
+ *                  `stream` has passed the call.  The tables and the Fresnel coefficients arrive there in ONE copy on `stream`,
+ *                  from a pinned block the library recycles; the intermediates (E, IL of every analysis, the reflexion
+ *                  blocks) live behind them.  Nothing beyond sosgpu_surface_batch_work_bytes(...) bytes is touched.
+ * Asynchronous: one copy and at most six launches whatever njobs is, nothing is waited for, no device memory is allocated.
+ * Checked on the host before anything is queued: SOSGPU_E_ARG for n outside 1..85, the order bounds and the LDS limit of
+ * sosgpu_glitter, NULL mu, chr, jobs, d_status, d_work or a NULL d_rsurf, njobs < 0 or njobs > 65535, an isurf outside
+ * {1, 3, 4, 5, 6, 7}, a misaligned d_work, work_bytes too small; SOSGPU_E_UNSUPPORTED for isurf = 6, as sosgpu_land_surface.
+ * njobs = 0 returns SOSGPU_OK with nothing queued.  sosgpu_surface_batch_work_bytes returns 0 for arguments the call would
+ * refuse (it does not look at d_rsurf, so that the area can be sized before the blocks exist). */
+typedef struct sosgpu_surface_job {
+    int32_t isurf;          /* 1 Cox-Munk sea; 3, 4, 5, 7 land (6: SOSGPU_E_UNSUPPORTED, as sosgpu_land_surface) */
+    int32_t reserved;
+    double  wind, ind;      /* sea: wind speed, water index; land 4, 5, 7: ind of the BPDF; land 3: ind ignored */
+    double  k0, k1, k2, coef_c;
+    float  *d_rsurf;        /* DEVICE output block [os_nb+1][9][N][N], reference surface-file record order */
+} sosgpu_surface_job;
+size_t sosgpu_surface_batch_work_bytes(int n, int os_nb, int os_ns, int os_nm, const sosgpu_surface_job *jobs, int njobs);
+int    sosgpu_surface_batch(int device, int n, const double *mu, const double *chr, int os_nb, int os_ns, int os_nm,
+                            const sosgpu_surface_job *jobs, int njobs, int32_t *d_status /*[njobs]*/,
+                            void *d_work, size_t work_bytes, void *stream);
 
 /* Scratch requirements (bytes) of the context on its device, for memory planning. */
 size_t sosgpu_ctx_bytes(const sosgpu_ctx *cx);

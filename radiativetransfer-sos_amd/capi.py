@@ -28,6 +28,7 @@ EXPORTS = [
     "sosgpu_profile_true", "sosgpu_profile_spectrum_true", "sosgpu_output_depths", "sosgpu_level_transmission",
     "sosgpu_channel_accumulate", "sosgpu_channel_accumulate_work_bytes", "sosgpu_channel_finish",
     "sosgpu_trans_spectrum", "sosgpu_trans_spectrum_work_bytes",
+    "sosgpu_surface_batch", "sosgpu_surface_batch_work_bytes",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -104,6 +105,12 @@ class TrphiJob(C.Structure):
     _fields_ = [("cx", C.c_void_p), ("d_rec", C.c_void_p), ("nf", C.c_int32), ("igli", C.c_int32),
                 ("phi_off", C.c_int32), ("nphi", C.c_int32), ("tau", C.c_double), ("tauout", C.c_double), ("wind", C.c_double),
                 ("land", C.POINTER(Land))]
+
+
+class SurfaceJob(C.Structure):
+    """sosgpu_surface_job (include/sosgpu.h): one surface of sosgpu_surface_batch."""
+    _fields_ = [("isurf", C.c_int32), ("reserved", C.c_int32), ("wind", C.c_double), ("ind", C.c_double), ("k0", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("coef_c", C.c_double), ("d_rsurf", C.c_void_p)]
 
 
 class FluxJob(C.Structure):
@@ -245,6 +252,10 @@ def lib():
         L.sosgpu_channel_finish.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp]
         L.sosgpu_land_surface.restype = i32
         L.sosgpu_land_surface.argtypes = [i32, C.POINTER(Land), i32, vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_int32), vp]
+        L.sosgpu_surface_batch_work_bytes.restype = C.c_size_t
+        L.sosgpu_surface_batch_work_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(SurfaceJob), i32]
+        L.sosgpu_surface_batch.restype = i32
+        L.sosgpu_surface_batch.argtypes = [i32, i32, vp, vp, i32, i32, i32, C.POINTER(SurfaceJob), i32, vp, vp, C.c_size_t, vp]
         L.sosgpu_debug_phase_buffer.restype = i32
         L.sosgpu_debug_phase_buffer.argtypes = [vp, vp]
         L.sosgpu_debug_scratch.restype = i32

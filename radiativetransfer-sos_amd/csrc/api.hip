@@ -1579,6 +1579,189 @@ extern "C" int sosgpu_land_surface(int device, const sosgpu_land *land, int n, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// sosgpu_surface_batch: the two entry points above for many jobs on one angle set.  The host finds the distinct parameter sets
+// (exact equality of the doubles, compared as bit patterns), lays the work area out and fills the tables; the device side is
+// the table forms of the same kernels (glitter.hip, land.hip) and one compose kernel.
+// Work area, every section 8-byte aligned; [tables] travel in the one staged copy:
+//   [ mu[n] | fcoef[nind][4][os_ns+1] | sigma2[nwind] | C[nmaignan] | SurfReflSet[nrefl] | SurfTriple[ntrip] | SurfJobDev[njobs]
+//     | model[nconst] | flag[ntrip] (zero) ]
+//   il[nan][npairs] | e[nan][npairs][os_nm+1] | il_nn[ntrip][n^2] | e_nn[ntrip][n^2][os_nb+1] | refl[nrefl][os_nb+1][9][n][n]
+// nan = nwind + nmaignan + nconst analyses, in that order.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct SurfacePlan {
+    std::vector<double> winds, cs, inds;             // distinct values, in order of first appearance
+    std::vector<int32_t> models;                     // constant analyses present: 0 Rondeaux-Herman, 1 Breon
+    std::vector<SurfReflSet> refl;
+    std::vector<SurfTriple> trip;
+    std::vector<int32_t> job_refl, job_trip;         // per job, -1: none
+    size_t o_fc, o_par0, o_par1, o_refl, o_trip, o_jobs, o_models, o_flags, table_bytes;
+    size_t o_il, o_e, o_ilnn, o_enn, o_rb, total;
+    int nan() const { return (int)(winds.size() + cs.size() + models.size()); }
+};
+
+uint64_t dbl_bits(double v) { uint64_t b; memcpy(&b, &v, sizeof b); return b; }
+
+// the refusals that need no device, and the plan; SOSGPU_OK, SOSGPU_E_ARG or SOSGPU_E_UNSUPPORTED
+int surface_plan(int n, int os_nb, int os_ns, int os_nm, const sosgpu_surface_job *jobs, int njobs, SurfacePlan *pl)
+{
+    if (n < 1 || n > 85 || !jobs || njobs < 0 || njobs > 65535) return SOSGPU_E_ARG;
+    if (os_nb < 0 || os_ns < 2 || os_nm < os_nb + os_ns || os_nm > 2000) return SOSGPU_E_ARG;
+    if (mat_reflexion_lds_bytes(os_ns, os_nm) > kLdsMaxBytes) return SOSGPU_E_ARG;    // k_mat_reflexion could not be launched
+    bool nadal = false;
+    for (int j = 0; j < njobs; j++) {
+        const int s = jobs[j].isurf;
+        if (s != 1 && (s < 3 || s > 7)) return SOSGPU_E_ARG;
+        nadal = nadal || s == 6;
+    }
+    if (nadal) return SOSGPU_E_UNSUPPORTED;          // Nadal: refused by the reference's SOS_PROC as well
+    std::map<uint64_t, int> wind_of, c_of, ind_of;
+    std::map<std::pair<int, int>, int> refl_of;      // (analysis key, ind) -> block; analysis key: see below
+    std::map<std::vector<uint64_t>, int> trip_of;
+    auto distinct = [](std::map<uint64_t, int> &m, std::vector<double> &v, double x) {
+        auto it = m.find(dbl_bits(x));
+        if (it != m.end()) return it->second;
+        v.push_back(x);
+        return m[dbl_bits(x)] = (int)v.size() - 1;
+    };
+    int const_of[2] = {-1, -1};
+    // first pass: the analyses, so that their final indices (winds, then Maignan, then constant) are known
+    struct Need { int kind, idx, ind; };             // kind 0 Cox-Munk, 1 Maignan, 2 constant, -1 none
+    std::vector<Need> need(njobs);
+    for (int j = 0; j < njobs; j++) {
+        const sosgpu_surface_job &jb = jobs[j];
+        Need &q = need[j];
+        q.kind = -1; q.idx = q.ind = 0;
+        if (jb.isurf == 1) { q.kind = 0; q.idx = distinct(wind_of, pl->winds, jb.wind); }
+        else if (jb.isurf == 7) { q.kind = 1; q.idx = distinct(c_of, pl->cs, jb.coef_c); }
+        else if (jb.isurf == 4 || jb.isurf == 5) {
+            const int m = jb.isurf == 4 ? 0 : 1;
+            if (const_of[m] < 0) { const_of[m] = (int)pl->models.size(); pl->models.push_back(m); }
+            q.kind = 2; q.idx = const_of[m];
+        }
+        if (q.kind >= 0) q.ind = distinct(ind_of, pl->inds, jb.ind);
+    }
+    const int nwind = (int)pl->winds.size(), ncm = (int)pl->cs.size();
+    pl->job_refl.assign(njobs, -1);
+    pl->job_trip.assign(njobs, -1);
+    for (int j = 0; j < njobs; j++) {
+        const sosgpu_surface_job &jb = jobs[j];
+        const Need &q = need[j];
+        if (q.kind >= 0) {
+            const int an = q.kind == 0 ? q.idx : q.kind == 1 ? nwind + q.idx : nwind + ncm + q.idx;
+            auto it = refl_of.find({an, q.ind});
+            if (it == refl_of.end()) {
+                SurfReflSet r;
+                r.coef = q.kind == 0 ? 1. / sigma2_of_wind(pl->winds[q.idx]) : 1.0;
+                r.analysis = an; r.ind = q.ind;
+                pl->refl.push_back(r);
+                it = refl_of.emplace(std::make_pair(an, q.ind), (int)pl->refl.size() - 1).first;
+            }
+            pl->job_refl[j] = it->second;
+        }
+        if (jb.isurf >= 3) {
+            const std::vector<uint64_t> key = {dbl_bits(jb.k0), dbl_bits(jb.k1), dbl_bits(jb.k2)};
+            auto it = trip_of.find(key);
+            if (it == trip_of.end()) {
+                pl->trip.push_back({jb.k0, jb.k1, jb.k2});
+                it = trip_of.emplace(key, (int)pl->trip.size() - 1).first;
+            }
+            pl->job_trip[j] = it->second;
+        }
+    }
+    auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    const size_t npairs = (size_t)n * (n + 1) / 2, nn = (size_t)n * n, cnt = (size_t)(os_nb + 1) * 9 * nn;
+    const size_t nan = (size_t)pl->nan(), ntrip = pl->trip.size(), nrefl = pl->refl.size();
+    pl->o_fc = (size_t)n * 8;
+    pl->o_par0 = pl->o_fc + pl->inds.size() * 4 * (os_ns + 1) * 8;
+    pl->o_par1 = pl->o_par0 + (size_t)nwind * 8;
+    pl->o_refl = pl->o_par1 + (size_t)ncm * 8;
+    pl->o_trip = pl->o_refl + nrefl * sizeof(SurfReflSet);
+    pl->o_jobs = pl->o_trip + ntrip * sizeof(SurfTriple);
+    pl->o_models = pl->o_jobs + (size_t)njobs * sizeof(SurfJobDev);
+    pl->o_flags = pl->o_models + up8(pl->models.size() * 4);
+    pl->table_bytes = pl->o_flags + up8(ntrip * 4);
+    pl->o_il = pl->table_bytes;
+    pl->o_e = pl->o_il + up8(nan * npairs * 4);
+    pl->o_ilnn = pl->o_e + nan * npairs * (os_nm + 1) * 8;
+    pl->o_enn = pl->o_ilnn + up8(ntrip * nn * 4);
+    pl->o_rb = pl->o_enn + ntrip * nn * (os_nb + 1) * 8;
+    pl->total = pl->o_rb + up8(nrefl * cnt * 4);
+    return SOSGPU_OK;
+}
+}   // namespace
+static_assert(sizeof(SurfReflSet) % 8 == 0 && sizeof(SurfTriple) % 8 == 0 && sizeof(SurfJobDev) % 8 == 0, "8-byte sections");
+
+extern "C" size_t sosgpu_surface_batch_work_bytes(int n, int os_nb, int os_ns, int os_nm, const sosgpu_surface_job *jobs, int njobs)
+{
+    SurfacePlan pl;
+    if (surface_plan(n, os_nb, os_ns, os_nm, jobs, njobs, &pl) != SOSGPU_OK) return 0;
+    return pl.total;
+}
+
+extern "C" int sosgpu_surface_batch(int device, int n, const double *mu, const double *chr, int os_nb, int os_ns, int os_nm,
+                                    const sosgpu_surface_job *jobs, int njobs, int32_t *d_status, void *d_work,
+                                    size_t work_bytes, void *stream)
+{
+    if (!mu || !chr || !d_status || !d_work) return SOSGPU_E_ARG;
+    SurfacePlan pl;
+    if (const int rc = surface_plan(n, os_nb, os_ns, os_nm, jobs, njobs, &pl)) return rc;
+    for (int j = 0; j < njobs; j++)
+        if (!jobs[j].d_rsurf) return SOSGPU_E_ARG;
+    if (((unsigned long long)d_work & 7) || work_bytes < pl.total) return SOSGPU_E_ARG;
+    if (njobs == 0) return SOSGPU_OK;
+    if (const int rc = use_device(device)) return rc;
+    Staged s(device, pl.table_bytes);
+    if (s.rc) return s.rc;
+    char *hp = static_cast<char *>(s.host());
+    char *dp = static_cast<char *>(d_work);
+    const int nwind = (int)pl.winds.size(), ncm = (int)pl.cs.size(), nconst = (int)pl.models.size();
+    const int nrefl = (int)pl.refl.size(), ntrip = (int)pl.trip.size();
+    memset(hp + pl.o_models, 0, pl.table_bytes - pl.o_models);         // the flags, and the padding of both int sections
+    memcpy(hp, mu, (size_t)n * sizeof(double));
+    double *fc = reinterpret_cast<double *>(hp + pl.o_fc);
+    for (size_t i = 0; i < pl.inds.size(); i++)
+        if (const int rc = sosgpu_mat_fresnel_host(n, mu, chr, pl.inds[i], os_ns, fc + i * 4 * (os_ns + 1))) return rc;
+    double *par0 = reinterpret_cast<double *>(hp + pl.o_par0);
+    for (int i = 0; i < nwind; i++) par0[i] = sigma2_of_wind(pl.winds[i]);
+    if (ncm) memcpy(hp + pl.o_par1, pl.cs.data(), (size_t)ncm * sizeof(double));
+    if (nrefl) memcpy(hp + pl.o_refl, pl.refl.data(), (size_t)nrefl * sizeof(SurfReflSet));
+    if (ntrip) memcpy(hp + pl.o_trip, pl.trip.data(), (size_t)ntrip * sizeof(SurfTriple));
+    SurfJobDev *jt = reinterpret_cast<SurfJobDev *>(hp + pl.o_jobs);
+    for (int j = 0; j < njobs; j++) {
+        jt[j].out = jobs[j].d_rsurf; jt[j].isurf = jobs[j].isurf; jt[j].refl = pl.job_refl[j]; jt[j].trip = pl.job_trip[j];
+        jt[j].pad = 0;
+    }
+    if (nconst) memcpy(hp + pl.o_models, pl.models.data(), (size_t)nconst * sizeof(int32_t));
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(s.send(d_work, st));
+    const double *d_mu = reinterpret_cast<const double *>(dp);
+    const size_t npairs = (size_t)n * (n + 1) / 2;
+    int32_t *d_il = reinterpret_cast<int32_t *>(dp + pl.o_il);
+    double *d_e = reinterpret_cast<double *>(dp + pl.o_e);
+    int32_t *d_flags = reinterpret_cast<int32_t *>(dp + pl.o_flags);
+    double *d_enn = reinterpret_cast<double *>(dp + pl.o_enn);
+    float *d_rb = reinterpret_cast<float *>(dp + pl.o_rb);
+    if (nwind) launch_gsf_table(0, n, d_mu, reinterpret_cast<const double *>(dp + pl.o_par0), nwind, os_nm, d_il, d_e, st);
+    if (ncm)
+        launch_gsf_table(1, n, d_mu, reinterpret_cast<const double *>(dp + pl.o_par1), ncm, os_nm, d_il + (size_t)nwind * npairs,
+                         d_e + (size_t)nwind * npairs * (os_nm + 1), st);
+    if (nconst)
+        launch_gsf_const_table(n, nconst, reinterpret_cast<const int32_t *>(dp + pl.o_models), d_mu, os_nm,
+                               d_il + (size_t)(nwind + ncm) * npairs, d_e + (size_t)(nwind + ncm) * npairs * (os_nm + 1), st);
+    if (nrefl)
+        launch_mat_reflexion_table(n, d_mu, reinterpret_cast<const SurfReflSet *>(dp + pl.o_refl), nrefl, os_nb, os_ns, os_nm,
+                                   reinterpret_cast<const double *>(dp + pl.o_fc), d_il, d_e, d_rb, st);
+    if (ntrip)
+        launch_fsf_table(n, d_mu, os_nb, reinterpret_cast<const SurfTriple *>(dp + pl.o_trip), ntrip,
+                         reinterpret_cast<int32_t *>(dp + pl.o_ilnn), d_enn, d_flags, st);
+    launch_surface_compose(n, os_nb, reinterpret_cast<const SurfJobDev *>(dp + pl.o_jobs), njobs, d_rb, d_enn, d_flags, d_status,
+                           st);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // SOS_PROFILE on the device (profile.hip): the no-gas profile (SOS_PROFIL.F:349-489), the same for every bin of a wavelength, by
 // one wavefront, the per-bin gas step by one wavefront per bin.
 // ---------------------------------------------------------------------------------------------

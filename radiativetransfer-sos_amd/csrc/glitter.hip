@@ -17,6 +17,8 @@
 // Kernel k_mat_reflexion: one workgroup per pair; thread k builds the Fresnel kernels of Fourier index k
 // (sequential Legendre recurrence + sums in the reference's order), then thread s forms the 17 sums over
 // k of order s (reference order, un-fused) and stores the REAL*4 results directly in FICSURF record order.
+// k_gsf_table / k_mat_reflexion_table: the same bodies for the distinct parameter sets of many jobs (sosgpu_surface_batch), one
+// launch each, the set's entry taken from a device table by scalar loads.
 #include "sos_common.h"
 #include "kernels.h"
 
@@ -51,12 +53,12 @@ __device__ __forceinline__ double wave_sum(double v)
 
 // il[pair], e[pair][os_nm+1] (zero beyond IL); pairs ordered (I1 = 1..N, I2 = 1..I1).  The same quadrature serves
 // SOS_GSF (MODEL 0) and SOS_GSF_MAIGNAN (MODEL 1, SOS_SURFACE_BPDF.F:1305-1600): only the function differs.
+// (the body of one pair, shared by k_gsf and the table form k_gsf_table: the same bits; u: PH_NU + 1 doubles of LDS)
 template <int MODEL>
-__global__ __launch_bounds__(64) void k_gsf(const double *__restrict__ mu, double sig, int os_nm,
-                                           int32_t *__restrict__ il_out, double *__restrict__ e_out)
+__device__ __forceinline__ void gsf_body(const double *__restrict__ mu, const double sig, const int os_nm, const int pair,
+                                         double *u, int32_t *__restrict__ il_out, double *__restrict__ e_out)
 {
-    __shared__ double u[PH_NU + 1];
-    const int pair = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     int i1 = 0;
     while ((i1 + 1) * (i1 + 2) / 2 <= pair) i1++;
     const int i2 = pair - i1 * (i1 + 1) / 2;     // 0-based, i2 <= i1
@@ -115,6 +117,28 @@ __global__ __launch_bounds__(64) void k_gsf(const double *__restrict__ mu, doubl
         if (!(fabs(t1 - gmax) / gmax > (double).001f)) { il = is; break; }
     }
     if (lane == 0) il_out[pair] = il;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_gsf(const double *__restrict__ mu, double sig, int os_nm,
+                                           int32_t *__restrict__ il_out, double *__restrict__ e_out)
+{
+    __shared__ double u[PH_NU + 1];
+    gsf_body<MODEL>(mu, sig, os_nm, blockIdx.x, u, il_out, e_out);
+}
+
+// Table form (sosgpu_surface_batch): one wavefront per (set, pair), flat in blockIdx.x; set = blockIdx.x / npairs takes its
+// parameter par[set] by a scalar load and writes il[set][npairs], e[set][npairs][os_nm+1].
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_gsf_table(const double *__restrict__ mu, const double *par, int npairs, int os_nm,
+                                                 int32_t *__restrict__ il_out, double *__restrict__ e_out)
+{
+    __shared__ double u[PH_NU + 1];
+    typedef const __attribute__((address_space(4))) double ParK;
+    const int set = __builtin_amdgcn_readfirstlane(blockIdx.x / npairs);
+    const int pair = blockIdx.x - set * npairs;
+    const double sig = ((ParK *)(unsigned long long)par)[set];
+    gsf_body<MODEL>(mu, sig, os_nm, pair, u, il_out + (size_t)set * npairs, e_out + (size_t)set * npairs * (os_nm + 1));
 }
 
 // Fresnel kernels of SOS_NOYAUX_FRESNEL for Fourier index `is` at the angle pair (r1, r2); results
@@ -207,14 +231,15 @@ __device__ void noyaux_fresnel_one(int is, double r1, double r2, int os_ns, cons
 }
 
 // rsurf[((s*9 + ab)*N + (J-1))*N + (I-1)] = P_ab(I,J)
-__global__ void k_mat_reflexion(int n, const double *__restrict__ mu, double coef, int os_nb, int os_ns, int os_nm,
-                                const double *__restrict__ fcoef /* [4][os_ns+1] */, const int32_t *__restrict__ il_in,
-                                const double *__restrict__ e_in, float *__restrict__ rsurf)
+// (the body of one pair, shared by k_mat_reflexion and the table form k_mat_reflexion_table: the same bits; sm: the dynamic LDS)
+__device__ __forceinline__ void mat_reflexion_body(const int n, const double *__restrict__ mu, const double coef, const int os_nb,
+                                                   const int os_ns, const int os_nm, const double *__restrict__ fcoef,
+                                                   const int32_t *__restrict__ il_in, const double *__restrict__ e_in,
+                                                   float *__restrict__ rsurf, const int pair, double *sm)
 {
-    extern __shared__ double sm[];
     double *g = sm;                                // [os_nm+1]
     double *kern = g + (os_nm + 1);                // [os_ns+1][12]
-    const int pair = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     int i1 = 0;
     while ((i1 + 1) * (i1 + 2) / 2 <= pair) i1++;
     const int i2 = pair - i1 * (i1 + 1) / 2;
@@ -259,11 +284,54 @@ __global__ void k_mat_reflexion(int n, const double *__restrict__ mu, double coe
 #undef KX
 }
 
+__global__ void k_mat_reflexion(int n, const double *__restrict__ mu, double coef, int os_nb, int os_ns, int os_nm,
+                                const double *__restrict__ fcoef /* [4][os_ns+1] */, const int32_t *__restrict__ il_in,
+                                const double *__restrict__ e_in, float *__restrict__ rsurf)
+{
+    extern __shared__ double sm[];
+    mat_reflexion_body(n, mu, coef, os_nb, os_ns, os_nm, fcoef, il_in, e_in, rsurf, blockIdx.x, sm);
+}
+
+// Table form (sosgpu_surface_batch): one workgroup per (set, pair), flat in blockIdx.x; set = blockIdx.x / npairs takes coef,
+// its analysis (il, e) and its Fresnel coefficients from the entry sets[set] by scalar loads and writes block `set` of rsurf.
+__global__ void k_mat_reflexion_table(int n, const double *__restrict__ mu, const SurfReflSet *sets, int os_nb, int os_ns,
+                                      int os_nm, const double *__restrict__ fcoef /* [nind][4][os_ns+1] */,
+                                      const int32_t *__restrict__ il_in, const double *__restrict__ e_in,
+                                      float *__restrict__ rsurf)
+{
+    extern __shared__ double sm[];
+    typedef const __attribute__((address_space(4))) SurfReflSet SetK;
+    const int npairs = n * (n + 1) / 2;
+    const int set = __builtin_amdgcn_readfirstlane(blockIdx.x / npairs);
+    const int pair = blockIdx.x - set * npairs;
+    SetK &e = ((SetK *)(unsigned long long)sets)[set];
+    const double coef = e.coef;
+    const int an = e.analysis, fi = e.ind;
+    mat_reflexion_body(n, mu, coef, os_nb, os_ns, os_nm, fcoef + (size_t)fi * 4 * (os_ns + 1), il_in + (size_t)an * npairs,
+                       e_in + (size_t)an * npairs * (os_nm + 1), rsurf + (size_t)set * (os_nb + 1) * 9 * n * n, pair, sm);
+}
+
 void launch_gsf(int model, int n, const double *d_mu, double par, int os_nm, int32_t *d_il, double *d_e, hipStream_t st)
 {
     const int npairs = n * (n + 1) / 2;
     if (model == 0) k_gsf<0><<<npairs, 64, 0, st>>>(d_mu, par, os_nm, d_il, d_e);
     else k_gsf<1><<<npairs, 64, 0, st>>>(d_mu, par, os_nm, d_il, d_e);
+}
+
+void launch_gsf_table(int model, int n, const double *d_mu, const double *d_par, int nsets, int os_nm, int32_t *d_il, double *d_e,
+                      hipStream_t st)
+{
+    const int npairs = n * (n + 1) / 2;
+    if (model == 0) k_gsf_table<0><<<nsets * npairs, 64, 0, st>>>(d_mu, d_par, npairs, os_nm, d_il, d_e);
+    else k_gsf_table<1><<<nsets * npairs, 64, 0, st>>>(d_mu, d_par, npairs, os_nm, d_il, d_e);
+}
+
+void launch_mat_reflexion_table(int n, const double *d_mu, const SurfReflSet *d_sets, int nsets, int os_nb, int os_ns, int os_nm,
+                                const double *d_fcoef, const int32_t *d_il, const double *d_e, float *d_refl, hipStream_t st)
+{
+    const size_t sh = mat_reflexion_lds_bytes(os_ns, os_nm);
+    k_mat_reflexion_table<<<nsets * (n * (n + 1) / 2), 128, sh, st>>>(n, d_mu, d_sets, os_nb, os_ns, os_nm, d_fcoef, d_il, d_e,
+                                                                      d_refl);
 }
 
 void launch_mat_reflexion(int n, const double *d_mu, double coef, int os_nb, int os_ns, int os_nm, const double *d_fcoef,

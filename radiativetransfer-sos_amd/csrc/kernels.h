@@ -72,6 +72,31 @@ constexpr size_t kLdsMaxBytes = 160 * 1024;
 // land surfaces (-SURF.Type 3, 4, 5, 7): Roujean BRDF, + Rondeaux-Herman / Breon / Maignan BPDF
 void launch_land(int isurf, int n, const double *d_mu, double k0, double k1, double k2, double coef_c, int os_nb, int os_ns, int os_nm, const double *d_fcoef, double *d_e_nn, int32_t *d_il_nn,
                  double *d_e, int32_t *d_il, float *d_tmp, float *d_rsurf, int32_t *d_err, hipStream_t st);
+// Table forms of the surface-matrix kernels (sosgpu_surface_batch): the distinct parameter sets of many jobs, one launch per
+// kernel.  The tables sit in the caller's work area; every kernel takes its entry by scalar loads.
+struct SurfReflSet {          // one SOS_MAT_REFLEXION result: COEF, the azimuth analysis it reads, its Fresnel coefficients
+    double coef;
+    int32_t analysis, ind;
+};
+struct SurfTriple { double k0, k1, k2; };
+struct SurfJobDev {
+    float *out;               // the job's block [os_nb+1][9][N][N]
+    int32_t isurf, refl, trip, pad;   // refl / trip: index of its reflexion block / Roujean triple, -1: none
+};
+// analyses of nsets parameters d_par[nsets] (model as launch_gsf): il[nsets][npairs], e[nsets][npairs][os_nm+1]
+void launch_gsf_table(int model, int n, const double *d_mu, const double *d_par, int nsets, int os_nm, int32_t *d_il, double *d_e,
+                      hipStream_t st);
+// constant analyses (d_models[s] = 0 Rondeaux-Herman, 1 Breon): the same layout
+void launch_gsf_const_table(int n, int nsets, const int32_t *d_models, const double *d_mu, int os_nm, int32_t *d_il, double *d_e,
+                            hipStream_t st);
+// d_refl[nsets][os_nb+1][9][N][N]; d_il / d_e: analysis 0 of the call, d_fcoef[nind][4][os_ns+1]
+void launch_mat_reflexion_table(int n, const double *d_mu, const SurfReflSet *d_sets, int nsets, int os_nb, int os_ns, int os_nm,
+                                const double *d_fcoef, const int32_t *d_il, const double *d_e, float *d_refl, hipStream_t st);
+// Roujean analyses of ntrip triples: il_nn[ntrip][N^2], e_nn[ntrip][N^2][os_nb+1], flags[ntrip] (cleared by the caller)
+void launch_fsf_table(int n, const double *d_mu, int os_nb, const SurfTriple *d_trip, int ntrip, int32_t *d_il_nn, double *d_e_nn,
+                      int32_t *d_flags, hipStream_t st);
+void launch_surface_compose(int n, int os_nb, const SurfJobDev *d_jobs, int njobs, const float *d_refl, const double *d_e_nn,
+                            const int32_t *d_flags, int32_t *d_status, hipStream_t st);
 struct LandTerms {            // direct surface terms of the land models in SOS_TRPHI (SOS_PREPA_OS.F:479-497 flags)
     int iroujean, irondeaux, ibreon, imaignan;
     double k0, k1, k2, coef_c;

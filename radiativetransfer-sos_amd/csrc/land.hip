@@ -14,6 +14,8 @@
 // and the maximum relative error B1 of the recombined series (:601-623) are wave reductions, and the reference's stop rule
 // (B1 <= 1e-3, or B1 growing) is wave-uniform.  FP64 transcendental bound (one cos per sample and order), no HBM traffic
 // besides the result.
+// k_fsf_table / k_gsf_const_table: the same bodies for the distinct triples and constant models of many jobs
+// (sosgpu_surface_batch); k_surface_compose writes every job's block and status in one launch.
 #include "sos_common.h"
 #include "kernels.h"
 
@@ -37,10 +39,12 @@ __device__ __forceinline__ double wmax(double v)
 
 // Roujean BRDF (p = K0, K1, K2); keeps E(IS) of every order it computed (the reference stores all of them, :640-643).
 // e_out[pair][os_nb+1], pair = (I1-1)*N + (I2-1); err[0] |= 1 when the function goes negative (IER = -1, :548).
-__global__ __launch_bounds__(64) void k_fsf(int n, const double *__restrict__ mu, int os_nb, double p0, double p1, double p2,
-                                           int32_t *__restrict__ il_out, double *__restrict__ e_out, int32_t *__restrict__ err)
+// (the body of one pair, shared by k_fsf and the table form k_fsf_table: the same bits)
+__device__ __forceinline__ void fsf_body(const int n, const double *__restrict__ mu, const int os_nb, const double p0,
+                                         const double p1, const double p2, const int pair, int32_t *__restrict__ il_out,
+                                         double *__restrict__ e_out, int32_t *__restrict__ err)
 {
-    const int pair = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     const int i1 = pair / n, i2 = pair % n;
     const double pi = acos(-1.0);
     const double c1 = mu[i1], s1 = sqrt(1 - c1 * c1), c2 = mu[i2], s2 = sqrt(1 - c2 * c2);
@@ -87,13 +91,34 @@ __global__ __launch_bounds__(64) void k_fsf(int n, const double *__restrict__ mu
     if (lane == 0) il_out[pair] = il;
 }
 
+__global__ __launch_bounds__(64) void k_fsf(int n, const double *__restrict__ mu, int os_nb, double p0, double p1, double p2,
+                                           int32_t *__restrict__ il_out, double *__restrict__ e_out, int32_t *__restrict__ err)
+{
+    fsf_body(n, mu, os_nb, p0, p1, p2, blockIdx.x, il_out, e_out, err);
+}
+
+// Table form (sosgpu_surface_batch): one wavefront per (triple, pair), flat in blockIdx.x; triple = blockIdx.x / N^2 takes
+// (K0, K1, K2) from trip[triple] by scalar loads, writes il[triple][N^2], e[triple][N^2][os_nb+1] and ORs its negative flag
+// into err[triple].
+__global__ __launch_bounds__(64) void k_fsf_table(int n, const double *__restrict__ mu, int os_nb, const SurfTriple *trip,
+                                                 int32_t *__restrict__ il_out, double *__restrict__ e_out,
+                                                 int32_t *__restrict__ err)
+{
+    typedef const __attribute__((address_space(4))) SurfTriple TripK;
+    const int nn = n * n;
+    const int set = __builtin_amdgcn_readfirstlane(blockIdx.x / nn);
+    const int pair = blockIdx.x - set * nn;
+    TripK &e = ((TripK *)(unsigned long long)trip)[set];
+    const double p0 = e.k0, p1 = e.k1, p2 = e.k2;
+    fsf_body(n, mu, os_nb, p0, p1, p2, pair, il_out + (size_t)set * nn, e_out + (size_t)set * nn * (os_nb + 1), err + set);
+}
+
 // Rondeaux-Herman (MODEL 0: E(0) = 1/(1/C1 + 1/C2)) and Breon (MODEL 1: E(0) = 1): azimuth-independent, IL = 0
 // (SOS_SURFACE_BPDF.F:560-575).  Pairs (I1 >= I2) as SOS_MAT_REFLEXION reads them.
-__global__ void k_gsf_const(int n, int model, const double *__restrict__ mu, int os_nm, int32_t *__restrict__ il_out,
-                            double *__restrict__ e_out)
+// (the body of one pair, shared by k_gsf_const and the table form k_gsf_const_table: the same bits)
+__device__ __forceinline__ void gsf_const_body(const int model, const double *__restrict__ mu, const int os_nm, const int pair,
+                                               int32_t *__restrict__ il_out, double *__restrict__ e_out)
 {
-    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pair >= n * (n + 1) / 2) return;
     int i1 = 0;
     while ((i1 + 1) * (i1 + 2) / 2 <= pair) i1++;
     const int i2 = pair - i1 * (i1 + 1) / 2;
@@ -101,6 +126,26 @@ __global__ void k_gsf_const(int n, int model, const double *__restrict__ mu, int
     for (int s = 0; s <= os_nm; s++) e[s] = 0.;
     e[0] = model == 0 ? 1. / (1. / mu[i1] + 1. / mu[i2]) : 1.;
     il_out[pair] = 0;
+}
+
+// Table form (sosgpu_surface_batch): one thread per (set, pair); set s has the model models[s] and writes il[first + s][npairs],
+// e[first + s][npairs][os_nm+1] (the caller hands over the pointers of analysis `first`).
+__global__ void k_gsf_const_table(int n, int nsets, const int32_t *__restrict__ models, const double *__restrict__ mu, int os_nm,
+                                  int32_t *__restrict__ il_out, double *__restrict__ e_out)
+{
+    const int npairs = n * (n + 1) / 2;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nsets * npairs) return;
+    const int set = idx / npairs, pair = idx - set * npairs;
+    gsf_const_body(models[set], mu, os_nm, pair, il_out + (size_t)set * npairs, e_out + (size_t)set * npairs * (os_nm + 1));
+}
+
+__global__ void k_gsf_const(int n, int model, const double *__restrict__ mu, int os_nm, int32_t *__restrict__ il_out,
+                            double *__restrict__ e_out)
+{
+    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pair >= n * (n + 1) / 2) return;
+    gsf_const_body(model, mu, os_nm, pair, il_out, e_out);
 }
 
 // SOS_MISE_FORMAT_RJ (SOS_ROUJEAN.F:1102-1224): P11(I,J) = REAL(E_(I,J)(IS)), every other element zero
@@ -118,6 +163,52 @@ __global__ void k_add_f32(size_t cnt, const float *__restrict__ a, float *__rest
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < cnt) io[idx] = io[idx] + a[idx];
+}
+
+// The blocks of every job of sosgpu_surface_batch: blockIdx.y = job (its entry by scalar loads), one thread per element of the
+// job's block [os_nb+1][9][N][N].  isurf 1: the job's reflexion block; 3: k_roujean_format of its triple; 4, 5, 7: the
+// REAL*4 sum of the two with k_add_f32's operands (for ab != 0 too: -0.f + 0.f is +0.f).  The first thread of a job writes its
+// status from the triple's negative flag.
+__global__ void k_surface_compose(int n, int os_nb, const SurfJobDev *jobs, const float *__restrict__ refl,
+                                  const double *__restrict__ e_nn, const int32_t *__restrict__ flags,
+                                  int32_t *__restrict__ status)
+{
+    typedef const __attribute__((address_space(4))) SurfJobDev JobK;
+    JobK &jb = ((JobK *)(unsigned long long)jobs)[blockIdx.y];
+    const int isurf = jb.isurf, ir = jb.refl, it = jb.trip;
+    float *out = jb.out;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t nn = (size_t)n * n, tot = (size_t)(os_nb + 1) * 9 * nn;
+    if (idx == 0) status[blockIdx.y] = (it >= 0 && flags[it] != 0) ? -1 : 0;
+    if (idx >= tot) return;
+    float r = 0.f, b = 0.f;
+    if (ir >= 0) r = refl[(size_t)ir * tot + idx];
+    if (it >= 0) {
+        const int i = (int)(idx % n), j = (int)((idx / n) % n), ab = (int)((idx / nn) % 9), s = (int)(idx / ((size_t)9 * nn));
+        b = (ab == 0) ? (float)e_nn[(size_t)it * nn * (os_nb + 1) + ((size_t)i * n + j) * (os_nb + 1) + s] : 0.f;
+    }
+    out[idx] = isurf == 1 ? r : isurf == 3 ? b : r + b;
+}
+
+void launch_fsf_table(int n, const double *d_mu, int os_nb, const SurfTriple *d_trip, int ntrip, int32_t *d_il_nn, double *d_e_nn,
+                      int32_t *d_flags, hipStream_t st)
+{
+    k_fsf_table<<<ntrip * n * n, 64, 0, st>>>(n, d_mu, os_nb, d_trip, d_il_nn, d_e_nn, d_flags);
+}
+
+void launch_gsf_const_table(int n, int nsets, const int32_t *d_models, const double *d_mu, int os_nm, int32_t *d_il, double *d_e,
+                            hipStream_t st)
+{
+    const int cnt = nsets * (n * (n + 1) / 2);
+    k_gsf_const_table<<<(cnt + 63) / 64, 64, 0, st>>>(n, nsets, d_models, d_mu, os_nm, d_il, d_e);
+}
+
+void launch_surface_compose(int n, int os_nb, const SurfJobDev *d_jobs, int njobs, const float *d_refl, const double *d_e_nn,
+                            const int32_t *d_flags, int32_t *d_status, hipStream_t st)
+{
+    const size_t cnt = (size_t)(os_nb + 1) * 9 * n * n;
+    k_surface_compose<<<dim3((unsigned)((cnt + 255) / 256), (unsigned)njobs), 256, 0, st>>>(n, os_nb, d_jobs, d_refl, d_e_nn, d_flags,
+                                                                                          d_status);
 }
 
 // isurf 3: Roujean; 4: + Rondeaux-Herman; 5: + Breon; 7: + Maignan

@@ -730,8 +730,133 @@ _SURF_LOCK = threading.Lock()
 _SURF_CACHE_MAX = 8
 
 
+# The surface matrices of a spectrum chunk, queued ahead of its per-wavelength preparation (_prefetch_surfaces): the table of the
+# calling thread, key of _prepare -> (block, slot of its status word).  _surface_cached consults it before the cache above.
+_SURF_PREFETCH = threading.local()
+
+
+def _surface_request(p, device):
+    """(group, key, job) of the surface matrices _prepare will ask for with the validated keyword set p: group = (mu bytes, weight
+    bytes, os_nb, os_ns, os_nm), key = the key _prepare forms for _surface_cached, job = the surface.surface_job of the batch.  None
+    for -SURF.Type 0 / 2, a -SURF.File call, or parameters the real pass refuses (it reports)."""
+    from . import surface as _surface
+    try:
+        isurf = int(p["isurf"])
+        if isurf not in (1, 3, 4, 5, 7) or str(p["ficsurf"]).strip() != "DEFAULT":
+            return None
+        if p["tetas"] == _D or not (0.0 <= p["tetas"] < 90.0):
+            return None
+        nb_lum = CTE_DEFAULT_NBMU_LUM if p["nbmu_gauss_lum"] == _I else int(p["nbmu_gauss_lum"])
+        os_nb = CTE_DEFAULT_OS_NB if p["nbmu_gauss_mie"] == _I else 2 * int(p["nbmu_gauss_mie"])
+        if p["nbmu_gauss_lum"] == _I:
+            os_ns, os_nm = CTE_DEFAULT_OS_NS, CTE_DEFAULT_OS_NM
+        else:
+            os_ns = 2 * nb_lum
+            os_nm = os_nb + os_ns
+        mu, ga, _, _ = angles(nb_lum, p["tetas"], p["ficangles_user_lum"])
+        if isurf == 1:
+            if _D in (p["wind"], p["surf_ind"]):
+                return None
+            key = ("glitter", mu.tobytes(), ga.tobytes(), float(p["wind"]), float(p["surf_ind"]), os_nb, os_ns, os_nm, device)
+            job = _surface.surface_job(1, wind=p["wind"], ind=p["surf_ind"])
+        else:
+            if _D in (p["k0_roujean"], p["k1_roujean"], p["k2_roujean"]) or (isurf >= 4 and p["surf_ind"] == _D) or \
+                    (isurf == 7 and p["coef_c_maignan"] == _D):
+                return None
+            land = _surface.land_model(isurf, p["k0_roujean"], p["k1_roujean"], p["k2_roujean"], p["alpha_nadal"], p["beta_nadal"],
+                                       p["coef_c_maignan"])
+            ind_l = p["surf_ind"] if isurf >= 4 else 1.0
+            key = ("land", isurf, float(land.k0), float(land.k1), float(land.k2), float(land.alpha), float(land.beta),
+                   float(land.coef_c), mu.tobytes(), ga.tobytes(), float(ind_l), os_nb, os_ns, os_nm, device)
+            job = _surface.surface_job(isurf, ind=ind_l, k0=land.k0, k1=land.k1, k2=land.k2, coef_c=land.coef_c)
+        return (mu.tobytes(), ga.tobytes(), os_nb, os_ns, os_nm), key, job
+    except Exception:
+        return None
+
+
+def _surface_requests(validated_calls, device=0):
+    """The surface batches of a list of validated keyword sets (_validated): one entry per (angle set, os_nb, os_ns, os_nm), in
+    order of first appearance -- dict(mu, ga, os_nb, os_ns, os_nm, keys, jobs) with the distinct keys of the group's calls, exactly
+    as _prepare forms them, and the surface.surface_job of each.  -SURF.Type 0 / 2 and -SURF.File calls are left out."""
+    groups = collections.OrderedDict()
+    for p in validated_calls:
+        r = _surface_request(p, device) if p is not None else None
+        if r is None:
+            continue
+        g, key, job = r
+        e = groups.get(g)
+        if e is None:
+            e = groups[g] = dict(mu=np.frombuffer(g[0], dtype=np.float64).copy(), ga=np.frombuffer(g[1], dtype=np.float64).copy(),
+                                 os_nb=g[2], os_ns=g[3], os_nm=g[4], keys=[], jobs=[])
+        if key not in e["keys"]:
+            e["keys"].append(key)
+            e["jobs"].append(job)
+    return list(groups.values())
+
+
+def _prefetch_surfaces(validated_calls, device):
+    """Queues the surface matrices of a chunk's calls on the current stream: one surface.surface_matrices_many call per group of
+    _surface_requests (keys the cache already holds are left out), then one pinned copy of all status words and an event.  The
+    first _surface_cached that finds its key in the table waits for that event -- the one host wait of the chunk -- after
+    which every block is complete for any stream."""
+    import torch
+    from . import surface as _surface
+    groups = _surface_requests(validated_calls, device)
+    with _SURF_LOCK:
+        for e in groups:
+            keep = [k not in _SURF_CACHE for k in e["keys"]]
+            e["keys"] = [k for k, ok in zip(e["keys"], keep) if ok]
+            e["jobs"] = [j for j, ok in zip(e["jobs"], keep) if ok]
+    total = sum(len(e["keys"]) for e in groups)
+    if not total:
+        return
+    dev = torch.device("cuda", device)
+    status = torch.zeros(total, dtype=torch.int32, device=dev)
+    blocks, pos = {}, 0
+    for e in groups:
+        nj = len(e["keys"])
+        if not nj:
+            continue
+        try:
+            made, _ = _surface.surface_matrices_many(e["jobs"], e["mu"], e["ga"], e["os_nb"], e["os_ns"], e["os_nm"], device=device,
+                                                     status=status[pos:pos + nj])
+        except Exception:                          # a refused group keeps the per-call path, whose error is the documented one
+            made = None
+        if made is not None:
+            for j, (k, t) in enumerate(zip(e["keys"], made)):
+                blocks[k] = (t, pos + j)
+        pos += nj
+    if not blocks:
+        return
+    host = torch.empty(total, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    # keep: a chunk of few surfaces (a spectrum over one surface) hands its blocks on to the cache, so that later chunks hit it
+    _SURF_PREFETCH.table = dict(blocks=blocks, status=status, host=host, event=ev, codes=None, keep=total <= _SURF_CACHE_MAX)
+
+
+def _drop_prefetched_surfaces():
+    _SURF_PREFETCH.table = None
+
+
 def _surface_cached(key, make, device):
     import torch
+    pre = getattr(_SURF_PREFETCH, "table", None)
+    if pre is not None and key in pre["blocks"]:
+        r, slot = pre["blocks"][key]
+        if pre["codes"] is None:
+            pre["event"].synchronize()
+            pre["codes"] = pre["host"].numpy()
+        if pre["codes"][slot] != 0:
+            from . import surface as _surface
+            raise ValueError(_surface.NEGATIVE_ROUJEAN_MESSAGE)
+        if pre["keep"]:
+            with _SURF_LOCK:
+                _SURF_CACHE[key] = r
+                while len(_SURF_CACHE) > _SURF_CACHE_MAX:
+                    _SURF_CACHE.popitem(last=False)
+        return r
     with _SURF_LOCK:
         hit = _SURF_CACHE.get(key)
         if hit is not None:
@@ -1580,18 +1705,22 @@ def spectrum_costs(kwargs_list):
     return costs
 
 
-def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_gas_tables=False):
+def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_gas_tables=False, batch_surfaces=False):
     """The shared host work of a spectrum chunk `idx`, queued ahead of its per-wavelength preparation: the size-distribution
     integrals (aerosols.prefetch_size_integrals), the gas tables interpolated to the layers in one pass, and SOS_AEROSOLS at the
     simulation wavelength of each call.  Returns {index: aerosols at the simulation wavelength} for _prepare(aer_at_wa=...).
     device_gas_tables: the calls whose profiles _prepare can defer (as far as the keywords alone tell: -AP.AerProfile.Type 1,
     no -SOS.Trans, -SOS.AbsModeCKD 1) get their layer tables from the device, so the one-pass host interpolation leaves them
-    out; a call _prepare then does not defer after all interpolates its own tables there."""
+    out; a call _prepare then does not defer after all interpolates its own tables there.
+    batch_surfaces: the sea and land surface matrices of the chunk's calls are queued first, one sosgpu_surface_batch per angle
+    set (_prefetch_surfaces); they run on the device while the host does the rest of this function."""
     import torch
     from . import aerosols as _aer
     from . import absorption as _abs
-    # the size-distribution integrals of the chunk's wavelengths, queued ahead (aerosols.prefetch_size_integrals)
     valid = {i: v for i, v in ((i, _validated(kwargs_list[i])) for i in idx) if v is not None}
+    if batch_surfaces:
+        _prefetch_surfaces(list(valid.values()), device)
+    # the size-distribution integrals of the chunk's wavelengths, queued ahead (aerosols.prefetch_size_integrals)
     acalls = {i: c for i, c in ((i, _aerosol_call(v, aer_phases[i])) for i, v in valid.items()) if c is not None}
     reqs = []
     for c in acalls.values():
@@ -1732,6 +1861,9 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     # at most five launches for the part; SOS_SPECTRUM_OPERATORS_PER_CALL=1: four or five launches per wavelength on its side
     # stream, as sos_proc makes them (A/B timing)
     batch_operators = not os.environ.get("SOS_SPECTRUM_OPERATORS_PER_CALL")
+    # the sea and land surface matrices of a chunk's calls come from one asynchronous sosgpu_surface_batch per angle set, queued by
+    # the prefetch; SOS_SPECTRUM_SURFACE_PER_CALL=1: every call that misses the cache makes its own synchronous call (A/B timing)
+    batch_surfaces = not os.environ.get("SOS_SPECTRUM_SURFACE_PER_CALL")
     where, err = -1, None                               # the wavelength being worked on (named by a failure)
     # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
     # a growing list of result tuples, and the collections this triggers re-walk the results again and again (SOS_SPECTRUM_KEEP_GC=1
@@ -1752,7 +1884,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 # device, and the launches below wait for all of them
                 for st in side + [aer_st]:
                     st.wait_stream(main_st)
-                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_tables)
+                aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_tables, batch_surfaces)
                 ckd_checks = []                   # (status tensor of a part's device gas tables, the plans it speaks of)
                 # The chunk goes to the solver in a few parts: the solves of a part run on the device while the host prepares the
                 # next one, so that only the last part's solve is waited for below.
@@ -1965,6 +2097,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 for st in side + [aer_st]:
                     st.synchronize()
                 main_st.synchronize()                             # the table launches read every context's operators
+                _drop_prefetched_surfaces()
                 for pl in plans:
                     pl.ctx.close()
     except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
@@ -2176,6 +2309,11 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
          CKD files (sosgpu_ckd_layer_tables); its per-wavelength status comes back with the band scalars of step 3, and a
          wavelength it flags raises the SosProcError sos_proc raises for that call (SOS_SPECTRUM_HOST_GAS_TABLES=1 in the
          environment: the tables are interpolated on the host and uploaded, for A/B timing).
+         The sea and land surface matrices (-SURF.Type 1, 3, 4, 5, 7 without -SURF.File) of the chunk's calls that the surface
+         cache does not hold are queued ahead of all this, one sosgpu_surface_batch per angle set
+         (surface.surface_matrices_many), with one host wait per chunk for their status words; a call whose Roujean function
+         goes negative raises sos_proc's error for it (SOS_SPECTRUM_SURFACE_PER_CALL=1 in the environment: one synchronous
+         sosgpu_glitter / sosgpu_land_surface call per wavelength that misses the cache, for A/B timing).
          Calls with -SOS.Trans, -SOS.AbsModeCKD 2 or an aerosol layer
          (-AP.AerProfile.Type 2), and a call whose profile the library refuses (its error is then sos_proc's), make their own
          profile launches (sosgpu_absprofile + sosgpu_profile) as sos_proc does;

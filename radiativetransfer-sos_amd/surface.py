@@ -71,5 +71,54 @@ def land_matrices(land, mu, chr_, ind, os_nb, os_ns, os_nm, device=0):
                                               chr_.ctypes.data_as(C.c_void_p), float(ind), int(os_nb), int(os_ns), int(os_nm),
                                               C.c_void_p(rsurf.data_ptr()), C.byref(ier), st), "sosgpu_land_surface")
     if ier.value != 0:
-        raise ValueError("SOS_FSF_ROUJEAN: BRDF < 0 for some geometry -- unsuitable Roujean coefficients (IER = -1)")
+        raise ValueError(NEGATIVE_ROUJEAN_MESSAGE)
     return rsurf
+
+
+NEGATIVE_ROUJEAN_MESSAGE = "SOS_FSF_ROUJEAN: BRDF < 0 for some geometry -- unsuitable Roujean coefficients (IER = -1)"
+
+
+def surface_job(isurf, wind=0.0, ind=0.0, k0=0.0, k1=0.0, k2=0.0, coef_c=0.0):
+    """One job of surface_matrices_many: -SURF.Type 1 (wind, ind) or 3, 4, 5, 7 (k0, k1, k2; ind and coef_c where the model has them)."""
+    return dict(isurf=int(isurf), wind=float(wind), ind=float(ind), k0=float(k0), k1=float(k1), k2=float(k2), coef_c=float(coef_c))
+
+
+def surface_job_array(jobs, ptrs=None):
+    """The capi.SurfaceJob array of a list of surface_job dicts (ptrs: the device address of every block, None: NULL)."""
+    arr = (capi.SurfaceJob * max(1, len(jobs)))()
+    for j, jb in enumerate(jobs):
+        arr[j] = capi.SurfaceJob(isurf=jb["isurf"], reserved=0, wind=jb["wind"], ind=jb["ind"], k0=jb["k0"], k1=jb["k1"],
+                                 k2=jb["k2"], coef_c=jb["coef_c"], d_rsurf=None if ptrs is None else ptrs[j])
+    return arr
+
+
+def surface_matrices_many(jobs, mu, chr_, os_nb, os_ns, os_nm, device=0, status=None):
+    """The matrices glitter_matrices(...)["rsurf"] / land_matrices(...) give for every job of `jobs` (surface_job dicts), bit
+    for bit, from ONE sosgpu_surface_batch call on the current stream: one allocation for all blocks, one work allocation,
+    nothing waited for.  What the jobs share -- the azimuth analysis of a wind or a Maignan C, the BPDF part of an index, the
+    Roujean analysis of a triple -- is computed once.
+    status: an int32 cuda tensor [len(jobs)] to write into (a slice of the caller's), None: a new one.
+    Returns (blocks, status): the float32 cuda views [os_nb+1][9][N][N] of the jobs, and the status tensor -- 0, or -1 where
+    land_matrices would raise (negative Roujean function; that job's block is unspecified)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("surface_matrices_many needs a GPU (gfx950); there is no CPU fallback in the product path")
+    mu = np.ascontiguousarray(mu, dtype=np.float64)
+    chr_ = np.ascontiguousarray(chr_, dtype=np.float64)
+    n, nj = len(mu), len(jobs)
+    dev = torch.device("cuda", device)
+    if status is None:
+        status = torch.empty(nj, dtype=torch.int32, device=dev)
+    if nj == 0:
+        return [], status
+    out = torch.empty((nj, int(os_nb) + 1, 9, n, n), dtype=torch.float32, device=dev)
+    step = out[0].numel() * 4
+    arr = surface_job_array(jobs, [out.data_ptr() + j * step for j in range(nj)])
+    L = capi.lib()
+    need = L.sosgpu_surface_batch_work_bytes(n, int(os_nb), int(os_ns), int(os_nm), arr, nj)
+    work = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)    # (need = 0: the call below refuses, with its code)
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    capi.check(L.sosgpu_surface_batch(device, n, mu.ctypes.data_as(C.c_void_p), chr_.ctypes.data_as(C.c_void_p), int(os_nb),
+                                      int(os_ns), int(os_nm), arr, nj, C.c_void_p(status.data_ptr()),
+                                      C.c_void_p(work.data_ptr()), need, st), "sosgpu_surface_batch")
+    # (the work area is read by the launches just queued: the caching allocator hands it out again in stream order only)
+    return [out[j] for j in range(nj)], status

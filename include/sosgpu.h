@@ -259,6 +259,36 @@ int    sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d
                              const int32_t *d_nt, const double *d_prof,
                              double *d_tdifmug /*[nb][N]*/, void *d_work, size_t work_bytes, void *stream);
 
+/* Spherical albedo of the atmosphere for the bins of many wavelengths, in ONE order-0 solve.  Per bin
+ *   d_salb[b] = 2 sum_j ga_j mu_j A_j,     d_plane[b][j-1] = A_j (the plane albedo for incidence mu_j),
+ * with A_j the up-going flux (the d_flux[.][1] of sosgpu_os_solve) of the order-0 solve over a black ground with incidence
+ * J = j that sosgpu_trans_spectrum queues -- the same child table, items, work area and solve.  The sum runs in ascending j,
+ * s = s + ((2 ga_j) mu_j) A_j.  Directions of quadrature weight 0 (the inserted solar angle, the user angles) are not
+ * solved: their column of d_plane is 0 and they add nothing.
+ *  from_below != 0   the atmosphere is lit from the GROUND: every item's profile is mirrored in the vertical about the bin's own
+ *                    NT (h'[k] = h[NT] - h[NT-k], xdel'[k] = xdel[NT-k], ydel'[k] = ydel[NT-k], zeros past NT).  This is the S
+ *                    of rho_toa = rho_path + T_down T_up rho_s / (1 - S rho_s): with it the ground flux of sosgpu_os_solve
+ *                    over a Lambert ground of albedo a obeys E_down(a) (1 - a S) = E_down(0) to the stop test of the
+ *                    scattering orders.  0: seen from space over a black ground (the planetary quantity).
+ *  d_plane           [nb][N], or NULL when only d_salb is wanted
+ * S belongs to the truncated, equivalent atmosphere of d_prof, as TDIFMUG does.  A malformed bin (NT < 1, NT >= lp, context
+ * index out of range) gets d_salb = 0 and a zero row of d_plane.
+ * Everything else -- ctxs, d_ctx_of_bin, d_nt, d_prof, d_work and its size (sosgpu_albedo_spectrum_work_bytes equals
+ * sosgpu_trans_spectrum_work_bytes), asynchrony, the refusals (d_salb in the place of d_tdifmug) checked before anything is
+ * queued or a staging block is taken, nb = 0, the noted stream -- is as sosgpu_trans_spectrum states it.  Launches: two for
+ * the child table, one for the items, the solve, one for the sums. */
+size_t sosgpu_albedo_spectrum_work_bytes(sosgpu_ctx *const *ctxs, int nctx, int nb, int lp);
+int    sosgpu_albedo_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp,
+                              const int32_t *d_nt, const double *d_prof, int from_below,
+                              double *d_plane /*[nb][N], may be NULL*/, double *d_salb /*[nb]*/,
+                              void *d_work, size_t work_bytes, void *stream);
+/* Band value of the spherical albedo: d_out[g] = sum_b d_aik[b] d_salb[b] over the bins d_seg[g] .. d_seg[g+1]-1 of segment g
+ * (sosgpu_aggregate's per-thread striding and fixed tree; a segment of one bin gives aik * salb exactly).  With sum aik = 1 it
+ * is the aik-weighted mean; the coupling formula is exact per bin only.  One launch; nseg = 0 queues nothing; SOSGPU_E_ARG for
+ * nseg < 0 or a NULL pointer.  No context is needed. */
+int    sosgpu_albedo_band(int nseg, const int32_t *d_seg /*[nseg+1]*/, const double *d_aik, const double *d_salb,
+                          double *d_out /*[nseg]*/, int device, void *stream);
+
 /* Replaces SOS_AGGREGATE (SOS_AGGREGATE.F:372-488) for nseg independent wavelengths/bands at once:
  * segment g covers bins seg[g]..seg[g+1]-1 of d_rec; seg[0] = 0, seg[nseg] = nb.  One big band (nseg = 1,
  * nb > 128) is reduced in chunks of 64 bins (deterministic; the strict serial bin order of the reference is kept for

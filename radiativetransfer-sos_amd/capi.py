@@ -29,6 +29,7 @@ EXPORTS = [
     "sosgpu_channel_accumulate", "sosgpu_channel_accumulate_work_bytes", "sosgpu_channel_finish",
     "sosgpu_trans_spectrum", "sosgpu_trans_spectrum_work_bytes",
     "sosgpu_surface_batch", "sosgpu_surface_batch_work_bytes",
+    "sosgpu_albedo_spectrum", "sosgpu_albedo_spectrum_work_bytes", "sosgpu_albedo_band",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -264,6 +265,12 @@ def lib():
         L.sosgpu_trans_spectrum_work_bytes.argtypes = [C.POINTER(vp), i32, i32, i32]
         L.sosgpu_trans_spectrum.restype = i32
         L.sosgpu_trans_spectrum.argtypes = [C.POINTER(vp), i32, vp, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
+        L.sosgpu_albedo_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_albedo_spectrum_work_bytes.argtypes = [C.POINTER(vp), i32, i32, i32]
+        L.sosgpu_albedo_spectrum.restype = i32
+        L.sosgpu_albedo_spectrum.argtypes = [C.POINTER(vp), i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, C.c_size_t, vp]
+        L.sosgpu_albedo_band.restype = i32
+        L.sosgpu_albedo_band.argtypes = [i32, vp, vp, vp, vp, i32, vp]
         L.sosgpu_debug_stage_blocks.restype = i32
         L.sosgpu_debug_stage_blocks.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
         L.sosgpu_debug_solve_plan.restype = i32

@@ -14,6 +14,8 @@
 
 #pragma clang fp contract(off)
 
+#include "tree256.h"
+
 // Orders a bin did not run (s >= norders[b]) are NOT read: the solver leaves them unwritten (the reference's shorter
 // FICOS file, zero-padded by SOS_AGGREGATE.F:357-413), and a failed bin (norders < 0, the reference's IER = -1)
 // contributes nothing -- it is reported through the scalar block instead.
@@ -65,18 +67,8 @@ __global__ void k_aggregate_final(int nel, int nchunk, const double *partial, do
 #define SCB 10
 // The two pieces k_aggregate_scal and k_level_transmission share, so that equal depths give equal bits: the term of a bin in a
 // band transmission, and the fixed-shape tree over the 256 per-thread partials (columns in MAXMASK combine with MAX).
+// (the tree: tree256.h, which k_albedo_band of albedo.hip shares)
 __device__ __forceinline__ double transmission_term(double w, double tau) { return w * exp(-tau); }
-
-template <int NC, unsigned MAXMASK>
-__device__ __forceinline__ void tree256(double (*sm)[NC], const int t)
-{
-    for (int st = 128; st > 0; st >>= 1) {
-        if (t < st)
-            for (int i = 0; i < NC; i++)
-                sm[t][i] = ((MAXMASK >> i) & 1u) ? fmax(sm[t][i], sm[t + st][i]) : sm[t][i] + sm[t + st][i];
-        __syncthreads();
-    }
-}
 
 __global__ void k_aggregate_scal(int n, const int32_t *seg, const double *aik, const int32_t *norders,
                                  const double *flux, const double *scal, const double *tdifmug, double *out)

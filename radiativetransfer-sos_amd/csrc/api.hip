@@ -919,7 +919,8 @@ extern "C" int sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table,
 
 // Diffuse transmissions of -SOS.Trans for the bins of many wavelengths (SOS.F:600-635): every (context, direction) pair becomes
 // a child entry of a context table in the work area, every (bin, direction) pair an item of ONE order-0 multi-wavelength solve
-// (trans.hip).  Work area, from its first 256-byte boundary, every block at a multiple of 256 bytes:
+// (trans.hip).  The spherical albedo (sosgpu_albedo_spectrum, albedo.hip) is the same stage with items of its own and the other
+// flux kept.  Work area, from its first 256-byte boundary, every block at a multiple of 256 bytes:
 //   parents [nctx] SosDev | children [nctx N] SosDev | sv [nctx N][4][kp] | ctx_of_item, nt, iborm, norders, iglast [nb N] int32
 //   | flux [nb N][2] | rec [nb N][3][W] | prof [nb N][3][lp]
 namespace {
@@ -967,11 +968,15 @@ extern "C" size_t sosgpu_trans_spectrum_work_bytes(sosgpu_ctx *const *ctxs, int 
     return L.total;
 }
 
-extern "C" int sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp,
-                                     const int32_t *d_nt, const double *d_prof, double *d_tdifmug, void *d_work,
-                                     size_t work_bytes, void *stream)
+// What sosgpu_trans_spectrum and sosgpu_albedo_spectrum share: the refusals, the parents' copy, the child table, the items and
+// the order-0 solve.  d_out: the output neither call can do without (refused when NULL).  albedo: 0 the items of
+// k_trans_items; 1, 2 those of k_albedo_items, 2 with the mirrored profile.  *q describes the items for the kernels behind
+// the solve (unset where the call refuses or nb = 0 queues nothing).
+static int trans_stage(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp, const int32_t *d_nt,
+                       const double *d_prof, const void *d_out, void *d_work, size_t work_bytes, void *stream, int albedo,
+                       AlbedoItems *q)
 {
-    if (!d_nt || !d_prof || !d_tdifmug || !d_work || nb < 0 || lp < 2) return SOSGPU_E_ARG;
+    if (!d_nt || !d_prof || !d_out || !d_work || nb < 0 || lp < 2) return SOSGPU_E_ARG;
     if (!trans_ctxs_ok(ctxs, nctx) || (!d_ctx_of_bin && nctx > 1)) return SOSGPU_E_ARG;
     if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
     const SosDev &p0 = ctxs[0]->d;
@@ -994,7 +999,7 @@ extern "C" int sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const in
     }
     const int nchild = nctx * p0.n, nitems = nb * p0.n;
     launch_trans_table(d_parents, nchild, p0.n, d_children, reinterpret_cast<double *>(base + L.sv), os_nb_max, st);
-    TransItems it;
+    TransItems &it = q->t;
     it.nb = nb; it.n = p0.n; it.lp = lp; it.nctx = nctx;
     it.ctx_of_bin = d_ctx_of_bin; it.nt = d_nt; it.prof = d_prof;
     it.ctx_of_item = reinterpret_cast<int32_t *>(base + L.ctx_of_item);
@@ -1002,7 +1007,9 @@ extern "C" int sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const in
     it.iborm_item = reinterpret_cast<int32_t *>(base + L.iborm);
     it.prof_item = reinterpret_cast<double *>(base + L.prof);
     it.flux = reinterpret_cast<double *>(base + L.flux);
-    launch_trans_items(it, st);
+    q->parents = d_parents; q->from_below = albedo == 2;
+    if (albedo) launch_albedo_items(*q, st);
+    else launch_trans_items(it, st);
     HIPCHK(hipGetLastError());
     // what the children have in common: order 0 only, a black ground without matrices (variant and record layout of the solve)
     SosDev as = p0;
@@ -1013,8 +1020,48 @@ extern "C" int sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const in
                                  reinterpret_cast<int32_t *>(base + L.norders), reinterpret_cast<int32_t *>(base + L.iglast),
                                  it.flux, stream, 0, &as, 4);
     for (int i = 0; i < nctx; i++) note_stream(ctxs[i], st);       // (the kernels queued so far read their tables)
-    if (rc) return rc;
-    launch_trans_gather((size_t)nitems, it.flux, d_tdifmug, st);
+    return rc;
+}
+
+extern "C" int sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp,
+                                     const int32_t *d_nt, const double *d_prof, double *d_tdifmug, void *d_work,
+                                     size_t work_bytes, void *stream)
+{
+    AlbedoItems q;
+    const int rc = trans_stage(ctxs, nctx, d_ctx_of_bin, nb, lp, d_nt, d_prof, d_tdifmug, d_work, work_bytes, stream, 0, &q);
+    if (rc || nb == 0) return rc;
+    launch_trans_gather((size_t)q.t.nb * q.t.n, q.t.flux, d_tdifmug, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
+// Spherical albedo of the atmosphere per bin (albedo.hip): the stage of sosgpu_trans_spectrum -- its work area, child table and
+// solve -- with the items of k_albedo_items, and the up-going flux of every item summed over the directions.
+extern "C" size_t sosgpu_albedo_spectrum_work_bytes(sosgpu_ctx *const *ctxs, int nctx, int nb, int lp)
+{
+    return sosgpu_trans_spectrum_work_bytes(ctxs, nctx, nb, lp);
+}
+
+extern "C" int sosgpu_albedo_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp,
+                                      const int32_t *d_nt, const double *d_prof, int from_below, double *d_plane, double *d_salb,
+                                      void *d_work, size_t work_bytes, void *stream)
+{
+    AlbedoItems q;
+    const int rc = trans_stage(ctxs, nctx, d_ctx_of_bin, nb, lp, d_nt, d_prof, d_salb, d_work, work_bytes, stream,
+                               from_below ? 2 : 1, &q);
+    if (rc || nb == 0) return rc;
+    launch_albedo_sum(q, d_plane, d_salb, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
+
+extern "C" int sosgpu_albedo_band(int nseg, const int32_t *d_seg, const double *d_aik, const double *d_salb, double *d_out,
+                                  int device, void *stream)
+{
+    if (nseg < 0 || !d_seg || !d_aik || !d_salb || !d_out) return SOSGPU_E_ARG;
+    if (nseg == 0) return SOSGPU_OK;
+    if (const int rc = use_device(device)) return rc;
+    launch_albedo_band(nseg, d_seg, d_aik, d_salb, d_out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;
 }

@@ -47,6 +47,21 @@ void launch_trans_items(const TransItems &a, hipStream_t st);
 // tdifmug[i] = EMOINS of item i; one launch
 void launch_trans_gather(size_t nitems, const double *d_flux, double *d_tdifmug, hipStream_t st);
 
+// The same stage for the spherical albedo (albedo.hip, sosgpu_albedo_spectrum): the items of launch_trans_items with, from_below
+// != 0, the profile rows mirrored about each bin's nt, and with the items of weight-0 directions made malformed (parents: the
+// device table [t.nctx] the children were made from, read for ga and mu); one launch
+struct AlbedoItems {
+    TransItems t;
+    const SosDev *parents;
+    int from_below;
+};
+void launch_albedo_items(const AlbedoItems &q, hipStream_t st);
+// plane[b][j] = EPLUS of item (b, j + 1), 0 in weight-0 columns (d_plane may be null); salb[b] = sum_j ((2 ga_j) mu_j) plane[b][j]
+// in ascending j; one launch of nb workgroups
+void launch_albedo_sum(const AlbedoItems &q, double *d_plane, double *d_salb, hipStream_t st);
+// out[g] = sum aik * salb over the bins of segment g (k_aggregate_scal's striding and tree); one launch of nseg workgroups
+void launch_albedo_band(int nseg, const int32_t *d_seg, const double *d_aik, const double *d_salb, double *d_out, hipStream_t st);
+
 void launch_aggregate(const SosDev &cx, int nseg, const int32_t *d_seg, const double *d_aik,
                       const double *d_rec, const int32_t *d_norders, const double *d_flux, const double *d_scal,
                       const double *d_tdifmug, double *d_out_rec, double *d_out_scal, hipStream_t st, int nb_single,

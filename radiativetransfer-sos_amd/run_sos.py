@@ -1760,7 +1760,7 @@ def _first_failed_index(index, device):
 
 
 def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False,
-                   split=False, chan=None, trans=False):
+                   split=False, chan=None, trans=False, salb=False):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
     launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop.
@@ -1771,7 +1771,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     Returns what _channel_results makes of the accumulator and of the per-call scalars.
     trans (transmissions=True of the two entry points): after a part's operators are queued, ONE
     solver.diffuse_transmissions_many call per group of equal direction count gives the diffuse transmissions of every bin of
-    the part; they ride the groups' and the singles' aggregates, and the pass also returns one trans_entry per call."""
+    the part; they ride the groups' and the singles' aggregates, and the pass also returns one trans_entry per call.
+    salb (spherical_albedo=True, only with trans): next to it ONE solver.spherical_albedo_many call per such group and one
+    solver.albedo_band launch for the group's calls; the band values come down with the chunk's band scalars and become the
+    key s_alb of the entries."""
     import time
     import torch
     from . import capi, solver
@@ -1889,6 +1892,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 # The chunk goes to the solver in a few parts: the solves of a part run on the device while the host prepares the
                 # next one, so that only the last part's solve is waited for below.
                 solved = []                       # (plans, rec [K][nw][S][3][W], scal [K][nw][10+N], table) device tensors
+                salb_bands = []                   # salb: (plans, their band spherical albedos [len(plans)], a device tensor)
                 # (at least 32 wavelengths per part -- a launch per kernel variant each; SOS_SPECTRUM_MIN_PART: the tests' override)
                 nsub = max(1, min(int(parts), len(idx) // max(1, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32")))))
                 step = max(1, -(-len(idx) // nsub))
@@ -1960,6 +1964,12 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                                     sc = pl.bins["scal"] = solver._dev_f64(np.asarray(sc), dev)
                                 sc[:, 0] = tdifmus[b0:b1]
                                 b0 = b1
+                            if salb:
+                                # the spherical albedo of the same bins seen from the ground, and its aik-weighted sum per call
+                                s_bin, _ = solver.spherical_albedo_many([pl.ctx for pl in gp], tbins, tcob)
+                                seg = np.concatenate([[0], np.cumsum([pl.bins["nb"] for pl in gp])]).astype(np.int32)
+                                aik = solver._dev_f64(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp]), dev)
+                                salb_bands.append((gp, solver.albedo_band(seg, aik, s_bin)))
                     t1 = time.perf_counter()
                     tm["prepare"] += t1 - t0
                     # --- groups of wavelengths one launch can cover
@@ -2007,8 +2017,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     tm["fluxes"] += time.perf_counter() - tf
                 t2 = time.perf_counter()
                 # --- one copy of all band scalars (waits for the solves), then every azimuth recomposition back to back
-                # (the status words of the device gas tables ride at its end)
-                scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in solved] +
+                # (the band spherical albedos and the status words of the device gas tables ride at its end)
+                scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in solved] + [s for _, s in salb_bands] +
                                      [s.to(torch.float64) for s, _ in ckd_checks]).cpu().numpy()
                 t3 = time.perf_counter()
                 tm["wait"] += t3 - t2
@@ -2019,6 +2029,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                             where = pl.index
                             raise SosProcError(_abs.CKD_STATUS_MESSAGES.get(int(code), "COEFF_ABS_CKD failed"), ier=-1)
                     pos += len(pls)
+                s_alb, pos = {}, sum(s.numel() for _, _, s, _ in solved)
+                for gp, _ in salb_bands:
+                    s_alb.update((pl.index, float(v)) for pl, v in zip(gp, scal_all[pos:pos + len(gp)]))
+                    pos += len(gp)
                 todo, pos = [], 0                               # (plan, slot, record, finish_scalars, segment)
                 for gp, rec, scal, _ in solved:
                     sw = scal.shape[2]
@@ -2036,6 +2050,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                             trans_out[pl.index] = trans_entry(pl.p["tetas"], pl.mu, float(fins[0]["ttot_tronc"][g]),
                                                               float(fins[0]["ttot_vrai"][g]), float(fins[0]["tdifmus"][g]),
                                                               np.array(fins[0]["tdifmug"][g], dtype=np.float64))
+                            if salb:                            # (a call without bins took no part in the stage)
+                                trans_out[pl.index]["s_alb"] = s_alb.get(pl.index, 0.0)
                 # one launch for every (wavelength, altitude) of the chunk, its flat result downloaded as it is
                 flat, shapes = _trphi_launch_many([(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
                                                    for pl, _, r, f, g in todo])
@@ -2296,8 +2312,18 @@ def _transmissions_argument(fn, kwargs_list, transmissions):
     return bool(transmissions)
 
 
+def _spherical_albedo_argument(fn, spherical_albedo, trans):
+    """The rule of spherical_albedo=True, checked before any library call: a bool, and only next to transmissions=True (the
+    value is a key of the entries that keyword returns)."""
+    if not isinstance(spherical_albedo, (bool, np.bool_)):
+        raise ValueError("%s: spherical_albedo must be True or False, got %r" % (fn, spherical_albedo))
+    if spherical_albedo and not trans:
+        raise ValueError("%s: spherical_albedo=True requires transmissions=True (s_alb is a key of the trans entries)" % fn)
+    return bool(spherical_albedo)
+
+
 def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16, parts=4,
-                 transmissions=False):
+                 transmissions=False, spherical_albedo=False):
     """A spectrum of sos_proc calls -- one per wavelength, as the reference issues them one after the other
     (binding/run_sos.py:640-695; the bin loop of each is SOS_PROC.F:3459-3594) -- as ONE pass over the GPU:
 
@@ -2356,14 +2382,28 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     ALL bins of a part come from ONE order-0 solve per direction count (solver.diffuse_transmissions_many,
     sosgpu_trans_spectrum: no context per direction), whatever mix of grouped, single, no-gas, -SOS.AbsModeCKD 2 and aerosol-layer
     calls the part holds, and ride the aggregates that run anyway; the 23-tuples keep their bits.  With gather=True the
-    entries travel with the compacted tuples.  With the default the return value, the launches and the bits are unchanged."""
+    entries travel with the compacted tuples.  With the default the return value, the launches and the bits are unchanged.
+
+    spherical_albedo=True (a bool, and only with transmissions=True: ValueError otherwise, before any library call): every
+    trans[i] has one more key, s_alb, the spherical albedo S of the atmosphere seen from the ground -- the third quantity of
+        rho_toa = rho_path + T_down * T_up * rho_s / (1 - S * rho_s).
+    Per CKD bin S = 2 sum_j ga_j mu_j A_j, A_j being the up-going flux of an order-0 solve over a black ground with the
+    vertically MIRRORED profile and incidence mu_j (solver.spherical_albedo_many, sosgpu_albedo_spectrum): one more solve of
+    the transmission stage's shape per part and direction count, minus the weight-0 directions, whatever path a call takes
+    otherwise; one sosgpu_albedo_band launch per such group forms the band value sum aik * S_b, which comes down with the band
+    scalars (no host wait is added).  S belongs to the truncated, equivalent atmosphere the solver sees, as tdifmug does; for
+    a band of several CKD bins s_alb is the aik-weighted mean, and the coupling formula is exact per bin only.  With S the
+    ground flux over a Lambert ground of albedo a obeys E_down(a) (1 - a S) = E_down(0); a Lambert coupling of the RADIANCE
+    through t_dif_up is not claimed.  Not covered: the -SOS.Trans file path of sos_proc, and bands sharded over ranks.  Every
+    other key, every tuple and, without the keyword, the keys themselves keep their bits."""
     trans = _transmissions_argument("sos_spectrum", kwargs_list, transmissions)
+    salb = _spherical_albedo_argument("sos_spectrum", spherical_albedo, trans)
     return _spectrum_pass("sos_spectrum", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
-                          trans=trans)
+                          trans=trans, salb=salb)
 
 
 def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16,
-                        parts=4, fluxes=False, split=False, transmissions=False):
+                        parts=4, fluxes=False, split=False, transmissions=False, spherical_albedo=False):
     """sos_spectrum for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output): every wavelength is
     prepared once, ALL bins of a group of wavelengths go through ONE launch of the fused solver per kernel variant with K output
     slots each (sosgpu_os_solve_multi_levels), then K segmented aggregates (each altitude with its own TAUOUT) and K azimuth
@@ -2401,11 +2441,14 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
     wavelength) -- not one per altitude -- puts their band transmissions into the scalar blocks that are downloaded anyway.
 
     transmissions=True: as sos_spectrum describes it; trans (one trans_entry per call: the values do not depend on the output
-    altitude) is appended behind spec, and behind flux with fluxes=True."""
+    altitude) is appended behind spec, and behind flux with fluxes=True.
+    spherical_albedo=True (only with transmissions=True): the key s_alb of every entry, as sos_spectrum describes it; it does
+    not depend on the output altitudes either."""
     trans = _transmissions_argument("sos_spectrum_levels", kwargs_list, transmissions)
+    salb = _spherical_albedo_argument("sos_spectrum_levels", spherical_albedo, trans)
     alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes, split)
     return _spectrum_pass("sos_spectrum_levels", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
-                          alts, bool(fluxes), bool(split), trans=trans)
+                          alts, bool(fluxes), bool(split), trans=trans, salb=salb)
 
 
 def trans_quantities(tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):

@@ -776,6 +776,53 @@ def diffuse_transmissions_many(ctxs, bins, ctx_of_bin=None):
     return tdifmug.gather(1, n0[cob.long()][:, None])[:, 0].contiguous(), tdifmug
 
 
+def spherical_albedo_many(ctxs, bins, ctx_of_bin=None, from_below=True):
+    """The spherical albedo of the atmosphere for the bins of MANY contexts in one call (sosgpu_albedo_spectrum): per bin
+    S = 2 sum_j ga_j mu_j A_j, with A_j the up-going flux of an order-0 solve over a black ground with incidence mu_j -- the
+    items, child table and solve of diffuse_transmissions_many, which keeps the other flux.  from_below=True lights the
+    atmosphere from the ground (every item's profile mirrored in the vertical about its own NT): the S of
+    rho_toa = rho_path + T_down T_up rho_s / (1 - S rho_s), for which the ground flux over a Lambert ground of albedo a obeys
+    E_down(a) (1 - a S) = E_down(0).  from_below=False: the spherical albedo seen from space over a black ground (the
+    planetary quantity).  S belongs to the truncated, equivalent atmosphere the solver sees, as tdifmug does.
+    ctxs, bins, ctx_of_bin: as diffuse_transmissions_many takes them.  Returns (salb[nb], plane[nb][N]) device tensors;
+    plane[b][j] is the plane albedo A_j, 0 in the columns of weight-0 directions (the inserted solar angle, user angles), which
+    are not solved; a malformed bin gives zeros.  Nothing is waited for."""
+    ctxs = list(ctxs)
+    if not ctxs:
+        raise ValueError("spherical_albedo_many needs at least one context")
+    for cx in ctxs:
+        cx._need_operators()
+    first = ctxs[0]
+    d, n, nb = first.device, first.n, int(bins["nb"])
+    if ctx_of_bin is None and len(ctxs) > 1:
+        raise ValueError("ctx_of_bin is required with more than one context")
+    cob = None if ctx_of_bin is None else _dev_i32(ctx_of_bin, d)
+    L = capi.lib()
+    hs = (C.c_void_p * len(ctxs))(*[cx._h for cx in ctxs])
+    salb = torch.empty(nb, dtype=torch.float64, device=d)
+    plane = torch.empty((nb, n), dtype=torch.float64, device=d)
+    need = int(L.sosgpu_albedo_spectrum_work_bytes(hs, len(ctxs), nb, bins["lp"]))
+    work = torch.empty(max(need, 8), dtype=torch.uint8, device=d)
+    capi.check(L.sosgpu_albedo_spectrum(hs, len(ctxs), _ptr(cob), nb, bins["lp"], _ptr(bins["nt"]), _ptr(bins["prof"]),
+                                        1 if from_below else 0, _ptr(plane), _ptr(salb), _ptr(work), need, first._stream()),
+               "sosgpu_albedo_spectrum")
+    return salb, plane
+
+
+def albedo_band(seg, aik, salb):
+    """sum aik * salb over the bins of every segment (sosgpu_albedo_band): seg int32 [nseg + 1] (host or device), aik and salb
+    [nb] device tensors.  Returns the device tensor [nseg]; one launch on the current stream, nothing waited for."""
+    d = salb.device
+    seg_t = _dev_i32(seg, d)
+    nseg = int(seg_t.numel()) - 1
+    out = torch.empty(max(nseg, 0), dtype=torch.float64, device=d)
+    if nseg < 1:
+        return out
+    capi.check(capi.lib().sosgpu_albedo_band(nseg, _ptr(seg_t), _ptr(aik), _ptr(salb), _ptr(out), d.index or 0,
+                                             C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "sosgpu_albedo_band")
+    return out
+
+
 def release_scratch():
     """Return the scratch buffers the library keeps from destroyed contexts (streamed solver; at most 8 GiB) to the device,
     and free the pinned staging blocks of the table-form calls whose copies have passed (sosgpu_trim)."""

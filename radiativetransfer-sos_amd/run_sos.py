@@ -735,41 +735,68 @@ _SURF_CACHE_MAX = 8
 _SURF_PREFETCH = threading.local()
 
 
+def _angle_counts(p):
+    """(nb_lum, nb_mie, os_nb, os_ns, os_nm) of SOS_ANGLES for the keyword set p (SOS_ANGLES.F:303-329)."""
+    nb_lum = CTE_DEFAULT_NBMU_LUM if p["nbmu_gauss_lum"] == _I else int(p["nbmu_gauss_lum"])
+    nb_mie = CTE_DEFAULT_NBMU_MIE if p["nbmu_gauss_mie"] == _I else int(p["nbmu_gauss_mie"])
+    os_nb = CTE_DEFAULT_OS_NB if p["nbmu_gauss_mie"] == _I else 2 * nb_mie          # SOS_ANGLES.F:303-312
+    if p["nbmu_gauss_lum"] == _I:
+        os_ns, os_nm = CTE_DEFAULT_OS_NS, CTE_DEFAULT_OS_NM
+    else:
+        os_ns = 2 * nb_lum
+        os_nm = os_nb + os_ns                                                        # SOS_ANGLES.F:325-329
+    return nb_lum, nb_mie, os_nb, os_ns, os_nm
+
+
+def _surface_rule(p, mu, ga, counts, device):
+    """The surface checks of the validated keyword set p (SOS_PREPA_OS.F:479-497), then (igli, ifresnel, imat, land, key, job):
+    land = the capi.Land of -SURF.Type >= 3, key / job = the _surface_cached key and the surface.surface_job of a computed sea
+    or land surface on the angles mu / ga and the counts of _angle_counts, None for -SURF.Type 0 / 2 and for a -SURF.File."""
+    from . import surface as _surface
+    _, _, os_nb, os_ns, os_nm = counts
+    isurf = int(p["isurf"])
+    igli, ifresnel, imat = int(isurf == 1), int(isurf == 2), int(isurf == 1 or isurf >= 3)
+    land = key = job = None
+    if (isurf in (1, 2) or isurf >= 4) and p["surf_ind"] == _D:
+        raise SosProcError("-SURF.Ind must be defined for sea surfaces and BPDF models")
+    if isurf >= 3:
+        if _D in (p["k0_roujean"], p["k1_roujean"], p["k2_roujean"]):
+            raise SosProcError("-SURF.Roujean.K0/K1/K2 must be defined for -SURF.Type >= 3")
+        if isurf == 6:                                    # the reference's own SOS_PROC refuses it with this message
+            raise SosProcError("The Nadal's BPDF model is not supported ==> Select another surface model")
+        if isurf == 7 and p["coef_c_maignan"] == _D:
+            raise SosProcError("-SURF.Maignan.C must be defined for -SURF.Type 7")
+        land = _surface.land_model(isurf, p["k0_roujean"], p["k1_roujean"], p["k2_roujean"], p["alpha_nadal"], p["beta_nadal"],
+                                   p["coef_c_maignan"])
+    user_surf = str(p["ficsurf"]).strip()
+    if imat and user_surf != "DEFAULT":
+        # -SURF.File: the user's reflection matrices replace the surface computation (SOS_PROC.F:3186-3189,
+        # SOS_PREPA_OS.F:605-658); the direct-beam terms of SOS_TRPHI still follow -SURF.Type
+        if not os.path.exists(user_surf):
+            raise SosProcError("-SURF.File %s does not exist (SOS_PREPA_OS ERROR_1020)" % user_surf, ier=-1)
+    elif isurf == 1:
+        if p["wind"] == _D:
+            raise SosProcError("-SURF.Glitter.Wind must be defined")
+        key = ("glitter", mu.tobytes(), ga.tobytes(), float(p["wind"]), float(p["surf_ind"]), os_nb, os_ns, os_nm, device)
+        job = _surface.surface_job(1, wind=p["wind"], ind=p["surf_ind"])
+    elif land is not None:
+        ind_l = p["surf_ind"] if isurf >= 4 else 1.0
+        k0, k1, k2, coef_c = float(land.k0), float(land.k1), float(land.k2), float(land.coef_c)
+        key = ("land", isurf, k0, k1, k2, float(land.alpha), float(land.beta), coef_c, mu.tobytes(), ga.tobytes(), float(ind_l),
+               os_nb, os_ns, os_nm, device)
+        job = _surface.surface_job(isurf, ind=ind_l, k0=k0, k1=k1, k2=k2, coef_c=coef_c)
+    return igli, ifresnel, imat, land, key, job
+
+
 def _surface_request(p, device):
     """(group, key, job) of the surface matrices _prepare will ask for with the validated keyword set p: group = (mu bytes, weight
-    bytes, os_nb, os_ns, os_nm), key = the key _prepare forms for _surface_cached, job = the surface.surface_job of the batch.  None
-    for -SURF.Type 0 / 2, a -SURF.File call, or parameters the real pass refuses (it reports)."""
-    from . import surface as _surface
+    bytes, os_nb, os_ns, os_nm), key and job = those of _surface_rule.  None for -SURF.Type 0 / 2, a -SURF.File call, or
+    parameters the real pass refuses (it reports)."""
     try:
-        isurf = int(p["isurf"])
-        if isurf not in (1, 3, 4, 5, 7) or str(p["ficsurf"]).strip() != "DEFAULT":
-            return None
-        if p["tetas"] == _D or not (0.0 <= p["tetas"] < 90.0):
-            return None
-        nb_lum = CTE_DEFAULT_NBMU_LUM if p["nbmu_gauss_lum"] == _I else int(p["nbmu_gauss_lum"])
-        os_nb = CTE_DEFAULT_OS_NB if p["nbmu_gauss_mie"] == _I else 2 * int(p["nbmu_gauss_mie"])
-        if p["nbmu_gauss_lum"] == _I:
-            os_ns, os_nm = CTE_DEFAULT_OS_NS, CTE_DEFAULT_OS_NM
-        else:
-            os_ns = 2 * nb_lum
-            os_nm = os_nb + os_ns
-        mu, ga, _, _ = angles(nb_lum, p["tetas"], p["ficangles_user_lum"])
-        if isurf == 1:
-            if _D in (p["wind"], p["surf_ind"]):
-                return None
-            key = ("glitter", mu.tobytes(), ga.tobytes(), float(p["wind"]), float(p["surf_ind"]), os_nb, os_ns, os_nm, device)
-            job = _surface.surface_job(1, wind=p["wind"], ind=p["surf_ind"])
-        else:
-            if _D in (p["k0_roujean"], p["k1_roujean"], p["k2_roujean"]) or (isurf >= 4 and p["surf_ind"] == _D) or \
-                    (isurf == 7 and p["coef_c_maignan"] == _D):
-                return None
-            land = _surface.land_model(isurf, p["k0_roujean"], p["k1_roujean"], p["k2_roujean"], p["alpha_nadal"], p["beta_nadal"],
-                                       p["coef_c_maignan"])
-            ind_l = p["surf_ind"] if isurf >= 4 else 1.0
-            key = ("land", isurf, float(land.k0), float(land.k1), float(land.k2), float(land.alpha), float(land.beta),
-                   float(land.coef_c), mu.tobytes(), ga.tobytes(), float(ind_l), os_nb, os_ns, os_nm, device)
-            job = _surface.surface_job(isurf, ind=ind_l, k0=land.k0, k1=land.k1, k2=land.k2, coef_c=land.coef_c)
-        return (mu.tobytes(), ga.tobytes(), os_nb, os_ns, os_nm), key, job
+        counts = _angle_counts(p)
+        mu, ga, _, _ = angles(counts[0], p["tetas"], p["ficangles_user_lum"])
+        key, job = _surface_rule(p, mu, ga, counts, device)[4:]
+        return None if key is None else ((mu.tobytes(), ga.tobytes()) + counts[2:], key, job)
     except Exception:
         return None
 
@@ -972,16 +999,42 @@ def _validated(kw):
         return None
 
 
+def _gas_rule(p):
+    """None for -AP.AbsProfile.Type 7, else the gas checks of the validated keyword set p and the arguments of
+    absorption.prepa_absprofile (SOS_PREPA_ABSPROFILE, SOS_PROC.F:3359-3416), which absorption.prefetch_gas_tables takes too."""
+    absprofil = int(p["absprofil"])
+    if absprofil == 7:
+        return None
+    if int(p["iprofil"]) == 2:                                                     # SOS_PROC.F:2352
+        raise SosProcError("-AP.AerProfile.Type 2 requires -AP.AbsProfile.Type 7 (no gas absorption)")
+    if p["nustep"] == _I:
+        raise SosProcError("-AP.SpectralResol must be defined with -AP.AbsProfile.Type != 7")
+    if absprofil == 0 and str(p["ficabsprofil"]).strip() == "NO_USER_ABS_PROFILE_FILE":
+        raise SosProcError("-AP.AbsProfile.UserFile must be defined with -AP.AbsProfile.Type 0")
+    return (p["wa_simu"], float(p["nustep"]), p["psurf"], p["h2o"], p["o3"], p["co2"], p["ch4"], absprofil,
+            str(p["ficabsprofil"]).strip())
+
+
+def _defers_by_keywords(p, use_gas):
+    """The keyword part of "the pass makes the profiles of this call": -AP.AerProfile.Type 1, no -SOS.Trans, -SOS.AbsModeCKD 1
+    where the call has gas.  (_prepare adds what needs the optical thicknesses, the rank split and the table sizes.)"""
+    return int(p["iprofil"]) == 1 and str(p["fictrans"]).strip() == "NO_OUTPUT" and (not use_gas or p["imode_ckd_calcul"] == 1)
+
+
+def _aerosol_rule(p, aer_phase):
+    """(use_model, at_wa) of the validated keyword set p: SOS_AEROSOLS runs (aerosols, no given expansion, no -AER.UserFile), and
+    it runs a second time at the simulation wavelength (-AER.Waref defined and different from -SOS_Main.Wa, SOS_PROC.F:2893)."""
+    use_model = p["aot_ref"] != 0.0 and aer_phase is None and str(p["ficuser_aer"]).strip() == "NO_USER_AEROSOLS"
+    if use_model and p["imod_aer"] not in (0, 1, 2, 3, 4, 5):
+        raise SosProcError("-AER.Model must be in 0..5")
+    return use_model, use_model and p["waref_aot"] != _D and p["wa_simu"] != p["waref_aot"]
+
+
 def _gas_table_request(p):
-    """The arguments of the SOS_PREPA_ABSPROFILE call _prepare will make for the validated keyword set p
-    (absorption.prefetch_gas_tables), or None when the call has no gas absorption or its parameters are refused (the real pass
-    reports)."""
+    """The arguments of the SOS_PREPA_ABSPROFILE call _prepare will make for the validated keyword set p (_gas_rule), or None when
+    the call has no gas absorption or its parameters are refused (the real pass reports)."""
     try:
-        absprofil = int(p["absprofil"])
-        if absprofil == _I or not 0 <= absprofil <= 6 or p["nustep"] == _I or p["wa_simu"] == _D:
-            return None
-        return (p["wa_simu"], float(p["nustep"]), p["psurf"], p["h2o"], p["o3"], p["co2"], p["ch4"], absprofil,
-                str(p["ficabsprofil"]).strip())
+        return _gas_rule(p)
     except Exception:
         return None
 
@@ -990,7 +1043,7 @@ def _gas_tables_on_device(p):
     """True when, as far as the validated keyword set p tells, _prepare will defer the profiles of this gas call (the rest of its
     rule needs the optical thicknesses)."""
     try:
-        return int(p["iprofil"]) == 1 and str(p["fictrans"]).strip() == "NO_OUTPUT" and int(p["imode_ckd_calcul"]) == 1
+        return _defers_by_keywords(p, True)
     except Exception:
         return False
 
@@ -999,11 +1052,9 @@ def _aerosol_call(p, aer_phase):
     """(p, nb_mie, os_nb) of the SOS_AEROSOLS run _prepare will make at the simulation wavelength for the validated keyword set p,
     or None when that step does not run or its parameters are refused (the real pass reports)."""
     try:
-        if (p["aot_ref"] in (0.0, _D) or aer_phase is not None or str(p["ficuser_aer"]).strip() != "NO_USER_AEROSOLS"
-                or p["waref_aot"] == _D or p["wa_simu"] in (_D, p["waref_aot"]) or p["imod_aer"] not in (0, 1, 2, 3, 4, 5)):
+        if not _aerosol_rule(p, aer_phase)[1]:
             return None
-        nb_mie = CTE_DEFAULT_NBMU_MIE if p["nbmu_gauss_mie"] == _I else int(p["nbmu_gauss_mie"])
-        os_nb = CTE_DEFAULT_OS_NB if p["nbmu_gauss_mie"] == _I else 2 * nb_mie
+        _, nb_mie, os_nb, _, _ = _angle_counts(p)
         return p, nb_mie, os_nb
     except Exception:
         return None
@@ -1054,11 +1105,288 @@ def _profiles_deferrable(tr, hr, ta, ha):
         return False
 
 
+def _prepare_checks(pl):
+    """The parameter checks the hot path depends on (SOS_PROC.F:1310-2700 has many more; same messages' intent)."""
+    p = pl.p
+    if p["wa_simu"] == _D:
+        raise SosProcError("-SOS_Main.Wa must be defined")
+    if p["tetas"] == _D or not (0.0 <= p["tetas"] < 90.0):
+        raise SosProcError("-ANG.Thetas must be defined in [0,90[")
+    pl.iprofil = int(p["iprofil"])
+    if pl.iprofil not in (1, 2):                                                   # SOS_PROC.F:2324-2325
+        raise SosProcError("-AP.AerProfile.Type must be 1 or 2")
+    if pl.iprofil == 2 and (p["zmin"] == _D or p["zmax"] == _D):                   # :2335-2338
+        raise SosProcError("-AP.AerLayer.Zmin and -AP.AerLayer.Zmax must be defined for -AP.AerProfile.Type 2")
+    pl.absprofil = int(p["absprofil"])
+    if pl.absprofil == _I or not 0 <= pl.absprofil <= 7:
+        raise SosProcError("-AP.AbsProfile.Type must be defined in 0..7")
+    if p["isurf"] not in (0, 1, 2, 3, 4, 5, 6, 7):
+        raise SosProcError("-SURF.Type must be in 0..7")
+    if p["rho"] == _D:
+        raise SosProcError("-SURF.Alb must be defined")
+    if p["aot_ref"] == _D:
+        raise SosProcError("-AER.AOTref must be defined")
+    pl.use_model, pl.aer_at_wa = _aerosol_rule(p, pl.aer_phase)
+    if p["hr"] == _D:
+        raise SosProcError("-AP.HR must be defined")
+    pl.itrphi = p["itrphi"]
+    if pl.itrphi == 1 and p["phios"] == _D:
+        raise SosProcError("-SOS.View.Phi must be defined for -SOS.View 1")
+    if pl.itrphi == 2 and p["pas_phi"] == _I:
+        raise SosProcError("-SOS.View.Dphi must be defined for -SOS.View 2")
+    pl.igmax = CTE_DEFAULT_IGMAX if p["igmax"] == _I else int(p["igmax"])
+
+
+def _prepare_angles(pl):
+    """SOS_ANGLES (SOS_PROC.F:2738)."""
+    pl.nb_lum, pl.nb_mie, pl.os_nb, pl.os_ns, pl.os_nm = _angle_counts(pl.p)
+    pl.mu, pl.ga, pl.n0, pl.ind_ang = angles(pl.nb_lum, pl.p["tetas"], pl.p["ficangles_user_lum"])
+    pl.n = len(pl.mu)
+
+
+def _prepare_aerosols(pl, aer_stream, aer_at_wa):
+    """Aerosols: none, a user Aerosols.txt (-AER.UserFile, SOS_PROC.F:2883-2934: SOS_AEROSOLS is not run, the file is read by
+    SOS_PREPA_OS.F:666-700), or a given expansion (stands for SOS_AEROSOLS -> Aerosols.txt)."""
+    import torch
+    p, device = pl.p, pl.device
+    pl.coef_tronca_out = None
+    ta_model = None
+    if pl.use_model:
+        # SOS_AEROSOLS at the reference wavelength, and again at the simulation wavelength when they differ: the optical
+        # thickness scales with the extinction cross sections (SOS_PROC.F:2883-3060)
+        from . import aerosols as _aer
+        if p["waref_aot"] == _D:
+            raise SosProcError("-AER.Waref must be defined")
+        import contextlib
+        try:
+            with (torch.cuda.stream(aer_stream) if aer_stream is not None else contextlib.nullcontext()):
+                pl.aer_phase = _aerosols_at_waref(p, pl.nb_mie, pl.os_nb, device)
+                ta_model = float(p["aot_ref"])
+                if pl.aer_at_wa:
+                    k_ref = pl.aer_phase["kmat1"]
+                    pl.aer_phase = (aer_at_wa if aer_at_wa is not None else
+                                    _aer.aerosols(p, p["wa_simu"], 0.1, pl.nb_mie, pl.os_nb, at_waref=False, device=device))
+                    ta_model = (pl.aer_phase["kmat1"] / k_ref) * p["aot_ref"]
+        except _aer.AerosolError as e:
+            raise SosProcError(str(e), ier=-1)
+        pl.coef_tronca_out = pl.aer_phase["coef_tronca"]
+    elif p["aot_ref"] != 0.0 and pl.aer_phase is None:
+        user_aer = str(p["ficuser_aer"]).strip()
+        if not os.path.exists(user_aer):
+            raise SosProcError("-AER.UserFile %s not found" % user_aer)
+        pl.aer_phase = read_aerosols_file(user_aer, pl.os_nb)
+        pl.coef_tronca_out = 0.0       # COEF_TRONCA is an output of SOS_AEROSOLS only: untouched (0) with a user file
+    if p["aot_ref"] == 0.0 or pl.aer_phase is None:
+        pl.ta = 0.0
+        pl.phase = (np.zeros(pl.os_nb + 1),) * 4
+        pl.piz, pl.piztr, pl.a_tronc = 0.0, 0.0, 0.0
+    else:
+        pl.ta = float(p["aot_ref"]) if ta_model is None else ta_model
+        pl.phase = tuple(np.asarray(pl.aer_phase[k], dtype=np.float64) for k in ("alpha", "beta", "gamma", "zeta"))
+        if len(pl.phase[1]) != pl.os_nb + 1:
+            raise SosProcError("aer_phase arrays must have OS_NB+1 = %d entries" % (pl.os_nb + 1))
+        pl.piz, pl.piztr = float(pl.aer_phase["piz"]), float(pl.aer_phase["piztr"])
+        pl.a_tronc = float(pl.aer_phase.get("a_tronc", 0.0))
+        if pl.iprofil == 1 and p["ha"] == _D:
+            raise SosProcError("-AP.AerHS.HA must be defined")
+
+
+def _prepare_thickness(pl, defer_profiles):
+    """The molecular optical thickness (SOS_PROC.F:3331-3351), whether the pass makes the profiles, else their head start."""
+    p = pl.p
+    pl.tr = p["tr"]
+    if pl.tr == _D:
+        if p["psurf"] == _D:
+            raise SosProcError("-AP.MOT or -AP.Psurf must be defined")
+        pl.tr = rayleigh_optical_thickness(p["wa_simu"], p["psurf"])
+    pl.ha = p["ha"] if pl.ta else 1.0
+    pl.zout = float(p["zout"])
+    # head start: the level placement of the wavelength's no-gas profile (a ~1 ms serial chain on one wavefront) is queued now and
+    # runs while the host prepares gas tables, surface and context (a refused profile is reported by make_profiles below)
+    pl.nogas = None
+    pl.defer = bool(defer_profiles) and _defers_by_keywords(p, pl.absprofil != 7) and \
+        _profiles_deferrable(pl.tr, p["hr"], pl.ta, pl.ha)
+    if pl.iprofil == 1 and not pl.defer:
+        try:
+            from .solver import nogas_profile
+            pl.nogas = nogas_profile(pl.tr, p["hr"], pl.ta, pl.ha, pl.device)
+        except Exception:
+            pl.nogas = None
+
+
+def _prepare_gas(pl, shard_bins, device_gas_tables):
+    """Gas absorption: SOS_PREPA_ABSPROFILE + the weights of the CKD bins (SOS_PROC.F:3359-3416); gas = (ik, aik, xk, ro_lay)."""
+    from . import absorption as _abs
+    request = _gas_rule(pl.p)
+    pl.use_gas, pl.prep, pl.gas = request is not None, None, None
+    if pl.use_gas:
+        try:
+            pl.prep = prep = _abs.prepa_absprofile(*request)
+            ik, aik, _ = _abs.bins(prep)
+            # (a sharded band; more levels than the kernels hold: the error is make_profiles')
+            pl.defer = pl.defer and not (_dist_rank_world()[1] > 1 and shard_bins or len(prep["altabs"]) > 64 or not len(aik))
+            if pl.defer and device_gas_tables and len(prep["altabs"]) == _abs.NLEVEL:
+                xk, ro_lay = None, _abs.layer_ro(prep)                              # xk: made on the device, for the whole part
+            else:
+                xk, ro_lay = _abs.layer_tables(prep)
+            pl.gas = (ik, aik, xk, ro_lay)
+        except _abs.AbsorptionError as e:
+            raise SosProcError(str(e), ier=-1)
+    pl.mode_ckd = int(pl.p["imode_ckd_calcul"])
+    if pl.mode_ckd not in (1, 2):
+        raise SosProcError("-SOS.AbsModeCKD must be 1 or 2")
+
+
+def _prepare_surface(pl):
+    """The surface (_surface_rule) and its reflection matrices: a -SURF.File, or computed once per key (_surface_cached)."""
+    from . import surface as _surface
+    p, mu, ga, device = pl.p, pl.mu, pl.ga, pl.device
+    os_nb, os_ns, os_nm = pl.os_nb, pl.os_ns, pl.os_nm
+    pl.igli, pl.ifresnel, pl.imat, pl.land, key, job = _surface_rule(p, mu, ga, (pl.nb_lum, pl.nb_mie, os_nb, os_ns, os_nm), device)
+    lta = pl.ta == 0.0 or pl.piztr == 0.0                                            # SOS.F:541-550: IBORM = 2 without aerosols
+    pl.iborm = min(2, os_nb) if lta else os_nb
+    rsurf = None
+    if key is None:
+        if pl.imat:                                                                  # -SURF.File
+            import torch
+            rsurf = torch.as_tensor(read_surface_file(str(p["ficsurf"]).strip(), pl.n, os_nb), device=torch.device("cuda", device))
+    elif pl.igli:
+        rsurf = _surface_cached(key, lambda: _surface.glitter_matrices(mu, ga, p["wind"], p["surf_ind"], os_nb, os_ns, os_nm,
+                                                                        device=device)["rsurf"], device)
+    else:
+        try:
+            rsurf = _surface_cached(key, lambda: _surface.land_matrices(pl.land, mu, ga, job["ind"], os_nb, os_ns, os_nm,
+                                                                        device=device), device)
+        except ValueError as e:
+            raise SosProcError(str(e), ier=-1)
+    if rsurf is not None and pl.iborm < os_nb:
+        rsurf = rsurf[:pl.iborm + 1].contiguous()
+    pl.rsurf = rsurf
+
+
+def _prepare_context(pl, defer_operators):
+    """The device context of the wavelength (SOS_PREPA_OS), unbuilt where the pass builds the operators of a whole part."""
+    from .solver import SosContext
+    p = pl.p
+    isurf = int(p["isurf"])
+    alpha, beta, gamma, zeta = pl.phase
+    pl.want_trans = str(p["fictrans"]).strip() != "NO_OUTPUT"
+    pl.ctx = SosContext(pl.mu, pl.ga, pl.n0, alpha, beta, gamma, zeta, iborm_max=pl.iborm, ro=p["rho"], imat_surf=pl.imat,
+                        ifresnel=pl.ifresnel, ind_surf=p["surf_ind"] if isurf in (1, 2) or isurf >= 4 else 1.34, ron=MDF_DEFAULT,
+                        ipolar=int(p["ipolar"]), igmax=pl.igmax, rsurf=pl.rsurf, device=pl.device,
+                        build=not (defer_operators and not pl.want_trans))
+    pl.tdifmug = None
+    # (_spectrum_pass with trans: the plan's rows of the part's diffuse_transmissions_many; a scalar block that came from the host)
+    pl.trans_rows = None
+    pl.host_scal = False
+
+
+def _layer_profile(pl, true_depth):
+    """The single profile of an aerosol layer between -AP.AerLayer.Zmin and Zmax (-AP.AerProfile.Type 2, no gas): made on the
+    host and uploaded.  Returns its bins."""
+    p, zout = pl.p, pl.zout
+    h, xdel, ydel, zprof = profile_layer(pl.tr, p["hr"], pl.ta, float(p["zmin"]), float(p["zmax"]))
+    ttot_vrai = h[-1]
+    h_kw = dict(hvrai=np.array(h, dtype=np.float64)[None]) if true_depth else {}   # H before the rescale
+    h, xdel, ydel, ib = rescale_profile(h, xdel, ydel, pl.a_tronc, pl.piz, pl.piztr, pl.os_nb)   # SOS.F:523-550
+    bins = pl.ctx.upload_bins(h[None], xdel[None], ydel[None], iborm=np.array([min(ib, pl.iborm)], dtype=np.int32),
+                              zout=zout, zprof=zprof[None], **h_kw)
+    if zout == -1.0:
+        tauout = h[0]                                                        # SOS.F:567-568
+    else:
+        j = int(bins["jout"][0])
+        zzv = float(bins["zz"][0])
+        tauout = (1 - zzv) * h[j - 1] + zzv * h[j]                           # SOS.F:572-581
+    bins["scal"] = np.array([[0.0, h[-1], ttot_vrai, tauout]])
+    return bins
+
+
+def _band_profiles(pl, shard_bins, true_kw):
+    """The profiles of the CKD bins of a gas band that this call makes itself.  Several GPUs (torch.distributed initialised, one
+    process per GPU): the bins of the band are dealt to the ranks by cost (dist.balanced_shards); solve_band's one all-reduce
+    joins them and every rank returns the same 23 outputs.  A rank may hold no bin at all.  (-SOS.AbsModeCKD 2 has a single
+    bin: not sharded.)"""
+    from . import absorption as _abs
+    ctx = pl.ctx
+    ik, aik, xk, ro_lay = pl.gas
+    rank, world = _dist_rank_world() if shard_bins else (0, 1)
+    pl.band_sharded = world > 1 and pl.mode_ckd != 2
+    tabs_last = None
+    if pl.band_sharded:
+        from . import dist as _dist
+        tabs_last = ctx.absorption_profiles(ik[-1:], xk, ro_lay)             # TAUABS of the band's last bin (Flux file)
+        mine = _dist.balanced_shards(_abs.bin_costs(ik, xk, ro_lay, pl.tr + pl.ta), world)[rank]
+        ik, aik = ik[mine], aik[mine]
+    tabs = ctx.absorption_profiles(ik, xk, ro_lay) if len(aik) else None     # SOS_ABSPROFILE of every bin of this rank
+    if pl.mode_ckd == 2:
+        # one profile from the band-mean transmission of every level (SOS_PROC.F:3609-3676)
+        tb = tabs.cpu().numpy()
+        trs = np.zeros(tb.shape[1])
+        for b in range(tb.shape[0]):
+            trs = trs + aik[b] * np.exp(-tb[b])
+        tabs = np.maximum(-np.log(trs), 0.0)[None]
+        aik = np.ones(1)
+    try:
+        if len(aik):
+            pl.bins = ctx.make_profiles(len(aik), pl.tr, pl.p["hr"], pl.ta, pl.ha, pl.prep["altabs"], tabs, a_tronc=pl.a_tronc,
+                                        piz=pl.piz, piztr=pl.piztr, zout=pl.zout, absprofil=pl.absprofil, nogas=pl.nogas,
+                                        **true_kw)
+        else:
+            pl.bins = dict(nb=0, scal=None)
+    except Exception as e:
+        raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
+    pl.aik = aik
+    pl.tabs_flux = tabs_last if pl.band_sharded else tabs
+
+
+def _prepare_profiles(pl, shard_bins, true_depth):
+    """The CKD bin loop (SOS_PROC.F:3459-3594): profiles of every bin on the device, or profile_request, what
+    solver.make_profiles_spectrum needs of a deferred wavelength.  band_sharded: every rank holds a slice of the band and the
+    partials are all-reduced; tabs_flux: TAUABS of the band's last bin (Flux file), host array or [.][nlev] device tensor."""
+    import torch
+    p, ctx = pl.p, pl.ctx
+    pl.band_sharded, pl.tabs_flux, pl.profile_request = False, None, None
+    common = dict(tr=pl.tr, hr=p["hr"], ta=pl.ta, ha=pl.ha, a_tronc=pl.a_tronc, piz=pl.piz, piztr=pl.piztr, zout=pl.zout,
+                  smax=ctx.smax)
+    true_kw = dict(true_depth=True) if true_depth else {}      # (split=False: the calls as they were)
+    if pl.defer and not pl.use_gas:
+        pl.profile_request = dict(common, ik=None, absprofil=7)
+        pl.bins, pl.aik = None, np.ones(1)
+    elif pl.defer:
+        ik, pl.aik, xk, ro_lay = pl.gas
+        pl.profile_request = dict(common, ik=ik, xk=xk, ro=ro_lay, altabs=pl.prep["altabs"], absprofil=pl.absprofil)
+        if xk is None:
+            pl.profile_request["prep"] = pl.prep
+        pl.bins = None
+    elif not pl.use_gas and pl.iprofil == 1:
+        # the single no-gas profile of the wavelength: SOS_PROFILE, the PROFIL-file round trip, the rescale, IBORM and the
+        # output level all inside sosgpu_profile (the Python restatement profile_nogas costs 2-3 ms and stays as the checker
+        # of tests/test_profile.py)
+        try:
+            pl.bins = ctx.make_profiles(1, pl.tr, p["hr"], pl.ta, pl.ha, None, None, a_tronc=pl.a_tronc, piz=pl.piz,
+                                        piztr=pl.piztr, zout=pl.zout, absprofil=7, nogas=pl.nogas, **true_kw)
+        except Exception as e:
+            raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
+        pl.aik = np.ones(1)
+    elif not pl.use_gas:
+        pl.bins, pl.aik = _layer_profile(pl, true_depth), np.ones(1)
+    else:
+        _band_profiles(pl, shard_bins, true_kw)
+    bins = pl.bins
+    if pl.want_trans and bins is not None and bins["nb"]:                            # SOS.F:600-635
+        tdifmus_b, pl.tdifmug = ctx.diffuse_transmissions(bins)
+        sc = bins["scal"] if hasattr(bins["scal"], "clone") else torch.from_numpy(np.asarray(bins["scal"])).to(ctx.device)
+        sc = sc.clone()
+        sc[:, 0] = tdifmus_b
+        bins["scal"] = sc
+
+
 def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False,
              device_gas_tables=False, defer_operators=False, true_depth=False):
     """Everything of one SOS_PROC call up to the CKD bin loop (SOS_PROC.F:1310-3458): parameter checks, SOS_ANGLES,
     SOS_AEROSOLS, SOS_SURFACE, SOS_PREPA_ABSPROFILE, SOS_PREPA_OS, and the profiles of every bin of the band on the device
-    (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Returns a _Plan whose `ctx` the caller closes.
+    (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Every stage fills its fields of the _Plan that comes back, whose `ctx`
+    the caller closes; what one decides from the keywords alone stands in the rule functions the prefetch's predictors read too.
     shard_bins: with torch.distributed initialised, keep only this rank's slice of the band's bins (sos_proc); False: the
     whole band stays on this rank (sos_spectrum distributes wavelengths, not bins).
     aer_stream: HIP stream (torch.cuda.Stream) for the aerosol step, whose device calls are host-synchronous -- sos_spectrum keeps
@@ -1073,297 +1401,33 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     before the truncation rescale (SosContext.make_profiles(true_depth=True); the aerosol-layer profile uploads its own).
     defer_operators (_spectrum_pass only): the context comes back unbuilt (SosContext(build=False)) and the pass fills the
     operator tables of a whole part in one solver.build_operators call -- unless this function uses the operators itself, which
-    only a -SOS.Trans call does (diffuse_transmissions below)."""
+    only a -SOS.Trans call does (diffuse_transmissions in _prepare_profiles)."""
     _seg(None)
     missing = [k for k in SOS_PROC_KWARGS if k not in kw]
     if missing:
         raise TypeError("sos_proc() missing keyword arguments: %s" % ", ".join(missing))
-    p = dict(kw)
-    validate_parameters(p)
-    from .solver import SosContext
-    from . import surface as _surface
-    from . import absorption as _abs
-    import torch
-
-    # --- parameter checks the hot path depends on (SOS_PROC.F:1310-2700 has many more; same messages' intent)
-    if p["wa_simu"] == _D:
-        raise SosProcError("-SOS_Main.Wa must be defined")
-    if p["tetas"] == _D or not (0.0 <= p["tetas"] < 90.0):
-        raise SosProcError("-ANG.Thetas must be defined in [0,90[")
-    iprofil = int(p["iprofil"])
-    if iprofil not in (1, 2):                                                      # SOS_PROC.F:2324-2325
-        raise SosProcError("-AP.AerProfile.Type must be 1 or 2")
-    if iprofil == 2 and (p["zmin"] == _D or p["zmax"] == _D):                      # :2335-2338
-        raise SosProcError("-AP.AerLayer.Zmin and -AP.AerLayer.Zmax must be defined for -AP.AerProfile.Type 2")
-    absprofil = int(p["absprofil"])
-    if absprofil == _I or not 0 <= absprofil <= 7:
-        raise SosProcError("-AP.AbsProfile.Type must be defined in 0..7")
-    if p["isurf"] not in (0, 1, 2, 3, 4, 5, 6, 7):
-        raise SosProcError("-SURF.Type must be in 0..7")
-    if p["rho"] == _D:
-        raise SosProcError("-SURF.Alb must be defined")
-    if p["aot_ref"] == _D:
-        raise SosProcError("-AER.AOTref must be defined")
-    user_aer = str(p["ficuser_aer"]).strip()
-    use_model = p["aot_ref"] != 0.0 and aer_phase is None and user_aer == "NO_USER_AEROSOLS"
-    if use_model and p["imod_aer"] not in (0, 1, 2, 3, 4, 5):
-        raise SosProcError("-AER.Model must be in 0..5")
-    if p["hr"] == _D:
-        raise SosProcError("-AP.HR must be defined")
-    itrphi = p["itrphi"]
-    if itrphi == 1 and p["phios"] == _D:
-        raise SosProcError("-SOS.View.Phi must be defined for -SOS.View 1")
-    if itrphi == 2 and p["pas_phi"] == _I:
-        raise SosProcError("-SOS.View.Dphi must be defined for -SOS.View 2")
-    igmax = CTE_DEFAULT_IGMAX if p["igmax"] == _I else int(p["igmax"])
-
-    _seg('checks')
-    # --- SOS_ANGLES (SOS_PROC.F:2738)
-    nb_lum = CTE_DEFAULT_NBMU_LUM if p["nbmu_gauss_lum"] == _I else int(p["nbmu_gauss_lum"])
-    nb_mie = CTE_DEFAULT_NBMU_MIE if p["nbmu_gauss_mie"] == _I else int(p["nbmu_gauss_mie"])
-    os_nb = CTE_DEFAULT_OS_NB if p["nbmu_gauss_mie"] == _I else 2 * nb_mie          # SOS_ANGLES.F:303-312
-    if p["nbmu_gauss_lum"] == _I:
-        os_ns, os_nm = CTE_DEFAULT_OS_NS, CTE_DEFAULT_OS_NM
-    else:
-        os_ns = 2 * nb_lum
-        os_nm = os_nb + os_ns                                                        # SOS_ANGLES.F:325-329
-    mu, ga, n0, ind_ang = angles(nb_lum, p["tetas"], p["ficangles_user_lum"])
-    n = len(mu)
-
-    _seg('angles')
-    # --- aerosols: none, a user Aerosols.txt (-AER.UserFile, SOS_PROC.F:2883-2934: SOS_AEROSOLS is not run, the file
-    # is read by SOS_PREPA_OS.F:666-700), or a given expansion (stands for SOS_AEROSOLS -> Aerosols.txt)
-    coef_tronca_out = None
-    ta_model = None
-    if use_model:
-        # SOS_AEROSOLS at the reference wavelength, and again at the simulation wavelength when they differ: the optical
-        # thickness scales with the extinction cross sections (SOS_PROC.F:2883-3060)
-        from . import aerosols as _aer
-        if p["waref_aot"] == _D:
-            raise SosProcError("-AER.Waref must be defined")
-        import contextlib
-        try:
-            with (torch.cuda.stream(aer_stream) if aer_stream is not None else contextlib.nullcontext()):
-                aer_phase = _aerosols_at_waref(p, nb_mie, os_nb, device)
-                ta_model = float(p["aot_ref"])
-                if p["wa_simu"] != p["waref_aot"]:
-                    k_ref = aer_phase["kmat1"]
-                    aer_phase = (aer_at_wa if aer_at_wa is not None else
-                                 _aer.aerosols(p, p["wa_simu"], 0.1, nb_mie, os_nb, at_waref=False, device=device))
-                    ta_model = (aer_phase["kmat1"] / k_ref) * p["aot_ref"]
-        except _aer.AerosolError as e:
-            raise SosProcError(str(e), ier=-1)
-        coef_tronca_out = aer_phase["coef_tronca"]
-    elif p["aot_ref"] != 0.0 and aer_phase is None:
-        if not os.path.exists(user_aer):
-            raise SosProcError("-AER.UserFile %s not found" % user_aer)
-        aer_phase = read_aerosols_file(user_aer, os_nb)
-        coef_tronca_out = 0.0          # COEF_TRONCA is an output of SOS_AEROSOLS only: untouched (0) with a user file
-    if p["aot_ref"] == 0.0 or aer_phase is None:
-        ta = 0.0
-        alpha = beta = gamma = zeta = np.zeros(os_nb + 1)
-        piz, piztr, a_tronc = 0.0, 0.0, 0.0
-    else:
-        ta = float(p["aot_ref"]) if ta_model is None else ta_model
-        alpha, beta, gamma, zeta = (np.asarray(aer_phase[k], dtype=np.float64) for k in ("alpha", "beta", "gamma", "zeta"))
-        if len(beta) != os_nb + 1:
-            raise SosProcError("aer_phase arrays must have OS_NB+1 = %d entries" % (os_nb + 1))
-        piz, piztr, a_tronc = float(aer_phase["piz"]), float(aer_phase["piztr"]), float(aer_phase.get("a_tronc", 0.0))
-        if iprofil == 1 and p["ha"] == _D:
-            raise SosProcError("-AP.AerHS.HA must be defined")
-
-    _seg('aerosols')
-    # --- molecular optical thickness (SOS_PROC.F:3331-3351)
-    tr = p["tr"]
-    if tr == _D:
-        if p["psurf"] == _D:
-            raise SosProcError("-AP.MOT or -AP.Psurf must be defined")
-        tr = rayleigh_optical_thickness(p["wa_simu"], p["psurf"])
-    ha = p["ha"] if ta else 1.0
-    zout = float(p["zout"])
-    # head start: the level placement of the wavelength's no-gas profile (a ~1 ms serial chain on one wavefront) is queued now and
-    # runs while the host prepares gas tables, surface and context (a refused profile is reported by make_profiles below)
-    nogas = None
-    defer = bool(defer_profiles) and iprofil == 1 and str(p["fictrans"]).strip() == "NO_OUTPUT" and \
-        (absprofil == 7 or p["imode_ckd_calcul"] == 1) and _profiles_deferrable(tr, p["hr"], ta, ha)
-    if iprofil == 1 and not defer:
-        try:
-            from .solver import nogas_profile
-            nogas = nogas_profile(tr, p["hr"], ta, ha, device)
-        except Exception:
-            nogas = None
-
-    # --- gas absorption: SOS_PREPA_ABSPROFILE + the weights of the CKD bins (SOS_PROC.F:3359-3416)
-    use_gas = absprofil != 7
-    prep = None
-    if iprofil == 2 and use_gas:                                                   # SOS_PROC.F:2352
-        raise SosProcError("-AP.AerProfile.Type 2 requires -AP.AbsProfile.Type 7 (no gas absorption)")
-    if use_gas:
-        if p["nustep"] == _I:
-            raise SosProcError("-AP.SpectralResol must be defined with -AP.AbsProfile.Type != 7")
-        if absprofil == 0 and str(p["ficabsprofil"]).strip() == "NO_USER_ABS_PROFILE_FILE":
-            raise SosProcError("-AP.AbsProfile.UserFile must be defined with -AP.AbsProfile.Type 0")
-        try:
-            prep = _abs.prepa_absprofile(p["wa_simu"], float(p["nustep"]), p["psurf"], p["h2o"], p["o3"], p["co2"], p["ch4"],
-                                         absprofil, str(p["ficabsprofil"]).strip())
-            ik, aik, _ = _abs.bins(prep)
-            # (a sharded band; more levels than the kernels hold: the error is make_profiles')
-            defer = defer and not (_dist_rank_world()[1] > 1 and shard_bins or len(prep["altabs"]) > 64 or not len(aik))
-            if defer and device_gas_tables and len(prep["altabs"]) == _abs.NLEVEL:
-                xk, ro_lay = None, _abs.layer_ro(prep)                              # xk: made on the device, for the whole part
-            else:
-                xk, ro_lay = _abs.layer_tables(prep)
-        except _abs.AbsorptionError as e:
-            raise SosProcError(str(e), ier=-1)
-    mode_ckd = int(p["imode_ckd_calcul"])
-    if mode_ckd not in (1, 2):
-        raise SosProcError("-SOS.AbsModeCKD must be 1 or 2")
-
-    _seg('gas tables')
-    # --- surface (SOS_PREPA_OS.F:479-497)
-    isurf = int(p["isurf"])
-    igli, ifresnel, imat = int(isurf == 1), int(isurf == 2), int(isurf == 1 or isurf >= 3)
-    rsurf = None
-    land = None
-    if (isurf in (1, 2) or isurf >= 4) and p["surf_ind"] == _D:
-        raise SosProcError("-SURF.Ind must be defined for sea surfaces and BPDF models")
-    if isurf >= 3:
-        if _D in (p["k0_roujean"], p["k1_roujean"], p["k2_roujean"]):
-            raise SosProcError("-SURF.Roujean.K0/K1/K2 must be defined for -SURF.Type >= 3")
-        if isurf == 6:                                    # the reference's own SOS_PROC refuses it with this message
-            raise SosProcError("The Nadal's BPDF model is not supported ==> Select another surface model")
-        if isurf == 7 and p["coef_c_maignan"] == _D:
-            raise SosProcError("-SURF.Maignan.C must be defined for -SURF.Type 7")
-        land = _surface.land_model(isurf, p["k0_roujean"], p["k1_roujean"], p["k2_roujean"], p["alpha_nadal"], p["beta_nadal"],
-                                   p["coef_c_maignan"])
-    lta = ta == 0.0 or piztr == 0.0                                                  # SOS.F:541-550: IBORM = 2 without aerosols
-    iborm = min(2, os_nb) if lta else os_nb
-    user_surf = str(p["ficsurf"]).strip()
-    if imat and user_surf != "DEFAULT":
-        # -SURF.File: the user's reflection matrices replace the surface computation (SOS_PROC.F:3186-3189,
-        # SOS_PREPA_OS.F:605-658); the direct-beam terms of SOS_TRPHI still follow -SURF.Type
-        if not os.path.exists(user_surf):
-            raise SosProcError("-SURF.File %s does not exist (SOS_PREPA_OS ERROR_1020)" % user_surf, ier=-1)
-        rsurf = torch.as_tensor(read_surface_file(user_surf, n, os_nb), device=torch.device("cuda", device))
-    elif isurf == 1:
-        if p["wind"] == _D:
-            raise SosProcError("-SURF.Glitter.Wind must be defined")
-        key = ("glitter", mu.tobytes(), ga.tobytes(), float(p["wind"]), float(p["surf_ind"]), os_nb, os_ns, os_nm, device)
-        rsurf = _surface_cached(key, lambda: _surface.glitter_matrices(mu, ga, p["wind"], p["surf_ind"], os_nb, os_ns, os_nm,
-                                                                        device=device)["rsurf"], device)
-    elif land is not None:
-        ind_l = p["surf_ind"] if isurf >= 4 else 1.0
-        key = ("land", isurf, float(land.k0), float(land.k1), float(land.k2), float(land.alpha), float(land.beta),
-               float(land.coef_c), mu.tobytes(), ga.tobytes(), float(ind_l), os_nb, os_ns, os_nm, device)
-        try:
-            rsurf = _surface_cached(key, lambda: _surface.land_matrices(land, mu, ga, ind_l, os_nb, os_ns, os_nm, device=device),
-                                    device)
-        except ValueError as e:
-            raise SosProcError(str(e), ier=-1)
-    if rsurf is not None and iborm < os_nb:
-        rsurf = rsurf[:iborm + 1].contiguous()
-
-    _seg('surface')
-    want_trans = str(p["fictrans"]).strip() != "NO_OUTPUT"
-    ctx = SosContext(mu, ga, n0, alpha, beta, gamma, zeta, iborm_max=iborm, ro=p["rho"], imat_surf=imat,
-                     ifresnel=ifresnel, ind_surf=p["surf_ind"] if isurf in (1, 2) or isurf >= 4 else 1.34, ron=MDF_DEFAULT,
-                     ipolar=int(p["ipolar"]), igmax=igmax, rsurf=rsurf, device=device,
-                     build=not (defer_operators and not want_trans))
-    _seg('context')
     pl = _Plan()
-    pl.p, pl.ctx, pl.device = p, ctx, device
-    pl.n, pl.mu, pl.ga, pl.n0, pl.ind_ang = n, mu, ga, n0, ind_ang
-    pl.nb_lum, pl.nb_mie, pl.os_nb, pl.os_ns, pl.os_nm = nb_lum, nb_mie, os_nb, os_ns, os_nm
-    pl.use_model, pl.aer_phase, pl.coef_tronca_out, pl.a_tronc = use_model, aer_phase, coef_tronca_out, a_tronc
-    pl.tr, pl.ta, pl.ha, pl.use_gas, pl.prep = tr, ta, ha, use_gas, prep
-    pl.itrphi, pl.igli, pl.land = itrphi, igli, land
-    pl.tdifmug = None
-    pl.want_trans = want_trans
-    # (_spectrum_pass with trans: the plan's rows of the part's diffuse_transmissions_many; a scalar block that came from the host)
-    pl.trans_rows = None
-    pl.host_scal = False
+    pl.p, pl.device, pl.aer_phase = dict(kw), device, aer_phase
+    validate_parameters(pl.p)
+    _prepare_checks(pl)
+    _seg('checks')
+    _prepare_angles(pl)
+    _seg('angles')
+    _prepare_aerosols(pl, aer_stream, aer_at_wa)
+    _seg('aerosols')
+    _prepare_thickness(pl, defer_profiles)
+    _prepare_gas(pl, shard_bins, device_gas_tables)
+    _seg('gas tables')
+    _prepare_surface(pl)
+    _seg('surface')
+    _prepare_context(pl, defer_operators)
+    _seg('context')
     try:
-        # --- the CKD bin loop (SOS_PROC.F:3459-3594): profiles of every bin on the device
-        band_sharded = False                          # True: every rank holds a slice of the band and the partials are all-reduced
-        tabs_flux = None                              # TAUABS of the band's last bin (Flux file): host array or [.][nlev] device tensor
-        request = None                                # deferred: what solver.make_profiles_spectrum needs of this wavelength
-        common = dict(tr=tr, hr=p["hr"], ta=ta, ha=ha, a_tronc=a_tronc, piz=piz, piztr=piztr, zout=zout, smax=ctx.smax)
-        true_kw = dict(true_depth=True) if true_depth else {}      # (split=False: the calls as they were)
-        if defer and not use_gas:
-            request = dict(common, ik=None, absprofil=7)
-            bins, aik = None, np.ones(1)
-        elif defer:
-            request = dict(common, ik=ik, xk=xk, ro=ro_lay, altabs=prep["altabs"], absprofil=absprofil)
-            if xk is None:
-                request["prep"] = prep
-            bins = None
-        elif not use_gas and iprofil == 1:
-            # the single no-gas profile of the wavelength: SOS_PROFILE, the PROFIL-file round trip, the rescale, IBORM and the
-            # output level all inside sosgpu_profile (the Python restatement profile_nogas costs 2-3 ms and stays as the checker
-            # of tests/test_profile.py)
-            try:
-                bins = ctx.make_profiles(1, tr, p["hr"], ta, ha, None, None, a_tronc=a_tronc, piz=piz, piztr=piztr, zout=zout,
-                                         absprofil=7, nogas=nogas, **true_kw)
-            except Exception as e:
-                raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
-            aik = np.ones(1)
-        elif not use_gas:
-            h, xdel, ydel, zprof = profile_layer(tr, p["hr"], ta, float(p["zmin"]), float(p["zmax"]))
-            ttot_vrai = h[-1]
-            h_kw = dict(hvrai=np.array(h, dtype=np.float64)[None]) if true_depth else {}   # H before the rescale
-            h, xdel, ydel, ib = rescale_profile(h, xdel, ydel, a_tronc, piz, piztr, os_nb)   # SOS.F:523-550
-            bins = ctx.upload_bins(h[None], xdel[None], ydel[None], iborm=np.array([min(ib, iborm)], dtype=np.int32),
-                                   zout=zout, zprof=zprof[None], **h_kw)
-            if zout == -1.0:
-                tauout = h[0]                                                        # SOS.F:567-568
-            else:
-                j = int(bins["jout"][0])
-                zzv = float(bins["zz"][0])
-                tauout = (1 - zzv) * h[j - 1] + zzv * h[j]                           # SOS.F:572-581
-            bins["scal"] = np.array([[0.0, h[-1], ttot_vrai, tauout]])
-            aik = np.ones(1)
-        else:
-            # Several GPUs (torch.distributed initialised, one process per GPU): the bins of the band are dealt to the ranks
-            # by cost (dist.balanced_shards); solve_band's one all-reduce joins them and every rank returns the same 23
-            # outputs.  A rank may hold no bin at all.  (-SOS.AbsModeCKD 2 has a single bin: not sharded.)
-            rank, world = _dist_rank_world() if shard_bins else (0, 1)
-            band_sharded = world > 1 and mode_ckd != 2
-            tabs_last = None
-            if band_sharded:
-                from . import dist as _dist
-                tabs_last = ctx.absorption_profiles(ik[-1:], xk, ro_lay)             # TAUABS of the band's last bin (Flux file)
-                mine = _dist.balanced_shards(_abs.bin_costs(ik, xk, ro_lay, tr + ta), world)[rank]
-                ik, aik = ik[mine], aik[mine]
-            tabs = ctx.absorption_profiles(ik, xk, ro_lay) if len(aik) else None     # SOS_ABSPROFILE of every bin of this rank
-            if mode_ckd == 2:
-                # one profile from the band-mean transmission of every level (SOS_PROC.F:3609-3676)
-                tb = tabs.cpu().numpy()
-                trs = np.zeros(tb.shape[1])
-                for b in range(tb.shape[0]):
-                    trs = trs + aik[b] * np.exp(-tb[b])
-                tabs = np.maximum(-np.log(trs), 0.0)[None]
-                aik = np.ones(1)
-            try:
-                if len(aik):
-                    bins = ctx.make_profiles(len(aik), tr, p["hr"], ta, ha, prep["altabs"], tabs, a_tronc=a_tronc, piz=piz,
-                                             piztr=piztr, zout=zout, absprofil=absprofil, nogas=nogas, **true_kw)
-                else:
-                    bins = dict(nb=0, scal=None)
-            except Exception as e:
-                raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
-            tabs_flux = tabs_last if band_sharded else tabs
-        if pl.want_trans and bins is not None and bins["nb"]:                        # SOS.F:600-635
-            tdifmus_b, pl.tdifmug = ctx.diffuse_transmissions(bins)
-            sc = bins["scal"] if hasattr(bins["scal"], "clone") else torch.from_numpy(np.asarray(bins["scal"])).to(ctx.device)
-            sc = sc.clone()
-            sc[:, 0] = tdifmus_b
-            bins["scal"] = sc
+        _prepare_profiles(pl, shard_bins, true_depth)
     except BaseException:
-        ctx.close()
+        pl.ctx.close()
         raise
     _seg('profiles')
-    pl.bins, pl.aik, pl.band_sharded, pl.tabs_flux = bins, aik, band_sharded, tabs_flux
-    pl.profile_request = request
     return pl
 
 
@@ -1709,9 +1773,9 @@ def _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_gas_
     """The shared host work of a spectrum chunk `idx`, queued ahead of its per-wavelength preparation: the size-distribution
     integrals (aerosols.prefetch_size_integrals), the gas tables interpolated to the layers in one pass, and SOS_AEROSOLS at the
     simulation wavelength of each call.  Returns {index: aerosols at the simulation wavelength} for _prepare(aer_at_wa=...).
-    device_gas_tables: the calls whose profiles _prepare can defer (as far as the keywords alone tell: -AP.AerProfile.Type 1,
-    no -SOS.Trans, -SOS.AbsModeCKD 1) get their layer tables from the device, so the one-pass host interpolation leaves them
-    out; a call _prepare then does not defer after all interpolates its own tables there.
+    device_gas_tables: the calls whose profiles _prepare can defer as far as the keywords alone tell (_defers_by_keywords) get
+    their layer tables from the device, so the one-pass host interpolation leaves them out; a call _prepare then does not defer
+    after all interpolates its own tables there.
     batch_surfaces: the sea and land surface matrices of the chunk's calls are queued first, one sosgpu_surface_batch per angle
     set (_prefetch_surfaces); they run on the device while the host does the rest of this function."""
     import torch
@@ -2153,8 +2217,7 @@ def _channel_results(kw, chan, mine, acc, ang_rows, call_scal, alts, nflux, dev,
     from . import solver
     p = dict(kw)
     validate_parameters(p)
-    nb_lum = CTE_DEFAULT_NBMU_LUM if p["nbmu_gauss_lum"] == _I else int(p["nbmu_gauss_lum"])
-    mu, _, _, ind_ang = angles(nb_lum, p["tetas"], p["ficangles_user_lum"])
+    mu, _, _, ind_ang = angles(_angle_counts(p)[0], p["tetas"], p["ficangles_user_lum"])
     n = len(mu)
     w = 2 * n + 1
     _, rows, phi_fin = _trphi_azimuths(p["itrphi"], p["phios"], p["pas_phi"])

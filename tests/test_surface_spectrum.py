@@ -140,6 +140,68 @@ def test_keys_of_the_prefetch_are_the_keys_of_prepare(gpu_pkg, sequential, monke
 
 
 @pytest.mark.gpu
+def test_gas_requests_of_the_prefetch_are_the_calls_of_prepare(gpu_pkg, tmp_path, monkeypatch):
+    """Five gas calls in one chunk: the argument tuples _prepare hands to prepa_absprofile are the requests the prefetch formed."""
+    rs, A = gpu_pkg.run_sos, gpu_pkg.absorption
+    monkeypatch.setenv("SOS_ABS_ROOT", spectrum_cases.GOLD)
+    monkeypatch.setenv("SOS_SPECTRUM_MIN_PART", "2")
+    kw = spectrum_cases.build(rs, tmp_path, names=["ckd_o2a_5bins"])[0][0]
+    calls = [dict(kw, psurf=ps) for ps in (1013.0, 1005.0, 995.0, 985.0, 975.0)]
+    asked, formed, p0, f0 = [], [], A.prepa_absprofile, A.prefetch_gas_tables
+
+    def prepa(*a, **k):
+        if not k:                                        # (the prefetch itself calls it with root=...)
+            asked.append(a)
+        return p0(*a, **k)
+
+    def prefetch(requests, device_tables=()):
+        formed.extend(requests)
+        return f0(requests, device_tables=device_tables)
+
+    monkeypatch.setattr(A, "prepa_absprofile", prepa)
+    monkeypatch.setattr(A, "prefetch_gas_tables", prefetch)
+    out = rs.sos_spectrum(calls, chunk=5, parts=2)
+    assert len(out) == 5 and len(formed) == 5 and len(set(formed)) == 5
+    assert list(map(repr, asked)) == list(map(repr, formed))
+
+
+@pytest.mark.gpu
+def test_aerosol_runs_of_the_prefetch_leave_none_to_prepare(gpu_pkg, monkeypatch):
+    """Five model-aerosol calls away from -AER.Waref in one chunk: the prefetch forms the simulation-wavelength run of every one
+    (aerosols_many), so _prepare makes none of its own."""
+    from test_mie_batch import _kw, _wmo_user
+    rs, A = gpu_pkg.run_sos, gpu_pkg.aerosols
+    monkeypatch.setenv("SOS_ABS_ROOT", spectrum_cases.GOLD)
+    monkeypatch.setenv("SOS_SPECTRUM_MIN_PART", "2")
+    calls = [_kw(rs, _wmo_user(wa, 2)) for wa in (0.49, 0.56, 0.67, 0.78, 0.865)]
+    n = dict(inside=False, own=0, many=0, made=0)
+    a0, m0, p0 = A.aerosols, A.aerosols_many, rs._prepare
+
+    def aerosols(p, wa, ta, *a, at_waref=False, **k):
+        n["own"] += n["inside"] and not at_waref
+        return a0(p, wa, ta, *a, at_waref=at_waref, **k)
+
+    def many(jobs, *a, **k):
+        res = m0(jobs, *a, **k)
+        n["many"] += len(jobs)
+        n["made"] += sum(r is not None for r in res)
+        return res
+
+    def prepare(*a, **k):
+        n["inside"] = True
+        try:
+            return p0(*a, **k)
+        finally:
+            n["inside"] = False
+
+    monkeypatch.setattr(A, "aerosols", aerosols)
+    monkeypatch.setattr(A, "aerosols_many", many)
+    monkeypatch.setattr(rs, "_prepare", prepare)
+    out = rs.sos_spectrum(calls, chunk=5, parts=2)
+    assert len(out) == 5 and (n["many"], n["made"], n["own"]) == (5, 5, 0), n
+
+
+@pytest.mark.gpu
 def test_flagged_call_raises_what_sos_proc_raises(gpu_pkg, sequential, monkeypatch):
     rs = gpu_pkg.run_sos
     calls, seq = sequential

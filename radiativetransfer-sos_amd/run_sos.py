@@ -1592,10 +1592,7 @@ def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False, split=False):
                 flux_dev = solver.level_flux_many([(pl.ctx, rec[k]) for k in range(len(rec))])
             flat, shapes = _trphi_launch_many([(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]),
                                                 float(fin["tauout"][k])) for k in range(len(rec))])
-            flat, outs, pos = flat.cpu().numpy(), [], 0
-            for shp in shapes:
-                outs.append(flat[pos:pos + int(np.prod(shp))].reshape(shp))
-                pos += outs[-1].size
+            outs = solver._flat_blocks(flat.cpu().numpy(), shapes)
         tuples = [_finish(pl, outs[k], rec[k], fin, k) for k in range(len(rec))]
         if not fluxes:
             return tuples
@@ -1823,11 +1820,292 @@ def _first_failed_index(index, device):
     return int(t.item())
 
 
+class _Chunk:
+    """What the stages of one chunk of _spectrum_pass hand to each other: `plans` (every plan prepared, closed by the driver),
+    `solved` [(plans, rec [K][nw][S][3][W], scal [K][nw][10+N], table)] device tensors per launch, `salb_bands` [(plans, their
+    band spherical albedos [len(plans)], a device tensor)], `ckd_checks` [(status tensor of a part's device gas tables, the
+    plans it speaks of)] and `where`, the wavelength being worked on (named by a failure)."""
+
+
+def _part_bounds(n, parts, min_part):
+    """The (s0, s1) bounds of the parts a chunk of n wavelengths goes to the solver in: at most `parts` equal steps, as long
+    as n holds min_part wavelengths for each."""
+    nsub = max(1, min(int(parts), n // max(1, int(min_part))))
+    step = max(1, -(-n // nsub))
+    return [(s0, min(s0 + step, n)) for s0 in range(0, n, step)]
+
+
+def _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, aer_st, aer_wa, alts, true_kw, batch_profiles,
+                   device_tables, batch_operators, debug):
+    """The calls idx[s0:s1] of a chunk prepared on the side streams (_prepare; output_levels of the calls that have their
+    bins).  Returns the plans of the part."""
+    import torch
+    part = []
+    for k, i in enumerate(idx[s0:s1], s0):
+        ch.where = i
+        with torch.cuda.stream(side[k % len(side)]):
+            pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
+                          aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles, device_gas_tables=device_tables,
+                          defer_operators=batch_operators, **true_kw)
+            pl.writes_files = True
+            pl.index = i
+            ch.plans.append(pl)
+            if alts is not None and pl.bins is not None:
+                pl.levels = pl.ctx.output_levels(pl.bins, alts)
+        if debug:
+            torch.cuda.synchronize(torch.device("cuda", device))
+            print("[%s] prepared" % fn, i, flush=True)
+        part.append(pl)
+    return part
+
+
+def _stage_profiles(ch, part, alts, level_keys, true_kw, dev):
+    """The profiles of the part's qualifying wavelengths: three launches for all their bins (the operators the side streams
+    are still building are not needed for them), one more for the output slots."""
+    from . import solver
+    deferred = [pl for pl in part if pl.bins is None]
+    if not deferred:
+        return
+    ch.where = deferred[0].index
+    info = {}
+    try:
+        made = solver.make_profiles_spectrum([pl.profile_request for pl in deferred], dev, part=info, **true_kw)
+    except Exception as e:
+        if info.get("bad") is not None:
+            ch.where = deferred[info["bad"]].index
+        raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
+    if info.get("ckd_status") is not None:
+        ch.ckd_checks.append((info["ckd_status"], [deferred[g] for g in info["ckd_index"]]))
+    lv = None if alts is None else deferred[0].ctx.output_levels(info["bins"], alts)
+    for g, pl in enumerate(deferred):
+        # (views of the part's blocks: the plans keep them alive until the chunk's streams are synchronised)
+        pl.bins, pl.tabs_flux, pl.profile_part = made[g], info["tabs"][g], info
+        if lv is not None:
+            b0, b1 = int(info["seg"][g]), int(info["seg"][g + 1])
+            pl.levels = dict(nz=lv["nz"], **{k: lv[k][:, b0:b1] for k in level_keys})
+
+
+def _stage_operators(ch, part):
+    """The operators of the part's unbuilt contexts, grouped and single alike (after the driver's wait for the side streams:
+    the surface matrices come from them)."""
+    from . import solver
+    unbuilt = [pl for pl in part if not pl.ctx._built]
+    if unbuilt:
+        ch.where = unbuilt[0].index
+        solver.build_operators([pl.ctx for pl in unbuilt])
+
+
+def _stage_transmissions(ch, part, salb, dev):
+    """trans: the diffuse transmissions of every bin of the part: one call per direction count, whatever the calls are (it
+    reads the contexts' order-0 operators, queued by _stage_operators or by the side streams waited for); salb: next to it
+    the spherical albedo of the same bins."""
+    import torch
+    from . import solver
+    by_n = collections.OrderedDict()
+    for pl in part:
+        if pl.bins["nb"]:
+            by_n.setdefault(pl.n, []).append(pl)
+    for gp in by_n.values():
+        ch.where = gp[0].index
+        tbins, tcob = solver.concat_profiles([pl.bins for pl in gp])
+        tdifmus, tdifmug = solver.diffuse_transmissions_many([pl.ctx for pl in gp], tbins, tcob)
+        b0 = 0
+        for pl in gp:
+            b1 = b0 + pl.bins["nb"]
+            pl.trans_rows = tdifmug[b0:b1]
+            sc = pl.bins["scal"]                 # TDIFMUS into column 0, as _prepare does for -SOS.Trans
+            if not isinstance(sc, torch.Tensor):
+                pl.host_scal = True              # (a host profile: the call stays with the singles)
+                sc = pl.bins["scal"] = solver._dev_f64(np.asarray(sc), dev)
+            sc[:, 0] = tdifmus[b0:b1]
+            b0 = b1
+        if salb:
+            # the spherical albedo of the same bins seen from the ground, and its aik-weighted sum per call
+            s_bin, _ = solver.spherical_albedo_many([pl.ctx for pl in gp], tbins, tcob)
+            seg = np.concatenate([[0], np.cumsum([pl.bins["nb"] for pl in gp])]).astype(np.int32)
+            aik = solver._dev_f64(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp]), dev)
+            ch.salb_bands.append((gp, solver.albedo_band(seg, aik, s_bin)))
+
+
+def _group_key(pl):
+    """What the calls one launch covers agree in (the last entry is False throughout with output slots: their calls have
+    zout = -1)."""
+    b = pl.bins
+    return (pl.n, pl.ctx.smax, pl.ctx.os_nb, bool(pl.ctx._rsurf is not None), b["lp"], b["jout"] is not None)
+
+
+def _part_groups(part):
+    """The groups of wavelengths one launch can cover: (groups, singles), the lists of two or more plans of equal _group_key
+    in first-appearance order of the key, and the calls solved alone -- those with their own transmissions, without bins or
+    with host scalars, in part order, then the one-member groups in key order."""
+    import torch
+    groups = collections.OrderedDict()
+    single = []
+    for pl in part:
+        b = pl.bins
+        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor) or pl.host_scal:
+            single.append(pl)
+            continue
+        groups.setdefault(_group_key(pl), []).append(pl)
+    single += [gp[0] for gp in groups.values() if len(gp) == 1]
+    return [gp for gp in groups.values() if len(gp) > 1], single
+
+
+def _stage_solves(fn, ch, groups, single, solve_group, solve_single, alts, level_keys, dev, debug):
+    """The solves of a part, queued on the main stream: one per group, then one per single call; each adds its entry to
+    ch.solved."""
+    import torch
+    from . import solver
+    for gp in groups:
+        ch.where = gp[0].index
+        table = solver.ContextTable([pl.ctx for pl in gp])
+        bins, cob, seg = solver.concat_bins([pl.bins for pl in gp])
+        aik = solver._upload(torch.from_numpy(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp])), dev)
+        if debug:
+            print("[%s] group" % fn, _group_key(gp[0]), "wavelengths", [pl.index for pl in gp], "bins", bins["nb"], flush=True)
+        rec, scal = solve_group(table, gp, bins, cob, seg, aik)
+        if debug:
+            torch.cuda.synchronize(dev)
+            print("[%s]   done" % fn, flush=True)
+        ch.solved.append((gp, rec, scal, table))
+    for pl in single:
+        ch.where = pl.index
+        if alts is not None and pl.levels["jout"] is not None and not pl.levels["jout"].is_contiguous():
+            pl.levels = dict(pl.levels, **{k: pl.levels[k].contiguous() for k in level_keys})
+        rec, scal = solve_single(pl)
+        ch.solved.append(([pl], rec, scal, None))
+
+
+def _stage_flux_launch(ch, nz):
+    """fluxes: the flux pairs of every (wavelength, altitude) of the chunk: one launch behind the aggregates, in the order of
+    _stage_todo's list; the result comes down with the recompositions'."""
+    from . import solver
+    return solver.level_flux_many([(pl.ctx, rec[k][g]) for gp, rec, _, _ in ch.solved
+                                   for g, pl in enumerate(gp) for k in range(nz)])
+
+
+def _split_scalars(scal_all, shapes, n_alb, n_status):
+    """The host array of _download_scalars taken apart by its layout: shapes, the (nz, len(gp), sw) of every solved entry;
+    n_alb, the length of every salb_bands entry; n_status, that of every ckd_checks entry.  Returns (the reshaped scalar
+    blocks, one array per albedo group, one per status group), views of scal_all; ValueError if the sizes do not add up."""
+    from . import solver
+    cuts = list(shapes) + [(n,) for n in n_alb] + [(n,) for n in n_status]
+    if sum(math.prod(c) for c in cuts) != scal_all.size:
+        raise ValueError("the packed scalars hold %d values, their sections %s add up to %d"
+                         % (scal_all.size, cuts, sum(math.prod(c) for c in cuts)))
+    out = solver._flat_blocks(scal_all, cuts)
+    a, b = len(shapes), len(shapes) + len(n_alb)
+    return out[:a], out[a:b], out[b:]
+
+
+def _download_scalars(ch, nz):
+    """The chunk's one copy of all band scalars (waits for the solves), and the only statement of its layout: the scalar
+    blocks of ch.solved, in order; then the band spherical albedos of ch.salb_bands; then the status words of the device gas
+    tables of ch.ckd_checks (as float64).  Returns what _split_scalars makes of it."""
+    import torch
+    scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in ch.solved] + [s for _, s in ch.salb_bands] +
+                         [s.to(torch.float64) for s, _ in ch.ckd_checks]).cpu().numpy()
+    return _split_scalars(scal_all, [(nz, len(gp), s.shape[2]) for gp, _, s, _ in ch.solved],
+                          [len(gp) for gp, _ in ch.salb_bands], [len(pls) for _, pls in ch.ckd_checks])
+
+
+def _stage_todo(ch, nz, blocks, albs, status, trans_out, salb):
+    """The sections of the download read: the CKD status check first, the spherical albedos, then the jobs of the chunk's
+    recompositions [(plan, slot, record, finish_scalars, segment)] with the malformed-bin check, and (trans_out not None) the
+    trans_entry of every call."""
+    from . import dist as _dist
+    from . import absorption as _abs
+    for (_, pls), codes in zip(ch.ckd_checks, status):
+        for pl, code in zip(pls, codes):
+            if code != 0:                           # COEFF_ABS_CKD failed for this wavelength: sos_proc's error for it
+                ch.where = pl.index
+                raise SosProcError(_abs.CKD_STATUS_MESSAGES.get(int(code), "COEFF_ABS_CKD failed"), ier=-1)
+    s_alb = {}
+    for (gp, _), vals in zip(ch.salb_bands, albs):
+        s_alb.update((pl.index, float(v)) for pl, v in zip(gp, vals))
+    todo = []
+    for (gp, rec, _, _), blk in zip(ch.solved, blocks):
+        fins = [_dist.finish_scalars(blk[k]) for k in range(nz)]
+        recs = [rec[k] for k in range(nz)]
+        for g, pl in enumerate(gp):
+            if any(f["min_orders"][g] < 0 for f in fins):
+                ch.where = pl.index
+                raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
+                                   "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
+            todo += [(pl, k, recs[k][g], fins[k], g) for k in range(nz)]
+            if trans_out is not None:               # (the same values in every slot: they ignore the altitude)
+                trans_out[pl.index] = trans_entry(pl.p["tetas"], pl.mu, float(fins[0]["ttot_tronc"][g]),
+                                                  float(fins[0]["ttot_vrai"][g]), float(fins[0]["tdifmus"][g]),
+                                                  np.array(fins[0]["tdifmug"][g], dtype=np.float64))
+                if salb:                            # (a call without bins took no part in the stage)
+                    trans_out[pl.index]["s_alb"] = s_alb.get(pl.index, 0.0)
+    return todo
+
+
+def _stage_flux_rows(todo, flux_dev, flux_rows, flux_row, ncol, alts):
+    """fluxes: the flux rows [K][ncol] of the chunk's calls from the downloaded pairs of _stage_flux_launch."""
+    e = flux_dev.cpu().numpy()                      # (complete: queued ahead of the recompositions just downloaded)
+    for j, (pl, k, r, f, g) in enumerate(todo):
+        if flux_rows[pl.index] is None:
+            flux_rows[pl.index] = np.empty((len(alts), ncol))
+        flux_rows[pl.index][k] = flux_row(pl, alts[k], f, g, e[j])
+
+
+def _channel_terms(chan, nz, indices):
+    """The arguments (ncalls, first, job, wgt) of solver.channel_accumulate for a chunk; indices: the call index of every
+    entry of the todo list, the nz slots of a call side by side, so that call indices[j nz] is job j.  A channel names its
+    calls of the chunk in ascending call index, whatever the job order is; first[c]:first[c + 1] are the terms of channel c."""
+    job_of = {indices[j * nz]: j for j in range(len(indices) // nz)}
+    calls = sorted(job_of)
+    first, job, wgt = [0], [], []
+    for c in range(chan.shape[0]):
+        for i in calls:
+            if chan[c, i] != 0.0:
+                job.append(job_of[i])
+                wgt.append(chan[c, i])
+        first.append(len(job))
+    return len(calls), first, job, wgt
+
+
+def _stage_channels(fn, todo, flat, shapes, chan, nz, acc, ang_rows, call_scal, flux_rows, dev):
+    """chan: the chunk's blocks stay on the device: one launch adds them onto the accumulator.  todo holds the K slots of a
+    call side by side, in group order: block (j, k) of call todo[j K].  Returns (acc, ang_rows), made by the first chunk."""
+    import torch
+    from . import solver
+    if len(set(shapes)) != 1:
+        raise ValueError("%s: the calls do not share one block shape [nphi][7][W]: %s" % (fn, sorted(set(shapes))))
+    nphi, _, w = shapes[0]
+    if acc is None:
+        acc = torch.zeros((chan.shape[0], nz, nphi, 3, w), dtype=torch.float64, device=dev)
+        ang_rows = flat[:nphi * 7 * w].view(nphi, 7, w)[:, 3, :].clone()
+    ncalls, first, job, wgt = _channel_terms(chan, nz, [t[0].index for t in todo])
+    solver.channel_accumulate(flat, ncalls, nz, nphi, w, first, job, wgt, acc)
+    for pl, k, r, f, g in todo:
+        row = _finish_scalars(pl, f, g)
+        if flux_rows is not None:
+            row = row + tuple(flux_rows[pl.index][k])
+        call_scal.setdefault(pl.index, [None] * nz)[k] = row
+    return acc, ang_rows
+
+
+def _stage_tuples(ch, todo, flat, shapes, results, nrows, nz):
+    """The 23-tuples of the chunk's (wavelength, altitude) jobs from the downloaded recompositions, into results[index][k]."""
+    from . import solver
+    blocks = _zero_pages((len(todo), 2, 7, 361, 81))    # the result tables of the chunk's wavelengths (views of it)
+    for j, ((pl, k, r, f, g), blk) in enumerate(zip(todo, solver._flat_blocks(flat, shapes))):
+        ch.where = pl.index
+        if results[pl.index] is None:
+            results[pl.index] = [None] * nz
+        results[pl.index][k] = _finish(pl, blk, r, f, g, blocks[j])
+        nrows[pl.index] = len(pl.rows)
+
+
 def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False,
                    split=False, chan=None, trans=False, salb=False):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
     launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop.
+    The phases of a chunk are the functions above, which hand the _Chunk to each other; the clock is read between them.
     split (with fluxes): the bins carry the untruncated depth rows, the levels `tauvrai`, and the flux rows two more columns.
     chan (sos_spectrum_channels: the weights [C][calls] of the sensor channels, None: the pass as it was): the recomposition
     blocks of a chunk stay on the device and are added, weight by weight, onto one accumulator [C][K][nphi][3][W] that lives
@@ -1897,7 +2175,6 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if chan is not None:
         mine = sorted(mine)                             # a rank adds its calls in ascending call index
         lead = rank == min(r for r in range(world) if len(shards[r]))    # the rank whose ANGDIFF rows the all-reduce carries
-        n_chan = chan.shape[0]
         acc = ang_rows = None                           # the accumulator and the ANGDIFF rows [nphi][W] of one block
         call_scal = {}                                  # call -> [K][5 (+ flux columns)]: elements 18..22 (and the flux row)
     results = [None] * nwl                              # K 23-tuples per wavelength
@@ -1931,7 +2208,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     # the sea and land surface matrices of a chunk's calls come from one asynchronous sosgpu_surface_batch per angle set, queued by
     # the prefetch; SOS_SPECTRUM_SURFACE_PER_CALL=1: every call that misses the cache makes its own synchronous call (A/B timing)
     batch_surfaces = not os.environ.get("SOS_SPECTRUM_SURFACE_PER_CALL")
-    where, err = -1, None                               # the wavelength being worked on (named by a failure)
+    ch, err = _Chunk(), None
+    ch.where = -1                                       # the wavelength being worked on (named by a failure)
     # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
     # a growing list of result tuples, and the collections this triggers re-walk the results again and again (SOS_SPECTRUM_KEEP_GC=1
     # leaves the collector alone).  Nothing here relies on it: contexts are closed explicitly, tensors are freed by reference count.
@@ -1942,181 +2220,46 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     try:
         for c0 in range(0, len(mine), per_chunk):
             idx = mine[c0:c0 + per_chunk]
-            plans = []
+            ch.plans, ch.solved, ch.salb_bands, ch.ckd_checks = [], [], [], []
             try:
                 t0 = time.perf_counter()
-                where = idx[0]
+                ch.where = idx[0]
                 # the preparation of wavelength k queues its device work (source operators, absorption and level profiles of its
                 # bins: latency-bound kernels of 0.1-2 ms on a few wavefronts) on side stream k mod n: the wavelengths overlap on the
                 # device, and the launches below wait for all of them
                 for st in side + [aer_st]:
                     st.wait_stream(main_st)
                 aer_wa = _spectrum_prefetch(kwargs_list, aer_phases, idx, device, aer_st, device_tables, batch_surfaces)
-                ckd_checks = []                   # (status tensor of a part's device gas tables, the plans it speaks of)
                 # The chunk goes to the solver in a few parts: the solves of a part run on the device while the host prepares the
                 # next one, so that only the last part's solve is waited for below.
-                solved = []                       # (plans, rec [K][nw][S][3][W], scal [K][nw][10+N], table) device tensors
-                salb_bands = []                   # salb: (plans, their band spherical albedos [len(plans)], a device tensor)
                 # (at least 32 wavelengths per part -- a launch per kernel variant each; SOS_SPECTRUM_MIN_PART: the tests' override)
-                nsub = max(1, min(int(parts), len(idx) // max(1, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32")))))
-                step = max(1, -(-len(idx) // nsub))
-                for s0 in range(0, len(idx), step):
-                    part = []
-                    for k, i in enumerate(idx[s0:s0 + step], s0):
-                        where = i
-                        with torch.cuda.stream(side[k % len(side)]):
-                            pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
-                                          aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles, device_gas_tables=device_tables,
-                                          defer_operators=batch_operators, **true_kw)
-                            pl.writes_files = True
-                            pl.index = i
-                            plans.append(pl)
-                            if alts is not None and pl.bins is not None:
-                                pl.levels = pl.ctx.output_levels(pl.bins, alts)
-                        if debug:
-                            torch.cuda.synchronize(dev)
-                            print("[%s] prepared" % fn, i, flush=True)
-                        part.append(pl)
-                    # the profiles of the part's qualifying wavelengths: three launches for all their bins (the operators the side
-                    # streams are still building are not needed for them), one more for the output slots
-                    deferred = [pl for pl in part if pl.bins is None]
-                    if deferred:
-                        where = deferred[0].index
-                        info = {}
-                        try:
-                            made = solver.make_profiles_spectrum([pl.profile_request for pl in deferred], dev, part=info,
-                                                                 **true_kw)
-                        except Exception as e:
-                            if info.get("bad") is not None:
-                                where = deferred[info["bad"]].index
-                            raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
-                        if info.get("ckd_status") is not None:
-                            ckd_checks.append((info["ckd_status"], [deferred[g] for g in info["ckd_index"]]))
-                        lv = None if alts is None else deferred[0].ctx.output_levels(info["bins"], alts)
-                        for g, pl in enumerate(deferred):
-                            # (views of the part's blocks: the plans keep them alive until the chunk's streams are synchronised)
-                            pl.bins, pl.tabs_flux, pl.profile_part = made[g], info["tabs"][g], info
-                            if lv is not None:
-                                b0, b1 = int(info["seg"][g]), int(info["seg"][g + 1])
-                                pl.levels = dict(nz=lv["nz"], **{k: lv[k][:, b0:b1] for k in level_keys})
+                for s0, s1 in _part_bounds(len(idx), parts, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32"))):
+                    part = _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, aer_st, aer_wa, alts,
+                                          true_kw, batch_profiles, device_tables, batch_operators, debug)
+                    _stage_profiles(ch, part, alts, level_keys, true_kw, dev)
                     for st in side:
                         main_st.wait_stream(st)
-                    # the operators of the part's unbuilt contexts, grouped and single alike (after the wait: the surface
-                    # matrices come from the side streams)
-                    unbuilt = [pl for pl in part if not pl.ctx._built]
-                    if unbuilt:
-                        where = unbuilt[0].index
-                        solver.build_operators([pl.ctx for pl in unbuilt])
+                    _stage_operators(ch, part)
                     if trans:
-                        # the diffuse transmissions of every bin of the part: one call per direction count, whatever the calls
-                        # are (it reads the contexts' order-0 operators, queued above or by the side streams waited for)
-                        by_n = collections.OrderedDict()
-                        for pl in part:
-                            if pl.bins["nb"]:
-                                by_n.setdefault(pl.n, []).append(pl)
-                        for gp in by_n.values():
-                            where = gp[0].index
-                            tbins, tcob = solver.concat_profiles([pl.bins for pl in gp])
-                            tdifmus, tdifmug = solver.diffuse_transmissions_many([pl.ctx for pl in gp], tbins, tcob)
-                            b0 = 0
-                            for pl in gp:
-                                b1 = b0 + pl.bins["nb"]
-                                pl.trans_rows = tdifmug[b0:b1]
-                                sc = pl.bins["scal"]                 # TDIFMUS into column 0, as _prepare does for -SOS.Trans
-                                if not isinstance(sc, torch.Tensor):
-                                    pl.host_scal = True              # (a host profile: the call stays with the singles)
-                                    sc = pl.bins["scal"] = solver._dev_f64(np.asarray(sc), dev)
-                                sc[:, 0] = tdifmus[b0:b1]
-                                b0 = b1
-                            if salb:
-                                # the spherical albedo of the same bins seen from the ground, and its aik-weighted sum per call
-                                s_bin, _ = solver.spherical_albedo_many([pl.ctx for pl in gp], tbins, tcob)
-                                seg = np.concatenate([[0], np.cumsum([pl.bins["nb"] for pl in gp])]).astype(np.int32)
-                                aik = solver._dev_f64(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp]), dev)
-                                salb_bands.append((gp, solver.albedo_band(seg, aik, s_bin)))
+                        _stage_transmissions(ch, part, salb, dev)
                     t1 = time.perf_counter()
                     tm["prepare"] += t1 - t0
-                    # --- groups of wavelengths one launch can cover
-                    groups = collections.OrderedDict()
-                    single = []
-                    for pl in part:
-                        b = pl.bins
-                        if pl.tdifmug is not None or b["nb"] == 0 or not isinstance(b.get("scal"), torch.Tensor) or pl.host_scal:
-                            single.append(pl)
-                            continue
-                        # (the last entry is False throughout with output slots: their calls have zout = -1)
-                        key = (pl.n, pl.ctx.smax, pl.ctx.os_nb, bool(pl.ctx._rsurf is not None), b["lp"], b["jout"] is not None)
-                        groups.setdefault(key, []).append(pl)
-                    for key, gp in groups.items():
-                        if len(gp) == 1:
-                            single.append(gp[0])
-                            continue
-                        where = gp[0].index
-                        table = solver.ContextTable([pl.ctx for pl in gp])
-                        bins, cob, seg = solver.concat_bins([pl.bins for pl in gp])
-                        aik = solver._upload(torch.from_numpy(np.concatenate([np.asarray(pl.aik, dtype=np.float64) for pl in gp])),
-                                             dev)
-                        if debug:
-                            print("[%s] group" % fn, key, "wavelengths", [pl.index for pl in gp], "bins", bins["nb"], flush=True)
-                        rec, scal = solve_group(table, gp, bins, cob, seg, aik)
-                        if debug:
-                            torch.cuda.synchronize(dev)
-                            print("[%s]   done" % fn, flush=True)
-                        solved.append((gp, rec, scal, table))
-                    for pl in single:
-                        where = pl.index
-                        if alts is not None and pl.levels["jout"] is not None and not pl.levels["jout"].is_contiguous():
-                            pl.levels = dict(pl.levels, **{k: pl.levels[k].contiguous() for k in level_keys})
-                        rec, scal = solve_single(pl)
-                        solved.append(([pl], rec, scal, None))
+                    groups, single = _part_groups(part)
+                    _stage_solves(fn, ch, groups, single, solve_group, solve_single, alts, level_keys, dev, debug)
                     t0 = time.perf_counter()
                     tm["solve_launch"] += t0 - t1
                 flux_dev = None
                 if fluxes:
-                    # the flux pairs of every (wavelength, altitude) of the chunk: one launch behind the aggregates, in the order
-                    # of `todo` below; the result comes down with the recompositions'
                     tf = time.perf_counter()
-                    flux_dev = solver.level_flux_many([(pl.ctx, rec[k][g]) for gp, rec, _, _ in solved
-                                                       for g, pl in enumerate(gp) for k in range(nz)])
+                    flux_dev = _stage_flux_launch(ch, nz)
                     tm["fluxes"] += time.perf_counter() - tf
                 t2 = time.perf_counter()
-                # --- one copy of all band scalars (waits for the solves), then every azimuth recomposition back to back
-                # (the band spherical albedos and the status words of the device gas tables ride at its end)
-                scal_all = torch.cat([s.reshape(-1) for _, _, s, _ in solved] + [s for _, s in salb_bands] +
-                                     [s.to(torch.float64) for s, _ in ckd_checks]).cpu().numpy()
+                blocks, albs, status = _download_scalars(ch, nz)
                 t3 = time.perf_counter()
                 tm["wait"] += t3 - t2
-                pos = scal_all.size - sum(len(pls) for _, pls in ckd_checks)
-                for _, pls in ckd_checks:
-                    for pl, code in zip(pls, scal_all[pos:pos + len(pls)]):
-                        if code != 0:                           # COEFF_ABS_CKD failed for this wavelength: sos_proc's error for it
-                            where = pl.index
-                            raise SosProcError(_abs.CKD_STATUS_MESSAGES.get(int(code), "COEFF_ABS_CKD failed"), ier=-1)
-                    pos += len(pls)
-                s_alb, pos = {}, sum(s.numel() for _, _, s, _ in solved)
-                for gp, _ in salb_bands:
-                    s_alb.update((pl.index, float(v)) for pl, v in zip(gp, scal_all[pos:pos + len(gp)]))
-                    pos += len(gp)
-                todo, pos = [], 0                               # (plan, slot, record, finish_scalars, segment)
-                for gp, rec, scal, _ in solved:
-                    sw = scal.shape[2]
-                    blk = scal_all[pos:pos + nz * len(gp) * sw].reshape(nz, len(gp), sw)
-                    pos += nz * len(gp) * sw
-                    fins = [_dist.finish_scalars(blk[k]) for k in range(nz)]
-                    recs = [rec[k] for k in range(nz)]
-                    for g, pl in enumerate(gp):
-                        if any(f["min_orders"][g] < 0 for f in fins):
-                            where = pl.index
-                            raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
-                                               "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
-                        todo += [(pl, k, recs[k][g], fins[k], g) for k in range(nz)]
-                        if trans:                               # (the same values in every slot: they ignore the altitude)
-                            trans_out[pl.index] = trans_entry(pl.p["tetas"], pl.mu, float(fins[0]["ttot_tronc"][g]),
-                                                              float(fins[0]["ttot_vrai"][g]), float(fins[0]["tdifmus"][g]),
-                                                              np.array(fins[0]["tdifmug"][g], dtype=np.float64))
-                            if salb:                            # (a call without bins took no part in the stage)
-                                trans_out[pl.index]["s_alb"] = s_alb.get(pl.index, 0.0)
-                # one launch for every (wavelength, altitude) of the chunk, its flat result downloaded as it is
+                todo = _stage_todo(ch, nz, blocks, albs, status, trans_out, salb)
+                # then every azimuth recomposition back to back: one launch for every (wavelength, altitude) of the chunk, its
+                # flat result downloaded as it is
                 flat, shapes = _trphi_launch_many([(pl, r, int(f["n_orders"][g]), float(f["ttot_tronc"][g]), float(f["tauout"][g]))
                                                    for pl, _, r, f, g in todo])
                 if chan is None:
@@ -2124,52 +2267,16 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 t4 = time.perf_counter()
                 tm["trphi"] += t4 - t3
                 if fluxes:
-                    e = flux_dev.cpu().numpy()                  # (complete: queued ahead of the recompositions just downloaded)
-                    for j, (pl, k, r, f, g) in enumerate(todo):
-                        if flux_rows[pl.index] is None:
-                            flux_rows[pl.index] = np.empty((nz, len(flux_names)))
-                        flux_rows[pl.index][k] = flux_row(pl, alts[k], f, g, e[j])
+                    _stage_flux_rows(todo, flux_dev, flux_rows, flux_row, len(flux_names), alts)
                     t5 = time.perf_counter()
                     tm["fluxes"] += t5 - t4
                     t4 = t5
                 if chan is not None:
-                    # the chunk's blocks stay on the device: one launch adds them onto the accumulator.  todo holds the K slots
-                    # of a call side by side, in group order: block (j, k) of call todo[j K].  A channel names its calls of the
-                    # chunk in ascending call index, whatever that order is.
-                    where = idx[0]
-                    if len(set(shapes)) != 1:
-                        raise ValueError("%s: the calls do not share one block shape [nphi][7][W]: %s" % (fn, sorted(set(shapes))))
-                    nphi, _, w = shapes[0]
-                    if acc is None:
-                        acc = torch.zeros((n_chan, nz, nphi, 3, w), dtype=torch.float64, device=dev)
-                        ang_rows = flat[:nphi * 7 * w].view(nphi, 7, w)[:, 3, :].clone()
-                    job_of = {todo[j * nz][0].index: j for j in range(len(todo) // nz)}
-                    calls = sorted(job_of)
-                    first, job, wgt = [0], [], []
-                    for c in range(n_chan):
-                        for i in calls:
-                            if chan[c, i] != 0.0:
-                                job.append(job_of[i])
-                                wgt.append(chan[c, i])
-                        first.append(len(job))
-                    solver.channel_accumulate(flat, len(calls), nz, nphi, w, first, job, wgt, acc)
-                    for pl, k, r, f, g in todo:
-                        row = _finish_scalars(pl, f, g)
-                        if fluxes:
-                            row = row + tuple(flux_rows[pl.index][k])
-                        call_scal.setdefault(pl.index, [None] * nz)[k] = row
+                    ch.where = idx[0]
+                    acc, ang_rows = _stage_channels(fn, todo, flat, shapes, chan, nz, acc, ang_rows, call_scal, flux_rows, dev)
                     tm["channels"] += time.perf_counter() - t4
                     continue
-                pos = 0
-                blocks = _zero_pages((len(todo), 2, 7, 361, 81))  # the result tables of the chunk's wavelengths (views of it)
-                for j, ((pl, k, r, f, g), shp) in enumerate(zip(todo, shapes)):
-                    where = pl.index
-                    if results[pl.index] is None:
-                        results[pl.index] = [None] * nz
-                    cnt = shp[0] * shp[1] * shp[2]
-                    results[pl.index][k] = _finish(pl, flat[pos:pos + cnt].reshape(shp), r, f, g, blocks[j])
-                    nrows[pl.index] = len(pl.rows)
-                    pos += cnt
+                _stage_tuples(ch, todo, flat, shapes, results, nrows, nz)
                 tm["finish"] += time.perf_counter() - t4
             finally:
                 _aer.drop_prefetched_size_integrals()
@@ -2178,7 +2285,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     st.synchronize()
                 main_st.synchronize()                             # the table launches read every context's operators
                 _drop_prefetched_surfaces()
-                for pl in plans:
+                for pl in ch.plans:
                     pl.ctx.close()
     except Exception as e:                         # noqa: BLE001 -- re-raised below, after the ranks have agreed
         err = e
@@ -2187,10 +2294,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
             gc.enable()
     if world > 1:
         # a call failing on one rank must not leave the others waiting in the gather: the ranks agree first (one integer)
-        bad = _first_failed_index(max(where, 0) if err is not None else -1, device)
+        bad = _first_failed_index(max(ch.where, 0) if err is not None else -1, device)
         if bad >= 0:
             if err is not None:
-                raise SosProcError("%s: wavelength %d failed: %s" % (fn, where, err), ier=getattr(err, "ier", 1)) from err
+                raise SosProcError("%s: wavelength %d failed: %s" % (fn, ch.where, err), ier=getattr(err, "ier", 1)) from err
             raise SosProcError("%s: wavelength %d failed on another rank" % (fn, bad), ier=-1)
     if err is not None:
         raise err

@@ -7,6 +7,7 @@ Mirrors the reference per-wavelength sequence of SOS_PROC (src/SOS_PROC.F:3423-3
 """
 import collections
 import ctypes as C
+import math
 import threading
 
 import numpy as np
@@ -638,12 +639,17 @@ def trphi_many(items):
     work = torch.empty(int(L.sosgpu_trphi_spectrum_work_bytes(n)), dtype=torch.uint8, device=d)
     capi.check(L.sosgpu_trphi_spectrum(jobs, n, _ptr(phis), int(phis.numel()), _ptr(flat), _ptr(work), items[0][0]._stream()),
                "sosgpu_trphi_spectrum")
-    views, pos = [], 0
+    return flat, _flat_blocks(flat, shapes)
+
+
+def _flat_blocks(flat, shapes):
+    """A flat array (numpy array or tensor) of blocks lying back to back, cut into one view per shape, in order."""
+    blocks, pos = [], 0
     for shp in shapes:
-        m = shp[0] * shp[1] * shp[2]
-        views.append(flat[pos:pos + m].view(shp))
+        m = math.prod(shp)
+        blocks.append(flat[pos:pos + m].reshape(shp))
         pos += m
-    return flat, views
+    return blocks
 
 
 def _flux_row(rec, device, w):
@@ -745,6 +751,23 @@ def build_operators(ctxs):
     return n
 
 
+def _many_contexts(fn, ctxs, bins, ctx_of_bin):
+    """The common opening of diffuse_transmissions_many and spherical_albedo_many (`fn`, named by the errors): the context list
+    with its operators asked for, the ctx_of_bin rule and the handle array.  Returns (ctxs, first, device, N, nb, ctx_of_bin on
+    the device or None, the library, the handles)."""
+    ctxs = list(ctxs)
+    if not ctxs:
+        raise ValueError("%s needs at least one context" % fn)
+    for cx in ctxs:
+        cx._need_operators()
+    first = ctxs[0]
+    d, n, nb = first.device, first.n, int(bins["nb"])
+    if ctx_of_bin is None and len(ctxs) > 1:
+        raise ValueError("ctx_of_bin is required with more than one context")
+    cob = None if ctx_of_bin is None else _dev_i32(ctx_of_bin, d)
+    return ctxs, first, d, n, nb, cob, capi.lib(), (C.c_void_p * len(ctxs))(*[cx._h for cx in ctxs])
+
+
 def diffuse_transmissions_many(ctxs, bins, ctx_of_bin=None):
     """SosContext.diffuse_transmissions for the bins of MANY contexts in one call (sosgpu_trans_spectrum): every (bin,
     direction) pair is an item of ONE order-0 solve, every (context, direction) pair an entry of a device table that shares
@@ -753,18 +776,7 @@ def diffuse_transmissions_many(ctxs, bins, ctx_of_bin=None):
     context); ctx_of_bin[nb]: int32 index into ctxs of every bin (None with one context).  Returns (tdifmus[nb],
     tdifmug[nb][N]) device tensors with the bits of the per-direction loop; tdifmus[b] is column n0 - 1 of the bin's context.
     The work area comes from torch's allocator and is dropped at return (the allocator keeps it for the stream)."""
-    ctxs = list(ctxs)
-    if not ctxs:
-        raise ValueError("diffuse_transmissions_many needs at least one context")
-    for cx in ctxs:
-        cx._need_operators()
-    first = ctxs[0]
-    d, n, nb = first.device, first.n, int(bins["nb"])
-    if ctx_of_bin is None and len(ctxs) > 1:
-        raise ValueError("ctx_of_bin is required with more than one context")
-    cob = None if ctx_of_bin is None else _dev_i32(ctx_of_bin, d)
-    L = capi.lib()
-    hs = (C.c_void_p * len(ctxs))(*[cx._h for cx in ctxs])
+    ctxs, first, d, n, nb, cob, L, hs = _many_contexts("diffuse_transmissions_many", ctxs, bins, ctx_of_bin)
     tdifmug = torch.empty((nb, n), dtype=torch.float64, device=d)
     need = int(L.sosgpu_trans_spectrum_work_bytes(hs, len(ctxs), nb, bins["lp"]))
     work = torch.empty(max(need, 8), dtype=torch.uint8, device=d)
@@ -787,18 +799,7 @@ def spherical_albedo_many(ctxs, bins, ctx_of_bin=None, from_below=True):
     ctxs, bins, ctx_of_bin: as diffuse_transmissions_many takes them.  Returns (salb[nb], plane[nb][N]) device tensors;
     plane[b][j] is the plane albedo A_j, 0 in the columns of weight-0 directions (the inserted solar angle, user angles), which
     are not solved; a malformed bin gives zeros.  Nothing is waited for."""
-    ctxs = list(ctxs)
-    if not ctxs:
-        raise ValueError("spherical_albedo_many needs at least one context")
-    for cx in ctxs:
-        cx._need_operators()
-    first = ctxs[0]
-    d, n, nb = first.device, first.n, int(bins["nb"])
-    if ctx_of_bin is None and len(ctxs) > 1:
-        raise ValueError("ctx_of_bin is required with more than one context")
-    cob = None if ctx_of_bin is None else _dev_i32(ctx_of_bin, d)
-    L = capi.lib()
-    hs = (C.c_void_p * len(ctxs))(*[cx._h for cx in ctxs])
+    ctxs, first, d, n, nb, cob, L, hs = _many_contexts("spherical_albedo_many", ctxs, bins, ctx_of_bin)
     salb = torch.empty(nb, dtype=torch.float64, device=d)
     plane = torch.empty((nb, n), dtype=torch.float64, device=d)
     need = int(L.sosgpu_albedo_spectrum_work_bytes(hs, len(ctxs), nb, bins["lp"]))

@@ -25,6 +25,15 @@
  * work area from a pinned block the library recycles: nothing is waited for and no context owns it, so any context of such a
  * call may be destroyed as soon as the call has returned (sosgpu_destroy waits for the context's streams, as ever).
  *
+ * Work areas (the contract of every `void *d_work, size_t work_bytes` pair).  A table-form entry point sosgpu_<name> keeps its
+ * table and its intermediates in a DEVICE area the caller provides, of work_bytes >= sosgpu_<name>_work_bytes(...) bytes:
+ *   - the area is 8-byte aligned and the caller's until `stream` has passed the call (an allocator that recycles memory in
+ *     stream order may drop it when the call returns); the table arrives there in ONE copy on `stream`;
+ *   - nothing beyond the first sosgpu_<name>_work_bytes(...) bytes is read or written;
+ *   - a NULL or misaligned d_work and a work_bytes below the query are refused with SOSGPU_E_ARG before anything is queued, a
+ *     staging block is taken or a context is changed (sosgpu_mie_batch alone answers SOSGPU_E_UNSUPPORTED for a short area);
+ *   - the query is host arithmetic (no device call) and returns 0 for arguments the call would refuse.
+ *
  * Each entry point replaces one routine of the reference per-wavelength pipeline that
  * binding/run_sos.py reaches through sos.sos_proc (binding/run_sos.py:640, SOS_PROC.F:415):
  *
@@ -118,17 +127,18 @@ int  sosgpu_noyaux(sosgpu_ctx *cx, void *stream);
  *                  imat_surf = 0.  The whole argument may be NULL when no context has matrices (the fifth launch, the ground
  *                  operators, is made only when some entry is non-NULL).  Keep the matrices allocated until `stream` has passed
  *                  the call.
- *  d_work          DEVICE area of nctx * (sosgpu_ctx_table_entry_bytes() + 8) bytes, 8-byte aligned, the caller's until `stream`
- *                  has passed the call: the table of the contexts and the list of matrix pointers arrive there in ONE copy on
- *                  `stream`, from a pinned block the library recycles.
+ *  d_work, work_bytes   see "Work areas": the table of the contexts and the list of matrix pointers,
+ *                  sosgpu_noyaux_spectrum_work_bytes(nctx) bytes
  * Asynchronous: nothing is waited for and no device memory is allocated.  On return every context is in the host-side state the
  * two calls leave (its ground operators registered, `stream` noted for sosgpu_destroy); once `stream` has passed the call its
  * tables are filled.  Call sosgpu_ctx_table AFTER this call, not before: the table copies the ground-operator pointers this
  * call registers.
  * Checked before anything is queued or any context is changed, SOSGPU_E_ARG for: NULL ctxs or d_work, a NULL entry of ctxs,
  * nctx < 0 or nctx > 65535, contexts on different devices, imat_surf = 1 with a NULL matrix pointer, a matrix pointer for a
- * context with imat_surf = 0, a misaligned d_work.  nctx = 0 returns SOSGPU_OK with nothing queued. */
-int  sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const float *const *d_rsurf, void *d_work, void *stream);
+ * context with imat_surf = 0, the work area's rules.  nctx = 0 returns SOSGPU_OK with nothing queued. */
+size_t sosgpu_noyaux_spectrum_work_bytes(int nctx);
+int  sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const float *const *d_rsurf, void *d_work, size_t work_bytes,
+                            void *stream);
 /* Debug/parity accessor: copies the six kernels of order `is` to host as the reference lays them
  * out, X[(j+N)*W + (k+N)] = X(J,K), in the order BP,GR,GT,ARR,ART,ATT, then XPL,XRL,XTL (W each).
  * Synchronous.  out must hold 6*W*W + 3*W doubles. */
@@ -240,9 +250,7 @@ int  sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table, const int
  *  d_ctx_of_bin[nb]  index into ctxs of every bin (int32), or NULL with nctx = 1; a bin whose index is out of range is
  *                    treated as malformed
  *  d_nt[nb], d_prof[nb][3][lp]   as sosgpu_os_solve takes them
- *  d_work            DEVICE area of work_bytes >= sosgpu_trans_spectrum_work_bytes(ctxs, nctx, nb, lp) bytes, 8-byte aligned, the
- *                    caller's until `stream` has passed the call: the context table arrives there in ONE copy on `stream` from a
- *                    pinned block the library recycles, followed by the child table, the children's vectors and the items'
+ *  d_work, work_bytes   see "Work areas": the context table, followed by the child table, the children's vectors and the items'
  *                    arrays (the profile rows are replicated per direction: 24 N lp bytes per bin)
  * Asynchronous: nothing is waited for and no device memory is allocated -- except for level grids beyond the LDS-resident
  * solver (lp > 64), whose streamed-field scratch comes from where sosgpu_os_solve_multi takes it (ctxs[0], at most 4 GiB at a
@@ -251,9 +259,8 @@ int  sosgpu_os_solve_multi_levels(sosgpu_ctx *cx, const void *d_table, const int
  * the solve is split only where 4 GiB of scratch do not hold all items.  `stream` is noted for sosgpu_destroy on every context.
  * Checked before anything is queued or a staging block is taken, SOSGPU_E_ARG for: NULL ctxs, d_nt, d_prof, d_tdifmug or
  * d_work, a NULL context or one whose operators were never queued, contexts on different devices or with different N,
- * nctx < 1, nb < 0, lp < 2, d_ctx_of_bin = NULL with nctx > 1, work_bytes too small, a misaligned d_work; SOSGPU_E_UNSUPPORTED
- * when (N, lp) has no solver variant.  nb = 0 returns SOSGPU_OK with nothing queued.  sosgpu_trans_spectrum_work_bytes returns 0
- * for arguments the call would refuse. */
+ * nctx < 1, nb < 0, lp < 2, d_ctx_of_bin = NULL with nctx > 1, the work area's rules; SOSGPU_E_UNSUPPORTED when (N, lp) has no
+ * solver variant.  nb = 0 returns SOSGPU_OK with nothing queued. */
 size_t sosgpu_trans_spectrum_work_bytes(sosgpu_ctx *const *ctxs, int nctx, int nb, int lp);
 int    sosgpu_trans_spectrum(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_of_bin, int nb, int lp,
                              const int32_t *d_nt, const double *d_prof,
@@ -381,14 +388,12 @@ int  sosgpu_trphi(sosgpu_ctx *cx, int nf, const double *d_rec, double tau, doubl
  *  jobs[njobs]     HOST array; jobs may share a context, a record pointer and an azimuth range
  *  d_phi[nphi_total]  DEVICE azimuths (radians) of the whole call; job j reads d_phi[phi_off .. phi_off + nphi)
  *  d_out           DEVICE, the blocks [nphi_j][7][W_j] of the jobs back to back, in job order
- *  d_work          DEVICE area of sosgpu_trphi_spectrum_work_bytes(njobs) bytes, 8-byte aligned, the caller's until `stream` has
- *                  passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block the library
- *                  recycles.
+ *  d_work, work_bytes   see "Work areas": the job entries, sosgpu_trphi_spectrum_work_bytes(njobs) bytes
  * Asynchronous: one launch, nothing is waited for and no device memory is allocated; `stream` is noted for sosgpu_destroy on
  * every context of the call.  Records, azimuths and contexts must stay alive until `stream` has passed the call.
  * Checked before anything is queued, SOSGPU_E_ARG for: NULL jobs, d_phi, d_out or d_work, njobs < 0 or njobs > 65535, a NULL cx
  * or d_rec, nf < 1 or nf > iborm_max + 1 of the job's context, nphi < 1, phi_off < 0 or phi_off + nphi > nphi_total, contexts
- * on different devices, a land->isurf outside 3..7, a misaligned d_work; SOSGPU_E_UNSUPPORTED for isurf = 6, as sosgpu_trphi.
+ * on different devices, a land->isurf outside 3..7, the work area's rules; SOSGPU_E_UNSUPPORTED for isurf = 6, as sosgpu_trphi.
  * njobs = 0 returns SOSGPU_OK with nothing queued. */
 typedef struct sosgpu_trphi_job {
     sosgpu_ctx *cx;            /* context of the wavelength (HOST handle) */
@@ -400,7 +405,7 @@ typedef struct sosgpu_trphi_job {
 } sosgpu_trphi_job;
 size_t sosgpu_trphi_spectrum_work_bytes(int njobs);
 int  sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, const double *d_phi, int nphi_total,
-                           double *d_out, void *d_work, void *stream);
+                           double *d_out, void *d_work, size_t work_bytes, void *stream);
 
 /* Diffuse fluxes of an aggregated record at its output altitude: d_out[0] = E-(z), d_out[1] = E+(z), the Gauss quadrature the
  * reference applies to the order-0 intensity at the ground and at the top of the atmosphere (EMOINS / EPLUS, SOS_OS.F:1447-1456):
@@ -414,17 +419,15 @@ int  sosgpu_level_flux(sosgpu_ctx *cx, const double *d_rec, double *d_out /*[2]*
  * launch: one thread per (job, hemisphere).  d_out[j][0..1] holds, bit for bit, what sosgpu_level_flux writes for job j.
  *  jobs[njobs]     HOST array; jobs may share a context and a record pointer
  *  d_out[njobs][2] DEVICE
- *  d_work          DEVICE area of sosgpu_level_flux_spectrum_work_bytes(njobs) bytes, 8-byte aligned, the caller's until `stream`
- *                  has passed the call: the job entries arrive there in ONE copy on `stream`, from a pinned block the library
- *                  recycles.
+ *  d_work, work_bytes   see "Work areas": the job entries, sosgpu_level_flux_spectrum_work_bytes(njobs) bytes
  * Asynchronous: one launch, nothing is waited for and no device memory is allocated; `stream` is noted for sosgpu_destroy on
  * every context of the call (the kernel reads their mu and ga).  Records and contexts must stay alive until `stream` has passed
  * the call.  Checked before anything is queued, SOSGPU_E_ARG for: NULL jobs, d_out or d_work, njobs < 0 (or > 2^30 - 1), a NULL
- * cx or d_rec, contexts on different devices, a misaligned d_work.  njobs = 0 returns SOSGPU_OK with nothing queued. */
+ * cx or d_rec, contexts on different devices, the work area's rules.  njobs = 0 returns SOSGPU_OK with nothing queued. */
 typedef struct sosgpu_flux_job { sosgpu_ctx *cx; const double *d_rec; } sosgpu_flux_job;
 size_t sosgpu_level_flux_spectrum_work_bytes(int njobs);
 int  sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out /*[njobs][2]*/,
-                                void *d_work, void *stream);
+                                void *d_work, size_t work_bytes, void *stream);
 
 /* Sensor channels of a spectrum: response-weighted sums of recomposition blocks over the wavelengths, on the device.
  * A call adds the terms of nchan channels onto an accumulator that lives for the whole spectrum:
@@ -439,13 +442,11 @@ int  sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *
  *  first[nchan+1]  HOST, non-decreasing from first[0] = 0; first[nchan] = the number of terms of the call
  *  job[], wgt[]    HOST, first[nchan] entries each: block index 0..njobs-1 and finite weight of every term
  *  d_acc           DEVICE, [nchan][nslots][nphi][3][W]; the caller zeroes it before the first call of a spectrum
- *  d_work          DEVICE area of work_bytes >= sosgpu_channel_accumulate_work_bytes(nchan, first[nchan]) bytes, 8-byte
- *                  aligned, the caller's until `stream` has passed the call: the term table arrives there in ONE copy on
- *                  `stream`, from a pinned block the library recycles.
+ *  d_work, work_bytes   see "Work areas": the term table, sosgpu_channel_accumulate_work_bytes(nchan, first[nchan]) bytes
  * Asynchronous: one launch, nothing is waited for, no device memory is allocated and no context is needed.
  * Checked before anything is queued, SOSGPU_E_ARG for: njobs, nslots, nphi, w or nchan < 1 (or nslots, nchan > 65535,
  * nphi * 7 * w > 2^31 - 1), a NULL pointer, first[0] != 0 or a decreasing first, a job outside 0..njobs-1, a weight that is
- * not finite, a misaligned d_work, work_bytes too small.  A call without a term returns SOSGPU_OK with nothing queued. */
+ * not finite, the work area's rules.  A call without a term returns SOSGPU_OK with nothing queued. */
 size_t sosgpu_channel_accumulate_work_bytes(int nchan, int nterms);
 int  sosgpu_channel_accumulate(int device, const double *d_blocks, int njobs, int nslots, int nphi, int w, int nchan,
                                const int32_t *first, const int32_t *job, const double *wgt, double *d_acc, void *d_work,
@@ -482,16 +483,14 @@ int  sosgpu_land_surface(int device, const sosgpu_land *land, int n, const doubl
  *  d_status[njobs] DEVICE, written on `stream` for every job: 0, or -1 when the Roujean function goes negative for the job's
  *                  coefficients (the reference's IER = -1, SOS_ROUJEAN.F:548).  A flagged job disturbs no other job; the
  *                  content of its block is unspecified.
- *  d_work          DEVICE area of work_bytes >= sosgpu_surface_batch_work_bytes(...) bytes, 8-byte aligned, the caller's until
- *                  `stream` has passed the call.  The tables and the Fresnel coefficients arrive there in ONE copy on `stream`,
- *                  from a pinned block the library recycles; the intermediates (E, IL of every analysis, the reflexion
- *                  blocks) live behind them.  Nothing beyond sosgpu_surface_batch_work_bytes(...) bytes is touched.
+ *  d_work, work_bytes   see "Work areas": the tables and the Fresnel coefficients; the intermediates (E, IL of every analysis,
+ *                  the reflexion blocks) live behind them
  * Asynchronous: one copy and at most six launches whatever njobs is, nothing is waited for, no device memory is allocated.
  * Checked on the host before anything is queued: SOSGPU_E_ARG for n outside 1..85, the order bounds and the LDS limit of
  * sosgpu_glitter, NULL mu, chr, jobs, d_status, d_work or a NULL d_rsurf, njobs < 0 or njobs > 65535, an isurf outside
- * {1, 3, 4, 5, 6, 7}, a misaligned d_work, work_bytes too small; SOSGPU_E_UNSUPPORTED for isurf = 6, as sosgpu_land_surface.
- * njobs = 0 returns SOSGPU_OK with nothing queued.  sosgpu_surface_batch_work_bytes returns 0 for arguments the call would
- * refuse (it does not look at d_rsurf, so that the area can be sized before the blocks exist). */
+ * {1, 3, 4, 5, 6, 7}, the work area's rules; SOSGPU_E_UNSUPPORTED for isurf = 6, as sosgpu_land_surface.
+ * njobs = 0 returns SOSGPU_OK with nothing queued.  sosgpu_surface_batch_work_bytes does not look at d_rsurf, so that the area
+ * can be sized before the blocks exist. */
 typedef struct sosgpu_surface_job {
     int32_t isurf;          /* 1 Cox-Munk sea; 3, 4, 5, 7 land (6: SOSGPU_E_UNSUPPORTED, as sosgpu_land_surface) */
     int32_t reserved;
@@ -585,9 +584,8 @@ int  sosgpu_absprofile(int device, int nb, int nlev, int nterm, const int32_t *d
  *   d_wl_of_bin[nb]      index into wl of every bin (int32);  d_ik[nb][8] as sosgpu_absprofile (rows of no-gas bins unused)
  *   d_gas[gas_doubles]   the wavelengths' tables, packed; nblev (2..64) is common to the launch; both unused when no
  *                        wavelength has gas (NULL, 0, nblev 0, d_ik and d_tabs NULL)
- *   d_table              DEVICE work area of nwl * sosgpu_profile_table_entry_bytes() bytes: the per-wavelength table, copied
- *                        there on `stream` from a pinned block the library recycles
- *   d_nogas[nwl][4][SOSGPU_NOGAS_LEVELS]   DEVICE work area: the no-gas block of every wavelength
+ *   d_work, work_bytes   see "Work areas": the no-gas blocks [nwl][4][SOSGPU_NOGAS_LEVELS] (doubles) of the wavelengths first,
+ *                        the per-wavelength table behind them; sosgpu_profile_spectrum_work_bytes(nwl) bytes
  * Outputs (device) for the concatenated bins: d_tabs[nb][nblev] (TAUABS, as sosgpu_absprofile; rows of no-gas bins are not
  * written), d_prof[nb][3][lp], d_nt[nb], d_iborm[nb], d_zprof[nb][lp], d_scal[nb][4] as sosgpu_profile; d_jout[nb] /
  * d_zz[nb] are written for the bins of wavelengths with zout != -1 only (both may be NULL when no wavelength has one).
@@ -602,19 +600,19 @@ typedef struct sosgpu_profile_wl {
     int64_t xk_off, ro_off, alt_off;
     int32_t nterm, nbins, absprofil, smax;
 } sosgpu_profile_wl;
-size_t sosgpu_profile_table_entry_bytes(void);
 /* level count NT of the no-gas grid of (tr, ta) (SOS_PROFIL.F:349-366), or -1: more than CTE_OS_NT levels / no scatterer */
 int  sosgpu_profile_nogas_levels(double tr, double ta);
+size_t sosgpu_profile_spectrum_work_bytes(int nwl);
 int  sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
                              const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
-                             void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
+                             void *d_work, size_t work_bytes, double *d_tabs, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
                              double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal, int *bad_wl, void *stream);
 /* ... with d_hvrai[nb][lp] for the concatenated bins, as sosgpu_profile_true (NULL = sosgpu_profile_spectrum) */
 int  sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
                                   const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
-                                  void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
-                                  double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal, int *bad_wl, double *d_hvrai,
-                                  void *stream);
+                                  void *d_work, size_t work_bytes, double *d_tabs, double *d_prof, int32_t *d_nt,
+                                  int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
+                                  int *bad_wl, double *d_hvrai, void *stream);
 
 /* Replaces the calls `CALL COEFF_ABS_CKD` of SOS_ABSPROFILE's gas and layer loops (src/SOS_ABSPROFILE.F:325-353; the routine:
  * src/SOS_SUB_TRS.F:171-393) for MANY wavelengths in one launch: k_i of every (gas, exponential term) table of every
@@ -632,8 +630,8 @@ int  sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_profile_wl *
  *                        [np][nt] of the (gas, term), for gas 0 [nc][np][nt]; NULL = no absorption (a term >= NEXP of the gas,
  *                        a table that is all zero): the slot's layers are written +0.0
  *   d_axes[axes_doubles] the axes and layer states, packed;  nlay 1..63 is common to the launch (49 in the reference)
- *   d_work               DEVICE work area of nwl * sosgpu_ckd_table_entry_bytes() + nslots * 8 bytes (8-byte aligned): table and
- *                        slot pointers are copied there on `stream` from a pinned block the library recycles
+ *   d_work, work_bytes   see "Work areas": the per-wavelength table and the slot pointers,
+ *                        sosgpu_ckd_layer_tables_work_bytes(nwl, nslots) bytes
  *   d_out[out_doubles]   every xk block is written in full (nothing needs clearing); it may be the d_gas buffer of
  *                        sosgpu_profile_spectrum, the xk_off being that call's, when this call is queued first on the same stream
  *   d_status[nwl]        int32, cleared by this call on `stream`, then 0 = ok, 1 = SOS_SPLINT met two equal temperature nodes
@@ -649,10 +647,10 @@ typedef struct sosgpu_ckd_wl {
     int64_t xk_off;
     int32_t nterm, nt, np, nc;
 } sosgpu_ckd_wl;
-size_t sosgpu_ckd_table_entry_bytes(void);
+size_t sosgpu_ckd_layer_tables_work_bytes(int nwl, int nslots);
 int  sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl *wl, int nslots, const double *const *ki,
-                             const double *d_axes, size_t axes_doubles, int nlay, void *d_work, double *d_out,
-                             size_t out_doubles, int32_t *d_status, int *bad_wl, void *stream);
+                             const double *d_axes, size_t axes_doubles, int nlay, void *d_work, size_t work_bytes,
+                             double *d_out, size_t out_doubles, int32_t *d_status, int *bad_wl, void *stream);
 
 /* Replaces SOS_MIE + SOS_FPHASE_MIE (src/SOS_MIE.F:205, :801) for a whole grid of size parameters, no MIE cache file:
  *   xmu[2 nbmu + 1]  cosines RMU(-nbmu:nbmu) of the Mie angle set (host); rn, in: refractive index (in <= 0)
@@ -674,11 +672,9 @@ int  sosgpu_mie(int device, int nbmu, const double *xmu, double rn, double in, i
  *       alphas[nalpha]   HOST, positive and ascending; jobs that pass the same pointer and length share one uploaded copy
  *       d_rec, d_g       DEVICE outputs of the job, [nalpha][4 + 3 (2 nbmu + 1)] REAL*4 and [nalpha] doubles as sosgpu_mie writes
  *                        them: the same bits (both entry points run the same device code per size parameter)
- *   d_work               DEVICE work area of sosgpu_mie_batch_work_bytes(nbmu, count, jobs) bytes, 8-byte aligned: the angle
- *                        set, the lists and the job table arrive there in ONE copy on `stream` from a pinned block the library
- *                        recycles; behind them the coefficient scratch of the sizes past alpha = 850, one for the whole batch:
- *                        min(such items, 2048) slots of 11 (2 A + 24) doubles, A the largest alpha of the batch.  Free again once
- *                        `stream` has passed the call.
+ *   d_work, work_bytes   see "Work areas": the angle set, the lists and the job table; behind them the coefficient scratch of
+ *                        the sizes past alpha = 850, one for the whole batch: min(such items, 2048) slots of 11 (2 A + 24)
+ *                        doubles, A the largest alpha of the batch
  *   d_status[count]      int32, cleared by this call on `stream`, then 0 = ok, bit 0 = a size parameter of the job did not fit
  *                        the coefficient arrays (what sosgpu_mie reports as SOSGPU_E_UNSUPPORTED after its own wait)
  * The work unit is one (job, size parameter), not one job: the items of all jobs are split by the size of their coefficient

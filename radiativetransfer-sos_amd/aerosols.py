@@ -209,6 +209,7 @@ def prefetch_mie_records(keys):
     parameters past the kernel's dimension) is left out: the call that needs its records reports it.  Returns {key: entry} of
     the sets it queued (the caller's reference: the cache may drop a set again under a small budget)."""
     import torch
+    from .solver import _work_area
     groups = collections.OrderedDict()
     for k in keys:
         k = (k[0], float(k[1]), float(k[2]), float(k[3]), float(k[4]), int(k[5]))
@@ -232,11 +233,11 @@ def prefetch_mie_records(keys):
             jobs[j] = capi.MieJob(k[1], k[2], al.ctypes.data, len(al), 0, rec.data_ptr(), g.data_ptr())
             sets.append((rec, g))
         L = capi.lib()
-        nbytes = L.sosgpu_mie_batch_work_bytes((w - 1) // 2, len(todo), jobs)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)                # (this stream's memory: free behind the call)
+        need = int(L.sosgpu_mie_batch_work_bytes((w - 1) // 2, len(todo), jobs))
+        work = _work_area(need, dev)
         status = torch.empty(len(todo), dtype=torch.int32, device=dev)
         rc = L.sosgpu_mie_batch(device, (w - 1) // 2, xmu.ctypes.data_as(C.c_void_p), len(todo), jobs, C.c_void_p(work.data_ptr()),
-                                nbytes, C.c_void_p(status.data_ptr()), C.c_void_p(st.cuda_stream))
+                                need, C.c_void_p(status.data_ptr()), C.c_void_p(st.cuda_stream))
         if rc == -3:
             raise AerosolError(_MIE_TOO_LARGE % max(k[4] for k, _ in todo))
         capi.check(rc, "sosgpu_mie_batch")

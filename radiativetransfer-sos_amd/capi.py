@@ -21,9 +21,9 @@ EXPORTS = [
     "sosgpu_granu_batch", "sosgpu_mie_batch", "sosgpu_mie_batch_work_bytes",
     "sosgpu_ctx_table_entry_bytes", "sosgpu_ctx_table", "sosgpu_os_solve_multi", "sosgpu_trim",
     "sosgpu_os_solve_levels", "sosgpu_output_levels", "sosgpu_os_solve_multi_levels",
-    "sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
-    "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes", "sosgpu_debug_solve_plan",
-    "sosgpu_noyaux_spectrum", "sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes",
+    "sosgpu_profile_spectrum", "sosgpu_profile_spectrum_work_bytes", "sosgpu_profile_nogas_levels", "sosgpu_debug_roundtrip",
+    "sosgpu_debug_tables", "sosgpu_ckd_layer_tables", "sosgpu_ckd_layer_tables_work_bytes", "sosgpu_debug_solve_plan",
+    "sosgpu_noyaux_spectrum", "sosgpu_noyaux_spectrum_work_bytes", "sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes",
     "sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes", "sosgpu_debug_stage_blocks",
     "sosgpu_profile_true", "sosgpu_profile_spectrum_true", "sosgpu_output_depths", "sosgpu_level_transmission",
     "sosgpu_channel_accumulate", "sosgpu_channel_accumulate_work_bytes", "sosgpu_channel_finish",
@@ -153,8 +153,10 @@ def lib():
         L.sosgpu_set_surface_matrices_async.argtypes = [vp, vp, vp]
         L.sosgpu_noyaux.restype = i32
         L.sosgpu_noyaux.argtypes = [vp, vp]
+        L.sosgpu_noyaux_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_noyaux_spectrum_work_bytes.argtypes = [i32]
         L.sosgpu_noyaux_spectrum.restype = i32
-        L.sosgpu_noyaux_spectrum.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), vp, vp]
+        L.sosgpu_noyaux_spectrum.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), vp, C.c_size_t, vp]
         L.sosgpu_noyaux_fetch.restype = i32
         L.sosgpu_noyaux_fetch.argtypes = [vp, i32, vp]
         L.sosgpu_os_solve.restype = i32
@@ -212,19 +214,20 @@ def lib():
         L.sosgpu_profile_true.argtypes = L.sosgpu_profile.argtypes[:-1] + [vp, vp]
         L.sosgpu_profile_nogas.restype = i32
         L.sosgpu_profile_nogas.argtypes = [i32, dbl, dbl, dbl, dbl, vp, vp]
-        L.sosgpu_profile_table_entry_bytes.restype = C.c_size_t
-        L.sosgpu_profile_table_entry_bytes.argtypes = []
+        L.sosgpu_profile_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_profile_spectrum_work_bytes.argtypes = [i32]
         L.sosgpu_profile_nogas_levels.restype = i32
         L.sosgpu_profile_nogas_levels.argtypes = [dbl, dbl]
         L.sosgpu_profile_spectrum.restype = i32
-        L.sosgpu_profile_spectrum.argtypes = [i32, i32, vp, i32, vp, vp, vp, C.c_size_t, i32, i32, vp, vp, vp, vp, vp, vp, vp,
-                                              vp, vp, vp, C.POINTER(i32), vp]
+        L.sosgpu_profile_spectrum.argtypes = [i32, i32, vp, i32, vp, vp, vp, C.c_size_t, i32, i32, vp, C.c_size_t, vp, vp, vp, vp,
+                                              vp, vp, vp, vp, C.POINTER(i32), vp]
         L.sosgpu_profile_spectrum_true.restype = i32
         L.sosgpu_profile_spectrum_true.argtypes = L.sosgpu_profile_spectrum.argtypes[:-1] + [vp, vp]
-        L.sosgpu_ckd_table_entry_bytes.restype = C.c_size_t
-        L.sosgpu_ckd_table_entry_bytes.argtypes = []
+        L.sosgpu_ckd_layer_tables_work_bytes.restype = C.c_size_t
+        L.sosgpu_ckd_layer_tables_work_bytes.argtypes = [i32, i32]
         L.sosgpu_ckd_layer_tables.restype = i32
-        L.sosgpu_ckd_layer_tables.argtypes = [i32, i32, vp, i32, vp, vp, C.c_size_t, i32, vp, vp, C.c_size_t, vp, C.POINTER(i32), vp]
+        L.sosgpu_ckd_layer_tables.argtypes = [i32, i32, vp, i32, vp, vp, C.c_size_t, i32, vp, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(i32),
+                                              vp]
         L.sosgpu_os_flops.restype = i32
         L.sosgpu_os_flops.argtypes = [vp, i32, vp, vp, vp, C.POINTER(dbl)]
         L.sosgpu_last_solve_ms.restype = i32
@@ -238,13 +241,13 @@ def lib():
         L.sosgpu_trphi_spectrum_work_bytes.restype = C.c_size_t
         L.sosgpu_trphi_spectrum_work_bytes.argtypes = [i32]
         L.sosgpu_trphi_spectrum.restype = i32
-        L.sosgpu_trphi_spectrum.argtypes = [C.POINTER(TrphiJob), i32, vp, i32, vp, vp, vp]
+        L.sosgpu_trphi_spectrum.argtypes = [C.POINTER(TrphiJob), i32, vp, i32, vp, vp, C.c_size_t, vp]
         L.sosgpu_level_flux.restype = i32
         L.sosgpu_level_flux.argtypes = [vp, vp, vp, vp]
         L.sosgpu_level_flux_spectrum_work_bytes.restype = C.c_size_t
         L.sosgpu_level_flux_spectrum_work_bytes.argtypes = [i32]
         L.sosgpu_level_flux_spectrum.restype = i32
-        L.sosgpu_level_flux_spectrum.argtypes = [C.POINTER(FluxJob), i32, vp, vp, vp]
+        L.sosgpu_level_flux_spectrum.argtypes = [C.POINTER(FluxJob), i32, vp, vp, C.c_size_t, vp]
         L.sosgpu_channel_accumulate_work_bytes.restype = C.c_size_t
         L.sosgpu_channel_accumulate_work_bytes.argtypes = [i32, i32]
         L.sosgpu_channel_accumulate.restype = i32

@@ -483,6 +483,32 @@ public:
         return e;
     }
 };
+
+// Work areas (include/sosgpu.h, "Work areas").  A layout is written once, as a function that take()s its sections in order: the
+// _work_bytes query returns its total, the call places its pointers at the offsets take() gave.
+struct WorkLayout {
+    size_t total = 0;
+    // a section of `bytes` at the running total, which then moves to the next multiple of `align` behind it
+    size_t take(size_t bytes, size_t align)
+    {
+        const size_t at = total;
+        total = (total + bytes + align - 1) & ~(align - 1);
+        return at;
+    }
+};
+
+// what every table-form call asks of its area: there, 8-byte aligned, `need` bytes at least
+bool work_area_ok(const void *d_work, size_t work_bytes, size_t need)
+{
+    return d_work && ((uintptr_t)d_work & 7) == 0 && work_bytes >= need;
+}
+
+// closing of a host-synchronous entry point: `st` is waited for whatever `e` says; the first error of the two
+hipError_t finish_sync(hipError_t e, hipStream_t st)
+{
+    const hipError_t s = hipStreamSynchronize(st);
+    return e == hipSuccess ? s : e;
+}
 }   // namespace
 
 extern "C" int sosgpu_trim(void)
@@ -631,11 +657,32 @@ extern "C" int sosgpu_noyaux(sosgpu_ctx *cx, void *stream)
 // sosgpu_set_surface_matrices_async + sosgpu_noyaux of nctx contexts in at most five launches (the table forms of their
 // kernels, noyaux.hip / k_pack_ground_table).  d_work = [SosDev entries | matrix pointers], filled by one copy from a recycled
 // pinned block (Staged).  Everything is checked before a context is touched.
-extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const float *const *d_rsurf, void *d_work, void *stream)
+namespace {
+struct NoyauxLayout { size_t tab, rsurf, total; };
+NoyauxLayout noyaux_layout(int nctx)
+{
+    static_assert(sizeof(SosDev) % 8 == 0, "the pointer list follows the entries");
+    WorkLayout w;
+    NoyauxLayout L;
+    L.tab = w.take((size_t)nctx * sizeof(SosDev), 8);
+    L.rsurf = w.take((size_t)nctx * sizeof(const float *), 8);
+    L.total = w.total;
+    return L;
+}
+}   // namespace
+
+extern "C" size_t sosgpu_noyaux_spectrum_work_bytes(int nctx)
+{
+    return nctx > 0 && nctx <= 65535 ? noyaux_layout(nctx).total : 0;
+}
+
+extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const float *const *d_rsurf, void *d_work,
+                                      size_t work_bytes, void *stream)
 {
     if (!ctxs || !d_work || nctx < 0 || nctx > 65535) return SOSGPU_E_ARG;
     if (nctx == 0) return SOSGPU_OK;
-    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    const NoyauxLayout L = noyaux_layout(nctx);
+    if (!work_area_ok(d_work, work_bytes, L.total)) return SOSGPU_E_ARG;
     NoyauxTableGrid g = {0, 0, 0};
     size_t gnd_elems = 0;                       // ground launch: largest max(per, 3N) and smax over the contexts with matrices
     int gnd_smax = -1;
@@ -650,13 +697,11 @@ extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const f
         if (r) { gnd_elems = std::max(gnd_elems, std::max(per, (size_t)3 * cx->d.n)); gnd_smax = std::max(gnd_smax, cx->d.smax); }
     }
     HIPCHK(hipSetDevice(ctxs[0]->device));
-    const size_t n_tab = (size_t)nctx * sizeof(SosDev), n_all = n_tab + (size_t)nctx * sizeof(const float *);
-    static_assert(sizeof(SosDev) % 8 == 0, "the pointer list follows the entries");
-    Staged s(ctxs[0]->device, n_all);
+    Staged s(ctxs[0]->device, L.total);
     if (s.rc) return s.rc;
     char *stage = static_cast<char *>(s.host());
-    SosDev *tab = reinterpret_cast<SosDev *>(stage);
-    const float **rs = reinterpret_cast<const float **>(stage + n_tab);
+    SosDev *tab = reinterpret_cast<SosDev *>(stage + L.tab);
+    const float **rs = reinterpret_cast<const float **>(stage + L.rsurf);
     for (int i = 0; i < nctx; i++) {
         sosgpu_ctx *cx = ctxs[i];
         rs[i] = d_rsurf ? d_rsurf[i] : nullptr;
@@ -666,10 +711,11 @@ extern "C" int sosgpu_noyaux_spectrum(sosgpu_ctx *const *ctxs, int nctx, const f
     }
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(s.send(d_work, st));
-    const SosDev *d_tab = static_cast<const SosDev *>(d_work);
+    char *dp = static_cast<char *>(d_work);
+    const SosDev *d_tab = reinterpret_cast<const SosDev *>(dp + L.tab);
     if (gnd_smax >= 0) {
         dim3 grid((unsigned)((gnd_elems + 255) / 256), (unsigned)gnd_smax + 1, (unsigned)nctx);
-        k_pack_ground_table<<<grid, 256, 0, st>>>(d_tab, reinterpret_cast<const float *const *>(static_cast<char *>(d_work) + n_tab));
+        k_pack_ground_table<<<grid, 256, 0, st>>>(d_tab, reinterpret_cast<const float *const *>(dp + L.rsurf));
     }
     launch_noyaux_table(d_tab, nctx, g, st);
     HIPCHK(hipGetLastError());
@@ -932,21 +978,20 @@ bool trans_layout(int n, int kp, int nctx, int nb, int lp, TransLayout *out)
     const size_t nchild = (size_t)nctx * n, nitems = (size_t)nb * n;
     // children and items are counted in int by the kernels and the solver; the item kernel has one thread per profile element
     if (nchild > (size_t)INT_MAX || nitems > (size_t)INT_MAX || nitems * 3 * lp / 256 >= (size_t)INT_MAX) return false;
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+    WorkLayout w;
     TransLayout L;
-    L.parents = take((size_t)nctx * sizeof(SosDev));
-    L.children = take(nchild * sizeof(SosDev));
-    L.sv = take(nchild * 4 * kp * sizeof(double));
-    L.ctx_of_item = take(nitems * sizeof(int32_t));
-    L.nt = take(nitems * sizeof(int32_t));
-    L.iborm = take(nitems * sizeof(int32_t));
-    L.norders = take(nitems * sizeof(int32_t));
-    L.iglast = take(nitems * sizeof(int32_t));
-    L.flux = take(nitems * 2 * sizeof(double));
-    L.rec = take(nitems * 3 * (2 * (size_t)n + 1) * sizeof(double));
-    L.prof = take(nitems * 3 * lp * sizeof(double));
-    L.total = o + 256;                                      // (the caller's area need only be 8-byte aligned)
+    L.parents = w.take((size_t)nctx * sizeof(SosDev), 256);
+    L.children = w.take(nchild * sizeof(SosDev), 256);
+    L.sv = w.take(nchild * 4 * kp * sizeof(double), 256);
+    L.ctx_of_item = w.take(nitems * sizeof(int32_t), 256);
+    L.nt = w.take(nitems * sizeof(int32_t), 256);
+    L.iborm = w.take(nitems * sizeof(int32_t), 256);
+    L.norders = w.take(nitems * sizeof(int32_t), 256);
+    L.iglast = w.take(nitems * sizeof(int32_t), 256);
+    L.flux = w.take(nitems * 2 * sizeof(double), 256);
+    L.rec = w.take(nitems * 3 * (2 * (size_t)n + 1) * sizeof(double), 256);
+    L.prof = w.take(nitems * 3 * lp * sizeof(double), 256);
+    L.total = w.total + 256;                                // (the caller's area need only be 8-byte aligned)
     *out = L;
     return true;
 }
@@ -978,10 +1023,9 @@ static int trans_stage(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_o
 {
     if (!d_nt || !d_prof || !d_out || !d_work || nb < 0 || lp < 2) return SOSGPU_E_ARG;
     if (!trans_ctxs_ok(ctxs, nctx) || (!d_ctx_of_bin && nctx > 1)) return SOSGPU_E_ARG;
-    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
     const SosDev &p0 = ctxs[0]->d;
     TransLayout L;
-    if (!trans_layout(p0.n, p0.kp, nctx, nb, lp, &L) || work_bytes < L.total) return SOSGPU_E_ARG;
+    if (!trans_layout(p0.n, p0.kp, nctx, nb, lp, &L) || !work_area_ok(d_work, work_bytes, L.total)) return SOSGPU_E_ARG;
     if (const int rc = sos_os_variant(p0.n, lp - 1, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
     if (nb == 0) return SOSGPU_OK;
     const int device = ctxs[0]->device;
@@ -1393,9 +1437,7 @@ extern "C" int sosgpu_glitter(int device, int n, const double *mu, const double 
         launch_glitter(n, d_buf, sigma2_of_wind(wind), os_nb, os_ns, os_nm, d_buf + n, d_il, d_e, d_rsurf, st);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    HIPCHK(e);
+    HIPCHK(finish_sync(e, st));
     return SOSGPU_OK;
 }
 
@@ -1427,18 +1469,19 @@ extern "C" int sosgpu_trphi(sosgpu_ctx *cx, int nf, const double *d_rec, double 
 
 extern "C" size_t sosgpu_trphi_spectrum_work_bytes(int njobs)
 {
-    return njobs > 0 ? (size_t)njobs * sizeof(TrphiJobDev) : 0;
+    static_assert(sizeof(TrphiJobDev) % 8 == 0, "entries of pointers and doubles");
+    return njobs > 0 && njobs <= 65535 ? (size_t)njobs * sizeof(TrphiJobDev) : 0;
 }
 
 // sosgpu_trphi of njobs (context, record, azimuth range) jobs in ONE launch (k_trphi_table).  d_work = the job entries, filled
 // by one copy from a recycled pinned block (Staged).  Everything is checked before anything is queued.
 extern "C" int sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, const double *d_phi, int nphi_total,
-                                     double *d_out, void *d_work, void *stream)
+                                     double *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    if (!jobs || !d_phi || !d_out || !d_work || njobs < 0 || njobs > 65535) return SOSGPU_E_ARG;
-    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    if (!jobs || !d_phi || !d_out || njobs < 0 || njobs > 65535) return SOSGPU_E_ARG;
+    const size_t need = sosgpu_trphi_spectrum_work_bytes(njobs);
+    if (!work_area_ok(d_work, work_bytes, need)) return SOSGPU_E_ARG;
     if (njobs == 0) return SOSGPU_OK;
-    static_assert(sizeof(TrphiJobDev) % 8 == 0, "entries of pointers and doubles");
     long long nblocks = 0;
     int w_max = 0;
     bool nadal = false;
@@ -1455,7 +1498,7 @@ extern "C" int sosgpu_trphi_spectrum(const sosgpu_trphi_job *jobs, int njobs, co
     if (nblocks > 0x7fffffffLL) return SOSGPU_E_ARG;                 // (one grid dimension, first_block an int32)
     if (nadal) return SOSGPU_E_UNSUPPORTED;                          // Nadal: refused by the reference's SOS_PROC as well
     HIPCHK(hipSetDevice(jobs[0].cx->device));
-    Staged s(jobs[0].cx->device, (size_t)njobs * sizeof(TrphiJobDev));
+    Staged s(jobs[0].cx->device, need);
     if (s.rc) return s.rc;
     TrphiJobDev *tab = static_cast<TrphiJobDev *>(s.host());
     int first = 0;
@@ -1492,23 +1535,25 @@ extern "C" int sosgpu_level_flux(sosgpu_ctx *cx, const double *d_rec, double *d_
 
 extern "C" size_t sosgpu_level_flux_spectrum_work_bytes(int njobs)
 {
-    return njobs > 0 ? (size_t)njobs * sizeof(FluxJobDev) : 0;
+    static_assert(sizeof(FluxJobDev) % 8 == 0, "entries of pointers");
+    return njobs > 0 && njobs <= 0x3fffffff ? (size_t)njobs * sizeof(FluxJobDev) : 0;    // (2 njobs threads, an int32)
 }
 
 // sosgpu_level_flux of njobs (context, record) jobs in ONE launch (k_level_flux_table).  d_work = the job entries, filled by one
 // copy from a recycled pinned block (Staged).  Everything is checked before anything is queued.
-extern "C" int sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out, void *d_work, void *stream)
+extern "C" int sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out, void *d_work, size_t work_bytes,
+                                          void *stream)
 {
-    if (!jobs || !d_out || !d_work || njobs < 0 || njobs > 0x3fffffff) return SOSGPU_E_ARG;    // (2 njobs threads, an int32)
-    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
+    if (!jobs || !d_out || njobs < 0 || njobs > 0x3fffffff) return SOSGPU_E_ARG;
+    const size_t need = sosgpu_level_flux_spectrum_work_bytes(njobs);
+    if (!work_area_ok(d_work, work_bytes, need)) return SOSGPU_E_ARG;
     if (njobs == 0) return SOSGPU_OK;
-    static_assert(sizeof(FluxJobDev) % 8 == 0, "entries of pointers");
     for (int i = 0; i < njobs; i++)
         if (!jobs[i].cx || !jobs[i].d_rec) return SOSGPU_E_ARG;
     for (int i = 1; i < njobs; i++)
         if (jobs[i].cx->device != jobs[0].cx->device) return SOSGPU_E_ARG;
     HIPCHK(hipSetDevice(jobs[0].cx->device));
-    Staged s(jobs[0].cx->device, (size_t)njobs * sizeof(FluxJobDev));
+    Staged s(jobs[0].cx->device, need);
     if (s.rc) return s.rc;
     FluxJobDev *tab = static_cast<FluxJobDev *>(s.host());
     for (int i = 0; i < njobs; i++) {
@@ -1531,11 +1576,23 @@ static bool channel_shape_ok(int nchan, int nslots, int nphi, int w)
 }
 
 // the term table in the work area: wgt[nterms] | first[nchan + 1] | job[nterms], rounded up to 8 bytes
+namespace {
+struct ChannelLayout { size_t wgt, first, job, total; };
+ChannelLayout channel_layout(int nchan, int nterms)
+{
+    WorkLayout w;
+    ChannelLayout L;
+    L.wgt = w.take((size_t)nterms * sizeof(double), 8);
+    L.first = w.take(((size_t)nchan + 1) * sizeof(int32_t), 4);
+    L.job = w.take((size_t)nterms * sizeof(int32_t), 8);
+    L.total = w.total;
+    return L;
+}
+}   // namespace
+
 extern "C" size_t sosgpu_channel_accumulate_work_bytes(int nchan, int nterms)
 {
-    if (nchan < 1 || nterms < 0) return 0;
-    const size_t n = (size_t)nterms * (sizeof(double) + sizeof(int32_t)) + ((size_t)nchan + 1) * sizeof(int32_t);
-    return (n + 7) & ~(size_t)7;
+    return nchan < 1 || nterms < 0 ? 0 : channel_layout(nchan, nterms).total;
 }
 
 // The terms of nchan channels onto the accumulator in ONE launch (k_channel_accumulate).  d_work = the term table, filled by one
@@ -1546,30 +1603,29 @@ extern "C" int sosgpu_channel_accumulate(int device, const double *d_blocks, int
 {
     if (!d_blocks || !first || !job || !wgt || !d_acc || !d_work || njobs < 1) return SOSGPU_E_ARG;
     if (!channel_shape_ok(nchan, nslots, nphi, w)) return SOSGPU_E_ARG;
-    if ((unsigned long long)d_work & 7) return SOSGPU_E_ARG;
     if (first[0] != 0) return SOSGPU_E_ARG;
     for (int c = 0; c < nchan; c++)
         if (first[c + 1] < first[c]) return SOSGPU_E_ARG;
     const int nterms = first[nchan];
     for (int m = 0; m < nterms; m++)
         if (job[m] < 0 || job[m] >= njobs || !std::isfinite(wgt[m])) return SOSGPU_E_ARG;
-    const size_t bytes = sosgpu_channel_accumulate_work_bytes(nchan, nterms);
-    if (work_bytes < bytes) return SOSGPU_E_ARG;
+    const ChannelLayout L = channel_layout(nchan, nterms);
+    if (!work_area_ok(d_work, work_bytes, L.total)) return SOSGPU_E_ARG;
     if (nterms == 0) return SOSGPU_OK;
     if (const int rc = use_device(device)) return rc;
-    Staged s(device, bytes);
+    Staged s(device, L.total);
     if (s.rc) return s.rc;
     char *hp = static_cast<char *>(s.host());
-    const size_t off_first = (size_t)nterms * sizeof(double), off_job = off_first + ((size_t)nchan + 1) * sizeof(int32_t);
-    memcpy(hp, wgt, off_first);
-    memcpy(hp + off_first, first, off_job - off_first);
-    memcpy(hp + off_job, job, (size_t)nterms * sizeof(int32_t));
-    if (bytes > off_job + (size_t)nterms * sizeof(int32_t)) memset(hp + off_job + (size_t)nterms * sizeof(int32_t), 0, 4);
+    const size_t job_end = L.job + (size_t)nterms * sizeof(int32_t);
+    memcpy(hp + L.wgt, wgt, (size_t)nterms * sizeof(double));
+    memcpy(hp + L.first, first, ((size_t)nchan + 1) * sizeof(int32_t));
+    memcpy(hp + L.job, job, (size_t)nterms * sizeof(int32_t));
+    memset(hp + job_end, 0, L.total - job_end);                        // (the padding to 8 bytes)
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(s.send(d_work, st));
     const char *dp = static_cast<const char *>(d_work);
-    launch_channel_accumulate(d_blocks, nslots, nphi, w, nchan, reinterpret_cast<const int32_t *>(dp + off_first),
-                              reinterpret_cast<const int32_t *>(dp + off_job), reinterpret_cast<const double *>(dp), d_acc, st);
+    launch_channel_accumulate(d_blocks, nslots, nphi, w, nchan, reinterpret_cast<const int32_t *>(dp + L.first),
+                              reinterpret_cast<const int32_t *>(dp + L.job), reinterpret_cast<const double *>(dp + L.wgt), d_acc, st);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;
 }
@@ -1618,9 +1674,7 @@ extern "C" int sosgpu_land_surface(int device, const sosgpu_land *land, int n, c
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(err, d_err, sizeof err, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    HIPCHK(e);
+    HIPCHK(finish_sync(e, st));
     if (ier_out) *ier_out = err[0] ? -1 : 0;
     return SOSGPU_OK;
 }
@@ -1716,24 +1770,25 @@ int surface_plan(int n, int os_nb, int os_ns, int os_nm, const sosgpu_surface_jo
             pl->job_trip[j] = it->second;
         }
     }
-    auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
     const size_t npairs = (size_t)n * (n + 1) / 2, nn = (size_t)n * n, cnt = (size_t)(os_nb + 1) * 9 * nn;
     const size_t nan = (size_t)pl->nan(), ntrip = pl->trip.size(), nrefl = pl->refl.size();
-    pl->o_fc = (size_t)n * 8;
-    pl->o_par0 = pl->o_fc + pl->inds.size() * 4 * (os_ns + 1) * 8;
-    pl->o_par1 = pl->o_par0 + (size_t)nwind * 8;
-    pl->o_refl = pl->o_par1 + (size_t)ncm * 8;
-    pl->o_trip = pl->o_refl + nrefl * sizeof(SurfReflSet);
-    pl->o_jobs = pl->o_trip + ntrip * sizeof(SurfTriple);
-    pl->o_models = pl->o_jobs + (size_t)njobs * sizeof(SurfJobDev);
-    pl->o_flags = pl->o_models + up8(pl->models.size() * 4);
-    pl->table_bytes = pl->o_flags + up8(ntrip * 4);
-    pl->o_il = pl->table_bytes;
-    pl->o_e = pl->o_il + up8(nan * npairs * 4);
-    pl->o_ilnn = pl->o_e + nan * npairs * (os_nm + 1) * 8;
-    pl->o_enn = pl->o_ilnn + up8(ntrip * nn * 4);
-    pl->o_rb = pl->o_enn + ntrip * nn * (os_nb + 1) * 8;
-    pl->total = pl->o_rb + up8(nrefl * cnt * 4);
+    WorkLayout w;
+    w.take((size_t)n * 8, 8);                                  // mu, at the start of the area
+    pl->o_fc = w.take(pl->inds.size() * 4 * (os_ns + 1) * 8, 8);
+    pl->o_par0 = w.take((size_t)nwind * 8, 8);
+    pl->o_par1 = w.take((size_t)ncm * 8, 8);
+    pl->o_refl = w.take(nrefl * sizeof(SurfReflSet), 8);
+    pl->o_trip = w.take(ntrip * sizeof(SurfTriple), 8);
+    pl->o_jobs = w.take((size_t)njobs * sizeof(SurfJobDev), 8);
+    pl->o_models = w.take(pl->models.size() * 4, 8);
+    pl->o_flags = w.take(ntrip * 4, 8);
+    pl->table_bytes = w.total;                                 // (what travels in the staged copy)
+    pl->o_il = w.take(nan * npairs * 4, 8);
+    pl->o_e = w.take(nan * npairs * (os_nm + 1) * 8, 8);
+    pl->o_ilnn = w.take(ntrip * nn * 4, 8);
+    pl->o_enn = w.take(ntrip * nn * (os_nb + 1) * 8, 8);
+    pl->o_rb = w.take(nrefl * cnt * 4, 8);
+    pl->total = w.total;
     return SOSGPU_OK;
 }
 }   // namespace
@@ -1755,7 +1810,7 @@ extern "C" int sosgpu_surface_batch(int device, int n, const double *mu, const d
     if (const int rc = surface_plan(n, os_nb, os_ns, os_nm, jobs, njobs, &pl)) return rc;
     for (int j = 0; j < njobs; j++)
         if (!jobs[j].d_rsurf) return SOSGPU_E_ARG;
-    if (((unsigned long long)d_work & 7) || work_bytes < pl.total) return SOSGPU_E_ARG;
+    if (!work_area_ok(d_work, work_bytes, pl.total)) return SOSGPU_E_ARG;
     if (njobs == 0) return SOSGPU_OK;
     if (const int rc = use_device(device)) return rc;
     Staged s(device, pl.table_bytes);
@@ -1908,7 +1963,22 @@ extern "C" int sosgpu_absprofile(int device, int nb, int nlev, int nterm, const 
 // ---------------------------------------------------------------------------------------------
 // The profile stage of many wavelengths as three launches (profile.hip, the *_table kernels).
 // ---------------------------------------------------------------------------------------------
-extern "C" size_t sosgpu_profile_table_entry_bytes(void) { return sizeof(ProfileWl); }
+// work area: the no-gas blocks [nwl][4][SOSGPU_NOGAS_LEVELS] | the per-wavelength table
+namespace {
+struct ProfileLayout { size_t nogas, tab, total; };
+ProfileLayout profile_layout(int nwl)
+{
+    static_assert(sizeof(ProfileWl) % 8 == 0, "entries of doubles and int64");
+    WorkLayout w;
+    ProfileLayout L;
+    L.nogas = w.take((size_t)nwl * 4 * SOSGPU_NOGAS_LEVELS * sizeof(double), 8);
+    L.tab = w.take((size_t)nwl * sizeof(ProfileWl), 8);
+    L.total = w.total;
+    return L;
+}
+}   // namespace
+
+extern "C" size_t sosgpu_profile_spectrum_work_bytes(int nwl) { return nwl < 1 ? 0 : profile_layout(nwl).total; }
 
 extern "C" int sosgpu_profile_nogas_levels(double tr, double ta)
 {
@@ -1919,12 +1989,14 @@ extern "C" int sosgpu_profile_nogas_levels(double tr, double ta)
 
 extern "C" int sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
                                             const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
-                                            void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt,
+                                            void *d_work, size_t work_bytes, double *d_tabs, double *d_prof, int32_t *d_nt,
                                             int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
                                             int *bad_wl, double *d_hvrai, void *stream)
 {
     if (bad_wl) *bad_wl = -1;
-    if (nwl < 1 || !wl || nb < 1 || lp < 2 || !d_wl_of_bin || !d_table || !d_nogas) return SOSGPU_E_ARG;
+    if (nwl < 1 || !wl || nb < 1 || lp < 2 || !d_wl_of_bin) return SOSGPU_E_ARG;
+    const ProfileLayout L = profile_layout(nwl);
+    if (!work_area_ok(d_work, work_bytes, L.total)) return SOSGPU_E_ARG;
     if (!d_prof || !d_nt || !d_iborm || !d_zprof || !d_scal) return SOSGPU_E_ARG;
     if ((d_jout == nullptr) != (d_zz == nullptr)) return SOSGPU_E_ARG;
     // --- the rules of sosgpu_profile / sosgpu_absprofile, per wavelength, before anything is queued
@@ -1960,12 +2032,14 @@ extern "C" int sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_pr
     if (bins != nb) return SOSGPU_E_ARG;
     if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // --- the table: pinned block -> d_table on the caller's stream, nothing waited for
+    // --- the table: pinned block -> the work area on the caller's stream, nothing waited for
     Staged s(device, (size_t)nwl * sizeof(ProfileWl));
     if (s.rc) return s.rc;
     memcpy(s.host(), tab.data(), (size_t)nwl * sizeof(ProfileWl));
-    HIPCHK(s.send(d_table, st));
-    const ProfileWl *d_tab = (const ProfileWl *)d_table;
+    char *dp = static_cast<char *>(d_work);
+    HIPCHK(s.send(dp + L.tab, st));
+    const ProfileWl *d_tab = reinterpret_cast<const ProfileWl *>(dp + L.tab);
+    double *d_nogas = reinterpret_cast<double *>(dp + L.nogas);
     const int NG = SOSGPU_NOGAS_LEVELS;
     launch_profile_nogas_table(d_tab, nwl, d_nogas, NG, st);
     HIPCHK(hipGetLastError());
@@ -1985,25 +2059,44 @@ extern "C" int sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_pr
 
 extern "C" int sosgpu_profile_spectrum(int device, int nwl, const sosgpu_profile_wl *wl, int nb, const int32_t *d_wl_of_bin,
                                        const int32_t *d_ik, const double *d_gas, size_t gas_doubles, int nblev, int lp,
-                                       void *d_table, double *d_nogas, double *d_tabs, double *d_prof, int32_t *d_nt,
+                                       void *d_work, size_t work_bytes, double *d_tabs, double *d_prof, int32_t *d_nt,
                                        int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
                                        int *bad_wl, void *stream)
 {
-    return sosgpu_profile_spectrum_true(device, nwl, wl, nb, d_wl_of_bin, d_ik, d_gas, gas_doubles, nblev, lp, d_table, d_nogas,
+    return sosgpu_profile_spectrum_true(device, nwl, wl, nb, d_wl_of_bin, d_ik, d_gas, gas_doubles, nblev, lp, d_work, work_bytes,
                                         d_tabs, d_prof, d_nt, d_iborm, d_zprof, d_jout, d_zz, d_scal, bad_wl, nullptr, stream);
 }
 
 // COEFF_ABS_CKD of many wavelengths in one launch (ckd.hip): the per-wavelength table and the slot pointers go through one
 // recycled pinned block into the caller's work area, the status words are cleared, the kernel is queued -- all on `stream`.
-extern "C" size_t sosgpu_ckd_table_entry_bytes(void) { return sizeof(CkdWl); }
+// work area: the per-wavelength table | the slot pointers
+namespace {
+struct CkdLayout { size_t tab, slots, total; };
+CkdLayout ckd_layout(int nwl, int nslots)
+{
+    static_assert(sizeof(CkdWl) % 8 == 0, "the slot pointers follow the entries");
+    WorkLayout w;
+    CkdLayout L;
+    L.tab = w.take((size_t)nwl * sizeof(CkdWl), 8);
+    L.slots = w.take((size_t)nslots * sizeof(double *), 8);
+    L.total = w.total;
+    return L;
+}
+}   // namespace
+
+extern "C" size_t sosgpu_ckd_layer_tables_work_bytes(int nwl, int nslots)
+{
+    return nwl < 1 || nslots < 1 ? 0 : ckd_layout(nwl, nslots).total;
+}
 
 extern "C" int sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl *wl, int nslots, const double *const *ki,
-                                       const double *d_axes, size_t axes_doubles, int nlay, void *d_work, double *d_out,
-                                       size_t out_doubles, int32_t *d_status, int *bad_wl, void *stream)
+                                       const double *d_axes, size_t axes_doubles, int nlay, void *d_work, size_t work_bytes,
+                                       double *d_out, size_t out_doubles, int32_t *d_status, int *bad_wl, void *stream)
 {
     if (bad_wl) *bad_wl = -1;
-    if (nwl < 1 || !wl || nslots < 1 || !ki || !d_axes || !d_work || !d_out || !d_status) return SOSGPU_E_ARG;
-    if (((uintptr_t)d_work & 7) != 0) return SOSGPU_E_ARG;
+    if (nwl < 1 || !wl || nslots < 1 || !ki || !d_axes || !d_out || !d_status) return SOSGPU_E_ARG;
+    const CkdLayout L = ckd_layout(nwl, nslots);
+    if (!work_area_ok(d_work, work_bytes, L.total)) return SOSGPU_E_ARG;
     if (nlay < 1 || nlay > SOS_CKD_NLAY_MAX) return SOSGPU_E_UNSUPPORTED;
     // --- limits and argument rules per wavelength, before anything is queued
     std::vector<CkdWl> tab((size_t)nwl);
@@ -2034,16 +2127,16 @@ extern "C" int sosgpu_ckd_layer_tables(int device, int nwl, const sosgpu_ckd_wl 
     if (slots != nslots) return SOSGPU_E_ARG;
     if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t tbytes = (size_t)nwl * sizeof(CkdWl), pbytes = (size_t)nslots * sizeof(double *);
-    Staged s(device, tbytes + pbytes);
+    Staged s(device, L.total);
     if (s.rc) return s.rc;
     char *hp = (char *)s.host();
-    memcpy(hp, tab.data(), tbytes);
-    memcpy(hp + tbytes, ki, pbytes);
+    memcpy(hp + L.tab, tab.data(), (size_t)nwl * sizeof(CkdWl));
+    memcpy(hp + L.slots, ki, (size_t)nslots * sizeof(double *));
     HIPCHK(s.send(d_work, st));
     HIPCHK(hipMemsetAsync(d_status, 0, (size_t)nwl * sizeof(int32_t), st));
-    launch_coeff_abs_ckd_table((const CkdWl *)d_work, nwl, max_slots, (const double *const *)((const char *)d_work + tbytes), d_axes,
-                               nlay, d_out, d_status, st);
+    const char *dp = (const char *)d_work;
+    launch_coeff_abs_ckd_table((const CkdWl *)(dp + L.tab), nwl, max_slots, (const double *const *)(dp + L.slots), d_axes, nlay,
+                               d_out, d_status, st);
     HIPCHK(hipGetLastError());
     return SOSGPU_OK;
 }
@@ -2081,8 +2174,7 @@ extern "C" int sosgpu_mie(int device, int nbmu, const double *xmu, double rn, do
         if (rc == 0) e = hipGetLastError();
     }
     if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
+    e = finish_sync(e, st);
     if (rc == -3) return SOSGPU_E_UNSUPPORTED;
     if (rc == -2) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
     HIPCHK(e);
@@ -2099,7 +2191,8 @@ struct MieBatchPlan {
     std::vector<std::pair<const double *, int>> lists;       // the distinct lists, in upload order
     int nitems[MIE_BATCH_CLASSES + 1];
     double scr_alpha;
-    size_t al_doubles, head_bytes, scr_doubles;
+    size_t al_doubles, scr_doubles;
+    size_t o_al, o_tab, o_first, head_bytes, o_scr, total;
 };
 
 int mie_batch_plan(int nbmu, int count, const sosgpu_mie_job *jobs, MieBatchPlan &p)
@@ -2148,9 +2241,15 @@ int mie_batch_plan(int nbmu, int count, const sosgpu_mie_job *jobs, MieBatchPlan
         p.first[(size_t)c * (count + 1) + count] = (int)n[c];
         p.nitems[c] = (int)n[c];
     }
-    p.head_bytes = ((size_t)W + p.al_doubles) * sizeof(double) + (size_t)count * sizeof(MieBatchJob) +
-                   (((size_t)NC * (count + 1) * sizeof(int) + 7) & ~(size_t)7);
     p.scr_doubles = p.nitems[NC - 1] ? (size_t)mie_batch_slots(p.nitems[NC - 1]) * 11 * (size_t)(int)(2 * p.scr_alpha + 24) : 0;
+    WorkLayout w;
+    w.take((size_t)W * sizeof(double), 8);                     // xmu, at the start of the area
+    p.o_al = w.take(p.al_doubles * sizeof(double), 8);
+    p.o_tab = w.take((size_t)count * sizeof(MieBatchJob), 8);
+    p.o_first = w.take((size_t)NC * (count + 1) * sizeof(int), 8);
+    p.head_bytes = w.total;                                    // (what travels in the staged copy)
+    p.o_scr = w.take(p.scr_doubles * sizeof(double), 8);
+    p.total = w.total;
     return SOSGPU_OK;
 }
 }  // namespace
@@ -2159,7 +2258,7 @@ extern "C" size_t sosgpu_mie_batch_work_bytes(int nbmu, int count, const sosgpu_
 {
     MieBatchPlan p;
     if (mie_batch_plan(nbmu, count, jobs, p) != SOSGPU_OK || !count) return 0;
-    return p.head_bytes + p.scr_doubles * sizeof(double);
+    return p.total;
 }
 
 extern "C" int sosgpu_mie_batch(int device, int nbmu, const double *xmu, int count, const sosgpu_mie_job *jobs, void *d_work,
@@ -2168,28 +2267,25 @@ extern "C" int sosgpu_mie_batch(int device, int nbmu, const double *xmu, int cou
     MieBatchPlan p;
     if (int rc = mie_batch_plan(nbmu, count, jobs, p)) return rc;
     if (!count) return SOSGPU_OK;
-    if (!xmu || !d_work || !d_status || ((uintptr_t)d_work & 7) != 0) return SOSGPU_E_ARG;
-    if (work_bytes < p.head_bytes + p.scr_doubles * sizeof(double)) return SOSGPU_E_UNSUPPORTED;
+    if (!xmu || !d_status || !work_area_ok(d_work, work_bytes, 0)) return SOSGPU_E_ARG;
+    if (work_bytes < p.total) return SOSGPU_E_UNSUPPORTED;             // (this entry point's code for a short area)
     if (const int rc = use_device(device)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int W = 2 * nbmu + 1;
     // --- angle set, lists, job table and item offsets: one pinned block -> d_work on the caller's stream, nothing waited for
     Staged s(device, p.head_bytes);
     if (s.rc) return s.rc;
     char *hp = (char *)s.host();
-    const size_t off_al = (size_t)W * sizeof(double), off_tab = off_al + p.al_doubles * sizeof(double),
-                 off_first = off_tab + (size_t)count * sizeof(MieBatchJob);
-    memcpy(hp, xmu, off_al);
-    size_t o = off_al;
+    memcpy(hp, xmu, p.o_al);
+    size_t o = p.o_al;
     for (const auto &l : p.lists) { memcpy(hp + o, l.first, (size_t)l.second * sizeof(double)); o += (size_t)l.second * sizeof(double); }
-    memcpy(hp + off_tab, p.tab.data(), (size_t)count * sizeof(MieBatchJob));
-    memcpy(hp + off_first, p.first.data(), p.first.size() * sizeof(int));
+    memcpy(hp + p.o_tab, p.tab.data(), (size_t)count * sizeof(MieBatchJob));
+    memcpy(hp + p.o_first, p.first.data(), p.first.size() * sizeof(int));
     HIPCHK(s.send(d_work, st));
     HIPCHK(hipMemsetAsync(d_status, 0, (size_t)count * sizeof(int32_t), st));
     char *dw = (char *)d_work;
-    const int rc = launch_mie_batch(nbmu, (const double *)dw, count, (const MieBatchJob *)(dw + off_tab), (const int *)(dw + off_first),
-                                    p.nitems, (const double *)(dw + off_al), p.scr_alpha,
-                                    p.scr_doubles ? (double *)(dw + p.head_bytes) : nullptr, d_status, st);
+    const int rc = launch_mie_batch(nbmu, (const double *)dw, count, (const MieBatchJob *)(dw + p.o_tab), (const int *)(dw + p.o_first),
+                                    p.nitems, (const double *)(dw + p.o_al), p.scr_alpha,
+                                    p.scr_doubles ? (double *)(dw + p.o_scr) : nullptr, d_status, st);
     if (rc == -3) return SOSGPU_E_UNSUPPORTED;
     if (rc == -2) { g_last_hip = (int)hipGetLastError(); return SOSGPU_E_HIP; }
     HIPCHK(hipGetLastError());
@@ -2209,9 +2305,7 @@ extern "C" int sosgpu_granu(int device, int nbmu, int nalpha, const float *d_rec
     launch_granu(nalpha, nbmu, d_rec, igranu, v1, v2, v3, wa, alphaf, d_work, d_out, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    HIPCHK(e);
+    HIPCHK(finish_sync(e, st));
     return SOSGPU_OK;
 }
 

@@ -75,6 +75,27 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _work_area(need, device):
+    """The work area of a table-form call (include/sosgpu.h, "Work areas"): `need` bytes, as the call's _work_bytes query gave
+    them, from torch's allocator -- which keeps an area dropped at return for the stream it was used on.  Never empty (an empty
+    tensor has a NULL pointer): with need = 0 the call refuses, or queues nothing, with a code of its own.  The call takes
+    _ptr(area) and need."""
+    return torch.empty(max(int(need), 8), dtype=torch.uint8, device=device)
+
+
+def _ckd_table_ptr(tables, dev):
+    """table_ptr of pack_ckd_requests on a GPU: absorption.ckd_device_tables of each interval file, made once and kept in
+    `tables` (id(prep) -> (prep, addresses, tensors)) for as long as the launch needs them."""
+    from . import absorption as _abs
+
+    def table_ptr(prep, k):
+        hit = tables.get(id(prep))
+        if hit is None:
+            hit = tables[id(prep)] = (prep,) + _abs.ckd_device_tables(prep, dev)
+        return hit[1][k]
+    return table_ptr
+
+
 def nogas_profile(tr, hr, ta, ha, device=0):
     """Queue the no-gas profile of a wavelength (SOS_PROFIL.F:349-489) on the current stream ahead of make_profiles
     (sosgpu_profile_nogas): its level placement is a ~1 ms serial chain on one wavefront that only needs the two optical
@@ -636,9 +657,10 @@ def trphi_many(items):
         shapes.append((nphi, 7, cx.w))
         count += nphi * 7 * cx.w
     flat = torch.empty(count, dtype=torch.float64, device=d)
-    work = torch.empty(int(L.sosgpu_trphi_spectrum_work_bytes(n)), dtype=torch.uint8, device=d)
-    capi.check(L.sosgpu_trphi_spectrum(jobs, n, _ptr(phis), int(phis.numel()), _ptr(flat), _ptr(work), items[0][0]._stream()),
-               "sosgpu_trphi_spectrum")
+    need = int(L.sosgpu_trphi_spectrum_work_bytes(n))
+    work = _work_area(need, d)
+    capi.check(L.sosgpu_trphi_spectrum(jobs, n, _ptr(phis), int(phis.numel()), _ptr(flat), _ptr(work), need,
+                                       items[0][0]._stream()), "sosgpu_trphi_spectrum")
     return flat, _flat_blocks(flat, shapes)
 
 
@@ -677,8 +699,10 @@ def level_flux_many(items):
         rows.append(row)
         j.cx, j.d_rec = cx._h.value, row.data_ptr()
     out = torch.empty((n, 2), dtype=torch.float64, device=d)
-    work = torch.empty(int(L.sosgpu_level_flux_spectrum_work_bytes(n)), dtype=torch.uint8, device=d)
-    capi.check(L.sosgpu_level_flux_spectrum(jobs, n, _ptr(out), _ptr(work), items[0][0]._stream()), "sosgpu_level_flux_spectrum")
+    need = int(L.sosgpu_level_flux_spectrum_work_bytes(n))
+    work = _work_area(need, d)
+    capi.check(L.sosgpu_level_flux_spectrum(jobs, n, _ptr(out), _ptr(work), need, items[0][0]._stream()),
+               "sosgpu_level_flux_spectrum")
     return out
 
 
@@ -701,11 +725,11 @@ def channel_accumulate(flat, njobs, K, nphi, W, first, job, wgt, acc):
         raise ValueError("acc is a contiguous float64 tensor [C][K][nphi][3][W] on the device of the blocks")
     L = capi.lib()
     d = flat.device
-    nbytes = int(L.sosgpu_channel_accumulate_work_bytes(nchan, job.size))
-    work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=d)
+    need = int(L.sosgpu_channel_accumulate_work_bytes(nchan, job.size))
+    work = _work_area(need, d)
     ip = lambda a: a.ctypes.data_as(C.c_void_p)
     capi.check(L.sosgpu_channel_accumulate(d.index or 0, _ptr(flat), int(njobs), int(K), int(nphi), int(W), nchan, ip(first),
-                                           ip(job), ip(wgt), _ptr(acc), _ptr(work), nbytes,
+                                           ip(job), ip(wgt), _ptr(acc), _ptr(work), need,
                                            C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "sosgpu_channel_accumulate")
     return acc
 
@@ -740,12 +764,13 @@ def build_operators(ctxs):
     L = capi.lib()
     n = len(todo)
     first = todo[0]
-    work = torch.empty(n * (int(L.sosgpu_ctx_table_entry_bytes()) + 8), dtype=torch.uint8, device=first.device)
+    need = int(L.sosgpu_noyaux_spectrum_work_bytes(n))
+    work = _work_area(need, first.device)
     hs = (C.c_void_p * n)(*[cx._h for cx in todo])
     rs = None
     if any(cx._rsurf is not None for cx in todo):
         rs = (C.c_void_p * n)(*[None if cx._rsurf is None else cx._rsurf.data_ptr() for cx in todo])
-    capi.check(L.sosgpu_noyaux_spectrum(hs, n, rs, _ptr(work), first._stream()), "sosgpu_noyaux_spectrum")
+    capi.check(L.sosgpu_noyaux_spectrum(hs, n, rs, _ptr(work), need, first._stream()), "sosgpu_noyaux_spectrum")
     for cx in todo:
         cx._built = True
     return n
@@ -779,7 +804,7 @@ def diffuse_transmissions_many(ctxs, bins, ctx_of_bin=None):
     ctxs, first, d, n, nb, cob, L, hs = _many_contexts("diffuse_transmissions_many", ctxs, bins, ctx_of_bin)
     tdifmug = torch.empty((nb, n), dtype=torch.float64, device=d)
     need = int(L.sosgpu_trans_spectrum_work_bytes(hs, len(ctxs), nb, bins["lp"]))
-    work = torch.empty(max(need, 8), dtype=torch.uint8, device=d)
+    work = _work_area(need, d)
     capi.check(L.sosgpu_trans_spectrum(hs, len(ctxs), _ptr(cob), nb, bins["lp"], _ptr(bins["nt"]), _ptr(bins["prof"]),
                                        _ptr(tdifmug), _ptr(work), need, first._stream()), "sosgpu_trans_spectrum")
     if len({cx.n0 for cx in ctxs}) == 1:
@@ -803,7 +828,7 @@ def spherical_albedo_many(ctxs, bins, ctx_of_bin=None, from_below=True):
     salb = torch.empty(nb, dtype=torch.float64, device=d)
     plane = torch.empty((nb, n), dtype=torch.float64, device=d)
     need = int(L.sosgpu_albedo_spectrum_work_bytes(hs, len(ctxs), nb, bins["lp"]))
-    work = torch.empty(max(need, 8), dtype=torch.uint8, device=d)
+    work = _work_area(need, d)
     capi.check(L.sosgpu_albedo_spectrum(hs, len(ctxs), _ptr(cob), nb, bins["lp"], _ptr(bins["nt"]), _ptr(bins["prof"]),
                                         1 if from_below else 0, _ptr(plane), _ptr(salb), _ptr(work), need, first._stream()),
                "sosgpu_albedo_spectrum")
@@ -912,8 +937,7 @@ def solve_spectrum(table, bins, ctx_of_bin, seg, aik, out=None, order="cost", td
     return cx.aggregate(out, aik, seg=seg, scal=bins.get("scal"), tdifmug=tdifmug)
 
 
-CKD_WL_DTYPE = np.dtype([("pres_off", "<i8"), ("temp_off", "<i8"), ("conc_off", "<i8"), ("prs_off", "<i8"), ("tmp_off", "<i8"),
-                         ("cl_off", "<i8"), ("xk_off", "<i8"), ("nterm", "<i4"), ("nt", "<i4"), ("np", "<i4"), ("nc", "<i4")])   # capi.CkdWl
+CKD_WL_DTYPE = np.dtype(capi.CkdWl)          # sosgpu_ckd_wl as a numpy record
 
 
 def pack_ckd_requests(preps, table_ptr, xk_off=None, base=0):
@@ -967,13 +991,14 @@ def pack_ckd_requests(preps, table_ptr, xk_off=None, base=0):
 
 def _ckd_launch(L, dev, pk, axes_t, axes_doubles, out_t, out_doubles, st, where):
     """Queue sosgpu_ckd_layer_tables for the packed requests pk on stream handle st; returns (status tensor, work area)."""
-    nwl = len(pk["wl"])
-    work = torch.empty(nwl * int(L.sosgpu_ckd_table_entry_bytes()) + 8 * pk["slots"].size, dtype=torch.uint8, device=dev)
+    nwl, nslots = len(pk["wl"]), int(pk["slots"].size)
+    need = int(L.sosgpu_ckd_layer_tables_work_bytes(nwl, nslots))
+    work = _work_area(need, dev)
     status = torch.empty(nwl, dtype=torch.int32, device=dev)
     bad = C.c_int(-1)
-    rc = L.sosgpu_ckd_layer_tables(dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), int(pk["slots"].size),
+    rc = L.sosgpu_ckd_layer_tables(dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), nslots,
                                    pk["slots"].ctypes.data_as(C.c_void_p), _ptr(axes_t), axes_doubles, pk["nlay"], _ptr(work),
-                                   _ptr(out_t), out_doubles, _ptr(status), C.byref(bad), st)
+                                   need, _ptr(out_t), out_doubles, _ptr(status), C.byref(bad), st)
     if rc != 0 and bad.value >= 0 and where is not None:
         where["bad"] = int(bad.value)
     capi.check(rc, "sosgpu_ckd_layer_tables")
@@ -990,14 +1015,7 @@ def ckd_layer_tables(preps, device=0, stream=None):
     from . import absorption as _abs
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     tables = {}
-
-    def table_ptr(prep, k):
-        hit = tables.get(id(prep))
-        if hit is None:
-            hit = tables[id(prep)] = (prep,) + _abs.ckd_device_tables(prep, dev)
-        return hit[1][k]
-
-    pk = pack_ckd_requests(preps, table_ptr)
+    pk = pack_ckd_requests(preps, _ckd_table_ptr(tables, dev))
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         axes = _upload(torch.from_numpy(pk["axes"]), dev)
@@ -1009,9 +1027,7 @@ def ckd_layer_tables(preps, device=0, stream=None):
     return xk, [_abs.layer_ro(p) for p in preps], status
 
 
-PROFILE_WL_DTYPE = np.dtype([("tr", "<f8"), ("hr", "<f8"), ("ta", "<f8"), ("ha", "<f8"), ("a_tronc", "<f8"), ("piz", "<f8"),
-                             ("piztr", "<f8"), ("zout", "<f8"), ("xk_off", "<i8"), ("ro_off", "<i8"), ("alt_off", "<i8"),
-                             ("nterm", "<i4"), ("nbins", "<i4"), ("absprofil", "<i4"), ("smax", "<i4")])   # capi.ProfileWl
+PROFILE_WL_DTYPE = np.dtype(capi.ProfileWl)  # sosgpu_profile_wl as a numpy record
 
 
 def pack_profile_requests(requests, table_ptr=None):
@@ -1116,19 +1132,10 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None, t
     rows, as SosContext.make_profiles(true_depth=True) returns them), inside the same cleared block."""
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     tables = {}
-
-    def table_ptr(prep, k):
-        from . import absorption as _abs
-        hit = tables.get(id(prep))
-        if hit is None:
-            hit = tables[id(prep)] = (prep,) + _abs.ckd_device_tables(prep, dev)
-        return hit[1][k]
-
-    pk = pack_profile_requests(requests, table_ptr)
+    pk = pack_profile_requests(requests, _ckd_table_ptr(tables, dev))
     nwl, nb, nblev, seg = len(requests), pk["nb"], pk["nblev"], pk["seg"]
     L = capi.lib()
-    ng = capi.NOGAS_LEVELS
-    tab_d = -(-nwl * int(L.sosgpu_profile_table_entry_bytes()) // 8)
+    need = int(L.sosgpu_profile_spectrum_work_bytes(nwl))          # (no-gas blocks, then the table: whole doubles)
     if part is None:
         part = {}
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
@@ -1146,10 +1153,10 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None, t
             finally:
                 if "bad" in refused:
                     part["bad"] = int(pk["ckd_index"][refused["bad"]])
-        # (two cleared blocks for the whole part; the work areas of the launch -- table, no-gas blocks -- ride at the end)
+        # (two cleared blocks for the whole part; the work area of the launch rides at the end of the first)
         o_z, o_s, o_zz, o_t = nb * 3 * lp, nb * 4 * lp, nb * (4 * lp + 4), nb * (4 * lp + 5)
-        o_ng, o_tab = o_t + nb * nblev, o_t + nb * nblev + nwl * 4 * ng
-        o_hv = o_tab + tab_d
+        o_ng = o_t + nb * nblev
+        o_hv = o_ng + need // 8
         fb = torch.zeros(o_hv + (nb * lp if true_depth else 0), dtype=torch.float64, device=dev)
         hvrai = fb[o_hv:].view(nb, lp) if true_depth else None
         ib = torch.zeros(3 * nb, dtype=torch.int32, device=dev)
@@ -1161,7 +1168,7 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None, t
         bad = C.c_int(-1)
         args = (dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), nb, _ptr(up[pk["wob_off"]:]),
                 _ptr(ik_t), _ptr(up) if nblev else None, pk["gas_doubles"] if ckd is None else up.numel(), nblev, lp,
-                _ptr(fb[o_tab:o_hv]), _ptr(fb[o_ng:o_tab]), _ptr(tabs), _ptr(prof), _ptr(nt), _ptr(iborm),
+                _ptr(fb[o_ng:o_hv]), need, _ptr(tabs), _ptr(prof), _ptr(nt), _ptr(iborm),
                 _ptr(zprof), _ptr(jout) if any_out else None, _ptr(zz) if any_out else None, _ptr(scal), C.byref(bad))
         rc = L.sosgpu_profile_spectrum_true(*args, _ptr(hvrai), st) if true_depth else L.sosgpu_profile_spectrum(*args, st)
     if rc != 0 and bad.value >= 0:

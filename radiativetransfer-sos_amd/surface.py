@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import capi
+from .solver import _work_area
 
 
 def mat_fresnel(mu, chr_, ind, os_ns):
@@ -114,8 +115,8 @@ def surface_matrices_many(jobs, mu, chr_, os_nb, os_ns, os_nm, device=0, status=
     step = out[0].numel() * 4
     arr = surface_job_array(jobs, [out.data_ptr() + j * step for j in range(nj)])
     L = capi.lib()
-    need = L.sosgpu_surface_batch_work_bytes(n, int(os_nb), int(os_ns), int(os_nm), arr, nj)
-    work = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)    # (need = 0: the call below refuses, with its code)
+    need = int(L.sosgpu_surface_batch_work_bytes(n, int(os_nb), int(os_ns), int(os_nm), arr, nj))
+    work = _work_area(need, dev)
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     capi.check(L.sosgpu_surface_batch(device, n, mu.ctypes.data_as(C.c_void_p), chr_.ctypes.data_as(C.c_void_p), int(os_nb),
                                       int(os_ns), int(os_nm), arr, nj, C.c_void_p(status.data_ptr()),

@@ -94,14 +94,15 @@ def run(pkg, cells, xk_off=None, out_doubles=None, stream=None):
     nout = off if out_doubles is None else int(out_doubles)
     ax = torch.from_numpy(np.concatenate(parts)).to(dev)
     out = torch.full((nout,), float("nan"), dtype=torch.float64, device=dev)
-    work = torch.empty(len(cells) * int(L.sosgpu_ckd_table_entry_bytes()) + 8 * len(ptrs), dtype=torch.uint8, device=dev)
+    nw = int(L.sosgpu_ckd_layer_tables_work_bytes(len(cells), len(ptrs)))
+    work = torch.empty(nw, dtype=torch.uint8, device=dev)
     status = torch.full((len(cells),), 77, dtype=torch.int32, device=dev)          # (the call clears it)
     slots = (C.c_uint64 * len(ptrs))(*ptrs)
     bad = C.c_int(-5)
     torch.cuda.synchronize()
     st = torch.cuda.current_stream(dev) if stream is None else stream
     rc = L.sosgpu_ckd_layer_tables(0, len(cells), wl, len(ptrs), slots, C.c_void_p(ax.data_ptr()), n, nlay,
-                                   C.c_void_p(work.data_ptr()), C.c_void_p(out.data_ptr()), nout,
+                                   C.c_void_p(work.data_ptr()), nw, C.c_void_p(out.data_ptr()), nout,
                                    C.c_void_p(status.data_ptr()), C.byref(bad), C.c_void_p(st.cuda_stream))
     assert rc == 0 and bad.value == -1, (rc, bad.value)
     st.synchronize()

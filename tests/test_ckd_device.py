@@ -57,14 +57,10 @@ def test_new_symbols_in_header_and_export_list(pkg):
     hdr = open(os.path.join(ROOT, "include", "sosgpu.h")).read()
     declared = set(re.findall(r"\b(sosgpu_[a-z_0-9]+)\s*\(", hdr))
     L = pkg.capi.lib()
-    for sym in ("sosgpu_ckd_layer_tables", "sosgpu_ckd_table_entry_bytes"):
+    for sym in ("sosgpu_ckd_layer_tables", "sosgpu_ckd_layer_tables_work_bytes"):
         assert sym in declared and sym in pkg.capi.EXPORTS and hasattr(L, sym), sym
     assert "sosgpu_ckd_wl" in hdr
-    dt = pkg.solver.CKD_WL_DTYPE
-    assert C.sizeof(pkg.capi.CkdWl) == dt.itemsize == 72
-    for f, _ in pkg.capi.CkdWl._fields_:
-        assert getattr(pkg.capi.CkdWl, f).offset == dt.fields[f][1], f
-    assert L.sosgpu_ckd_table_entry_bytes() % 8 == 0 and L.sosgpu_ckd_table_entry_bytes() >= 72
+    assert C.sizeof(pkg.capi.CkdWl) == pkg.solver.CKD_WL_DTYPE.itemsize == 72
 
 
 def test_pack_ckd_requests_reproduces_every_request(pkg, fic):
@@ -137,14 +133,15 @@ def test_argument_rules_and_limits_before_any_device_work(pkg):
         a = dict(wl=wl, ki=slots, d_axes=fake, d_work=fake, d_out=fake, d_status=fake)
         a.update(nulls)
         rc = L.sosgpu_ckd_layer_tables(0, len(entries), a["wl"], 40 * len(entries) if nslots is None else nslots, a["ki"],
-                                       a["d_axes"], axes, nlay, a["d_work"], a["d_out"], out, a["d_status"], C.byref(bad), None)
+                                       a["d_axes"], axes, nlay, a["d_work"], 1 << 30, a["d_out"], out, a["d_status"],
+                                       C.byref(bad), None)
         return rc, bad.value
 
     ok = _entry(pkg)
     for name in ("wl", "ki", "d_axes", "d_work", "d_out", "d_status"):
         assert call([ok], **{name: None}) == (-1, -1), name
     assert call([ok], d_work=C.c_void_p(0x1004)) == (-1, -1)                       # work area not 8-byte aligned
-    assert L.sosgpu_ckd_layer_tables(0, 0, None, 0, None, None, 0, 49, None, None, 0, None, None, None) == -1
+    assert L.sosgpu_ckd_layer_tables(0, 0, None, 0, None, None, 0, 49, None, 0, None, 0, None, None, None) == -1
     assert call([ok, ok], nslots=79) == (-1, -1)                                   # nslots != sum of 8 * nterm
     assert call([ok, _entry(pkg, nterm=0)]) == (-1, 1)
     for k in ("pres_off", "temp_off", "conc_off", "prs_off", "tmp_off", "cl_off", "xk_off"):

@@ -36,7 +36,7 @@ def test_symbols_are_declared_exported_and_listed(pkg):
     assert re.search(r"typedef struct sosgpu_flux_job \{\s*sosgpu_ctx \*cx;\s*const double \*d_rec;\s*\} sosgpu_flux_job;", hdr)
     assert re.search(r"\bsize_t\s+sosgpu_level_flux_spectrum_work_bytes\s*\(int njobs\);", hdr)
     assert re.search(r"\bint\s+sosgpu_level_flux_spectrum\s*\(const sosgpu_flux_job \*jobs, int njobs, double \*d_out[^,)]*,\s*"
-                     r"void \*d_work, void \*stream\);", hdr)
+                     r"void \*d_work, size_t work_bytes, void \*stream\);", hdr)
     for sym in ("sosgpu_level_flux", "sosgpu_level_flux_spectrum", "sosgpu_level_flux_spectrum_work_bytes"):
         assert sym in pkg.capi.EXPORTS
         assert hasattr(pkg.capi.lib(), sym)
@@ -52,22 +52,22 @@ def test_arguments_are_refused_without_a_device(pkg):
     record and a misaligned work area of the spectrum call are refused, and njobs = 0 is accepted, before any device is looked
     for (the rule for contexts on different devices needs two devices and is not exercised here)."""
     L = pkg.capi.lib()
-    p = C.c_void_p(4096)                                     # never dereferenced: nothing is queued by these calls
+    p, nw = C.c_void_p(4096), 1 << 30                        # never dereferenced: nothing is queued by these calls
     assert L.sosgpu_level_flux(None, p, p, None) == E_ARG
     assert L.sosgpu_level_flux(p, None, p, None) == E_ARG
     assert L.sosgpu_level_flux(p, p, None, None) == E_ARG
     jobs = (pkg.capi.FluxJob * 2)()
-    assert L.sosgpu_level_flux_spectrum(None, 1, p, p, None) == E_ARG
-    assert L.sosgpu_level_flux_spectrum(jobs, 1, None, p, None) == E_ARG
-    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, None, None) == E_ARG
-    assert L.sosgpu_level_flux_spectrum(jobs, -1, p, p, None) == E_ARG
-    assert L.sosgpu_level_flux_spectrum(jobs, 2, p, p, None) == E_ARG            # both jobs empty: NULL context
+    assert L.sosgpu_level_flux_spectrum(None, 1, p, p, nw, None) == E_ARG
+    assert L.sosgpu_level_flux_spectrum(jobs, 1, None, p, nw, None) == E_ARG
+    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, None, nw, None) == E_ARG
+    assert L.sosgpu_level_flux_spectrum(jobs, -1, p, p, nw, None) == E_ARG
+    assert L.sosgpu_level_flux_spectrum(jobs, 2, p, p, nw, None) == E_ARG            # both jobs empty: NULL context
     jobs[0].cx, jobs[0].d_rec = 4096, None
-    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, p, None) == E_ARG            # NULL record
+    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, p, nw, None) == E_ARG            # NULL record
     jobs[0].cx, jobs[0].d_rec = None, 4096
-    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, p, None) == E_ARG            # NULL context
-    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, C.c_void_p(4100), None) == E_ARG
-    assert L.sosgpu_level_flux_spectrum(jobs, 0, p, p, None) == 0
+    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, p, nw, None) == E_ARG            # NULL context
+    assert L.sosgpu_level_flux_spectrum(jobs, 1, p, C.c_void_p(4100), nw, None) == E_ARG
+    assert L.sosgpu_level_flux_spectrum(jobs, 0, p, p, nw, None) == 0
 
 
 def test_work_bytes(pkg):
@@ -158,8 +158,10 @@ def _flux_call(gpu_pkg, items):
     for j, (cx, rec) in zip(jobs, items):
         j.cx, j.d_rec = cx._h.value, rec.data_ptr()
     out = torch.full((2 * n + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    work = torch.empty(int(L.sosgpu_level_flux_spectrum_work_bytes(n)), dtype=torch.uint8, device="cuda")
-    rc = L.sosgpu_level_flux_spectrum(jobs, n, C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()), items[0][0]._stream())
+    nw = int(L.sosgpu_level_flux_spectrum_work_bytes(n))
+    work = torch.empty(nw, dtype=torch.uint8, device="cuda")
+    rc = L.sosgpu_level_flux_spectrum(jobs, n, C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()), nw,
+                                      items[0][0]._stream())
     torch.cuda.synchronize()
     out = out.cpu().numpy()
     return rc, out[:2 * n].reshape(n, 2), out[2 * n:]

@@ -70,7 +70,7 @@ def test_arguments_are_refused_without_a_device(pkg):
     # the twins of the profile entry points keep their neighbours' refusals (NULL context / no wavelength)
     assert L.sosgpu_profile_true(None, 1, 0.1, 8.0, 0.1, 2.0, 7, 0, None, None, 0.0, 1.0, 1.0, -1.0, 608, p, p, p, p, None, None,
                                  p, None, p, None) == E_ARG
-    assert L.sosgpu_profile_spectrum_true(0, 0, p, 1, p, None, None, 0, 0, 608, p, p, None, p, p, p, p, None, None, p, None, p,
+    assert L.sosgpu_profile_spectrum_true(0, 0, p, 1, p, None, None, 0, 0, 608, p, 1 << 30, None, p, p, p, p, None, None, p, None, p,
                                           None) == E_ARG
 
 

@@ -28,21 +28,22 @@ E_ARG = -1
 def test_symbol_is_declared_exported_and_listed(pkg):
     hdr = open(os.path.join(ROOT, "include", "sosgpu.h")).read()
     assert re.search(r"\bint\s+sosgpu_noyaux_spectrum\s*\(sosgpu_ctx \*const \*ctxs, int nctx, const float \*const \*d_rsurf, "
-                     r"void \*d_work, void \*stream\);", hdr)
-    assert "sosgpu_noyaux_spectrum" in pkg.capi.EXPORTS
-    assert hasattr(pkg.capi.lib(), "sosgpu_noyaux_spectrum")
+                     r"void \*d_work, size_t work_bytes,\s*void \*stream\);", hdr)
+    assert re.search(r"\bsize_t\s+sosgpu_noyaux_spectrum_work_bytes\s*\(int nctx\);", hdr)
+    for sym in ("sosgpu_noyaux_spectrum", "sosgpu_noyaux_spectrum_work_bytes"):
+        assert sym in pkg.capi.EXPORTS and hasattr(pkg.capi.lib(), sym)
 
 
 def test_arguments_are_refused_without_a_device(pkg):
     """NULL ctxs, NULL d_work and nctx = -1 are refused, and nctx = 0 is accepted, before any device is looked for."""
     L = pkg.capi.lib()
     hs = (C.c_void_p * 1)(None)
-    work = C.c_void_p(4096)                                  # never dereferenced: nothing is queued by these calls
-    assert L.sosgpu_noyaux_spectrum(None, 1, None, work, None) == E_ARG
-    assert L.sosgpu_noyaux_spectrum(hs, 1, None, None, None) == E_ARG
-    assert L.sosgpu_noyaux_spectrum(hs, -1, None, work, None) == E_ARG
-    assert L.sosgpu_noyaux_spectrum(hs, 65536, None, work, None) == E_ARG
-    assert L.sosgpu_noyaux_spectrum(hs, 0, None, work, None) == 0
+    work, nw = C.c_void_p(4096), 1 << 30                     # never dereferenced: nothing is queued by these calls
+    assert L.sosgpu_noyaux_spectrum(None, 1, None, work, nw, None) == E_ARG
+    assert L.sosgpu_noyaux_spectrum(hs, 1, None, None, nw, None) == E_ARG
+    assert L.sosgpu_noyaux_spectrum(hs, -1, None, work, nw, None) == E_ARG
+    assert L.sosgpu_noyaux_spectrum(hs, 65536, None, work, nw, None) == E_ARG
+    assert L.sosgpu_noyaux_spectrum(hs, 0, None, work, nw, None) == 0
 
 
 def test_batch_covers_the_mix_it_claims():
@@ -200,8 +201,8 @@ def test_refusals_change_nothing(gpu_pkg):
     for a context without matrices give SOSGPU_E_ARG; the same contexts built properly afterwards hold the right tables."""
     import torch
     L, S = gpu_pkg.capi.lib(), gpu_pkg.solver
-    n_entry = int(L.sosgpu_ctx_table_entry_bytes()) + 8
-    work = torch.empty(4 * n_entry, dtype=torch.uint8, device="cuda")
+    nw = int(L.sosgpu_noyaux_spectrum_work_bytes(4))
+    work = torch.empty(nw, dtype=torch.uint8, device="cuda")
     wp = C.c_void_p(work.data_ptr())
     for case in ("null context", "null matrices", "null matrix argument", "matrices for none"):
         plain, gnd = _unbuilt(gpu_pkg, "n5"), _unbuilt(gpu_pkg, "gnd_n5")
@@ -209,23 +210,24 @@ def test_refusals_change_nothing(gpu_pkg):
             st = plain._stream()
             r = C.c_void_p(gnd._rsurf.data_ptr())
             if case == "null context":
-                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 3)(plain._h, gnd._h, None), 3, (C.c_void_p * 3)(None, r, None), wp, st)
+                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 3)(plain._h, gnd._h, None), 3, (C.c_void_p * 3)(None, r, None), wp, nw, st)
             elif case == "null matrices":
-                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(plain._h, gnd._h), 2, (C.c_void_p * 2)(None, None), wp, st)
+                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(plain._h, gnd._h), 2, (C.c_void_p * 2)(None, None), wp, nw, st)
             elif case == "null matrix argument":
-                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(plain._h, gnd._h), 2, None, wp, st)
+                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(plain._h, gnd._h), 2, None, wp, nw, st)
             else:
-                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(plain._h, gnd._h), 2, (C.c_void_p * 2)(r, r), wp, st)
+                rc = L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(plain._h, gnd._h), 2, (C.c_void_p * 2)(r, r), wp, nw, st)
             assert rc == E_ARG, case
             assert S.build_operators([plain, gnd]) == 2
             _assert_same_tables(gpu_pkg, plain, "n5", case)
             _assert_same_tables(gpu_pkg, gnd, "gnd_n5", case)
         finally:
             _close([plain, gnd])
-    bad = torch.empty(n_entry + 8, dtype=torch.uint8, device="cuda")
+    bad = torch.empty(nw + 8, dtype=torch.uint8, device="cuda")
     plain = _unbuilt(gpu_pkg, "n5")
     try:
-        assert L.sosgpu_noyaux_spectrum((C.c_void_p * 1)(plain._h), 1, None, C.c_void_p(bad.data_ptr() + 4), plain._stream()) == E_ARG
+        assert L.sosgpu_noyaux_spectrum((C.c_void_p * 1)(plain._h), 1, None, C.c_void_p(bad.data_ptr() + 4), nw,
+                                        plain._stream()) == E_ARG
         with pytest.raises(RuntimeError):
             plain.solve(dict(nb=0))
     finally:

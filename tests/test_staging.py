@@ -63,7 +63,8 @@ def _trphi_args(gpu_pkg, items, phis):
 def _trphi_call(gpu_pkg, items, phis, args):
     jobs, out, work = args
     return gpu_pkg.capi.lib().sosgpu_trphi_spectrum(jobs, len(items), C.c_void_p(phis.data_ptr()), int(phis.numel()),
-                                                    C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()), items[0][0]._stream())
+                                                    C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()), work.numel(),
+                                                    items[0][0]._stream())
 
 
 def _flux_args(gpu_pkg, items):
@@ -80,7 +81,7 @@ def _flux_args(gpu_pkg, items):
 def _flux_call(gpu_pkg, items, args):
     jobs, out, work = args
     return gpu_pkg.capi.lib().sosgpu_level_flux_spectrum(jobs, len(items), C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()),
-                                                         items[0][0]._stream())
+                                                         work.numel(), items[0][0]._stream())
 
 
 @pytest.fixture()
@@ -195,7 +196,8 @@ def test_refusals_take_nothing(gpu_pkg, ctxs):
         assert before[0] >= 1
         refused = {
             "sosgpu_ctx_table": lambda: L.sosgpu_ctx_table((C.c_void_p * 2)(ctxs[0]._h, other._h), 2, wp, st),
-            "sosgpu_noyaux_spectrum": lambda: L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(ctxs[0]._h, None), 2, None, wp, st),
+            "sosgpu_noyaux_spectrum": lambda: L.sosgpu_noyaux_spectrum((C.c_void_p * 2)(ctxs[0]._h, None), 2, None, wp,
+                                                                       work.numel(), st),
             "sosgpu_trphi_spectrum": lambda: _trphi_call(gpu_pkg, t_items, phis, t_args),
             "sosgpu_level_flux_spectrum": lambda: _flux_call(gpu_pkg, f_items, f_args),
         }

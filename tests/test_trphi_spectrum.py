@@ -28,7 +28,7 @@ def test_symbols_are_declared_exported_and_listed(pkg):
                      hdr)
     assert re.search(r"\bsize_t\s+sosgpu_trphi_spectrum_work_bytes\s*\(int njobs\);", hdr)
     assert re.search(r"\bint\s+sosgpu_trphi_spectrum\s*\(const sosgpu_trphi_job \*jobs, int njobs, const double \*d_phi, "
-                     r"int nphi_total,\s*double \*d_out, void \*d_work, void \*stream\);", hdr)
+                     r"int nphi_total,\s*double \*d_out, void \*d_work, size_t work_bytes, void \*stream\);", hdr)
     for sym in ("sosgpu_trphi_spectrum", "sosgpu_trphi_spectrum_work_bytes"):
         assert sym in pkg.capi.EXPORTS
         assert hasattr(pkg.capi.lib(), sym)
@@ -42,15 +42,15 @@ def test_arguments_are_refused_without_a_device(pkg):
     accepted, before any device is looked for."""
     L = pkg.capi.lib()
     jobs = (pkg.capi.TrphiJob * 1)()
-    p = C.c_void_p(4096)                                     # never dereferenced: nothing is queued by these calls
-    assert L.sosgpu_trphi_spectrum(None, 1, p, 1, p, p, None) == E_ARG
-    assert L.sosgpu_trphi_spectrum(jobs, 1, None, 1, p, p, None) == E_ARG
-    assert L.sosgpu_trphi_spectrum(jobs, 1, p, 1, None, p, None) == E_ARG
-    assert L.sosgpu_trphi_spectrum(jobs, 1, p, 1, p, None, None) == E_ARG
-    assert L.sosgpu_trphi_spectrum(jobs, -1, p, 1, p, p, None) == E_ARG
-    assert L.sosgpu_trphi_spectrum(jobs, 65536, p, 1, p, p, None) == E_ARG
-    assert L.sosgpu_trphi_spectrum(jobs, 1, p, 1, p, C.c_void_p(4100), None) == E_ARG
-    assert L.sosgpu_trphi_spectrum(jobs, 0, p, 0, p, p, None) == 0
+    p, nw = C.c_void_p(4096), 1 << 30                        # never dereferenced: nothing is queued by these calls
+    assert L.sosgpu_trphi_spectrum(None, 1, p, 1, p, p, nw, None) == E_ARG
+    assert L.sosgpu_trphi_spectrum(jobs, 1, None, 1, p, p, nw, None) == E_ARG
+    assert L.sosgpu_trphi_spectrum(jobs, 1, p, 1, None, p, nw, None) == E_ARG
+    assert L.sosgpu_trphi_spectrum(jobs, 1, p, 1, p, None, nw, None) == E_ARG
+    assert L.sosgpu_trphi_spectrum(jobs, -1, p, 1, p, p, nw, None) == E_ARG
+    assert L.sosgpu_trphi_spectrum(jobs, 65536, p, 1, p, p, nw, None) == E_ARG
+    assert L.sosgpu_trphi_spectrum(jobs, 1, p, 1, p, C.c_void_p(4100), nw, None) == E_ARG
+    assert L.sosgpu_trphi_spectrum(jobs, 0, p, 0, p, p, nw, None) == 0
 
 
 def test_work_bytes(pkg):
@@ -138,9 +138,11 @@ def _spectrum_call(gpu_pkg, items, work_offset=0, mutate=None, nphi_total=None):
         mutate(jobs)
     count = sum(a * b * c for a, b, c in shapes)
     out = torch.full((count + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    work = torch.empty(int(L.sosgpu_trphi_spectrum_work_bytes(len(items))) + 8, dtype=torch.uint8, device="cuda")
+    nw = int(L.sosgpu_trphi_spectrum_work_bytes(len(items)))
+    work = torch.empty(nw + 8, dtype=torch.uint8, device="cuda")
     rc = L.sosgpu_trphi_spectrum(jobs, len(items), C.c_void_p(phis.data_ptr()), total if nphi_total is None else nphi_total,
-                                 C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr() + work_offset), items[0][0]._stream())
+                                 C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr() + work_offset), nw,
+                                 items[0][0]._stream())
     torch.cuda.synchronize()
     if rc:
         return rc, None, out[count:]

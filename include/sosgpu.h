@@ -53,6 +53,7 @@
  *   sosgpu_trphi_spectrum     the same for the wavelengths and output altitudes of a part of a spectrum: one launch
  *   sosgpu_level_flux  <- EMOINS / EPLUS of SOS_OS  src/SOS_OS.F:1447-1456, at the output altitude of an aggregated record
  *   sosgpu_level_flux_spectrum   the same for the wavelengths and output altitudes of a part of a spectrum: one launch
+ *   sosgpu_level_absorption   actinic flux and absorbed power per km of a band at the output slots of a levels solve
  *
  * Index conventions (identical to oracle/sos_oracle.h): N = NBMU positive directions, mu[0..N-1] =
  * RMU(1..N) descending; direction jj in -N..N lives at offset jj+N of width W = 2N+1 (slot jj=0 is
@@ -428,6 +429,42 @@ typedef struct sosgpu_flux_job { sosgpu_ctx *cx; const double *d_rec; } sosgpu_f
 size_t sosgpu_level_flux_spectrum_work_bytes(int njobs);
 int  sosgpu_level_flux_spectrum(const sosgpu_flux_job *jobs, int njobs, double *d_out /*[njobs][2]*/,
                                 void *d_work, size_t work_bytes, void *stream);
+
+/* Actinic flux and absorbed power of a band at the output slots of a levels solve (sosgpu_os_solve_levels,
+ * sosgpu_os_solve_multi_levels): the angular moment of the captured order-0 field that carries no factor mu, and the radiative
+ * power absorbed per kilometre -- the shortwave heating rate up to the factor mu_s E0 / (rho c_p).  All values are in the unit
+ * of sosgpu_level_flux, i.e. relative to the irradiance mu_s E0 at the top of the atmosphere on a horizontal plane.  Per slot k
+ * and bin b, with N, n0, mu, ga of the bin's context, row = d_rec[k][b][0][0][0..W) (direction jj at offset jj + N),
+ * (j, zz) = (d_jout[k][b], d_zz[k][b]) and H / XDEL / YDEL = d_prof[b][0..2][.], every step one rounding, no FMA:
+ *   s_dn = sum_{jj=1..N} ga_jj row[N - jj]  (s_up: row[N + jj]; jj ascending),   a_dn = -s_dn * 2 / TAB,  a_up = -s_up * 2 / TAB,
+ *   TAB = -mu[n0-1]  (sosgpu_level_flux's statements without the factor mu),   a_dir = exp(-d_tauout[k][b] / mu_s) / mu_s,
+ *   om    = (1 - zz) (XDEL[j-1] + YDEL[j-1]) + zz (XDEL[j] + YDEL[j]),
+ *   slope = (H[j] - H[j-1]) / (zprof[j-1] - zprof[j]),   0 when zprof[j-1] <= zprof[j] (levels that coincide after F10.5),
+ *   q     = slope * (1 - om) * (a_dn + a_up + a_dir)          [per km].
+ * The single-scattering albedo is a LEVEL quantity here: the solver's discretisation obeys, for layer j,
+ *   F_net(j-1) - F_net(j) = dtau_j / 2 ((1 - om_{j-1}) A_{j-1} + (1 - om_j) A_j)
+ * with om_j = XDEL[j] + YDEL[j]; q follows the reference's linear interpolation between the two levels that bracket z, and its
+ * integral over a layer is q(z_mid) dz.  The truncation rescale leaves (1 - om) dtau unchanged: q belongs to the true atmosphere.
+ *   d_out[k][g][0..3] = sum_b d_aik[b] * {a_dir, a_dn, a_up, q}   over the bins d_seg[g] .. d_seg[g+1]-1 with d_norders[b] >= 0,
+ * with sosgpu_level_transmission's shape (256 threads stride over the bins, serial within a thread, fixed tree): a segment of
+ * one bin gives aik * term exactly.  a_dir of a band is the exact band mean sum aik exp(-tau_b / mu_s) / mu_s, not the value at
+ * the band-mean depth.  A standard-output slot (jout = 0) mixes the ground and the top of the atmosphere: its bins add nothing
+ * and its block is zeros.  A bin with jout outside 0 .. NT is skipped like a failed bin.
+ *  cx                the context of the bins; with d_table any context of the table (it provides N and iborm_max)
+ *  d_table, d_ctx_of_bin[nb]   NULL: every bin with cx; else the buffer of sosgpu_ctx_table and the entry of every bin, as
+ *                    sosgpu_os_solve_multi takes them (contexts of different mu but equal N)
+ *  d_nt[nb], d_prof[nb][3][lp]   as the solve took them;  d_zprof[nb][lp]   level altitudes (km, descending; sosgpu_profile)
+ *  d_jout, d_zz, d_tauout [nz][nb]   of sosgpu_output_levels;  d_rec[nz][nb][iborm_max+1][3][W], d_norders[nb]   of the solve
+ *  d_seg[nseg+1], d_aik[nb]   as sosgpu_aggregate takes them
+ * Asynchronous: one launch on `stream` (queue it behind the solve), no allocation, no work area; `stream` is noted for
+ * sosgpu_destroy on cx.  nb = 0 or nseg = 0 queues nothing.  Checked before anything is queued, SOSGPU_E_ARG for: a NULL cx,
+ * d_nt, d_prof, d_zprof, d_jout, d_zz, d_tauout, d_rec, d_norders, d_seg, d_aik or d_out, nz outside
+ * 1 .. SOSGPU_MAX_OUTPUT_LEVELS, lp < 2, nb < 0, nseg < 0, d_table without d_ctx_of_bin. */
+int  sosgpu_level_absorption(sosgpu_ctx *cx, const void *d_table /*NULL: cx alone*/, const int32_t *d_ctx_of_bin /*NULL with d_table NULL*/,
+                             int nb, int lp, const int32_t *d_nt, const double *d_prof, const double *d_zprof /*[nb][lp]*/, int nz,
+                             const int32_t *d_jout, const double *d_zz, const double *d_tauout /*[nz][nb] each*/,
+                             const double *d_rec /*[nz][nb][iborm_max+1][3][W]*/, const int32_t *d_norders, int nseg,
+                             const int32_t *d_seg, const double *d_aik, double *d_out /*[nz][nseg][4]*/, void *stream);
 
 /* Sensor channels of a spectrum: response-weighted sums of recomposition blocks over the wavelengths, on the device.
  * A call adds the terms of nchan channels onto an accumulator that lives for the whole spectrum:

@@ -30,6 +30,7 @@ EXPORTS = [
     "sosgpu_trans_spectrum", "sosgpu_trans_spectrum_work_bytes",
     "sosgpu_surface_batch", "sosgpu_surface_batch_work_bytes",
     "sosgpu_albedo_spectrum", "sosgpu_albedo_spectrum_work_bytes", "sosgpu_albedo_band",
+    "sosgpu_level_absorption",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -274,6 +275,8 @@ def lib():
         L.sosgpu_albedo_spectrum.argtypes = [C.POINTER(vp), i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, C.c_size_t, vp]
         L.sosgpu_albedo_band.restype = i32
         L.sosgpu_albedo_band.argtypes = [i32, vp, vp, vp, vp, i32, vp]
+        L.sosgpu_level_absorption.restype = i32
+        L.sosgpu_level_absorption.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.sosgpu_debug_stage_blocks.restype = i32
         L.sosgpu_debug_stage_blocks.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
         L.sosgpu_debug_solve_plan.restype = i32

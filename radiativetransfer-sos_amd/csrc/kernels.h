@@ -144,6 +144,14 @@ struct FluxJobDev {
 };
 void launch_level_flux_table(const FluxJobDev *d_jobs, int njobs, hipStream_t st);
 
+// Actinic flux and absorbed power of nz output slots (absorb.hip k_level_absorption): d_out[nz][nseg][4] = sum aik * {a_dir, a_dn,
+// a_up, q} over the bins of every segment, formed per bin from the slot's order-0 row of d_rec[nz][nb][smax+1][3][W], the
+// profile rows and level altitudes; d_table null: every bin with cx, else bin b with entry d_ctx_of_bin[b] (cx: the layout)
+void launch_level_absorption(const SosDev &cx, const SosDev *d_table, const int32_t *d_ctx_of_bin, int nb, int lp,
+                             const int32_t *d_nt, const double *d_prof, const double *d_zprof, int nz, const int32_t *d_jout,
+                             const double *d_zz, const double *d_tauout, const double *d_rec, const int32_t *d_norders, int nseg,
+                             const int32_t *d_seg, const double *d_aik, double *d_out, hipStream_t st);
+
 // Sensor channels of a spectrum (channels.hip).  launch_channel_accumulate: acc[nchan][nslots][nphi][3][W] += the terms
 // first[c] .. first[c + 1] - 1 of every channel c, term m = wgt[m] x rows 0..2 of block (job[m], slot) of d_blocks
 // [njobs][nslots][nphi][7][W]; one launch of (ceil(nphi 3 W / 256), nslots, nchan) workgroups, first / job / wgt on the device.

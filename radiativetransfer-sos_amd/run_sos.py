@@ -114,6 +114,8 @@ OUTPUT_NAMES = ["nblum", "ind_angout", "phi", "vza", "sca_ang_up", "i_up", "q_up
 LEVEL_FLUX_NAMES = ["flux_dir_down_tronc", "flux_diff_down_tronc", "flux_tot_down", "flux_diff_up", "flux_net"]
 # ... with split=True: the down-going flux split into the true direct beam and the true diffuse light at the altitude
 LEVEL_FLUX_SPLIT_NAMES = LEVEL_FLUX_NAMES + ["flux_dir_down", "flux_diff_down"]
+# columns of the per-altitude rows of absorption=True (_level_absorption_row): the actinic flux and the absorbed power per km
+LEVEL_ABSORPTION_NAMES = ["actinic_dir", "actinic_diff_down", "actinic_diff_up", "actinic_tot", "absorbed_per_km"]
 
 
 class SosProcError(RuntimeError):
@@ -1480,6 +1482,17 @@ def _level_flux_split_row(pl, alt, fin, g, e):
     return row + (tdir_vrai, float(e[0]) + row[0] - tdir_vrai)
 
 
+def _level_absorption_row(alt, a):
+    """One row of LEVEL_ABSORPTION_NAMES for output altitude `alt` from a = the band sums (a_dir, a_dn, a_up, q) of
+    sosgpu_level_absorption: the three parts of the actinic flux, their sum (down-going and up-going diffuse first, then the
+    direct beam, the order the kernel adds them in per bin), and the absorbed power per km.  The standard output (altitude -1)
+    mixes the ground and the top of the atmosphere: its row is NaN."""
+    if alt == -1.0:
+        return (float("nan"),) * len(LEVEL_ABSORPTION_NAMES)
+    a_dir, a_dn, a_up, q = (float(x) for x in a)
+    return (a_dir, a_dn, a_up, a_dn + a_up + a_dir, q)
+
+
 def _finish_scalars(pl, fin, g=0):
     """Elements 18..22 of the 23-tuple of plan pl (SOS_PROC.F:3831-3837): flux_dir_down, flux_diff_down, flux_tot_down,
     flux_diff_up and coef_tronca, from the finish_scalars dictionary `fin` and the wavelength's segment g in it."""
@@ -1548,11 +1561,13 @@ def sos_proc(aer_phase=None, device=0, **kw):
     return _band_call("sos_proc", kw, aer_phase, device)[0]
 
 
-def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False, split=False):
+def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False, split=False, absorption=False):
     """One band for sos_proc (alts None: solve_band, the kernels without output slots) or sos_proc_levels (alts: the K
     altitudes, solve_band_levels): prepare, let the ranks agree on an error flag, solve, SOS_TRPHI and _finish per output.
     Returns the list of 23-tuples (one without alts); with fluxes (alts only) the pair (that list, flux rows [K][5], or
-    [K][7] with split: the bins then carry the untruncated depth rows and the aggregates their band transmission)."""
+    [K][7] with split: the bins then carry the untruncated depth rows and the aggregates their band transmission); with
+    absorption (fluxes only) the triple (..., rows [K][5] of LEVEL_ABSORPTION_NAMES: one more launch behind the aggregates)."""
+    import torch
     from . import solver
     from .solver import SosBinError
     pl, levels, err = None, None, None
@@ -1581,7 +1596,9 @@ def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False, split=False):
             if alts is None:
                 rec, fin = pl.ctx.solve_band(pl.bins, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
             else:
-                rec, fin = pl.ctx.solve_band_levels(pl.bins, levels, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded)
+                ab = [] if absorption else None
+                rec, fin = pl.ctx.solve_band_levels(pl.bins, levels, pl.aik, tdifmug=pl.tdifmug, reduce=pl.band_sharded,
+                                                    **(dict(absorption=ab) if absorption else {}))
         except SosBinError as e:
             raise SosProcError(str(e), ier=-1)
         if alts is None:                           # sos_proc: the single call
@@ -1590,6 +1607,8 @@ def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False, split=False):
         else:                                      # the K altitudes in one launch, one download
             if fluxes:                             # (one more launch for the K flux pairs, on the reduced records)
                 flux_dev = solver.level_flux_many([(pl.ctx, rec[k]) for k in range(len(rec))])
+                if absorption:                     # (its block [K][4] comes down with the flux pairs)
+                    flux_dev = torch.cat([flux_dev, ab[0]], dim=1)
             flat, shapes = _trphi_launch_many([(pl, rec[k], int(fin["n_orders"][k]), float(fin["ttot_tronc"][k]),
                                                 float(fin["tauout"][k])) for k in range(len(rec))])
             outs = solver._flat_blocks(flat.cpu().numpy(), shapes)
@@ -1598,15 +1617,19 @@ def _band_call(fn, kw, aer_phase, device, alts=None, fluxes=False, split=False):
             return tuples
         e = flux_dev.cpu().numpy()                 # (complete: it was queued ahead of the recompositions just downloaded)
         row = _level_flux_split_row if split else _level_flux_row
-        return tuples, np.array([row(pl, alts[k], fin, k, e[k]) for k in range(len(rec))], dtype=np.float64)
+        flux = np.array([row(pl, alts[k], fin, k, e[k]) for k in range(len(rec))], dtype=np.float64)
+        if not absorption:
+            return tuples, flux
+        return tuples, flux, np.array([_level_absorption_row(alts[k], e[k][2:6]) for k in range(len(rec))], dtype=np.float64)
     finally:
         pl.ctx.close()
 
 
-def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False, split=False):
+def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False, split=False, absorption=False):
     """The argument rules of the output-slot entry points, checked before any device work: 1 to 16 altitudes, each passing the
     -SOS.OutputAlt rule (SosProcError 2611), and calls with zout = -1 and no -SOS_Main.ResRoot (ValueError).  Returns the
-    altitudes as floats.  fluxes, split: the entry point's flags, bools, split only with fluxes (ValueError)."""
+    altitudes as floats.  fluxes, split, absorption: the entry point's flags, bools, split and absorption only with fluxes;
+    absorption not in a channel pass, nor on a band whose bins are sharded over ranks (ValueError)."""
     from . import capi
     if not isinstance(fluxes, (bool, np.bool_)):
         raise ValueError("%s: fluxes must be True or False, got %r" % (fn, fluxes))
@@ -1614,6 +1637,17 @@ def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False, split=False):
         raise ValueError("%s: split must be True or False, got %r" % (fn, split))
     if split and not fluxes:
         raise ValueError("%s: split=True adds columns to the flux rows: it needs fluxes=True" % fn)
+    if not isinstance(absorption, (bool, np.bool_)):
+        raise ValueError("%s: absorption must be True or False, got %r" % (fn, absorption))
+    if absorption and not fluxes:
+        raise ValueError("%s: absorption=True returns its rows behind the flux rows: it needs fluxes=True" % fn)
+    if absorption and fn == "sos_spectrum_channels":
+        raise ValueError("%s: absorption=True is not available for sensor channels: the absorbed power is formed per CKD bin "
+                         "and returned per call (use sos_spectrum_levels and weight its rows)" % fn)
+    if absorption and fn == "sos_proc_levels" and _dist_rank_world()[1] > 1:
+        raise ValueError("%s: absorption=True is not available for a band whose bins are sharded over ranks: the absorbed "
+                         "power is a per-bin product that does not pass through the band's all-reduce (run the call on one "
+                         "rank, or deal whole wavelengths with sos_spectrum_levels)" % fn)
     alts = [float(z) for z in altitudes]
     if not 1 <= len(alts) <= capi.MAX_OUTPUT_LEVELS:
         raise ValueError("%s: 1 to %d altitudes, got %d" % (fn, capi.MAX_OUTPUT_LEVELS, len(alts)))
@@ -1631,7 +1665,7 @@ def _levels_arguments(fn, altitudes, kwargs_list, fluxes=False, split=False):
     return alts
 
 
-def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, split=False, **kw):
+def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, split=False, absorption=False, **kw):
     """sos_proc for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output) at once: ONE
     profile, context and solve, whose K output slots capture the field at each altitude (sosgpu_os_solve_levels), then
     one aggregate and SOS_TRPHI per altitude.  Returns a list of K 23-tuples in the order of `altitudes`; element k equals
@@ -1667,9 +1701,28 @@ def sos_proc_levels(altitudes, aer_phase=None, device=0, fluxes=False, split=Fal
     the limit altitude is ONE layer, and the interpolated depth there is far from the analytic one (up to 1.3 in optical
     depth in such a bin of the O2 A band): that is the reference's resolution at such altitudes, kept so that
     flux_dir_down + flux_diff_down equals flux_tot_down.  Without forward-peak truncation (a_tronc = 0) flux_dir_down equals
-    flux_dir_down_tronc."""
-    alts = _levels_arguments("sos_proc_levels", altitudes, [kw], fluxes, split)
-    return _band_call("sos_proc_levels", kw, aer_phase, device, alts, bool(fluxes), bool(split))
+    flux_dir_down_tronc.
+
+    absorption=True (a bool, and only with fluxes=True: ValueError otherwise, before any device work): returns (tuples, flux,
+    absorb) with absorb a numpy array [K][5], columns LEVEL_ABSORPTION_NAMES, in the unit of the flux columns (relative to the
+    irradiance mu_s E0 at the top of the atmosphere on a horizontal plane): the actinic flux at z -- 4 pi x the mean intensity,
+    the moment of the captured order-0 field WITHOUT the weight mu -- as actinic_dir (the direct beam,
+    sum aik exp(-tauout_b / mu_s) / mu_s), actinic_diff_down and actinic_diff_up (the two hemispheres of the diffuse field) and
+    actinic_tot, their sum; and absorbed_per_km, the radiative power absorbed per kilometre at z,
+    sum aik (1 - omega_b(z)) (dtau_b / dz) A_b(z): the shortwave heating rate up to the factor mu_s E0 / (rho c_p).  The
+    absorbed power of a CKD band is not linear in the aggregated record, so one launch behind the aggregates
+    (sosgpu_level_absorption) forms the products per bin and sums them with aik; its block comes down with the flux pairs.
+    Conventions: omega and the field are interpolated linearly between the two profile levels that bracket z, as the reference
+    interpolates the field, and dtau / dz is the slope of the layer between them, so that absorbed_per_km at the middle of a
+    layer times its thickness is the layer's net-flux divergence F_net(top) - F_net(bottom) (to some 1e-4 away from the two
+    layers next to the top and to the ground).  The truncation rescale leaves (1 - omega) dtau unchanged: absorbed_per_km
+    belongs to the true atmosphere.  actinic_dir of a band of several bins is the exact band mean of the bins' direct beams,
+    not flux_dir_down_tronc / mu_s, which the reference forms from the band-mean depth; the two agree for one bin.  The row of
+    altitude -1 (ground and top of the atmosphere mixed) is NaN.  Not available for a band whose bins are sharded over ranks
+    (ValueError: the per-bin products do not pass through the all-reduce).  With the default the return value, the launches
+    and the bits are unchanged."""
+    alts = _levels_arguments("sos_proc_levels", altitudes, [kw], fluxes, split, absorption)
+    return _band_call("sos_proc_levels", kw, aer_phase, device, alts, bool(fluxes), bool(split), bool(absorption))
 
 
 def sos_proc_many(kwargs_list, n_workers=8, device=0):
@@ -1713,16 +1766,16 @@ def _expand_outputs(c, block=None):
     return tuple(out)
 
 
-def _gather_results(results, mine, nrows, world, nz=None, flux=None, trans=None):
+def _gather_results(results, mine, nrows, world, nz=None, flux=None, trans=None, absorb=None):
     """Every rank receives the 23-tuples of the wavelengths the other ranks computed (all_gather_object of the compacted
     tuples; the only exchange of a wavelength-partitioned spectrum).  nz: every result is a list of nz 23-tuples (output
     altitudes) instead of one tuple.  flux: the per-wavelength flux rows of sos_spectrum_levels(fluxes=True), which travel with
     the compact tuples and are filled in the same way.  trans: the per-wavelength transmission entries
-    (transmissions=True), which travel and are filled like the flux rows."""
+    (transmissions=True), which travel and are filled like the flux rows; absorb: the rows of absorption=True, likewise."""
     import torch.distributed as dist
     per = 1 if nz is None else nz
     part = [(i, [_compact_outputs(t, nrows[i]) for t in ([results[i]] if nz is None else results[i])]) for i in mine]
-    extras = [x for x in (flux, trans) if x is not None]
+    extras = [x for x in (flux, trans, absorb) if x is not None]
     if extras:
         part = [(i, (cs,) + tuple(x[i] for x in extras)) for i, cs in part]
     parts = [None] * world
@@ -1824,7 +1877,8 @@ class _Chunk:
     """What the stages of one chunk of _spectrum_pass hand to each other: `plans` (every plan prepared, closed by the driver),
     `solved` [(plans, rec [K][nw][S][3][W], scal [K][nw][10+N], table)] device tensors per launch, `salb_bands` [(plans, their
     band spherical albedos [len(plans)], a device tensor)], `ckd_checks` [(status tensor of a part's device gas tables, the
-    plans it speaks of)] and `where`, the wavelength being worked on (named by a failure)."""
+    plans it speaks of)], `absorb` (absorption=True: parallel to `solved`, the device blocks [K][len(plans)][4] of
+    sosgpu_level_absorption) and `where`, the wavelength being worked on (named by a failure)."""
 
 
 def _part_bounds(n, parts, min_part):
@@ -1978,10 +2032,15 @@ def _stage_solves(fn, ch, groups, single, solve_group, solve_single, alts, level
 
 def _stage_flux_launch(ch, nz):
     """fluxes: the flux pairs of every (wavelength, altitude) of the chunk: one launch behind the aggregates, in the order of
-    _stage_todo's list; the result comes down with the recompositions'."""
+    _stage_todo's list; the result comes down with the recompositions'.  absorption: the blocks [K][calls][4] of ch.absorb, put
+    into that order, ride behind the pairs as columns 2..5."""
+    import torch
     from . import solver
-    return solver.level_flux_many([(pl.ctx, rec[k][g]) for gp, rec, _, _ in ch.solved
-                                   for g, pl in enumerate(gp) for k in range(nz)])
+    flux_dev = solver.level_flux_many([(pl.ctx, rec[k][g]) for gp, rec, _, _ in ch.solved
+                                       for g, pl in enumerate(gp) for k in range(nz)])
+    if ch.absorb:
+        flux_dev = torch.cat([flux_dev, torch.cat([a.transpose(0, 1).reshape(-1, 4) for a in ch.absorb])], dim=1)
+    return flux_dev
 
 
 def _split_scalars(scal_all, shapes, n_alb, n_status):
@@ -2042,13 +2101,18 @@ def _stage_todo(ch, nz, blocks, albs, status, trans_out, salb):
     return todo
 
 
-def _stage_flux_rows(todo, flux_dev, flux_rows, flux_row, ncol, alts):
-    """fluxes: the flux rows [K][ncol] of the chunk's calls from the downloaded pairs of _stage_flux_launch."""
+def _stage_flux_rows(todo, flux_dev, flux_rows, flux_row, ncol, alts, absorb_rows=None):
+    """fluxes: the flux rows [K][ncol] of the chunk's calls from the downloaded pairs of _stage_flux_launch; absorb_rows: the
+    rows [K][5] of LEVEL_ABSORPTION_NAMES from the columns behind the pairs."""
     e = flux_dev.cpu().numpy()                      # (complete: queued ahead of the recompositions just downloaded)
     for j, (pl, k, r, f, g) in enumerate(todo):
         if flux_rows[pl.index] is None:
             flux_rows[pl.index] = np.empty((len(alts), ncol))
         flux_rows[pl.index][k] = flux_row(pl, alts[k], f, g, e[j])
+        if absorb_rows is not None:
+            if absorb_rows[pl.index] is None:
+                absorb_rows[pl.index] = np.empty((len(alts), len(LEVEL_ABSORPTION_NAMES)))
+            absorb_rows[pl.index][k] = _level_absorption_row(alts[k], e[j][2:6])
 
 
 def _channel_terms(chan, nz, indices):
@@ -2101,12 +2165,14 @@ def _stage_tuples(ch, todo, flat, shapes, results, nrows, nz):
 
 
 def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False,
-                   split=False, chan=None, trans=False, salb=False):
+                   split=False, chan=None, trans=False, salb=False, absorption=False):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
     launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop.
     The phases of a chunk are the functions above, which hand the _Chunk to each other; the clock is read between them.
     split (with fluxes): the bins carry the untruncated depth rows, the levels `tauvrai`, and the flux rows two more columns.
+    absorption (with fluxes): every solve is followed by one sosgpu_level_absorption launch; the blocks come down with the flux
+    pairs and the pass also returns one array [K][5] of LEVEL_ABSORPTION_NAMES per call, behind the flux rows.
     chan (sos_spectrum_channels: the weights [C][calls] of the sensor channels, None: the pass as it was): the recomposition
     blocks of a chunk stay on the device and are added, weight by weight, onto one accumulator [C][K][nphi][3][W] that lives
     for the pass (solver.channel_accumulate, one call per chunk); no table is built and no 23-tuple formed per wavelength.
@@ -2129,7 +2195,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if len(aer_phases) != nwl:
         raise ValueError("aer_phases must be parallel to kwargs_list")
     if nwl == 0:
-        return tuple([] for _ in range(1 + bool(fluxes) + bool(trans))) if fluxes or trans else []
+        return tuple([] for _ in range(1 + bool(fluxes) + bool(absorption) + bool(trans))) if fluxes or trans else []
     capi.lib()
     dev = torch.device("cuda", device)
     # the per-bin diffuse transmissions of a plan: its own loop's (a -SOS.Trans call), or its rows of the part's
@@ -2155,13 +2221,26 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     else:
         nz, per_chunk = len(alts), max(1, int(chunk) // len(alts))      # the record-memory rule of sos_spectrum_levels
 
+        # absorption: the solves keep their per-bin records, and ONE sosgpu_level_absorption launch per solve, behind its
+        # aggregates, adds the block [K][calls][4] to ch.absorb (parallel to ch.solved); without it the calls are as they were
         def solve_group(table, gp, bins, cob, seg, aik):
-            return solver.solve_spectrum_levels(table, bins, cob, seg, aik, solver.concat_levels([pl.levels for pl in gp]),
-                                                order=None, **group_trans(gp))
+            levels = solver.concat_levels([pl.levels for pl in gp])
+            if not absorption:
+                return solver.solve_spectrum_levels(table, bins, cob, seg, aik, levels, order=None, **group_trans(gp))
+            cx = table.ctxs[0]
+            out = cx.alloc_outputs(bins["nb"], zero=False)
+            out["rec"] = torch.empty((nz, bins["nb"], cx.smax + 1, 3, cx.w), dtype=torch.float64, device=dev)
+            res = solver.solve_spectrum_levels(table, bins, cob, seg, aik, levels, out=out, order=None, **group_trans(gp))
+            zbins = dict(bins, zprof=torch.cat([solver.level_altitudes(pl.bins, bins["lp"]) for pl in gp]))
+            ch.absorb.append(solver.level_absorption_spectrum(table, zbins, cob, seg, aik, levels, out))
+            return res
 
         def solve_single(pl):
             out = pl.ctx.solve_levels(pl.bins, pl.levels) if pl.bins["nb"] else None
-            return pl.ctx.aggregate_levels(out, pl.levels, pl.aik, scal=pl.bins.get("scal"), tdifmug=single_trans(pl))
+            res = pl.ctx.aggregate_levels(out, pl.levels, pl.aik, scal=pl.bins.get("scal"), tdifmug=single_trans(pl))
+            if absorption:
+                ch.absorb.append(pl.ctx.level_absorption(pl.bins, pl.levels, out, pl.aik))
+            return res
     true_kw = dict(true_depth=True) if split else {}    # (split=False: the calls as they were)
     flux_row, flux_names = (_level_flux_split_row, LEVEL_FLUX_SPLIT_NAMES) if split else (_level_flux_row, LEVEL_FLUX_NAMES)
     level_keys = ("jout", "zz", "tauout") + (("tauvrai",) if split else ())
@@ -2179,6 +2258,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
         call_scal = {}                                  # call -> [K][5 (+ flux columns)]: elements 18..22 (and the flux row)
     results = [None] * nwl                              # K 23-tuples per wavelength
     flux_rows = [None] * nwl if fluxes else None        # fluxes: the [K][5] flux rows per wavelength
+    absorb_rows = [None] * nwl if absorption else None  # absorption: the [K][5] actinic / absorbed-power rows per wavelength
     trans_out = [None] * nwl if trans else None         # trans: the trans_entry of every wavelength
     debug = bool(os.environ.get("SOS_SPECTRUM_DEBUG"))
     nrows = {}
@@ -2220,7 +2300,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     try:
         for c0 in range(0, len(mine), per_chunk):
             idx = mine[c0:c0 + per_chunk]
-            ch.plans, ch.solved, ch.salb_bands, ch.ckd_checks = [], [], [], []
+            ch.plans, ch.solved, ch.salb_bands, ch.ckd_checks, ch.absorb = [], [], [], [], []
             try:
                 t0 = time.perf_counter()
                 ch.where = idx[0]
@@ -2267,7 +2347,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 t4 = time.perf_counter()
                 tm["trphi"] += t4 - t3
                 if fluxes:
-                    _stage_flux_rows(todo, flux_dev, flux_rows, flux_row, len(flux_names), alts)
+                    _stage_flux_rows(todo, flux_dev, flux_rows, flux_row, len(flux_names), alts, absorb_rows)
                     t5 = time.perf_counter()
                     tm["fluxes"] += t5 - t4
                     t4 = t5
@@ -2309,8 +2389,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if alts is None:
         results = [None if r is None else r[0] for r in results]
     if world > 1 and gather:
-        _gather_results(results, mine, nrows, world, None if alts is None else nz, flux_rows, trans_out)
-    ret = (results,) + ((flux_rows,) if fluxes else ()) + ((trans_out,) if trans else ())
+        _gather_results(results, mine, nrows, world, None if alts is None else nz, flux_rows, trans_out, absorb_rows)
+    ret = (results,) + ((flux_rows,) if fluxes else ()) + ((absorb_rows,) if absorption else ()) + ((trans_out,) if trans else ())
     return ret if len(ret) > 1 else results
 
 
@@ -2379,7 +2459,7 @@ def _channel_results(kw, chan, mine, acc, ang_rows, call_scal, alts, nflux, dev,
 _CHANNEL_SHARED = ("nbmu_gauss_lum", "tetas", "ficangles_user_lum", "itrphi", "phios", "pas_phi", "ipolar")
 
 
-def _channel_arguments(fn, kwargs_list, weights, normalize, altitudes, fluxes, split):
+def _channel_arguments(fn, kwargs_list, weights, normalize, altitudes, fluxes, split, absorption=False):
     """The argument rules of sos_spectrum_channels, checked before any device work (ValueError naming the first offending
     channel or call).  Returns (the weights [C][calls] as they are applied, the altitudes as floats or None)."""
     nwl = len(kwargs_list)
@@ -2419,12 +2499,15 @@ def _channel_arguments(fn, kwargs_list, weights, normalize, altitudes, fluxes, s
     if altitudes is None:
         if fluxes or split:
             raise ValueError("%s: fluxes and split belong to the altitudes of a levels call: give `altitudes`" % fn)
+        if absorption is not False:
+            raise ValueError("%s: absorption=True is not available for sensor channels (and belongs to a levels call), got %r"
+                             % (fn, absorption))
         return wts, None
-    return wts, _levels_arguments(fn, altitudes, kwargs_list, fluxes, split)
+    return wts, _levels_arguments(fn, altitudes, kwargs_list, fluxes, split, absorption)
 
 
 def sos_spectrum_channels(kwargs_list, weights, normalize=True, altitudes=None, fluxes=False, split=False, aer_phases=None,
-                          device=0, chunk=256, timings=None, prep_streams=16, parts=4):
+                          device=0, chunk=256, timings=None, prep_streams=16, parts=4, absorption=False):
     """The radiances of C sensor channels from a spectrum of sos_proc calls: the spectrum of sos_spectrum (or, with
     `altitudes`, of sos_spectrum_levels) weighted by each channel's spectral response and summed over the calls ON THE DEVICE,
     so that no per-wavelength block is downloaded, no per-wavelength table built and no per-wavelength 23-tuple formed.
@@ -2456,7 +2539,8 @@ def sos_spectrum_channels(kwargs_list, weights, normalize=True, altitudes=None, 
     block (-ANG.Rad.NbGauss, -ANG.Thetas, -ANG.Rad.UserAngFile, -SOS.View, -SOS.View.Phi, -SOS.View.Dphi, -SOS.Ipolar, and
     -SOS.OutputAlt when `altitudes` is None), a non-empty -SOS_Main.ResRoot (no per-wavelength files are written), and the
     rules of sos_spectrum_levels for altitudes, fluxes and split (fluxes and split need `altitudes`).  A call that fails raises
-    what sos_spectrum raises for it.
+    what sos_spectrum raises for it.  absorption=True (the keyword of sos_spectrum_levels) is refused with a ValueError: the
+    absorbed power is formed per CKD bin and returned per call, not per channel.
     aer_phases, device, chunk, timings, prep_streams, parts: as sos_spectrum; `timings` gains the host phase "channels" (the
     accumulate call and the per-call scalars) and its "finish" stays 0.
 
@@ -2464,7 +2548,7 @@ def sos_spectrum_channels(kwargs_list, weights, normalize=True, altitudes=None, 
     own calls; after the pass's failure agreement ONE all-reduce (SUM) of the accumulator and one of the packed scalar sums
     follow, then every rank finishes and returns the same objects.  The order of the sum across ranks differs from one
     process's, so the result equals a single process's to rounding, not to the bit."""
-    wts, alts = _channel_arguments("sos_spectrum_channels", kwargs_list, weights, normalize, altitudes, fluxes, split)
+    wts, alts = _channel_arguments("sos_spectrum_channels", kwargs_list, weights, normalize, altitudes, fluxes, split, absorption)
     return _spectrum_pass("sos_spectrum_channels", kwargs_list, aer_phases, device, True, chunk, timings, prep_streams, parts,
                           alts, bool(fluxes), bool(split), chan=wts)
 
@@ -2573,7 +2657,7 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
 
 
 def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None, prep_streams=16,
-                        parts=4, fluxes=False, split=False, transmissions=False, spherical_albedo=False):
+                        parts=4, fluxes=False, split=False, transmissions=False, spherical_albedo=False, absorption=False):
     """sos_spectrum for several output altitudes (-SOS.OutputAlt, km; -1 = the standard TOA / ground output): every wavelength is
     prepared once, ALL bins of a group of wavelengths go through ONE launch of the fused solver per kernel variant with K output
     slots each (sosgpu_os_solve_multi_levels), then K segmented aggregates (each altitude with its own TAUOUT) and K azimuth
@@ -2610,15 +2694,25 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
     part or wavelength gives the depths at the altitudes, and ONE sosgpu_level_transmission launch per solved group (or single
     wavelength) -- not one per altitude -- puts their band transmissions into the scalar blocks that are downloaded anyway.
 
+    absorption=True (a bool, and only with fluxes=True: ValueError otherwise, before any device work): returns (spec, flux,
+    absorb) with absorb[i] the numpy array [K][5] of call i, columns LEVEL_ABSORPTION_NAMES: the actinic flux (direct, diffuse
+    down, diffuse up, total) and the radiative power absorbed per kilometre at each altitude, as
+    sos_proc_levels(..., fluxes=True, absorption=True) describes them, with its conventions; absorb[i][k] equals that call's
+    row k bit for bit, whatever `chunk` is.  ONE sosgpu_level_absorption launch per solved group (or single wavelength) -- not
+    one per altitude -- queued behind its aggregates forms the per-bin products and their aik-weighted sums; the blocks come
+    down with the flux pairs.  With gather=True the rows travel with the compacted tuples.  Under torch.distributed the
+    wavelengths are dealt whole, so the keyword is available there.  With the default the return value, the launches and the
+    bits are unchanged.
+
     transmissions=True: as sos_spectrum describes it; trans (one trans_entry per call: the values do not depend on the output
-    altitude) is appended behind spec, and behind flux with fluxes=True.
+    altitude) is appended behind spec, behind flux with fluxes=True and behind absorb with absorption=True.
     spherical_albedo=True (only with transmissions=True): the key s_alb of every entry, as sos_spectrum describes it; it does
     not depend on the output altitudes either."""
     trans = _transmissions_argument("sos_spectrum_levels", kwargs_list, transmissions)
     salb = _spherical_albedo_argument("sos_spectrum_levels", spherical_albedo, trans)
-    alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes, split)
+    alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes, split, absorption)
     return _spectrum_pass("sos_spectrum_levels", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
-                          alts, bool(fluxes), bool(split), trans=trans, salb=salb)
+                          alts, bool(fluxes), bool(split), trans=trans, salb=salb, absorption=bool(absorption))
 
 
 def trans_quantities(tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):

@@ -440,14 +440,18 @@ class SosContext:
                                                      _ptr(out["flux"]), self._stream()), "sosgpu_os_solve_levels")
         return out
 
-    def solve_band_levels(self, bins, levels, aik, tdifmug=None, reduce=True, group=None):
+    def solve_band_levels(self, bins, levels, aik, tdifmug=None, reduce=True, group=None, absorption=None):
         """solve_band for K output altitudes: ONE solve (solve_levels), then every altitude's records aggregated with its
         own TAUOUT, and -- sharded over ranks -- one all-reduce covering the K record sets.  levels: output_levels of these
         bins (a rank without bins contributes K neutral elements).  Returns (rec[K][smax+1][3][W], finish_scalars dict with
-        one entry per altitude); raises SosBinError as solve_band does."""
+        one entry per altitude); raises SosBinError as solve_band does.
+        absorption: None, or a list that receives the device tensor [K][4] of level_absorption, queued behind the aggregates
+        (a band that is whole on this rank: the per-bin products do not pass through the all-reduce)."""
         from . import dist as _dist
         out = self.solve_levels(bins, levels) if bins["nb"] else None
         rec, scal = self.aggregate_levels(out, levels, aik, scal=bins.get("scal"), tdifmug=tdifmug)
+        if absorption is not None:
+            absorption.append(self.level_absorption(bins, levels, out, aik)[:, 0])
         rec, scal = rec[:, 0], scal[:, 0]                   # one segment: the band
         if reduce:
             buf = _dist.all_reduce_partial(_dist.pack_partial(rec, scal), scal.shape[1], group=group)
@@ -608,6 +612,15 @@ class SosContext:
         out = torch.empty(2, dtype=torch.float64, device=self.device)
         capi.check(capi.lib().sosgpu_level_flux(self._h, _ptr(row), _ptr(out), self._stream()), "sosgpu_level_flux")
         return out
+
+    def level_absorption(self, bins, levels, out, aik, seg=None):
+        """Actinic flux and absorbed power per km of a band at the K output slots of solve_levels (sosgpu_level_absorption, one
+        launch behind the solve): bins / levels as solve_levels took them, out its result (the per-bin records and norders),
+        aik[nb] and seg as aggregate takes them.  The level altitudes are bins["zprof"] (make_profiles), or the zprof_host of
+        upload_bins (the aerosol-layer profile), uploaded here.  Returns a device tensor [K][nseg][4]: the aik-weighted sums of
+        a_dir, a_dn, a_up (the direct, down-going and up-going parts of the actinic flux) and q (absorbed power per km), all in
+        the unit of the flux columns; zeros in a standard-output slot (altitude -1).  Nothing is waited for."""
+        return _level_absorption(self, None, None, bins, levels, out, aik, seg)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -847,6 +860,58 @@ def albedo_band(seg, aik, salb):
     capi.check(capi.lib().sosgpu_albedo_band(nseg, _ptr(seg_t), _ptr(aik), _ptr(salb), _ptr(out), d.index or 0,
                                              C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "sosgpu_albedo_band")
     return out
+
+
+def level_altitudes(bins, lp=None):
+    """The level altitudes of a bin dict as the device tensor [nb][lp] sosgpu_level_absorption takes: bins["zprof"]
+    (make_profiles) as it is, or the zprof_host of upload_bins (the aerosol-layer profile), uploaded with zeros past its levels;
+    lp: a larger level capacity to pad to (concat_bins).  ValueError for bins without altitudes."""
+    d = bins["prof"].device
+    lp = bins["lp"] if lp is None else lp
+    z = bins.get("zprof")
+    if not isinstance(z, torch.Tensor):
+        zh = bins.get("zprof_host")
+        if zh is None:
+            raise ValueError("the absorbed power needs the bins' level altitudes (make_profiles, or upload_bins with zprof)")
+        zp = np.zeros((bins["nb"], lp))
+        zp[:, :zh.shape[1]] = zh
+        return _dev_f64(zp, d)
+    z = z.to(device=d, dtype=torch.float64)
+    if z.shape[1] < lp:
+        z = torch.nn.functional.pad(z, (0, lp - z.shape[1]))
+    return z.contiguous()
+
+
+def _level_absorption(cx, table, ctx_of_bin, bins, levels, out, aik, seg):
+    """The one caller of sosgpu_level_absorption: SosContext.level_absorption (table None) and level_absorption_spectrum."""
+    d = cx.device
+    nz, nb = levels["nz"], bins["nb"]
+    if seg is None:
+        seg = np.array([0, nb], dtype=np.int32)
+    seg_t = _dev_i32(seg, d)
+    nseg = int(seg_t.numel()) - 1
+    res = torch.zeros((nz, max(nseg, 0), 4), dtype=torch.float64, device=d)
+    if nb == 0 or nseg < 1:
+        return res
+    zprof = level_altitudes(bins)
+    aik_t = _dev_f64(aik, d)
+    lv = [levels[k].contiguous() for k in ("jout", "zz", "tauout")]     # (views of a part's block: [K][nb] of their own here)
+    if tuple(zprof.shape) != (nb, bins["lp"]) or aik_t.numel() != nb or tuple(out["rec"].shape[:2]) != (nz, nb):
+        raise ValueError("level_absorption: zprof [nb][lp], aik [nb] and the records [K][nb] of solve_levels are needed")
+    capi.check(capi.lib().sosgpu_level_absorption(cx._h, None if table is None else _ptr(table.table), _ptr(ctx_of_bin), nb,
+                                                  bins["lp"], _ptr(bins["nt"]), _ptr(bins["prof"]), _ptr(zprof), nz,
+                                                  _ptr(lv[0]), _ptr(lv[1]), _ptr(lv[2]), _ptr(out["rec"]), _ptr(out["norders"]),
+                                                  nseg, _ptr(seg_t), _ptr(aik_t), _ptr(res), cx._stream()),
+               "sosgpu_level_absorption")
+    return res
+
+
+def level_absorption_spectrum(table, bins, ctx_of_bin, seg, aik, levels, out):
+    """SosContext.level_absorption for the bins of many wavelengths in ONE launch, behind solve_spectrum_levels: table, bins,
+    ctx_of_bin, seg, aik and levels as that call took them (bins with the level altitudes `zprof` [nb][lp]: concat_bins does
+    not carry them, see level_altitudes), out its per-bin result (rec [K][nb][smax+1][3][W], norders).  Bin b is read with mu,
+    ga and n0 of table.ctxs[ctx_of_bin[b]].  Returns a device tensor [K][nwavelengths][4]; nothing is waited for."""
+    return _level_absorption(table.ctxs[0], table, ctx_of_bin, bins, levels, out, aik, seg)
 
 
 def release_scratch():

@@ -788,11 +788,14 @@ enum { SOSGPU_FORM_LDS = 0,        /* field resident in LDS, one workgroup per b
        SOSGPU_FORM_SPEC = 3 };     /* streamed, order-parallel: rounds of `spec_k` orders of every bin */
 typedef struct sosgpu_solve_plan {
     int32_t nw, rtw, ct, big;      /* kernel variant: waves, row tiles per wave, column tiles, streamed (1) or LDS-resident (0) */
+    int32_t split, kht;            /* ... the shared-tile form of the LDS-resident contraction (five or six row tiles on four waves:
+                                    * N = 22 ... 32 at up to 32 levels), never with `big`; row tiles of the streamed field layout
+                                    * (4, 5, 6, 8 or 16; SOSGPU_STREAM_PERSIST != 0 widens 5 and 6 to 8), 0 when LDS-resident */
     int32_t form, opl, spec_k;     /* SOSGPU_FORM_*; orders per launch (STREAM, PERSIST); orders per round (SPEC), else 0 */
     int32_t needs_nt;              /* the order-parallel form is a candidate: the solve reads the batch's NT back */
     int32_t per_launch, lpb;       /* bins per sub-launch; level capacity of a work region (multiple of 32) */
     int32_t threads, q_tail;       /* workgroup size; SosBins::q_tail of the persistent form (-1: the launcher's default) */
-    size_t  lds_bytes;             /* dynamic LDS of the LDS-resident variant */
+    size_t  lds_bytes;             /* dynamic LDS the variant is launched with */
     size_t  per_bin, regions;      /* doubles per work region, number of work regions */
     size_t  off_i3, i3_doubles, off_queue, queue_doubles, off_slots, slot_stride, need;
 } sosgpu_solve_plan;

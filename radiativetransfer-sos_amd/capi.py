@@ -72,8 +72,8 @@ class TablesInfo(C.Structure):
 
 class SolvePlan(C.Structure):
     """sosgpu_solve_plan (include/sosgpu.h): launch form and scratch layout of a solve (sosgpu_debug_solve_plan)."""
-    _fields_ = [(k, C.c_int32) for k in ("nw", "rtw", "ct", "big", "form", "opl", "spec_k", "needs_nt", "per_launch", "lpb",
-                                         "threads", "q_tail")] + \
+    _fields_ = [(k, C.c_int32) for k in ("nw", "rtw", "ct", "big", "split", "kht", "form", "opl", "spec_k", "needs_nt",
+                                         "per_launch", "lpb", "threads", "q_tail")] + \
                [(k, C.c_size_t) for k in ("lds_bytes", "per_bin", "regions", "off_i3", "i3_doubles", "off_queue", "queue_doubles",
                                           "off_slots", "slot_stride", "need")]
 

@@ -777,7 +777,7 @@ static int ensure_scratch(sosgpu_ctx *cx, size_t need)
 // sosgpu_os_solve (table == null) and sosgpu_os_solve_multi (per-bin contexts from a device table)
 // nz > 0: sosgpu_os_solve_levels / sosgpu_os_solve_multi_levels (d_jout / d_zz / d_rec hold nz slots; a split batch reads
 // slot k of its bins at k nb + b0 -- bn.zbs is the whole batch's bin count)
-// Launch form, bins per launch and every scratch offset come from solve_plan (solve_plan.h).
+// Kernel variant, launch form, bins per launch and every scratch offset come from solve_plan (solve_plan.h); every launch takes `pl`.
 static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_ctx_of_bin, const int32_t *d_order, int nb, int lp, const int32_t *d_nt,
                          const int32_t *d_iborm, const double *d_prof, const int32_t *d_jout, const double *d_zz,
                          double *d_rec, int32_t *d_norders, int32_t *d_iglast, double *d_flux, void *stream, int nz = 0,
@@ -834,14 +834,14 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
             cx->dbg_spec_i3 = pl.off_i3;
             const int nt_max_r = pl.lpb - 1;           // level capacity of the regions (>= every valid NT of the batch)
             bn.spec_k = -pl.spec_k; bn.s_begin = 0; bn.s_end = 0;
-            rc = launch_sos_stream(dv, bn, nt_max_r, st, &g_last_hip);
+            rc = launch_sos_stream(dv, bn, pl, nt_max_r, st, &g_last_hip);
             bn.spec_k = pl.spec_k;
             // (a series typically ends after 25-50 of its up to 81 orders: 32 + 16 + ... wastes less than all at once, and a
             //  launch whose bins have all stopped costs a few microseconds)
             for (int s0 = 0, kr = pl.spec_k; s0 < S1 && rc == 0; s0 += kr, kr = std::max(1, pl.spec_k / 2)) {
                 bn.s_begin = s0; bn.s_end = std::min(S1, s0 + kr);
-                rc = launch_sos_stream(dv, bn, nt_max_r, st, &g_last_hip);
-                if (rc == 0) rc = launch_sos_stream_replay(dv, bn, bn.s_begin, bn.s_end, st, &g_last_hip);
+                rc = launch_sos_stream(dv, bn, pl, nt_max_r, st, &g_last_hip);
+                if (rc == 0) rc = launch_sos_stream_replay(dv, bn, pl, bn.s_begin, bn.s_end, st, &g_last_hip);
             }
         } else if (pl.big) {
             if (pl.form == SOSGPU_FORM_PERSIST) {
@@ -851,11 +851,11 @@ static int os_solve_impl(sosgpu_ctx *cx, const SosDev *table, const int32_t *d_c
             }
             for (int s0 = 0; s0 < S1 && rc == 0; s0 += pl.opl) {
                 bn.s_begin = s0; bn.s_end = std::min(S1, s0 + pl.opl);
-                rc = table ? launch_sos_stream_multi(dv, bn, nt_max, st, &g_last_hip)
-                           : launch_sos_stream(dv, bn, nt_max, st, &g_last_hip);
+                rc = table ? launch_sos_stream_multi(dv, bn, pl, nt_max, st, &g_last_hip)
+                           : launch_sos_stream(dv, bn, pl, nt_max, st, &g_last_hip);
             }
-        } else rc = table ? launch_sos_os_multi(dv, bn, nt_max, st, &g_last_hip)
-                          : launch_sos_os(dv, bn, nt_max, st, &g_last_hip);
+        } else rc = table ? launch_sos_os_multi(dv, bn, pl, st, &g_last_hip)
+                          : launch_sos_os(dv, bn, pl, st, &g_last_hip);
         if (rc == -2) return SOSGPU_E_HIP;
         if (rc) return rc;
     }
@@ -1026,7 +1026,8 @@ static int trans_stage(sosgpu_ctx *const *ctxs, int nctx, const int32_t *d_ctx_o
     const SosDev &p0 = ctxs[0]->d;
     TransLayout L;
     if (!trans_layout(p0.n, p0.kp, nctx, nb, lp, &L) || !work_area_ok(d_work, work_bytes, L.total)) return SOSGPU_E_ARG;
-    if (const int rc = sos_os_variant(p0.n, lp - 1, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    SolvePlan variant;                       // (refused here as the solve would refuse it; no switch changes that)
+    if (const int rc = solve_variant({p0.n, 0, nb, lp, 0, true}, SolveOverrides(), &variant)) return rc;
     if (nb == 0) return SOSGPU_OK;
     const int device = ctxs[0]->device;
     HIPCHK(hipSetDevice(device));

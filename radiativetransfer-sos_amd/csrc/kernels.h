@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/sosgpu.h"
 #include "sos_common.h"
+#include <atomic>
 
 void launch_noyaux(const SosDev &cx, hipStream_t st);
 void launch_noyaux_fetch(const SosDev &cx, int s, double *d_out, hipStream_t st);
@@ -13,22 +14,43 @@ struct NoyauxTableGrid {
 };
 void launch_noyaux_table(const SosDev *d_tab, int nctx, const NoyauxTableGrid &g, hipStream_t st);
 
-// Fused successive-orders solver.  Returns 0, SOSGPU_E_UNSUPPORTED when (N, max NT) has no variant, or -2 with the HIP
-// error code in *hip_err.
-int launch_sos_os(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err);
-// waves / row-tiles-per-wave / column tiles / LDS bytes the solver would use (for planning and tests); <0 if unsupported.
-int sos_os_variant(int n, int nt_max, int *nw, int *rtw, int *ct, size_t *lds_bytes, int *big);
-// Streamed-field solver (sos_stream.hip) for level grids beyond the LDS-resident variants: same contract as launch_sos_os.
-// bn.scratch holds bn.scr_stride >= sos_stream_scratch_doubles(n, lpb) doubles per bin, lpb a multiple of 32.
-int launch_sos_stream(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err);
-size_t sos_stream_scratch_doubles(int n, int lpb);
+// Fused successive-orders solver, LDS-resident variants (sos_os.hip).  `pl`: the solve's plan -- the launcher runs the
+// instantiation its variant fields name (solve_variant.h) and derives nothing itself.  Returns 0, SOSGPU_E_UNSUPPORTED when the
+// context does not fit that variant, or -2 with the HIP error code in *hip_err.
+int launch_sos_os(const SosDev &cx, const SosBins &bn, const sosgpu_solve_plan &pl, hipStream_t st, int *hip_err);
+// Streamed-field solver (sos_stream.hip) for level grids beyond the LDS-resident variants: same contract.  nt_max bounds every NT
+// of the launch; bn.scratch holds bn.scr_stride >= stream_scratch_doubles(pl.nw, pl.kht, bn.lpb) doubles per bin, bn.lpb a
+// multiple of 32.
+int launch_sos_stream(const SosDev &cx, const SosBins &bn, const sosgpu_solve_plan &pl, int nt_max, hipStream_t st, int *hip_err);
 // order-parallel form (bn.spec_k): the Fourier stop tests of orders [s0, s1) of every bin, after the order tasks of a round
-int launch_sos_stream_replay(const SosDev &cx, const SosBins &bn, int s0, int s1, hipStream_t st, int *hip_err);
-int sos_stream_threads(int n);
+int launch_sos_stream_replay(const SosDev &cx, const SosBins &bn, const sosgpu_solve_plan &pl, int s0, int s1, hipStream_t st,
+                             int *hip_err);
 // the same two solvers with a per-bin context (bn.ctxs, bn.ctx_of_bin; sos_os_multi.hip, sos_stream_multi.hip): `cx` is any
-// context of the table -- it selects the variant (N, surface-matrix flag), which the caller guarantees equal over the table
-int launch_sos_os_multi(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err);
-int launch_sos_stream_multi(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err);
+// context of the table -- its N and surface-matrix flag are what the caller guarantees equal over the table
+int launch_sos_os_multi(const SosDev &cx, const SosBins &bn, const sosgpu_solve_plan &pl, hipStream_t st, int *hip_err);
+int launch_sos_stream_multi(const SosDev &cx, const SosBins &bn, const sosgpu_solve_plan &pl, int nt_max, hipStream_t st,
+                            int *hip_err);
+// What the four launchers share.  The (output mode ZM, SURF) instantiation of a launcher template F<A, B, C, ZM, SURF>: ZM = 2
+// with output slots, 1 with one output altitude, else 0.
+#define SOS_LAUNCH_ZM_SURF(F, A, B, C, nz, zo, surf, ...)                                                        \
+    ((nz) > 0 ? ((surf) ? F<A, B, C, 2, true>(__VA_ARGS__) : F<A, B, C, 2, false>(__VA_ARGS__))                   \
+     : (surf) ? ((zo) ? F<A, B, C, 1, true>(__VA_ARGS__) : F<A, B, C, 0, true>(__VA_ARGS__))                      \
+              : ((zo) ? F<A, B, C, 1, false>(__VA_ARGS__) : F<A, B, C, 0, false>(__VA_ARGS__)))
+// The dynamic-LDS limit of a kernel is set once per device and size (the call costs tens of microseconds: with few bins per
+// wavelength the host launch path is what bounds a hyperspectral loop, scripts/spectrum_bench.py).  configured[16]: the sizes
+// set so far, one array per kernel (atomics: host threads of run_sos.sos_proc_many launch concurrently; a lost update only
+// repeats the call).  *dev: the current device.
+inline hipError_t sos_set_dynamic_lds(const void *kern, size_t lds, std::atomic<size_t> *configured, int *dev)
+{
+    int d = 0;
+    hipError_t e = hipGetDevice(&d);
+    if (e == hipSuccess && (d < 0 || d >= 16 || configured[d].load(std::memory_order_acquire) < lds)) {
+        e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess && d >= 0 && d < 16) configured[d].store(lds, std::memory_order_release);
+    }
+    if (dev) *dev = d;
+    return e;
+}
 
 // The stage around the solver for the diffuse transmissions of -SOS.Trans (trans.hip, sosgpu_trans_spectrum).
 // launch_trans_table: the nchild = nctx * n child entries (incidence J = 1..n of every parent, n common to the parents) and

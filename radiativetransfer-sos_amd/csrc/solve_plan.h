@@ -1,27 +1,10 @@
 // csrc/solve_plan.h -- launch form and scratch layout of the fused solver, stated once (host only).
 // os_solve_impl (api.hip) follows the plan; sosgpu_debug_solve_plan reports it.  Nothing here calls HIP, reads the environment
-// or touches a context: the plan is a function of the problem shape and of the overrides api.hip has read.
+// or touches a context: the plan is a function of the problem shape and of the overrides api.hip has read.  The kernel variant
+// in it is solve_variant's (solve_variant.h), which the launchers follow.
 #pragma once
-#include "kernels.h"
+#include "solve_variant.h"
 #include <algorithm>
-
-// the solver's environment switches, as read once per solve
-struct SolveOverrides {
-    long scratch_gib = 0;                          // SOSGPU_SCRATCH_GIB; <= 0: the default budget
-    bool spec_off = false;                         // SOSGPU_STREAM_SPEC=0
-    bool has_spec_maxbins = false; int spec_maxbins = 0;     // SOSGPU_STREAM_SPEC_MAXBINS
-    bool has_spec_k = false; int spec_k = 0;       // SOSGPU_STREAM_SPEC_K
-    int persist = 0;                               // SOSGPU_STREAM_PERSIST; non-zero: the persistent form
-    int orders_per_launch = 0;                     // SOSGPU_STREAM_ORDERS_PER_LAUNCH; <= 0: all orders in one launch
-    int q_tail = -1;                               // SOSGPU_STREAM_QTAIL; < 0: the launcher's default
-};
-
-struct SolveShape {
-    int n, smax, nb, lp, nz;
-    bool table;                                    // per-bin contexts from a device table (the _multi kernels)
-};
-
-typedef sosgpu_solve_plan SolvePlan;
 
 // output slots (sosgpu_os_solve_levels): lane-private state per work region, [nz][SOS_LV_N][threads] doubles, placed behind
 // the streamed kernel's regions at a 64-byte boundary
@@ -53,32 +36,29 @@ inline int solve_spec_max_bins(const SolveOverrides &ov)
 // has to wait for anyway.
 inline bool solve_plan_needs_nt(const SolveShape &sh, const SolveOverrides &ov)
 {
-    int big = 0;
-    if (sos_os_variant(sh.n, sh.lp - 1, nullptr, nullptr, nullptr, nullptr, &big) != 0 || !big) return false;
+    SolvePlan v;
+    if (solve_variant(sh, ov, &v) != 0 || !v.big) return false;
     return !sh.table && sh.nb <= solve_spec_max_bins(ov) && sh.smax >= 1;
 }
 
 // The plan of one solve.  nt_max: the largest valid NT of the batch, read only when solve_plan_needs_nt().  Returns 0 or the
-// code of sos_os_variant.  Scratch layout (doubles from the start of the context's scratch, each block from the end of the
+// code of solve_variant.  Scratch layout (doubles from the start of the context's scratch, each block from the end of the
 // one before it):
 //   work regions [regions][per_bin] | I3 hand-over block of the order-parallel form | task queues and per-bin order flags of
 //   the persistent form (ints) | lane-private state of the output slots [regions][slot_stride], from a 64-byte boundary
 inline int solve_plan(const SolveShape &sh, const SolveOverrides &ov, int nt_max, SolvePlan *out)
 {
     SolvePlan p = SolvePlan();
-    // variant: field in LDS, or (NT too large) field in a per-bin HBM scratch, launched in sub-batches so that the scratch
-    // stays below its budget.  lp - 1 bounds every NT of the batch (the host pads the level axis to lp).
-    int nw, rtw, ct, big;
-    const int rc = sos_os_variant(sh.n, sh.lp - 1, &nw, &rtw, &ct, &p.lds_bytes, &big);
+    // variant: field in LDS, or (too many levels) field in a per-bin HBM scratch, launched in sub-batches so that the scratch
+    // stays below its budget
+    const int rc = solve_variant(sh, ov, &p);
     if (rc) return rc;
-    p.nw = nw; p.rtw = rtw; p.ct = ct; p.big = big;
     const int s1n = sh.smax + 1;
     p.q_tail = ov.q_tail;
     p.lpb = sos_round_up(sh.lp, 32);
-    if (!big) {
+    if (!p.big) {
         // LDS-resident kernel: no scratch but the output slots' state, one region per bin
         p.form = SOSGPU_FORM_LDS;
-        p.threads = 64 * nw;
         p.per_launch = sh.nb;
         p.regions = (size_t)sh.nb;
         p.slot_stride = lv_stride(sh.nz, p.threads);
@@ -86,9 +66,8 @@ inline int solve_plan(const SolveShape &sh, const SolveOverrides &ov, int nt_max
         *out = p;
         return 0;
     }
-    p.threads = sos_stream_threads(sh.n);
     p.slot_stride = lv_stride(sh.nz, p.threads);
-    p.per_bin = sos_stream_scratch_doubles(sh.n, p.lpb);
+    p.per_bin = stream_scratch_doubles(p.nw, p.kht, p.lpb);
     const size_t cap = solve_scratch_cap(ov);
     // (output slots: a bin's work region also carries the slots' lane-private state)
     p.per_launch = (int)std::min<size_t>((size_t)sh.nb, std::max<size_t>(1, cap / (p.per_bin + p.slot_stride)));
@@ -103,7 +82,7 @@ inline int solve_plan(const SolveShape &sh, const SolveOverrides &ov, int nt_max
         const int lpb_full = p.lpb;
         const size_t per_bin_full = p.per_bin;
         p.lpb = std::min(p.lpb, sos_round_up(std::max(1, nt_max) + 1, 32));
-        p.per_bin = sos_stream_scratch_doubles(sh.n, p.lpb);
+        p.per_bin = stream_scratch_doubles(p.nw, p.kht, p.lpb);
         // at most 4 GiB of work regions (128 bins x 24 orders at 600 levels need 4.6): beyond, fewer orders per round
         const size_t soft = ((size_t)4 << 30) / sizeof(double);
         const size_t fit = soft / ((size_t)sh.nb * p.per_bin);

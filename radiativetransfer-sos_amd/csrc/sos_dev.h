@@ -5,8 +5,8 @@
 #pragma once
 #include <type_traits>
 #include "sos_common.h"
+#include "solve_variant.h"   // capacity constants of the variants: sos_khm / sos_fs / sos_ns, the streamed layout's COLS, skhm ...
 
-#define SOSGPU_E_UNSUPPORTED -3
 // Parity sums X+ +- X- of the B operands: formed by every wave inside the contraction (8 vector sums per k-pair and wave), or
 // once per step / chunk in LDS.  Measured (profiles/r02_flagship_instmix.txt): in the LDS-resident kernel the combine pass needs
 // a workgroup barrier of its own and LOSES 2.1 % (194.1 vs 198.2 k bins/s) -- off; in the streamed kernel it rides in the
@@ -677,12 +677,6 @@ __device__ __forceinline__ void ground_mfma(const double *__restrict__ gp, int k
         for (int rt = 0; rt < NA; rt++) bcv[(tile0 + rt * NW) * 16 + ((lane >> 2) & 3) * 4 + (lane >> 4)] = acc[rt];
     }
 }
-
-// Capacity constants of a variant (shared by the kernel and the host-side sizing below).
-//   KHM = rows per direction half (3N <= KHM), FS = level stride of the field, NS = row stride of the attenuation table
-__host__ __device__ constexpr int sos_khm(int nw, int rtwh) { return 16 * nw * rtwh; }
-__host__ __device__ constexpr int sos_fs(int nw, int rtwh) { return 2 * sos_khm(nw, rtwh) + 2; }
-__host__ __device__ constexpr int sos_ns(int nw, int rtwh) { return (sos_khm(nw, rtwh) / 3 + 1) & ~1; }
 
 // Formal solution of one row (SOS_INTEGR_EPOPT, SOS_OS.F:2279-2354).  With t = exp(-dtau/|mu|) and the source linear
 // in tau on the layer, both directions reduce to the same three-term recurrence

@@ -504,80 +504,21 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
 }
 
 // ---------------------------------------------------------------------------------------------
-// variant table
+// launch: the variant is the plan's (solve_variant.h); this file only maps it to its instantiation
 // ---------------------------------------------------------------------------------------------
-#ifndef SOS_MULTI
-static size_t lds_bytes_for(int nw, int rtw, int ct, bool big)
-{
-    const int cols = 16 * ct, fs = sos_fs(nw, rtw), ns = sos_ns(nw, rtw);
-    size_t dbl = (size_t)cols * fs + 3 * ns + 2 + 2 * ns + 16 + 2 * ns;
-    if (!big) dbl += (size_t)cols * ns + 7 * cols;
-    return dbl * sizeof(double);
-}
-
-// Variant of a problem size: waves per workgroup, row tiles per wave, column tiles per chunk, field in LDS or in HBM.
-//   NT+1 <= 32 : field in LDS, two column tiles, 4 waves (two workgroups per CU) -- the flagship
-//   NT+1 <= 64 : field in LDS, four column tiles; for 21 < N <= 42 EIGHT waves with one row tile each, so that the
-//                accumulators stay at 64 VGPRs and the CU still hosts two waves per SIMD although the 64-level field
-//                leaves room for one workgroup only (68.6k vs 61.3k bins/s for <4,2,4> at N = 41, NT = 60)
-//   NT+1 >  64 : field in the HBM scratch, two column tiles per contraction pass, two workgroups per CU (the 8-wave
-//                four-tile form was slower there: 21.8k vs 26.5k bins/s at NT = 100)
-//   N > 42     : eight waves, two row tiles each, two column tiles (LDS holds 32 levels of the 6N x 8 B rows)
-static void sos_os_shape(int n, int nt_max, int *nw, int *rtw, int *ct, int *big)
-{
-    const int kh = sos_round_up(3 * n, 8);
-    if (kh > 128) { *nw = 8; *rtw = 2; *ct = 2; *big = nt_max + 1 > 32; return; }
-    if (nt_max + 1 <= 32 || nt_max + 1 > 64) { *nw = 4; *rtw = kh <= 64 ? 1 : 2; *ct = 2; *big = nt_max + 1 > 64; return; }
-    *nw = kh <= 64 ? 4 : 8; *rtw = 1; *ct = 4; *big = 0;
-}
-
-// returns 0 and the variant (nw waves, rtw row tiles per wave and system, ct column tiles, big) or UNSUPPORTED
-int sos_os_variant(int n, int nt_max, int *nw, int *rtw, int *ct, size_t *lds_bytes, int *big)
-{
-    if (n < 1 || n > 85 || nt_max < 1 || nt_max > 1023) return SOSGPU_E_UNSUPPORTED;
-    int w, r, c, b;
-    sos_os_shape(n, nt_max, &w, &r, &c, &b);
-    const size_t lb = lds_bytes_for(w, r, c, b);
-    if (lb > 160 * 1024) return SOSGPU_E_UNSUPPORTED;
-    if (nw) *nw = w;
-    if (rtw) *rtw = r;
-    if (ct) *ct = c;
-    if (lds_bytes) *lds_bytes = lb;
-    if (big) *big = b;
-    return 0;
-}
-#endif
-
-// five or six row tiles on four waves, and room for the partials in the pad rows of the field (sos_dev.h gemm_source_split)
-static bool sos_split_applies(const SosDev &cx, int nw, int rtw, int ct)
-{
-#ifdef SOS_NO_SPLIT
-    return false;
-#else
-    return nw == 4 && rtw == 2 && ct == 2 && cx.rtph > nw && cx.rtph <= nw + 2 && 16 * cx.rtph + 16 * (cx.rtph - nw) <= sos_khm(nw, rtw);
-#endif
-}
-
 template <int NW, int RTWH, int CT, int ZM, bool SURF, bool SPLIT = false>
-static int launch_variant(const SosDev &cx, const SosBins &bn, size_t lds, hipStream_t st, int *hip_err)
+static int launch_variant(const SosDev &cx, const SosBins &bn, const SolvePlan &pl, hipStream_t st, int *hip_err)
 {
     if constexpr (!SPLIT && NW == 4 && RTWH == 2 && CT == 2) {
-        if (sos_split_applies(cx, NW, RTWH, CT)) return launch_variant<NW, RTWH, CT, ZM, SURF, true>(cx, bn, lds, st, hip_err);
+        if (pl.split) return launch_variant<NW, RTWH, CT, ZM, SURF, true>(cx, bn, pl, st, hip_err);
     }
     auto kern = k_sos_os<NW, RTWH, CT, ZM, SURF, SPLIT>;
+    size_t lds = pl.lds_bytes;
 #ifdef SOS_PROFILE_PHASES
     if (const char *e = getenv("SOSGPU_DEBUG_LDS_PAD")) lds += (size_t)atoi(e);   // diagnostic builds: force 1 workgroup per CU
 #endif
-    // the dynamic-LDS limit of a kernel is set once per device and size (the call costs tens of microseconds: with few bins per
-    // wavelength the host launch path is what bounds a hyperspectral loop, scripts/spectrum_bench.py)
-    // (atomics: host threads of run_sos.sos_proc_many launch concurrently; a lost update only repeats the call)
     static std::atomic<size_t> configured[16];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess && (dev < 0 || dev >= 16 || configured[dev].load(std::memory_order_acquire) < lds)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess && dev >= 0 && dev < 16) configured[dev].store(lds, std::memory_order_release);
-    }
+    hipError_t e = sos_set_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured, nullptr);
     if (e == hipSuccess) {
         kern<<<bn.nb, 64 * NW, lds, st>>>(cx, bn);
         e = hipGetLastError();
@@ -586,37 +527,20 @@ static int launch_variant(const SosDev &cx, const SosBins &bn, size_t lds, hipSt
     return 0;
 }
 
-int launch_sos_os(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err)
+int launch_sos_os(const SosDev &cx, const SosBins &bn, const SolvePlan &pl, hipStream_t st, int *hip_err)
 {
-    int nw, rtw, ct, big;
-    size_t lds;
-    const int rc = sos_os_variant(cx.n, nt_max, &nw, &rtw, &ct, &lds, &big);
-    if (rc) return rc;
-    if (cx.kh > sos_khm(nw, rtw) || cx.rtph * 16 < cx.kh) return SOSGPU_E_UNSUPPORTED;
-    if (big) return SOSGPU_E_UNSUPPORTED;                  // streamed variant: launch_sos_stream (sos_stream.hip)
-    const int zo = bn.jout != nullptr;
-#ifdef SOS_WIDE_REGS
-    if (nw == 8 && rtw == 1 && ct == 4) { nw = 4; rtw = 2; }      // same KHM, same LDS layout
-#endif
-#define V_LV(NWV, R, C)                                                                \
-        if (bn.nz > 0)                                                                 \
-            return cx.imat_surf ? launch_variant<NWV, R, C, 2, true>(cx, bn, lds, st, hip_err)  \
-                                : launch_variant<NWV, R, C, 2, false>(cx, bn, lds, st, hip_err);
-#define V(NWV, R, C)                                                                   \
-    if (nw == NWV && rtw == R && ct == C) {                                            \
-        V_LV(NWV, R, C)                                                                \
-        if (cx.imat_surf)                                                              \
-            return zo ? launch_variant<NWV, R, C, 1, true>(cx, bn, lds, st, hip_err)            \
-                      : launch_variant<NWV, R, C, 0, true>(cx, bn, lds, st, hip_err);          \
-        return zo ? launch_variant<NWV, R, C, 1, false>(cx, bn, lds, st, hip_err)               \
-                  : launch_variant<NWV, R, C, 0, false>(cx, bn, lds, st, hip_err);             \
-    }
+    if (cx.kh > sos_khm(pl.nw, pl.rtw) || cx.rtph * 16 < cx.kh) return SOSGPU_E_UNSUPPORTED;
+    if (pl.big) return SOSGPU_E_UNSUPPORTED;                  // streamed variant: launch_sos_stream (sos_stream.hip)
+    if (pl.split && (cx.rtph <= 4 || cx.rtph > 6)) return SOSGPU_E_UNSUPPORTED;    // the shared-tile form: five or six row tiles
+#define V(NWV, R, C)                                                                                                   \
+    if (pl.nw == NWV && pl.rtw == R && pl.ct == C)                                                                     \
+        return SOS_LAUNCH_ZM_SURF(launch_variant, NWV, R, C, bn.nz, bn.jout, cx.imat_surf, cx, bn, pl, st, hip_err);
     V(4, 1, 2) V(4, 2, 2) V(8, 2, 2)
     V(4, 1, 4) V(8, 1, 4)
 #ifdef SOS_WIDE_REGS
     V(4, 2, 4)
 #endif
 #undef V
-#undef V_LV
     return SOSGPU_E_UNSUPPORTED;
 }
+

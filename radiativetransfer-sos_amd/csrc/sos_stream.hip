@@ -43,7 +43,6 @@
 #ifndef SOS_STREAM_NT
 #define SOS_STREAM_NT 2
 #endif
-namespace {
 #ifndef SOS_STREAM_TOP_BARRIER
 #define SOS_STREAM_TOP_BARRIER 0   // 1: workgroup barrier between the store pass of a chunk and the staging of the next one
 #endif
@@ -52,31 +51,8 @@ namespace {
                                    // 22.1 k bins/s, profiles/r02_stream_experiments.txt): the per-unit address arithmetic of the
                                    // requests costs more vector issue than the hidden latency returns.  Kept as an experiment switch.
 #endif
-#ifndef SOS_STREAM_COLS
-#define SOS_STREAM_COLS 32
-#endif
-constexpr int COLS = SOS_STREAM_COLS;      // levels per chunk (two 16-column MFMA tiles; 16 = experiment: three workgroups per CU)
-constexpr int VPAD = 8;       // level vectors are stored with a +1 offset (entry e = level e-1) and a few spare entries
-}
-
-// Row capacity of the field layout.  Round 2 sized it by the wave shape alone, KHM = 16 NW RTWH rows per half: 64, 128, 256.  A half
-// system of 66 ... 96 rows (N = 22 ... 32 -- the reference's default of 24 Gauss angles is N = 25) then moved 128-row chunks through
-// LDS and HBM: N = 22 ran 32 % slower than N = 21 for 5 % more work (profiles/r03_n_sweep.txt).  The layout is now sized in row
-// tiles, KHT = 5 or 6 for those direction counts (KHM = 80 / 96, FS = 162 / 194: 41 / 50 KB chunks instead of 66 KB), the wave
-// shape staying <4,2> (wave 0, or waves 0 and 1, carry a second tile).  KHM = 16 KHT, FS = 2 KHM + 2 (still = 2 mod 4 doubles:
-// conflict-free ds_read_b128 of the B operands), NS = directions capacity.
-__host__ __device__ constexpr int skhm(int kht) { return 16 * kht; }
-__host__ __device__ constexpr int sfs(int kht) { return 2 * skhm(kht) + 2; }
-__host__ __device__ constexpr int sns(int kht) { return (skhm(kht) / 3 + 1) & ~1; }
-
-// scratch of one bin, in doubles (lpb = level capacity, a multiple of COLS)
-__host__ __device__ inline size_t stream_scratch_doubles(int nw, int kht, int lpb)
-{
-    const size_t fs = sfs(kht), ns = sns(kht), khm = skhm(kht), nch = lpb / COLS;
-    const size_t d = (size_t)lpb * fs + (size_t)(lpb + 1) * ns + 7 * (size_t)(lpb + VPAD) + nch * (2 * khm + 2 * ns) +
-                     2 * 64 * (size_t)nw + 8;                  // + state carried from one launch to the next (i4, i5 per thread)
-    return (d + 15) & ~(size_t)15;
-}
+// COLS levels per chunk, VPAD, the row capacity KHM = skhm(KHT) of the field layout and the sizes of the scratch and of the LDS
+// are those of solve_variant.h.
 
 // Homogeneous part of the up-going field of U levels: P <- P (1 - a), X = Q + P xin (see the header); q, qa move upwards.
 // (bases moved to the low end of the block and pinned: non-negative immediate offsets, see scan_block)
@@ -991,41 +967,12 @@ __global__ __launch_bounds__(64 * NW) void k_sos_stream_replay(const SosDev cx, 
     }
 }
 
+
 // ---------------------------------------------------------------------------------------------
-static size_t stream_lds_bytes(int kht)
-{
-    const int fs = sfs(kht), ns = sns(kht);
-    return ((size_t)COLS * fs + 3 * ns + 2 + 2 * ns + 16 + 2 * ns + (size_t)COLS * ns + 7 * (COLS + VPAD)) * sizeof(double);
-}
-
-// waves, row tiles per wave, row tiles of the layout for N directions
-static void stream_shape(int n, int *nw, int *rtw, int *kht)
-{
-    const int kh = sos_round_up(3 * n, 8);
-    if (kh > 128) { *nw = 8; *rtw = 2; *kht = 16; }
-    else if (kh <= 64) { *nw = 4; *rtw = 1; *kht = 4; }
-    else {
-        *nw = 4; *rtw = 2;
-        *kht = kh <= 80 ? 5 : kh <= 96 ? 6 : 8;
-#ifdef SOS_STREAM_WIDE
-        *kht = 8;                                          // round 2's layout (A/B measurements)
-#endif
-        // the persistent, order-scheduled form (opt-in) exists for the full-width layout only
-        if (const char *e = getenv("SOSGPU_STREAM_PERSIST")) { if (atoi(e) != 0) *kht = 8; }
-    }
-}
-
-#ifndef SOS_MULTI
-size_t sos_stream_scratch_doubles(int n, int lpb)
-{
-    int nw, rtw, kht;
-    stream_shape(n, &nw, &rtw, &kht);
-    return stream_scratch_doubles(nw, kht, lpb);
-}
-#endif
-
-template <int NW, int RTWH, int ZM, bool SURF, int KHT = NW * RTWH>
-static int launch_stream_variant(const SosDev &cx, const SosBins &bn, hipStream_t st, int *hip_err)
+// launch: the variant (wave shape, KHT, LDS bytes) is the plan's (solve_variant.h); this file only maps it to its instantiation
+// ---------------------------------------------------------------------------------------------
+template <int NW, int RTWH, int KHT, int ZM, bool SURF>
+static int launch_stream_variant(const SosDev &cx, const SosBins &bn, const SolvePlan &pl, hipStream_t st, int *hip_err)
 {
 #ifdef SOS_MULTI
     const bool persist = false;                            // (the per-bin context is bound to blockIdx.x)
@@ -1033,23 +980,16 @@ static int launch_stream_variant(const SosDev &cx, const SosBins &bn, hipStream_
     auto kern = k_sos_stream<NW, RTWH, ZM, SURF, false, KHT>;
 #else
     const bool persist = bn.queue != nullptr;
-    if (persist && KHT != NW * RTWH) return SOSGPU_E_UNSUPPORTED;       // (stream_shape keeps the full width for that form)
+    if (persist && KHT != NW * RTWH) return SOSGPU_E_UNSUPPORTED;       // (solve_variant keeps the full width for that form)
     if (persist && ZM == 2) return SOSGPU_E_UNSUPPORTED;                // (the caller launches output slots in the plain form)
     auto kern = k_sos_stream<NW, RTWH, ZM, SURF, false, KHT>;
     if constexpr (KHT == NW * RTWH && ZM != 2) { if (persist) kern = k_sos_stream<NW, RTWH, ZM, SURF, true, KHT>; }
 #endif
-    const size_t lds = stream_lds_bytes(KHT);
-    // the dynamic-LDS limit of a kernel is set once per device and size (the call costs tens of microseconds: with few bins per
-    // wavelength the host launch path is what bounds a hyperspectral loop, scripts/spectrum_bench.py)
-    // (atomics: host threads of run_sos.sos_proc_many launch concurrently; a lost update only repeats the call)
+    const size_t lds = pl.lds_bytes;
     static std::atomic<size_t> configured[2][16];           // (per instantiation of this function: one per kernel variant)
     static std::atomic<int> cus[16];
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess && (dev < 0 || dev >= 16 || configured[persist][dev].load(std::memory_order_acquire) < lds)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess && dev >= 0 && dev < 16) configured[persist][dev].store(lds, std::memory_order_release);
-    }
+    hipError_t e = sos_set_dynamic_lds(reinterpret_cast<const void *>(kern), lds, configured[persist], &dev);
     int grid = bn.spec_k > 0 ? bn.nb * bn.spec_k : bn.nb;
     if (e == hipSuccess && persist) {
         // as many workgroups as the chip hosts at once (two per CU for the 4-wave forms); fewer resident ones only cost speed
@@ -1071,21 +1011,12 @@ static int launch_stream_variant(const SosDev &cx, const SosBins &bn, hipStream_
 }
 
 #ifndef SOS_MULTI
-int sos_stream_threads(int n)
+int launch_sos_stream_replay(const SosDev &cx, const SosBins &bn, const SolvePlan &pl, int s0, int s1, hipStream_t st, int *hip_err)
 {
-    int nw, rtw, kht;
-    stream_shape(n, &nw, &rtw, &kht);
-    return 64 * nw;
-}
-
-int launch_sos_stream_replay(const SosDev &cx, const SosBins &bn, int s0, int s1, hipStream_t st, int *hip_err)
-{
-    int nw, rtw, kht;
-    stream_shape(cx.n, &nw, &rtw, &kht);
-    if (kht == 4) k_sos_stream_replay<4, 4><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
-    else if (kht == 5) k_sos_stream_replay<4, 5><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
-    else if (kht == 6) k_sos_stream_replay<4, 6><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
-    else if (kht == 8) k_sos_stream_replay<4, 8><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
+    if (pl.kht == 4) k_sos_stream_replay<4, 4><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
+    else if (pl.kht == 5) k_sos_stream_replay<4, 5><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
+    else if (pl.kht == 6) k_sos_stream_replay<4, 6><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
+    else if (pl.kht == 8) k_sos_stream_replay<4, 8><<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
     else k_sos_stream_replay<8, 16><<<bn.nb, 512, 0, st>>>(cx, bn, s0, s1);
     if (bn.nz > 1) k_sos_stream_lv_clear<<<bn.nb, 256, 0, st>>>(cx, bn, s0, s1);
     const hipError_t e = hipGetLastError();
@@ -1094,30 +1025,16 @@ int launch_sos_stream_replay(const SosDev &cx, const SosBins &bn, int s0, int s1
 }
 #endif
 
-int launch_sos_stream(const SosDev &cx, const SosBins &bn, int nt_max, hipStream_t st, int *hip_err)
+int launch_sos_stream(const SosDev &cx, const SosBins &bn, const SolvePlan &pl, int nt_max, hipStream_t st, int *hip_err)
 {
     if (cx.n < 1 || cx.n > 85 || nt_max < 1 || nt_max > 1023) return SOSGPU_E_UNSUPPORTED;
-    int nw, rtw, kht;
-    stream_shape(cx.n, &nw, &rtw, &kht);
-    if (cx.kh > skhm(kht) || cx.rtph * 16 < cx.kh || cx.rtph > kht) return SOSGPU_E_UNSUPPORTED;
-    if (!bn.scratch || bn.lpb < nt_max + 1 || bn.lpb % COLS || bn.scr_stride < stream_scratch_doubles(nw, kht, bn.lpb))
+    if (cx.kh > skhm(pl.kht) || cx.rtph * 16 < cx.kh || cx.rtph > pl.kht) return SOSGPU_E_UNSUPPORTED;
+    if (!bn.scratch || bn.lpb < nt_max + 1 || bn.lpb % COLS || bn.scr_stride < stream_scratch_doubles(pl.nw, pl.kht, bn.lpb))
         return SOSGPU_E_UNSUPPORTED;
-    const int zo = bn.jout != nullptr;
-#define V_LV(NWV, R, K)                                                                        \
-        if (bn.nz > 0)                                                                         \
-            return cx.imat_surf ? launch_stream_variant<NWV, R, 2, true, K>(cx, bn, st, hip_err)     \
-                                : launch_stream_variant<NWV, R, 2, false, K>(cx, bn, st, hip_err);
-#define V(NWV, R, K)                                                                           \
-    if (nw == NWV && rtw == R && kht == K) {                                                   \
-        V_LV(NWV, R, K)                                                                        \
-        if (cx.imat_surf)                                                                      \
-            return zo ? launch_stream_variant<NWV, R, 1, true, K>(cx, bn, st, hip_err)         \
-                      : launch_stream_variant<NWV, R, 0, true, K>(cx, bn, st, hip_err);       \
-        return zo ? launch_stream_variant<NWV, R, 1, false, K>(cx, bn, st, hip_err)            \
-                  : launch_stream_variant<NWV, R, 0, false, K>(cx, bn, st, hip_err);          \
-    }
+#define V(NWV, R, K)                                                                                                   \
+    if (pl.nw == NWV && pl.rtw == R && pl.kht == K)                                                                    \
+        return SOS_LAUNCH_ZM_SURF(launch_stream_variant, NWV, R, K, bn.nz, bn.jout, cx.imat_surf, cx, bn, pl, st, hip_err);
     V(4, 1, 4) V(4, 2, 5) V(4, 2, 6) V(4, 2, 8) V(8, 2, 16)
 #undef V
-#undef V_LV
     return SOSGPU_E_UNSUPPORTED;
 }

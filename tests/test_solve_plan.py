@@ -3,7 +3,8 @@ device, the environment switches read as a solve reads them).
 
 CPU: the Python restatement of the bins-per-launch rule (test_spectrum_levels._scratch_split) against the library; the scratch
 blocks of every plan of a grid disjoint, ordered and inside the allocation; one assertion per precedence rule of the
-environment switches.
+environment switches; the kernel variant in the plan (csrc/solve_variant.h) -- the row tiles of the streamed layout with and
+without SOSGPU_STREAM_PERSIST, the shared-tile form -- against the table of test_variant_matrix.
 GPU: a batch split into sub-launches by the scratch budget WITHOUT a context table (sosgpu_os_solve_levels), bit for bit the
 unsplit solve."""
 import ctypes as C
@@ -70,6 +71,64 @@ def test_scratch_split_restatement_against_the_library(pkg, env):
             assert (p.per_launch, p0.per_launch) == (with_slots, without), what
             assert p.per_bin == p0.per_bin == per_bin and p.lpb == vm._round_up(lp, 32), what
             assert p.slot_stride == lv and p0.slot_stride == 0 and p.threads * 8 * nz == lv, what
+
+
+def _stream_numbers(p, lp, kht_n):
+    """The streamed plan p against the restatement of test_spectrum_levels at a direction count kht_n of p's layout."""
+    per_bin = tsl._scratch_numbers(kht_n, lp, 0)[0]
+    khm, ns = 16 * p.kht, (16 * p.kht // 3 + 1) & ~1
+    # k_sos_stream's LDS: a 32-level chunk of the field, the ground / flux / Gauss vectors, the attenuations, seven level vectors
+    lds = 8 * (32 * (2 * khm + 2) + 3 * ns + 2 + 2 * ns + 16 + 2 * ns + 32 * ns + 7 * (32 + 8))
+    return (p.per_bin, p.threads, p.lds_bytes, p.nw * p.rtw >= p.kht) == (per_bin, 64 * p.nw, lds, True)
+
+
+def test_streamed_row_tiles_follow_the_table(pkg, env):
+    """SOSGPU_STREAM_PERSIST unset or 0: KHT is the third number of the table's streamed layouts over their N ranges."""
+    want = {n: int(lay[7:-1].split(",")[2]) for lay, (lo, hi) in vm.N_RANGE.items() if lay.startswith("stream")
+            for n in range(lo, hi + 1)}
+    assert sorted(set(want.values())) == [4, 5, 6, 8, 16] and sorted(want) == list(range(3, 86))
+    for ov in (dict(), dict(STREAM_PERSIST=0)):
+        env(**ov)
+        for n, kht in want.items():
+            for lp in (80, 608):
+                for table, nz in itertools.product((False, True), (0, 2)):
+                    p = _plan(pkg, n, 8, 340, lp, nz, table)
+                    assert p.big == 1 and p.split == 0 and p.kht == kht, (ov, n, lp, table, nz, p.kht)
+                    assert _stream_numbers(p, lp, n), (ov, n, lp, table, nz)
+
+
+def test_persist_switch_widens_the_narrow_layouts_in_every_form(pkg, env):
+    """SOSGPU_STREAM_PERSIST=1: the 8-tile layout for every N = 22 ... 32, with or without a table or output slots; the form
+    is the persistent one only without either and with all orders in one launch."""
+    capi = pkg.capi
+    env(STREAM_PERSIST=1)
+    for n in range(22, 33):
+        for lp in (80, 608):
+            for table, nz in itertools.product((False, True), (0, 2)):
+                p = _plan(pkg, n, 8, 5, lp, nz, table)
+                assert p.big == 1 and p.kht == 8 and (p.nw, p.rtw) == (4, 2), (n, lp, table, nz, p.kht)
+                assert _stream_numbers(p, lp, 33), (n, lp, table, nz)                  # (N = 33: 8 tiles by the table)
+                assert p.form == (capi.FORM_STREAM if table or nz else capi.FORM_PERSIST), (n, lp, table, nz, p.form)
+            env(STREAM_PERSIST=1, STREAM_ORDERS_PER_LAUNCH=3)
+            p = _plan(pkg, n, 8, 5, lp)
+            assert p.kht == 8 and p.form == capi.FORM_STREAM and _stream_numbers(p, lp, 33), (n, lp)
+            env(STREAM_PERSIST=1)
+    assert tsl._scratch_numbers(33, 608, 0) != tsl._scratch_numbers(32, 608, 0)
+    for n in (21, 33, 42, 43):                          # the other layouts are what they are without the switch
+        assert _plan(pkg, n, 8, 5, 608).kht == {21: 4, 33: 8, 42: 8, 43: 16}[n]
+
+
+def test_split_exactly_on_the_two_column_tile_route_of_n_22_to_32(pkg, env):
+    for ov in (dict(), dict(STREAM_PERSIST=1)):
+        env(**ov)
+        for n in range(3, 86):
+            for lp in vm.NTS:
+                for table, nz in itertools.product((False, True), (0, 2)):
+                    p = _plan(pkg, n, 8, 5, lp, nz, table)
+                    assert p.split == (22 <= n <= 32 and lp == 32), (ov, n, lp, table, nz)
+                    assert not (p.split and p.big) and (p.kht > 0) == (p.big == 1), (ov, n, lp, table, nz)
+                    if p.split:
+                        assert (p.nw, p.rtw, p.ct) == (4, 2, 2), (n, lp)
 
 
 GRID = list(itertools.product((13, 21, 43, 85), (32, 64, 608), (1, 40, 41, 128, 129, 340), (0, 1, 6), (False, True)))

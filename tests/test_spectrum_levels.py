@@ -106,7 +106,7 @@ def test_concat_levels_orders_and_pads_like_concat_bins(pkg):
 
 
 def _scratch_numbers(n, lp, nz):
-    """Doubles of one work region of the streamed kernel at lp padded levels (stream_scratch_doubles, csrc/sos_stream.hip) and
+    """Doubles of one work region of the streamed kernel at lp padded levels (stream_scratch_doubles, csrc/solve_variant.h) and
     of the lane-private state of nz output slots of that region (lv_stride, csrc/solve_plan.h)."""
     kh = vm._round_up(3 * n, 8)
     nw, kht = (8, 16) if kh > 128 else (4, 4) if kh <= 64 else (4, 5 if kh <= 80 else 6 if kh <= 96 else 8)

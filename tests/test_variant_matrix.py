@@ -2,10 +2,12 @@
 first and last direction count its layout accepts, against the C oracle; the launch forms bit for bit against each other;
 and the records independent of memory a kernel must not read (levels past a bin's NT, stale scratch).
 
-The routing from (N, padded level count lp) to a layout is mirrored in `route` below; `test_table_covers_every_instantiation`
-(CPU) checks the table against that mirror, and a rocprofv3 kernel trace of this module shows the launches where the table
-says they go (profiles/variant_matrix_kernel_stats.csv)."""
+The routing from (N, padded level count lp) to a layout is the library's: `route` below reads it from the plan a solve follows
+(sosgpu_debug_solve_plan; the rule is solve_variant, csrc/solve_variant.h, and the launchers take the plan's variant).  The
+literal tables LAYOUTS / N_RANGE / FULL_WIDTH are the independent statement; `test_table_covers_every_instantiation` (CPU)
+checks them against the library for every N = 3 ... 85 at every padded level count of NTS."""
 import ctypes as C
+import importlib
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -22,26 +24,14 @@ def _round_up(x, m):
 
 
 def route(n, lp):
-    """Layout that sosgpu_os_solve launches for N directions and the padded level count lp (nt_max = lp - 1).
-    Mirrors sos_os_shape (csrc/sos_os.hip), sos_split_applies (csrc/sos_os.hip) and stream_shape (csrc/sos_stream.hip),
-    without the diagnostic build flags and SOSGPU_STREAM_PERSIST (which widens <4,2,5> / <4,2,6> to <4,2,8>)."""
-    kh = _round_up(3 * n, 8)
-    lev = lp                                          # nt_max + 1
-    if kh > 128:                                      # sos_os_shape
-        nw, rtw, ct, big = 8, 2, 2, lev > 32
-    elif lev <= 32 or lev > 64:
-        nw, rtw, ct, big = 4, (1 if kh <= 64 else 2), 2, lev > 64
-    else:
-        nw, rtw, ct, big = (4 if kh <= 64 else 8), 1, 4, False
-    if big:                                           # stream_shape
-        if kh > 128:
-            return "stream<8,2,16>"
-        if kh <= 64:
-            return "stream<4,1,4>"
-        return "stream<4,2,%d>" % (5 if kh <= 80 else 6 if kh <= 96 else 8)
-    rtph = (kh + 15) // 16                            # sos_split_applies
-    split = nw == 4 and rtw == 2 and ct == 2 and nw < rtph <= nw + 2 and 16 * rtph + 16 * (rtph - nw) <= 16 * nw * rtw
-    return "os<%d,%d,%d%s>" % (nw, rtw, ct, ",SPLIT" if split else "")
+    """Layout that sosgpu_os_solve launches for N directions and the padded level count lp (nt_max = lp - 1), as the library's
+    plan names it -- under the switches of the environment: SOSGPU_STREAM_PERSIST widens <4,2,5> / <4,2,6> to <4,2,8>."""
+    capi = importlib.import_module("radiativetransfer-sos_amd.capi")
+    p = capi.SolvePlan()
+    capi.check(capi.lib().sosgpu_debug_solve_plan(n, 0, 1, lp, 0, 0, lp - 1, C.byref(p)), "sosgpu_debug_solve_plan")
+    if p.big:
+        return "stream<%d,%d,%d>" % (p.nw, p.rtw, p.kht)
+    return "os<%d,%d,%d%s>" % (p.nw, p.rtw, p.ct, ",SPLIT" if p.split else "")
 
 
 # layout -> [(N, padded level counts of its batches)]: the first and last N of the layout (3 = the smallest N of
@@ -208,8 +198,16 @@ def _oracle_futures(oracle, b):
 
 # ---- 4. the table itself (CPU) ------------------------------------------------------------------------------------------
 
-def test_table_covers_every_instantiation():
+def test_table_covers_every_instantiation(pkg, monkeypatch):
+    monkeypatch.delenv("SOSGPU_STREAM_PERSIST", raising=False)                    # (route reads the plan as a solve would)
     assert len(LAYOUTS) == 11 and set(N_RANGE) == set(LAYOUTS)
+    # every N at every padded level count: exactly one layout of the tables holds (N, lp) -- N in its range, lp between the
+    # smallest and the largest lp of its batches -- and it is the one the library's plan names
+    span = {lay: (min(lp for _, lps in c for lp in lps), max(lp for _, lps in c for lp in lps)) for lay, c in LAYOUTS.items()}
+    for lp in NTS:
+        for n in range(3, 86):
+            held = [lay for lay, (lo, hi) in N_RANGE.items() if lo <= n <= hi and span[lay][0] <= lp <= span[lay][1]]
+            assert held == [route(n, lp)], (n, lp, held, route(n, lp))
     cells = {(lay, zo, surf) for lay, zo, surf, _, _ in BATCHES}
     assert len(cells) == 44
     for lay, zo, surf, n, lp in BATCHES:
@@ -263,6 +261,17 @@ def test_batch_angles_and_levels():
 
 # ---- 1. the matrix against the oracle ----------------------------------------------------------------------------------
 
+def _assert_bin_vs_oracle(got, k, rec, ref, records, what):
+    """Row k of the fetched outputs `got`, its records `rec`, against the oracle's solve `ref` and its `records`."""
+    f = len(records)
+    assert np.isfinite(records).all() and np.isfinite(rec).all(), what
+    assert ref["ier"] == 0 and int(got["norders"][k]) == f, (what, int(got["norders"][k]), f)
+    assert np.array_equal(got["iglast"][k, :f], ref["ig_counts"]), (what, got["iglast"][k, :f], ref["ig_counts"])
+    cases.compare_records(rec[:f], records, 1e-9, what)
+    assert abs(got["flux"][k, 0] - ref["emoins"]) <= 1e-9 * abs(ref["emoins"]) + 1e-300, what
+    assert abs(got["flux"][k, 1] - ref["eplus"]) <= 1e-9 * abs(ref["eplus"]) + 1e-300, what
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("batch", BATCHES, ids=_batch_id)
 def test_instantiation_vs_oracle(gpu_pkg, oracle, batch):
@@ -275,13 +284,7 @@ def test_instantiation_vs_oracle(gpu_pkg, oracle, batch):
         ref = fut.result()
         what = "%s bin %d NT=%d IBORM=%d n0=%d %s" % (_batch_id(batch), k, b["nt"][k], b["iborm"][k], b["n0"],
                                                     {a: v for a, v in b["kw"].items() if a != "rsurf"})
-        f = len(ref["records"])
-        assert np.isfinite(ref["records"]).all() and np.isfinite(got["rec"][k]).all(), what
-        assert ref["ier"] == 0 and int(got["norders"][k]) == f, (what, int(got["norders"][k]), f)
-        assert np.array_equal(got["iglast"][k, :f], ref["ig_counts"]), (what, got["iglast"][k, :f], ref["ig_counts"])
-        cases.compare_records(got["rec"][k, :f], ref["records"], 1e-9, what)
-        assert abs(got["flux"][k, 0] - ref["emoins"]) <= 1e-9 * abs(ref["emoins"]) + 1e-300, what
-        assert abs(got["flux"][k, 1] - ref["eplus"]) <= 1e-9 * abs(ref["eplus"]) + 1e-300, what
+        _assert_bin_vs_oracle(got, k, got["rec"][k], ref, ref["records"], what)
 
 
 # ---- 2. launch forms and the multi-context kernels, bit for bit -------------------------------------------------------
@@ -319,6 +322,63 @@ def test_launch_forms_and_multi_context_bitwise(gpu_pkg, monkeypatch, batch):
     _assert_same({k: v[len(ra):] for k, v in got.items()}, ref_b, range(len(rb)), "%s multi ctx 1" % _batch_id(batch))
     cx.close()
     cx2.close()
+
+
+# ---- 2b. the widened layout in the plain form ------------------------------------------------------------------------------
+
+WIDENED = [("stream<4,2,5>", 22, 80), ("stream<4,2,6>", 32, 80)]
+
+
+def _oracle_levels(oracle, b, k, g, zouts):
+    al, be, ga, ze = S.hg_phase(b["os_nb"], g)
+    h, x, y, z = b["bins"][k]
+    kw = dict(b["kw"])
+    ib = int(b["iborm"][k])
+    if "rsurf" in kw:
+        kw["rsurf"] = kw["rsurf"][:ib + 1]
+    return oracle.sos_os_levels(b["mu"], b["w"], b["os_nb"], h, x, y, al, be, ga, ze, zouts, n0=b["n0"], zprof=z, iborm=ib, **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("surf", (False, True), ids=("noSURF", "SURF"))
+@pytest.mark.parametrize("lay,n,lp", WIDENED, ids=("N22", "N32"))
+def test_widened_layout_in_the_plain_form_vs_oracle(gpu_pkg, oracle, monkeypatch, lay, n, lp, surf):
+    """SOSGPU_STREAM_PERSIST=1 widens the five- and six-tile layouts to eight tiles; a context table and output slots then run
+    the plain form (one workgroup per bin) on that layout -- k_sos_stream<4,2,.,.,false,8> below its full row count, which no
+    other test launches.  (i) the bins split over two contexts with different phase functions in one solve_spectrum launch,
+    (ii) solve_levels with a standard and an interior slot; both against the oracle."""
+    import torch
+    b = make_batch(lay, False, surf, n, lp)
+    nb, zint = len(b["bins"]), 1.5
+    ra, rb = list(range(nb))[0::2], list(range(nb))[1::2]
+    refs = [_POOL.submit(_oracle_levels, oracle, b, k, 0.7, [-1.0, zint]) for k in range(nb)]
+    refs_b = {k: _POOL.submit(_oracle_levels, oracle, b, k, 0.8, [-1.0]) for k in rb}
+    monkeypatch.setenv("SOSGPU_STREAM_PERSIST", "1")
+    assert route(n, lp) == "stream<4,2,8>"
+    cx, cx2 = _context(gpu_pkg, b), _context(gpu_pkg, b, g=0.8)
+    try:
+        ba, bb = _upload(cx, b, ra), _upload(cx2, b, rb)
+        table = gpu_pkg.solver.ContextTable([cx, cx2])
+        bins, cob, seg = gpu_pkg.solver.concat_bins([ba, bb])
+        out = cx.alloc_outputs(bins["nb"])
+        gpu_pkg.solver.solve_spectrum(table, bins, cob, seg, torch.full((nb,), 1.0 / nb, dtype=torch.float64, device=cx.device),
+                                      out=out)
+        multi = _fetch(out)
+        full = _upload(cx, b)
+        lv = cx.output_levels(full, [-1.0, zint])
+        assert (lv["jout"][1] > 0).all()                                         # the second slot is interior in every bin
+        slots = _fetch(cx.solve_levels(full, lv))
+    finally:
+        cx.close()
+        cx2.close()
+    what = "%s PERSIST=1" % _batch_id((lay, False, surf, n, lp))
+    for r, k in enumerate(ra + rb):
+        ref = (refs[k] if k in ra else refs_b[k]).result()
+        _assert_bin_vs_oracle(multi, r, multi["rec"][r], ref, ref["records"][0], "%s table, bin %d" % (what, k))
+    for k in range(nb):
+        ref = refs[k].result()
+        for slot in (0, 1):
+            _assert_bin_vs_oracle(slots, k, slots["rec"][slot, k], ref, ref["records"][slot], "%s slot %d, bin %d" % (what, slot, k))
 
 
 # ---- 3. results independent of memory the kernel must not read ---------------------------------------------------------

@@ -7,12 +7,10 @@ tables that are in use, nothing else.  The legs alternate after a warm-up of bot
 Prints every pass with its host phases, then the sorted rates, the median and the spread (max - min) of each leg, the medians
 of the trphi / finish / channels phases, and the peak resident set after each leg's warm-up (resource.getrusage; the channel
 leg is warmed first, the counter only grows)."""
-import argparse, importlib, os, resource, statistics, sys, tempfile, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "4")
+import resource, time
+import ab_harness as ab
+QUEUES = ab.queues("4")
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "scripts"))
-import synth_ckd
 import hyperspectral_bench as hb
 from spectrum_levels_bench import ALTS
 
@@ -44,27 +42,22 @@ def host_convolution(tuples, w, nrow):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = ab.parser()
     ap.add_argument("--every", type=int, default=1)
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--chunk", type=int, default=256)
     ap.add_argument("--altitudes", type=int, default=0, help="0: sos_spectrum; K: sos_spectrum_levels at K altitudes")
     ap.add_argument("--one-leg", choices=["channels", "spectrum"], help="a single pass of one leg (for a kernel trace)")
     a = ap.parse_args()
-    import torch
-    pkg = importlib.import_module("radiativetransfer-sos_amd")
-    rs = pkg.run_sos
-    root = tempfile.mkdtemp(prefix="synth_fic_")
-    synth_ckd.write_tables(root)
-    hb.link_aerosol_tables(root)
-    os.environ["SOS_ABS_ROOT"] = root
+    rs = ab.package().run_sos
+    ab.synthetic_tables(link_aerosols=True)
     kws = hb.spectrum_kwargs(rs, a.every)
     kws = kws[:NCHAN * (len(kws) // NCHAN)]
     alts = ALTS[:a.altitudes]
     w = boxcars(len(kws))
     nrow = len(range(0, 361, int(kws[0]["pas_phi"])))
-    print("spectrum: %d wavelengths, %d box-car channels of %d, altitudes %s, chunk %d, GPU_MAX_HW_QUEUES=%s" % (
-        len(kws), NCHAN, len(kws) // NCHAN, alts or "(sos_spectrum)", a.chunk, os.environ.get("GPU_MAX_HW_QUEUES")), flush=True)
+    rep = ab.Report(a.out)
+    say = rep.say
+    say("spectrum: %d wavelengths, %d box-car channels of %d, altitudes %s, chunk %d, GPU_MAX_HW_QUEUES=%s" % (
+        len(kws), NCHAN, len(kws) // NCHAN, alts or "(sos_spectrum)", a.chunk, QUEUES))
 
     def leg(name):
         tm = {}
@@ -84,38 +77,23 @@ def main():
     def rss():
         return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
 
-    rs.sos_proc(**kws[0]); torch.cuda.synchronize()
+    ab.warm_up(rs, kws[0])
     if a.one_leg:
-        leg(a.one_leg)                                       # warm-up pass: tables parsed, caches filled
-        print("[%s] %.1f wavelengths/s" % (a.one_leg, leg(a.one_leg)[0]), flush=True)
-        return
+        return ab.one_pass(lambda: leg(a.one_leg), a.one_leg, "wavelengths/s")
     got = leg("channels")[2]
     rss_channels = rss()
     ref = leg("spectrum")[2]
     rss_spectrum = rss()
     # the device applies the reference's output thresholds to the sums; on this spectrum no sum comes near them
-    same = all(np.array_equal(x, y) for c1, c2 in zip(got, ref) for k1, k2 in zip(c1, c2) for x, y in zip(k1, k2))
-    print("warm-up passes done; I, Q, U of the two legs identical, bit for bit: %s" % same, flush=True)
-    print("peak resident set after the warm-up of the channel leg %.0f MB, after that of the spectrum leg %.0f MB" % (
-        rss_channels, rss_spectrum), flush=True)
+    say("warm-up passes done; I, Q, U of the two legs identical, bit for bit: %s" % ab.tuples_identical(got, ref))
+    say("peak resident set after the warm-up of the channel leg %.0f MB, after that of the spectrum leg %.0f MB" % (
+        rss_channels, rss_spectrum))
     del got, ref
-    rates = {"channels": [], "spectrum": []}
-    phases = {"channels": [], "spectrum": []}
-    for k in range(a.runs):
-        for name in ("channels", "spectrum"):
-            r, tm, _ = leg(name)
-            rates[name].append(r)
-            phases[name].append(tm)
-            print("[%s %d] %7.1f wavelengths/s   host phases per wavelength (ms): %s" % (
-                name, k + 1, r, ", ".join("%s %.4f" % (q, 1e3 * v / len(kws)) for q, v in tm.items())), flush=True)
-    for name, v in rates.items():
-        print("wavelengths/s  %-8s: %s   median %.1f, max - min %.1f" % (
-            name, " ".join("%.1f" % x for x in sorted(v)), statistics.median(v), max(v) - min(v)), flush=True)
-    for name, v in phases.items():
-        print("median host phase per wavelength (ms)  %-8s: trphi %.4f, finish %.4f, channels %.4f" % (
-            name, 1e3 * statistics.median(t["trphi"] for t in v) / len(kws), 1e3 * statistics.median(t["finish"] for t in v) / len(kws),
-            1e3 * statistics.median(t.get("channels", 0.0) for t in v) / len(kws)), flush=True)
-    print("peak resident set at the end %.0f MB" % rss(), flush=True)
+    _, phases = ab.alternate({name: (lambda name=name: leg(name)[:2]) for name in ("channels", "spectrum")}, a.runs,
+                             "wavelengths/s", say, per_pass=ab.host_phases(len(kws), "wavelength"))
+    ab.phase_medians(phases, len(kws), "wavelength", say, keys=("trphi", "finish", "channels"))
+    say("peak resident set at the end %.0f MB" % rss())
+    rep.close()
 
 
 if __name__ == "__main__":

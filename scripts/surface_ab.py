@@ -9,11 +9,10 @@ Legs, both through run_sos.sos_spectrum:
 The legs alternate after a warm-up of both (batch 1, per_call 1, batch 2, ...), each pass between two device synchronisations
 and with the surface cache emptied first.  Prints every pass, then the sorted rates, the median and the spread (max - min) of
 each leg in wavelengths per second, and writes the same lines to --out."""
-import argparse, importlib, os, statistics, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "4")
+import os, time
+import ab_harness as ab
+QUEUES = ab.queues("4")
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 BASE = {"-ANG.Thetas": 35.0, "-AP.HR": 8.0, "-AP.AerHS.HA": 2.0, "-AP.Psurf": 1013.0, "-AP.AbsProfile.Type": 7, "-AER.AOTref": 0.0,
         "-AER.Waref": 0.55, "-SOS.IGmax": 100, "-SOS.View": 2, "-SOS.View.Dphi": 120, "-SURF.Alb": 0.0,
@@ -36,57 +35,36 @@ def spectra(rs, n):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = ab.parser(out=os.path.join(ab.ROOT, "profiles", "surface_ab.txt"))
     ap.add_argument("--n", type=int, default=64, help="wavelengths of each spectrum")
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--chunk", type=int, default=256)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "surface_ab.txt"))
     a = ap.parse_args()
     import torch
-    pkg = importlib.import_module("radiativetransfer-sos_amd")
-    rs = pkg.run_sos
-    lines = []
-
-    def say(text):
-        print(text, flush=True)
-        lines.append(text)
+    rs = ab.package().run_sos
+    rep = ab.Report(a.out)
+    say = rep.say
 
     def leg(kws, name):
-        if name == "per_call":
-            os.environ["SOS_SPECTRUM_SURFACE_PER_CALL"] = "1"
-        else:
-            os.environ.pop("SOS_SPECTRUM_SURFACE_PER_CALL", None)
-        rs._SURF_CACHE.clear()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        tuples = rs.sos_spectrum(kws, chunk=a.chunk)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
+        with ab.switch("SOS_SPECTRUM_SURFACE_PER_CALL", name == "per_call"):
+            rs._SURF_CACHE.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tuples = rs.sos_spectrum(kws, chunk=a.chunk)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
         return len(kws) / dt, tuples
 
     say("GPU_MAX_HW_QUEUES=%s, chunk %d (both legs run in this process under that queue setting; the rates hold for it only)" % (
-        os.environ.get("GPU_MAX_HW_QUEUES"), a.chunk))
+        QUEUES, a.chunk))
     for which, kws in spectra(rs, a.n).items():
-        rs.sos_proc(**kws[0]); torch.cuda.synchronize()
+        ab.warm_up(rs, kws[0])
         _, t_b = leg(kws, "batch")
         _, t_p = leg(kws, "per_call")
-        same = all(np.array_equal(np.asarray(x), np.asarray(y)) for p, q in zip(t_b, t_p) for x, y in zip(p, q))
         say("%s spectrum: %d wavelengths, %d directions; warm-up passes done; the 23-tuples of the two legs identical, bit for "
-            "bit: %s" % (which, len(kws), int(t_b[0][0]), same))
+            "bit: %s" % (which, len(kws), int(t_b[0][0]), ab.tuples_identical(t_b, t_p)))
         del t_b, t_p
-        rates = {"batch": [], "per_call": []}
-        for k in range(a.runs):
-            for name in ("batch", "per_call"):
-                r = leg(kws, name)[0]
-                rates[name].append(r)
-                say("[%s %s %d] %8.1f wavelengths/s" % (which, name, k + 1, r))
-        for name, v in rates.items():
-            say("wavelengths/s  %-4s %-8s: %s   median %.1f, max - min %.1f" % (
-                which, name, " ".join("%.1f" % x for x in sorted(v)), statistics.median(v), max(v) - min(v)))
-    os.environ.pop("SOS_SPECTRUM_SURFACE_PER_CALL", None)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        ab.alternate({"%s %s" % (which, name): (lambda name=name: (leg(kws, name)[0], None)) for name in ("batch", "per_call")},
+                     a.runs, "wavelengths/s", say)
+    rep.close()
 
 
 if __name__ == "__main__":

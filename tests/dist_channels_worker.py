@@ -1,17 +1,11 @@
 """Worker of tests/test_spectrum_channels_dist.py: one rank of run_sos.sos_spectrum_channels -- plain, and at three altitudes
 with fluxes -- under torch.distributed (gloo, every rank on cuda:0).  Every rank saves what it returns and the calls it owns."""
 import argparse
-import importlib
 import os
-import sys
 
 import numpy as np
-import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dist_launch import rank_begin, rank_end
 
 ALTS = [-1.0, 0.0, 3.0]
 VARIANT = "lambert"
@@ -39,21 +33,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ["SOS_ABS_ROOT"] = os.path.join(ROOT, "tests", "golden")
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    pkg = importlib.import_module("radiativetransfer-sos_amd")
+    rank, world, pkg = rank_begin()
     rs = pkg.run_sos
     kws, w = inputs(rs, os.path.join(a.out, "rank%d" % rank))
     owned = np.array(sorted(int(i) for i in pkg.dist.balanced_shards(rs.spectrum_costs(kws), world)[rank]))
     plain = pack(rs.sos_spectrum_channels(kws, w))
     levels = pack(*rs.sos_spectrum_channels(kws, w, altitudes=ALTS, fluxes=True))
-    torch.cuda.synchronize()
     np.savez(os.path.join(a.out, "channels_rank%d.npz" % rank), owned=owned, **{"plain_" + k: v for k, v in plain.items()},
              **{"levels_" + k: v for k, v in levels.items()})
-    dist.barrier()
-    dist.destroy_process_group()
+    rank_end()
 
 
 if __name__ == "__main__":

@@ -1,21 +1,16 @@
-"""Worker of tests/test_dist_gpu.py: one rank of a sharded band solve on a real GPU (launched by torch.distributed.run).
+"""Worker of tests/test_dist_gpu.py: one rank of a sharded band solve on a real GPU (launched by tests/dist_launch.py).
 
 Every rank builds the same seeded bin list, solves ITS contiguous slice with SosContext.solve_band (fused solve, AIK-weighted
 aggregate incl. the TDIFMUG tail, ONE all-reduce) and rank 0 compares the band with the unsharded solve of all bins.
 --backend nccl: one GPU per rank (RCCL); --backend gloo: every rank on cuda:0 (the 1-GPU test box), tensors reduced by gloo."""
 import argparse
-import importlib
 import json
-import os
-import sys
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dist_launch import rank_begin, rank_end
 
 
 def main():
@@ -24,12 +19,8 @@ def main():
     ap.add_argument("--bins", type=int, default=7)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    local = int(os.environ.get("LOCAL_RANK", rank))
-    dev = local if a.backend == "nccl" else 0
-    torch.cuda.set_device(dev)
-    dist.init_process_group(a.backend, rank=rank, world_size=world)
-    pkg = importlib.import_module("radiativetransfer-sos_amd")
+    rank, world, pkg = rank_begin(abs_root=None, backend=a.backend)
+    dev = torch.cuda.current_device()
     S, D = pkg.synth, pkg.dist
     import cases
     c = cases.make_case("aer_n41")
@@ -71,9 +62,7 @@ def main():
         with open(a.out, "w") as f:
             json.dump(res, f)
     cx.close()
-    if world > 1:
-        dist.barrier()
-    dist.destroy_process_group()
+    rank_end()
 
 
 if __name__ == "__main__":

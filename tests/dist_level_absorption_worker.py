@@ -2,28 +2,20 @@
 fluxes=True, absorption=True under torch.distributed (two ranks on cuda:0, gloo).  The wavelengths are dealt whole to the ranks;
 with gather=True the rows travel with the compacted tuples, with gather=False the slots of the other rank stay None."""
 import argparse
-import importlib
 import json
 import os
-import sys
 
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dist_launch import rank_begin, rank_end
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    os.environ["SOS_ABS_ROOT"] = os.path.join(ROOT, "tests", "golden")
-    pkg = importlib.import_module("radiativetransfer-sos_amd")
+    rank, world, pkg = rank_begin()
     rs = pkg.run_sos
     import test_level_absorption as tla
     kws = tla.dist_kws(rs, os.path.join(os.path.dirname(a.out), "rank%d" % rank))
@@ -41,8 +33,7 @@ def main():
     if rank == 0:
         with open(a.out, "w") as f:
             json.dump({"world": world, "n": len(kws), "digests": dig, "owners": own, "partial_ok": ok}, f)
-    dist.barrier()
-    dist.destroy_process_group()
+    rank_end()
 
 
 if __name__ == "__main__":

@@ -3,17 +3,11 @@ over the ranks, the fluxes computed by every rank from the reduced records) and 
 on four wavelengths (dealt to the ranks, the flux rows gathered with the tuples), under torch.distributed (gloo, every rank on
 cuda:0).  Every rank saves its flux arrays."""
 import argparse
-import importlib
 import os
-import sys
 
 import numpy as np
-import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dist_launch import rank_begin, rank_end
 
 ALTS = [-1.0, 0.0, 3.0]
 BAND = "ckd_o2a_5bins"
@@ -32,11 +26,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ["SOS_ABS_ROOT"] = os.path.join(ROOT, "tests", "golden")
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    rs = importlib.import_module("radiativetransfer-sos_amd").run_sos
+    rank, world, pkg = rank_begin()
+    rs = pkg.run_sos
     band, spectrum = inputs(rs, os.path.join(a.out, "rank%d" % rank))
     tuples, flux = rs.sos_proc_levels(ALTS, fluxes=True, **band)
     assert len(tuples) == len(ALTS) and flux.shape == (len(ALTS), 5)
@@ -45,11 +36,9 @@ def main():
     part, pflux = rs.sos_spectrum_levels(ALTS, spectrum, fluxes=True, gather=False)
     assert [i for i, t in enumerate(part) if t is not None] == [i for i, f in enumerate(pflux) if f is not None]
     assert all(np.array_equal(f, sflux[i]) for i, f in enumerate(pflux) if f is not None)
-    torch.cuda.synchronize()
     np.savez(os.path.join(a.out, "flux_rank%d.npz" % rank), band=flux, spectrum=np.array(sflux),
              owned=np.array([f is not None for f in pflux]))
-    dist.barrier()
-    dist.destroy_process_group()
+    rank_end()
 
 
 if __name__ == "__main__":

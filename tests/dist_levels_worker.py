@@ -2,17 +2,13 @@
 cuda:0).  The CKD band's bins are sharded over the ranks and one all-reduce covers the K record sets; every rank must return,
 for each altitude, exactly what sos_proc with that altitude returns under the same sharding.  Rank 0 saves its outputs."""
 import argparse
-import importlib
 import json
 import os
-import sys
 
 import numpy as np
-import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from dist_launch import GOLD, rank_begin, rank_end
 
 ALTS = [-1.0, 3.0, 0.0, 120.0, 3.0]
 
@@ -21,12 +17,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ["SOS_ABS_ROOT"] = os.path.join(ROOT, "tests", "golden")
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    rs = importlib.import_module("radiativetransfer-sos_amd").run_sos
-    g = np.load(os.path.join(ROOT, "tests", "golden", "sos_proc_ckd_h2o_o2_25bins_flatsea.npz"))
+    rank, world, pkg = rank_begin()
+    rs = pkg.run_sos
+    g = np.load(os.path.join(GOLD, "sos_proc_ckd_h2o_o2_25bins_flatsea.npz"))
     user = json.loads(str(g["user_json"]))
     user.pop("-SOS.OutputAlt", None)
     user.update({"-SOS_Main.Log": "NO_LOG_FILE", "-SOS.Flux": "NO_OUTPUT", "-SOS_Main.ResRoot": ""})
@@ -44,7 +37,7 @@ def main():
             for i in range(23):
                 res["out_%d_%d" % (k, i)] = np.asarray(got[k][i])
         np.savez(a.out, **res)
-    dist.destroy_process_group()
+    rank_end()
 
 
 if __name__ == "__main__":

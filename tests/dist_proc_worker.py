@@ -1,18 +1,14 @@
 """Worker of tests/test_dist_gpu.py::test_sos_proc_sharded: run_sos.sos_proc under torch.distributed (several ranks on cuda:0,
 gloo reduce): every rank takes a slice of the CKD bins of the band and must return the reference's outputs."""
 import argparse
-import importlib
 import json
 import os
-import sys
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dist_launch import GOLD, rank_begin, rank_end
 
 
 def main():
@@ -20,14 +16,10 @@ def main():
     ap.add_argument("--case", required=True)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    os.environ["SOS_ABS_ROOT"] = os.path.join(ROOT, "tests", "golden")
-    pkg = importlib.import_module("radiativetransfer-sos_amd")
+    rank, world, pkg = rank_begin()
     rs = pkg.run_sos
     import cases
-    g = np.load(os.path.join(ROOT, "tests", "golden", "sos_proc_%s.npz" % a.case))
+    g = np.load(os.path.join(GOLD, "sos_proc_%s.npz" % a.case))
     user = json.loads(str(g["user_json"]))
     tmp = os.path.dirname(a.out)
     user.update({"-SOS_Main.Log": "NO_LOG_FILE", "-SOS_Main.ResRoot": os.path.join(tmp, "res")})
@@ -48,8 +40,7 @@ def main():
     if rank == 0:
         with open(a.out, "w") as f:
             json.dump({"world": world, "sums": allv, "files": files}, f)
-    dist.barrier()
-    dist.destroy_process_group()
+    rank_end()
 
 
 if __name__ == "__main__":

@@ -2,17 +2,11 @@
 run_sos.sos_spectrum_levels(..., fluxes=True, transmissions=True) under torch.distributed (gloo, every rank on cuda:0): the
 wavelengths are dealt to the ranks, the transmission entries travel with the gathered tuples.  Every rank saves its entries."""
 import argparse
-import importlib
 import os
-import sys
 
 import numpy as np
-import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dist_launch import rank_begin, rank_end
 
 ALTS = [-1.0, 2.0]
 KEYS = ("thetas", "thetav", "ttot_tronc", "ttot_vrai", "tdifmus", "tdifmug", "t_dir_down", "t_dif_down", "t_dif_up")
@@ -27,11 +21,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ["SOS_ABS_ROOT"] = os.path.join(ROOT, "tests", "golden")
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    rs = importlib.import_module("radiativetransfer-sos_amd").run_sos
+    rank, world, pkg = rank_begin()
+    rs = pkg.run_sos
     from test_spectrum_transmissions import spectrum_keywords
     kws = spectrum_keywords(rs, os.path.join(a.out, "rank%d" % rank))
     tuples, trans = rs.sos_spectrum(kws, transmissions=True)
@@ -40,11 +31,9 @@ def main():
     assert [i for i, t in enumerate(part) if t is not None] == [i for i, t in enumerate(ptrans) if t is not None]
     spec, flux, ltrans = rs.sos_spectrum_levels(ALTS, kws, fluxes=True, transmissions=True)
     assert len(spec) == len(flux) == len(ltrans) == len(kws)
-    torch.cuda.synchronize()
     np.savez(os.path.join(a.out, "trans_rank%d.npz" % rank), owned=np.array([t is not None for t in ptrans]),
              **flatten(trans, "s"), **flatten(ltrans, "l"))
-    dist.barrier()
-    dist.destroy_process_group()
+    rank_end()
 
 
 if __name__ == "__main__":

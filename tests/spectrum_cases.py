@@ -13,6 +13,13 @@ FIXED_CASES = ["cfg1_lambert", "cfg2_lnd_lambert", "cfg4_glitter_bilnd", "cfg5_c
                "land_breon", "land_rondeaux", "land_roujean", "layer_1_3km_lnd", "nopolar_polar"]
 
 
+def assert_tuples_equal(a, b, where=None):
+    """Two 23-tuples of outputs (sos_proc's return) equal bit for bit; a failure names `where` and the element."""
+    assert len(a) == len(b) == 23, (where, len(a), len(b))
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert np.array_equal(np.asarray(x), np.asarray(y)), (where, i)
+
+
 def build(rs, workdir, names=None, resroot=False):
     """Returns (kwargs_list, goldens, coef_tronca overrides, rtols) for the named goldens (default: the 20 random keyword sets
     twice + the fixed cases: 56 calls)."""

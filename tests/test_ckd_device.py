@@ -12,6 +12,7 @@ import pytest
 
 import ckd_cells
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = spectrum_cases.GOLD
@@ -422,12 +423,6 @@ END_TO_END = ["ckd_o2a_5bins", "ckd_h2o_o2_25bins_flatsea", "cfg1_lambert", "cfg
               "cfg2_lnd_lambert"]
 
 
-def _same23(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-
-
 def _watch(monkeypatch, pkg):
     """Wrappers round the host interpolation and the batched profile stage: which wavelengths (by wavenumber) were interpolated
     on the host, which were handed over with `prep`, which with host xk."""
@@ -495,14 +490,14 @@ def test_spectrum_equals_sequential_calls_bitwise(gpu_pkg, sequential, monkeypat
     assert len(gas) == 4 and len(trans) == 2 and len(kws) == 6
     seen = _watch(monkeypatch, gpu_pkg)
     for a, b in zip(seq, rs.sos_spectrum(kws)):
-        _same23(a, b)
+        assert_tuples_equal(a, b)
     if host_tables:
         assert not seen["prep"] and seen["xk"] == 2 and len(seen["host"]) == 4
     else:
         assert len(seen["prep"]) == 2 and seen["xk"] == 0
         assert not (set(seen["host"]) & set(seen["prep"])) and len(seen["host"]) == 2            # only the two -SOS.Trans calls
     for a, b in zip(seq, rs.sos_spectrum(kws, chunk=3)):
-        _same23(a, b)
+        assert_tuples_equal(a, b)
 
 
 @pytest.mark.gpu
@@ -516,7 +511,7 @@ def test_spectrum_levels_equal_sos_proc_per_altitude(gpu_pkg, sequential, monkey
     lev = rs.sos_spectrum_levels(alts, sub)
     for i, kw in enumerate(sub):
         for k, z in enumerate(alts):
-            _same23(rs.sos_proc(**dict(kw, zout=float(z))), lev[i][k])
+            assert_tuples_equal(rs.sos_proc(**dict(kw, zout=float(z))), lev[i][k])
 
 
 def _negate_interval(path, nu, nustep=10.0):
@@ -580,4 +575,4 @@ def test_error_923_in_a_spectrum_is_the_error_of_the_call_alone(gpu_pkg, tmp_pat
     assert inlist.value.ier == alone.value.ier
     outs = rs.sos_spectrum(good)
     for kw, o in zip(good, outs):
-        _same23(rs.sos_proc(**kw), o)
+        assert_tuples_equal(rs.sos_proc(**kw), o)

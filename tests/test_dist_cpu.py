@@ -2,7 +2,6 @@
 each rank forms the AIK-weighted partial sums of its shard, one all-reduce combines them, and the
 result equals the serial SOS_AGGREGATE of the whole bin list within fp64 summation noise."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -11,15 +10,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from dist_launch import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q, nb=13, balanced=False):
@@ -66,7 +59,7 @@ def test_sharded_aggregate_matches_serial(oracle, world, nb, balanced):
     3 ranks (one rank holds none and contributes the neutral element): the all-reduced band equals the serial SOS_AGGREGATE."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q, nb, balanced)) for r in range(world)]
     for p in procs:
         p.start()

@@ -1,33 +1,17 @@
 """The sharded band solve on real GPUs, several processes (the multi-rank product path had only run with
-fabricated partials on gloo).  torch.distributed.run starts the ranks; tests/dist_gpu_worker.py is one rank."""
+fabricated partials on gloo).  tests/dist_launch.py starts the ranks; tests/dist_gpu_worker.py is one rank."""
 import json
-import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from dist_launch import free_port, rank_env, run_ranks
 
 
 def _run(world, backend, tmp_path, bins):
     out = str(tmp_path / "res.json")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "dist_gpu_worker.py"), "--backend", backend, "--bins", str(bins),
-           "--out", out]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    run_ranks("dist_gpu_worker.py", ("--backend", backend, "--bins", bins, "--out", out), world=world, timeout=600)
     return json.load(open(out))
 
 
@@ -74,8 +58,7 @@ def test_rccl_collectives_of_the_band_reduce_on_one_rank(tmp_path):
         "assert torch.equal(buf, ref) and torch.equal(mx, ref[:, -44:-42])\n"
         "dist.destroy_process_group()\n"
         "print('rccl ok')\n")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = rank_env(dict(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port())))
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0 and "rccl ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
 
@@ -89,12 +72,7 @@ def test_sos_proc_sharded(tmp_path, case, world):
     the one all-reduce and returns the reference's outputs on every rank; a single-bin run (no gas absorption) is a replica on
     every rank and must not be reduced."""
     out = str(tmp_path / "res.json")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "dist_proc_worker.py"), "--case", case, "--out", out]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
-    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    run_ranks("dist_proc_worker.py", ("--case", case, "--out", out), world=world, timeout=900)
     r = json.load(open(out))
     assert r["world"] == world and len(set(r["sums"])) == 1, r["sums"]
     assert "SOS_Result.bin" in r["files"] and "SOS_UsedAngles.txt" in r["files"]

@@ -23,17 +23,16 @@ import json
 import math
 import os
 import re
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import cases
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 import test_level_conservation as tlc
 import test_variant_matrix as vm
+from dist_launch import run_ranks
 from test_level_flux import GOLD, host_flux
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -561,12 +560,6 @@ def test_band_sum_alone_on_synthetic_records(gpu_pkg):
 PIPE_ALTS = [-1, 0.0, 0.7, 3.0, 8.5]
 
 
-def _same(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-
-
 def _pipe_calls(rs, tmp_path):
     """(name, kwargs, aer_phase): a no-gas call with an absorbing aerosol (one bin), and the 5-bin CKD golden band."""
     al, be, ga, ze = S.hg_phase(80, 0.7)
@@ -603,7 +596,7 @@ def test_sos_proc_levels_rows(gpu_pkg, tmp_path, monkeypatch):
         plain_t, plain_f = rs.sos_proc_levels(PIPE_ALTS, aer_phase=aer, fluxes=True, **kw)
         assert np.array_equal(flux, plain_f) and len(tuples) == len(plain_t) == len(PIPE_ALTS)
         for a, b in zip(tuples, plain_t):
-            _same(a, b)
+            assert_tuples_equal(a, b)
         assert absorb.shape == (len(PIPE_ALTS), 5) and absorb.dtype == np.float64
         assert np.isnan(absorb[0]).all() and np.isfinite(absorb[1:]).all() and (absorb[1:] > 0).all(), (what, absorb.tolist())
         ab, hrows, jout, mus, nb = _pipe_chain(rs, kw, aer, PIPE_ALTS)
@@ -668,8 +661,8 @@ def test_sos_spectrum_levels_rows_and_launch_counts(gpu_pkg, tmp_path, monkeypat
     assert len(absorb) == len(absorb2) == 6
     for i in range(6):
         for k in range(3):
-            _same(got[i][k], ref[i][k])
-            _same(got2[i][k], ref[i][k])
+            assert_tuples_equal(got[i][k], ref[i][k])
+            assert_tuples_equal(got2[i][k], ref[i][k])
         assert np.array_equal(flux[i], ref_flux[i]) and np.array_equal(flux2[i], ref_flux[i])
         assert absorb[i].shape == (3, 5) and np.isnan(absorb[i][0]).all() and np.isfinite(absorb[i][1:]).all()
         assert np.array_equal(absorb[i][1:], absorb2[i][1:]), i
@@ -687,17 +680,8 @@ def test_two_ranks_on_one_gpu_return_the_same_rows(gpu_pkg, tmp_path, monkeypatc
     every rank returns the rows of this process, bit for bit; gather=False leaves None in the slots of the other rank."""
     rs = gpu_pkg.run_sos
     monkeypatch.setenv("SOS_ABS_ROOT", GOLD)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
     out = str(tmp_path / "res.json")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "dist_level_absorption_worker.py"), "--out", out]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    run_ranks("dist_level_absorption_worker.py", ("--out", out), timeout=600)
     r = json.load(open(out))
     kws = dist_kws(rs, tmp_path / "single")
     _, flux, absorb = rs.sos_spectrum_levels(DIST_ALTS, kws, fluxes=True, absorption=True)

@@ -18,6 +18,7 @@ import pytest
 
 import cases
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = spectrum_cases.GOLD
@@ -244,12 +245,6 @@ def _count(monkeypatch, pkg):
     return n
 
 
-def _same(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-
-
 @pytest.mark.gpu
 def test_one_call_per_chunk_and_the_flag_off_is_free(gpu_pkg, tmp_path, monkeypatch):
     """sos_spectrum_levels([-1, 0, 3], six calls, fluxes=True): one sosgpu_level_flux_spectrum call of 18 jobs; with chunk=6
@@ -285,12 +280,12 @@ def test_one_call_per_chunk_and_the_flag_off_is_free(gpu_pkg, tmp_path, monkeypa
     assert isinstance(ref, list) and isinstance(ref1, list) and len(ref) == 6 and len(ref1) == 3
     for i in range(6):
         for k in range(3):
-            _same(got[i][k], ref[i][k])
-            _same(got2[i][k], ref[i][k])
+            assert_tuples_equal(got[i][k], ref[i][k])
+            assert_tuples_equal(got2[i][k], ref[i][k])
         assert np.array_equal(flux[i], flux2[i])
     for k in range(3):
-        _same(got1[k], ref1[k])
-    _same(gotk[0], ref1[2])
+        assert_tuples_equal(got1[k], ref1[k])
+    assert_tuples_equal(gotk[0], ref1[2])
     assert flux1.shape == (3, 5) and np.array_equal(flux1, flux[0]) and np.array_equal(fluxk[0], flux1[2])
     for f in flux:
         assert np.isfinite(f).all()
@@ -327,7 +322,7 @@ def test_standard_output_row_vs_sos_proc(gpu_pkg, tmp_path, monkeypatch, name):
     print("%s: smallest order-0 intensity of the standard-output record %.3e" % (name, rows[0].min()))
     assert (rows[0] >= 0.0).all(), "a negative order-0 intensity: the bound's premise does not hold for this case"
     ref = rs.sos_proc(**kw)
-    _same(tuples[0], ref)
+    assert_tuples_equal(tuples[0], ref)
     tot, up = float(ref[20]), float(ref[21])
     print("%s: flux_tot_down %.17g vs %.17g, flux_diff_up %.17g vs %.17g" % (name, flux[0, 2], tot, flux[0, 3], up))
     assert tot > 0 and up > 0

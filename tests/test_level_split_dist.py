@@ -1,16 +1,12 @@
 """split=True of run_sos.sos_proc_levels and sos_spectrum_levels under torch.distributed: two ranks on one GPU
 (tests/dist_level_split_worker.py)."""
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import spectrum_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from dist_launch import run_ranks
 
 
 @pytest.mark.gpu
@@ -22,17 +18,8 @@ def test_split_two_ranks_on_one_gpu(gpu_pkg, tmp_path, monkeypatch):
     import dist_level_split_worker as worker
     rs = gpu_pkg.run_sos
     monkeypatch.setenv("SOS_ABS_ROOT", spectrum_cases.GOLD)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
     out = str(tmp_path)
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "dist_level_split_worker.py"), "--out", out]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    run_ranks("dist_level_split_worker.py", ("--out", out), timeout=600)
     r0, r1 = (np.load(os.path.join(out, "split_rank%d.npz" % r)) for r in (0, 1))
     assert r0["band"].shape == (len(worker.ALTS), 7) and r0["spectrum"].shape == (len(worker.SPECTRUM), len(worker.ALTS), 7)
     assert np.array_equal(r0["band"], r1["band"]) and np.array_equal(r0["spectrum"], r1["spectrum"])

@@ -10,6 +10,7 @@ import pytest
 
 import profile_cells as PC
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 
 GOLD = spectrum_cases.GOLD
 OUT = ("nt", "iborm", "prof", "zprof", "scal", "jout", "zz")
@@ -246,12 +247,6 @@ ALTS = [-1, 0.0, 3.0]
 _BAND = {}                                     # name -> (keywords, tuples, flux rows [3][7], a_tronc): computed once, shared
 
 
-def _same(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-
-
 def _band(gpu_pkg, workdir, monkeypatch, name):
     """sos_proc_levels(ALTS, fluxes=True, split=True) of a case, with the a_tronc its plan used."""
     if name not in _BAND:
@@ -289,7 +284,7 @@ def test_split_rows_of_a_band(gpu_pkg, tmp_path, monkeypatch, name):
     ref_t, ref_f = rs.sos_proc_levels(ALTS, fluxes=True, **kw)
     assert flux.shape == (3, 7) and flux.dtype == np.float64 and ref_f.shape == (3, 5) and np.isfinite(flux).all()
     for k in range(3):
-        _same(tuples[k], ref_t[k])
+        assert_tuples_equal(tuples[k], ref_t[k])
     assert np.array_equal(flux[:, :5], ref_f)
     print("%s: a_tronc %.5f, %d bin(s)\n%s" % (name, a_tronc, nbins, flux))
     assert _bits(flux[0, 5]) == _bits(float(tuples[0][18]))
@@ -399,7 +394,7 @@ def test_split_rows_of_a_spectrum(gpu_pkg, tmp_path, monkeypatch):
     for i, (kw, tuples, rows, _, _) in enumerate(want):
         assert flux[i].shape == (3, 7) and np.array_equal(flux[i], rows), names[i]
         for k in range(3):
-            _same(spec[i][k], tuples[k])
+            assert_tuples_equal(spec[i][k], tuples[k])
     n.update(profile=0, spectrum=0, depths=0, trans=[])
     spec0, flux0 = rs.sos_spectrum_levels(ALTS, kws, fluxes=True)
     one_t, one_f = rs.sos_proc_levels(ALTS, fluxes=True, **kws[2])

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 from test_context_tables import CELLS, RECYCLE, _context, _size_class, cell_inputs, check_tables, coefficients, directions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -290,12 +291,6 @@ END_TO_END = ["ckd_o2a_5bins", "ckd_h2o_o2_25bins_flatsea", "cfg1_lambert", "fla
               "rand_12", "cfg5_ckd_maignan_25bins", "glitter_polar", "land_roujean"]
 
 
-def _same(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-
-
 @pytest.mark.gpu
 def test_spectrum_outputs_equal_sequential_calls_bitwise(gpu_pkg, tmp_path, monkeypatch):
     """End to end with the batched operators: CKD 5- and 25-bin calls, no-gas calls, -SOS.Trans, an output altitude, a
@@ -319,9 +314,9 @@ def test_spectrum_outputs_equal_sequential_calls_bitwise(gpu_pkg, tmp_path, monk
         got = rs.sos_spectrum(kws, chunk=3)
         assert len(got) == len(kws)
         for a, b in zip(seq, got):
-            _same(a, b)
+            assert_tuples_equal(a, b)
         lev = rs.sos_spectrum_levels(alts, kws_levels)
         assert len(lev) == len(kws)
         for a, b in zip(seq_levels, lev):
             for k in range(len(alts)):
-                _same(a[k], b[k])
+                assert_tuples_equal(a[k], b[k])

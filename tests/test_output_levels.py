@@ -14,6 +14,8 @@ import pytest
 
 import cases
 import test_variant_matrix as vm
+from dist_launch import rank_env, run_ranks
+from spectrum_cases import assert_tuples_equal
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -236,12 +238,6 @@ def _proc_inputs(rs, name):
     return g, _user_kwargs(rs, user), aer, zout
 
 
-def _same_outputs(a, b, what):
-    assert len(a) == len(b) == 23
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(np.asarray(x), np.asarray(y)), (what, i)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", PROC_CASES)
 def test_sos_proc_levels_equals_sos_proc_per_altitude(gpu_pkg, name, monkeypatch):
@@ -253,7 +249,7 @@ def test_sos_proc_levels_equals_sos_proc_per_altitude(gpu_pkg, name, monkeypatch
     assert len(got) == len(alts)
     for k, z in enumerate(alts):
         ref = rs.sos_proc(aer_phase=aer, **dict(kw, zout=z))
-        _same_outputs(got[k], ref, "%s zout=%g" % (name, z))
+        assert_tuples_equal(got[k], ref, "%s zout=%g" % (name, z))
     if name == "flatsea_zout":
         cases.compare_proc_outputs(rs, got[-1], g)
 
@@ -262,23 +258,9 @@ def test_sos_proc_levels_equals_sos_proc_per_altitude(gpu_pkg, name, monkeypatch
 def test_sos_proc_levels_two_ranks_on_one_gpu(gpu_pkg, tmp_path, monkeypatch):
     """torch.distributed with two ranks on one GPU (tests/dist_levels_worker.py): bins sharded, one all-reduce for the K
     record sets, the same outputs as one process."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    import socket
     res = str(tmp_path / "levels_dist.npz")
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    env["SOS_ABS_ROOT"] = GOLD
     monkeypatch.setenv("SOS_ABS_ROOT", GOLD)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_levels_worker.py"), "--out", res]
-    r = subprocess.run(cmd, env=env, timeout=900, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    run_ranks("dist_levels_worker.py", ("--out", res), timeout=900, env=rank_env({"SOS_ABS_ROOT": GOLD}))
     rs = gpu_pkg.run_sos
     d = np.load(res, allow_pickle=True)
     _, kw, aer, _ = _proc_inputs(rs, "ckd_h2o_o2_25bins_flatsea")

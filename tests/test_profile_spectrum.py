@@ -9,6 +9,7 @@ import pytest
 
 import cases
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = spectrum_cases.GOLD
@@ -285,12 +286,6 @@ END_TO_END = ["ckd_o2a_5bins", "ckd_h2o_o2_25bins_flatsea", "cfg1_lambert", "fla
               "rand_12", "cfg5_ckd_maignan_25bins"]
 
 
-def _same(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-
-
 @pytest.mark.gpu
 def test_spectrum_outputs_equal_sequential_calls_bitwise(gpu_pkg, tmp_path, monkeypatch):
     """End to end with the batched profile stage: the 5- and 25-bin CKD goldens, no-gas calls, output levels and -SOS.Trans
@@ -303,12 +298,12 @@ def test_spectrum_outputs_equal_sequential_calls_bitwise(gpu_pkg, tmp_path, monk
     assert any(str(kw["fictrans"]).strip() != "NO_OUTPUT" for kw in kws) and any(kw["zout"] != -1.0 for kw in kws)
     seq = [rs.sos_proc(**kw) for kw in kws]
     for a, b in zip(seq, rs.sos_spectrum(kws)):
-        _same(a, b)
+        assert_tuples_equal(a, b)
     for a, b in zip(seq, rs.sos_spectrum(kws, chunk=3)):
-        _same(a, b)
+        assert_tuples_equal(a, b)
     monkeypatch.setenv("SOS_SPECTRUM_MIN_PART", "2")
     for a, b in zip(seq, rs.sos_spectrum(kws, parts=3)):
-        _same(a, b)
+        assert_tuples_equal(a, b)
     monkeypatch.delenv("SOS_SPECTRUM_MIN_PART")
     alts = [-1, 0.0, 3.0]
     kws_levels = [dict(kw, zout=-1.0) for kw in kws]
@@ -316,7 +311,7 @@ def test_spectrum_outputs_equal_sequential_calls_bitwise(gpu_pkg, tmp_path, monk
     assert len(lev) == len(kws)
     for i, kw in enumerate(kws_levels):
         for k, z in enumerate(alts):
-            _same(rs.sos_proc(**dict(kw, zout=float(z))), lev[i][k])
+            assert_tuples_equal(rs.sos_proc(**dict(kw, zout=float(z))), lev[i][k])
 
 
 @pytest.mark.gpu
@@ -337,4 +332,4 @@ def test_spectrum_raises_what_the_call_alone_raises(gpu_pkg, tmp_path, monkeypat
     assert inlist.value.ier == alone.value.ier
     outs = rs.sos_spectrum(kws)
     for kw, o in zip(kws, outs):
-        _same(rs.sos_proc(**kw), o)
+        assert_tuples_equal(rs.sos_proc(**kw), o)

@@ -3,8 +3,6 @@ all bins of all wavelengths in one launch per kernel variant (BASELINE config 5'
 wavelengths dealt to the ranks (gather only, no all-reduce)."""
 import json
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -12,17 +10,10 @@ import pytest
 
 import cases
 import spectrum_cases
+from dist_launch import free_port, run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = spectrum_cases.GOLD
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def test_spectrum_costs_and_balanced_shards(pkg, monkeypatch, tmp_path):
@@ -115,7 +106,7 @@ def test_wavelength_partition_gather_gloo(world):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_gather_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -191,7 +182,7 @@ def test_sos_spectrum_raises_the_failing_call(gpu_pkg, tmp_path, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 3])
 def test_sos_spectrum_wavelengths_over_ranks_on_one_gpu(tmp_path, world):
-    """torch.distributed.run starts `world` ranks sharing cuda:0 (gloo): the wavelengths are dealt to the ranks by cost, each
+    """tests/dist_launch.py starts `world` ranks sharing cuda:0 (gloo): the wavelengths are dealt to the ranks by cost, each
     rank runs its own through sos_spectrum's launches, one all_gather_object -- every rank ends with the full list, equal to
     the goldens and identical across ranks; a spectrum with one refused call makes every rank raise SosProcError naming it --
     no rank is left waiting in the gather."""
@@ -199,12 +190,7 @@ def test_sos_spectrum_wavelengths_over_ranks_on_one_gpu(tmp_path, world):
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     out = str(tmp_path / "res.json")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "dist_spectrum_worker.py"), "--out", out]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
-    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    run_ranks("dist_spectrum_worker.py", ("--out", out), world=world, timeout=900)
     r = json.load(open(out))
     assert r["world"] == world and len(set(r["digests"])) == 1, r["digests"]
     assert sorted(i for own in r["owners"] for i in own) == list(range(r["n"]))

@@ -65,7 +65,7 @@ def test_one_more_key_and_every_other_bit_unchanged(gpu_pkg, reference):
         TT.same_entry(t0, {k: t[k] for k in KEYS})
         assert isinstance(t["s_alb"], float) and 0.0 < t["s_alb"] < 1.0
     for a, b in zip(reference["tuples"], reference["tuples0"]):
-        TT._same_tuples(a, b)
+        spectrum_cases.assert_tuples_equal(a, b)
 
 
 @pytest.mark.gpu

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 
 GOLD = spectrum_cases.GOLD
 ALTS = [-1, 0.0, 3.0]
@@ -205,12 +206,6 @@ def test_channels_equal_the_host_convolution(gpu_pkg, oracle, spectra, monkeypat
     assert polar == [variant != "nopolar"] * len(w)
 
 
-def _same(a, b, where):
-    assert len(a) == len(b) == 23
-    for e, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(np.asarray(x), np.asarray(y)), (where, e)
-
-
 @pytest.mark.gpu
 def test_chunk_and_parts_do_not_change_a_bit(gpu_pkg, spectra, monkeypatch):
     """chunk=2 and chunk=256, parts=1 and parts=4 (parts of one call each): all 23 elements of every channel are equal."""
@@ -223,7 +218,7 @@ def test_chunk_and_parts_do_not_change_a_bit(gpu_pkg, spectra, monkeypatch):
     for kw in (dict(chunk=2, parts=1), dict(chunk=256, parts=4), dict(chunk=3, parts=4)):
         other = rs.sos_spectrum_channels(kws, w, **kw)
         for c in range(len(w)):
-            _same(base[c], other[c], (kw, c))
+            assert_tuples_equal(base[c], other[c], (kw, c))
 
 
 @pytest.mark.gpu
@@ -248,8 +243,8 @@ def test_levels_and_fluxes(gpu_pkg, oracle, spectra, monkeypatch):
     for c in range(len(w)):
         assert np.array_equal(sflux2[c], flux[c])
         for k in range(len(ALTS)):
-            _same(chan[c][k], plain[c][k], ("plain", c, k))
-            _same(chan[c][k], small[c][k], ("chunk 6", c, k))
+            assert_tuples_equal(chan[c][k], plain[c][k], ("plain", c, k))
+            assert_tuples_equal(chan[c][k], small[c][k], ("chunk 6", c, k))
 
 
 @pytest.mark.gpu
@@ -316,7 +311,7 @@ def test_library_calls(gpu_pkg, spectra, monkeypatch):
     again = rs.sos_spectrum(kws, chunk=2)
     assert (n["accumulate"], n["finish"], n["trphi"]) == (0, 0, 4), n
     for i, (a, b) in enumerate(zip(again, ref)):
-        _same(a, b, ("sos_spectrum", i))
+        assert_tuples_equal(a, b, ("sos_spectrum", i))
     n.update(trphi=0)
     rs.sos_spectrum_levels(ALTS, kws)
     assert (n["accumulate"], n["finish"], n["trphi"]) == (0, 0, 1), n

@@ -9,19 +9,16 @@ GPU: every layout x SURF cell split over two contexts in one launch, with and wi
 sub-launches; a flagged slot level; sos_spectrum_levels against sos_proc end to end and on two ranks."""
 import hashlib
 import json
-import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 import test_output_levels as tol
 import test_variant_matrix as vm
+from dist_launch import run_ranks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = spectrum_cases.GOLD
 
 
@@ -242,12 +239,6 @@ def _kws(rs, tmp, names=E2E_NAMES):
     return [dict(kw, zout=-1.0) for kw in kws]
 
 
-def _same(a, b, what):
-    assert len(a) == len(b) == 23
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(np.asarray(x), np.asarray(y)), (what, i)
-
-
 @pytest.mark.gpu
 def test_sos_spectrum_levels_equals_sos_proc_per_altitude(gpu_pkg, tmp_path, monkeypatch):
     rs = gpu_pkg.run_sos
@@ -269,17 +260,17 @@ def test_sos_spectrum_levels_equals_sos_proc_per_altitude(gpu_pkg, tmp_path, mon
     assert len(got) == len(kws) and all(len(g) == len(ALTS) for g in got)
     for i, kw in enumerate(kws):
         for k, z in enumerate(ALTS):
-            _same(got[i][k], rs.sos_proc(**dict(kw, zout=float(z))), "call %d zout=%g" % (i, z))
+            assert_tuples_equal(got[i][k], rs.sos_proc(**dict(kw, zout=float(z))), "call %d zout=%g" % (i, z))
     spec = rs.sos_spectrum(kws)
     for i in range(len(kws)):
-        _same(got[i][0], spec[i], "call %d vs sos_spectrum" % i)
+        assert_tuples_equal(got[i][0], spec[i], "call %d vs sos_spectrum" % i)
     # small chunks (one wavelength each at K = 6) and parts; then parts that still form groups
     monkeypatch.setenv("SOS_SPECTRUM_MIN_PART", "2")
     for kwargs, sub in ((dict(chunk=5, parts=3), slice(0, 12)), (dict(chunk=60, parts=3), slice(None))):
         again = rs.sos_spectrum_levels(ALTS, kws[sub], **kwargs)
         for i, g in enumerate(again):
             for k in range(len(ALTS)):
-                _same(g[k], got[sub][i][k], "%s call %d slot %d" % (kwargs, i, k))
+                assert_tuples_equal(g[k], got[sub][i][k], "%s call %d slot %d" % (kwargs, i, k))
 
 
 def _digest(outs):
@@ -301,17 +292,8 @@ def test_sos_spectrum_levels_two_ranks_on_one_gpu(gpu_pkg, tmp_path, monkeypatch
     a spectrum with one refused call makes every rank raise SosProcError -- no rank is left waiting in the gather."""
     rs = gpu_pkg.run_sos
     monkeypatch.setenv("SOS_ABS_ROOT", GOLD)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
     out = str(tmp_path / "res.json")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "dist_spectrum_levels_worker.py"), "--out", out]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    run_ranks("dist_spectrum_levels_worker.py", ("--out", out), timeout=600)
     r = json.load(open(out))
     single = rs.sos_spectrum_levels(ALTS, _kws(rs, tmp_path / "single", DIST_NAMES))
     assert r["world"] == 2 and r["digests"] == [_digest(single)] * 2, r["digests"]

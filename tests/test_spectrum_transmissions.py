@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 
 GOLD = spectrum_cases.GOLD
 # the 5- and the 25-bin band, a no-gas call, a -SOS.AbsModeCKD 2 call and an aerosol-layer call among qualifying calls
@@ -28,12 +29,6 @@ def same_entry(a, b):
     assert set(a) == set(b) == set(KEYS)
     for k in KEYS:
         assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
-
-
-def _same_tuples(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
 
 
 @pytest.fixture(scope="module")
@@ -111,7 +106,7 @@ def test_trans_equals_sequential_calls_bitwise(gpu_pkg, reference, env, chunk, p
     _check_against_sequential(trans, reference["seen"], rs)
     assert len(tuples) == len(reference["plain"])
     for a, b in zip(tuples, reference["plain"]):
-        _same_tuples(a, b)
+        assert_tuples_equal(a, b)
 
 
 @pytest.mark.gpu
@@ -125,7 +120,7 @@ def test_levels_return_the_same_trans_behind_spec_and_flux(gpu_pkg, reference, e
     for a, b, fa, fb in zip(spec, spec0, flux, flux0):
         assert np.array_equal(fa, fb)
         for k in range(len(alts)):
-            _same_tuples(a[k], b[k])
+            assert_tuples_equal(a[k], b[k])
     spec1, trans1 = rs.sos_spectrum_levels(alts, kws[:3], transmissions=True)
     assert len(spec1) == 3
     for a, b in zip(trans1, trans[:3]):

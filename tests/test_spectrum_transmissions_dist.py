@@ -1,16 +1,12 @@
 """transmissions=True of run_sos.sos_spectrum and sos_spectrum_levels under torch.distributed: two ranks on one GPU
 (tests/dist_spectrum_trans_worker.py)."""
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import spectrum_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from dist_launch import run_ranks
 
 
 @pytest.mark.gpu
@@ -21,17 +17,8 @@ def test_transmissions_two_ranks_on_one_gpu(gpu_pkg, tmp_path, monkeypatch):
     from test_spectrum_transmissions import spectrum_keywords
     rs = gpu_pkg.run_sos
     monkeypatch.setenv("SOS_ABS_ROOT", spectrum_cases.GOLD)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
     out = str(tmp_path)
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "dist_spectrum_trans_worker.py"), "--out", out]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    run_ranks("dist_spectrum_trans_worker.py", ("--out", out), timeout=600)
     r0, r1 = (np.load(os.path.join(out, "trans_rank%d.npz" % r)) for r in (0, 1))
     assert r0["owned"].any() and r1["owned"].any() and np.array_equal(r0["owned"], ~r1["owned"])
     kws = spectrum_keywords(rs, tmp_path / "single")

@@ -1,10 +1,10 @@
 """The surface matrices of a spectrum whose surface changes with the wavelength, queued once per chunk of the pass
 (run_sos._prefetch_surfaces -> surface.surface_matrices_many): sos_spectrum / sos_spectrum_levels against sequential
 sos_proc / sos_proc_levels bit for bit, the call counts of the batch and of the per-call entry points, and a failing call."""
-import numpy as np
 import pytest
 
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 from test_surface_matrix import NEGATIVE_TRIPLE, TRIPLES
 
 
@@ -36,12 +36,6 @@ def _calls(rs, workdir):
 
 def _groups(chunk):
     return len({(kw["nbmu_gauss_lum"], kw["nbmu_gauss_mie"], kw["tetas"]) for kw in chunk})
-
-
-def _same(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
 
 
 def _count(monkeypatch, pkg):
@@ -89,7 +83,7 @@ def test_spectrum_equals_sequential_calls_and_batches_once_per_chunk(gpu_pkg, se
     rs._SURF_CACHE.clear()
     out = rs.sos_spectrum(calls, chunk=5, parts=2)
     for a, b in zip(seq, out):
-        _same(a, b)
+        assert_tuples_equal(a, b)
     assert n["many"] == _groups(calls[:5]) + _groups(calls[5:]) == 4 and sum(n["jobs"]) == len(calls), n
     assert (n["glitter"], n["land"]) == (0, 0), n
     n.update(many=0, jobs=[])
@@ -97,7 +91,7 @@ def test_spectrum_equals_sequential_calls_and_batches_once_per_chunk(gpu_pkg, se
     monkeypatch.setenv("SOS_SPECTRUM_SURFACE_PER_CALL", "1")
     out = rs.sos_spectrum(calls, chunk=5, parts=2)
     for a, b in zip(seq, out):
-        _same(a, b)
+        assert_tuples_equal(a, b)
     assert n["many"] == 0 and (n["glitter"], n["land"]) == (4, 6), n
 
 
@@ -117,7 +111,7 @@ def test_spectrum_levels_equals_sequential_level_calls(gpu_pkg, sequential, monk
     assert n["many"] == _groups(kws[:5]) + _groups(kws[5:]) == 4 and (n["glitter"], n["land"]) == (0, 0), n
     for i in range(len(kws)):
         for k in range(len(alts)):
-            _same(ref[i][k], lev[i][k])
+            assert_tuples_equal(ref[i][k], lev[i][k])
 
 
 @pytest.mark.gpu
@@ -220,4 +214,4 @@ def test_flagged_call_raises_what_sos_proc_raises(gpu_pkg, sequential, monkeypat
     assert inlist.value.ier == alone.value.ier
     rs._SURF_CACHE.clear()
     for a, b in zip(seq[:5], rs.sos_spectrum(calls[:5])):
-        _same(a, b)
+        assert_tuples_equal(a, b)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import spectrum_cases
+from spectrum_cases import assert_tuples_equal
 from test_surface_matrix import TR_LAND, TR_OS_NB, angles, trphi_azimuths, trphi_records
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -297,12 +298,6 @@ def _count(monkeypatch, pkg):
     return n
 
 
-def _same(a, b):
-    assert len(a) == len(b) == 23
-    for x, y in zip(a, b):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-
-
 @pytest.mark.gpu
 def test_spectrum_pass_makes_one_call_per_chunk(gpu_pkg, tmp_path, monkeypatch):
     """sos_spectrum over the call list of spectrum_cases: one sosgpu_trphi_spectrum call per chunk (one chunk, and chunk=24:
@@ -325,7 +320,7 @@ def test_spectrum_pass_makes_one_call_per_chunk(gpu_pkg, tmp_path, monkeypatch):
     assert (n["single"], n["spectrum"]) == (len(kws), 0), n
     assert len(got) == len(ref) == len(kws)
     for a, b in zip(got, ref):
-        _same(a, b)
+        assert_tuples_equal(a, b)
 
 
 @pytest.mark.gpu
@@ -354,6 +349,6 @@ def test_levels_make_one_call(gpu_pkg, tmp_path, monkeypatch):
     assert len(got) == len(ref) == 6 and len(got1) == len(ref1) == 3
     for a, b in zip(got, ref):
         for k in range(3):
-            _same(a[k], b[k])
+            assert_tuples_equal(a[k], b[k])
     for k in range(3):
-        _same(got1[k], ref1[k])
+        assert_tuples_equal(got1[k], ref1[k])

@@ -466,6 +466,47 @@ int  sosgpu_level_absorption(sosgpu_ctx *cx, const void *d_table /*NULL: cx alon
                              const double *d_rec /*[nz][nb][iborm_max+1][3][W]*/, const int32_t *d_norders, int nseg,
                              const int32_t *d_seg, const double *d_aik, double *d_out /*[nz][nseg][4]*/, void *stream);
 
+/* Every irradiance quantity of a solved group at its output slots, in ONE launch: what the flux, split and absorption rows of a
+ * levels pass are made of, formed from the order-0 row of every bin and summed with aik -- without sosgpu_aggregate,
+ * sosgpu_level_flux_spectrum, sosgpu_level_transmission and sosgpu_level_absorption, whose statements it executes.  Only the
+ * order-0 intensity row d_rec[k][b][0][0][0..W) of every slot is read: iborm_max of the context may be 0 (a context that holds
+ * the order-0 operators alone, solved with d_iborm = 0), the record layout is the context's own [iborm_max+1][3][W].
+ *   d_out[k][g][c], c < SOSGPU_IRRADIANCE_COLS, over the bins d_seg[g] .. d_seg[g+1]-1 (bounds clamped to 0 .. nb) of slot k:
+ *     [0..3]  sum aik {a_dir, a_dn, a_up, q}: the bits of sosgpu_level_absorption's block
+ *     [4, 5]  sum aik {E-_b, E+_b}, E-+_b = sosgpu_level_flux's statement on the bin's OWN order-0 row (products (mu ga) I, j
+ *             ascending, E = -e * 2 / TAB), each then one multiply by aik and one add.  The chain through sosgpu_aggregate takes
+ *             the moment of the summed record instead: for a segment of one bin with aik = 1 the two are equal bit for bit,
+ *             for several bins at most nbins + 2 N roundings of non-negative terms differ (below 1e-13 relative for 300 bins,
+ *             N = 85).  A standard-output slot (jout = 0) is no exception: its record row is the ground going down and the top
+ *             going up, and [4, 5] are what sosgpu_level_flux gives for that slot (the flux rows of the levels passes); its
+ *             [0..3] are 0
+ *     [12,13] sum aik {EMOINS, EPLUS} of d_flux, the solve's own pair: the bits of elements 1 and 2 of sosgpu_aggregate's
+ *             scalar block, in every slot.  They agree with [4, 5] of a standard-output slot to rounding without surface
+ *             matrices and to some 1e-9 with them, as the reference's EPLUS and its own record do
+ *     [6..8]  sum aik exp(-{TTOT_TRONC, TTOT_VRAI, TAUOUT(slot k)}) from d_scal[b][1], d_scal[b][2] and d_tauout[k][b]: the
+ *             bits of elements 3, 4, 5 of sosgpu_aggregate's scalar block for that slot (whose d_scal[b][3] is d_tauout[k][b];
+ *             column 3 of the d_scal given here is not read)
+ *     [9]     sum aik        [10] -(min norders): > 0 when a bin of the segment failed; combines with MAX across segments or
+ *             ranks (elements 6 and 8 of that block)
+ *     [11]    sum aik exp(-d_tauvrai[k][b]): the bits of element 9 after sosgpu_level_transmission; 0 when d_tauvrai is NULL
+ *   with sosgpu_level_absorption's shape (256 threads stride over the bins, serial within a thread, fixed tree).  A bin with
+ *   d_norders[b] < 0 adds nothing and is reported through [10].  A bin with jout outside 0 .. NT or NT outside 1 .. lp-1 adds
+ *   nothing to [0..5], as in sosgpu_level_absorption (the solvers give such a bin norders = -1); the band scalars take it as
+ *   sosgpu_aggregate does.
+ *  d_flux[nb][2]     EMOINS, EPLUS of the solve;  d_scal[nb][4]   per-bin scalars as sosgpu_aggregate takes them
+ *  d_tauvrai[nz][nb] NULL, or sosgpu_output_depths on the d_hvrai of the profile stage
+ * Every other argument as sosgpu_level_absorption takes it.  Asynchronous: one launch on `stream` (queue it behind the solve),
+ * no allocation, no work area; `stream` is noted for sosgpu_destroy on cx.  nb = 0 or nseg = 0 queues nothing.  Checked before
+ * anything is queued, SOSGPU_E_ARG for: what sosgpu_level_absorption refuses, a NULL d_flux or d_scal. */
+#define SOSGPU_IRRADIANCE_COLS 14
+int  sosgpu_level_irradiance(sosgpu_ctx *cx, const void *d_table /*NULL: cx alone*/, const int32_t *d_ctx_of_bin /*NULL with d_table NULL*/,
+                             int nb, int lp, const int32_t *d_nt, const double *d_prof, const double *d_zprof /*[nb][lp]*/, int nz,
+                             const int32_t *d_jout, const double *d_zz, const double *d_tauout /*[nz][nb] each*/,
+                             const double *d_rec /*[nz][nb][iborm_max+1][3][W]*/, const int32_t *d_norders,
+                             const double *d_flux /*[nb][2]*/, const double *d_scal /*[nb][4]*/,
+                             const double *d_tauvrai /*[nz][nb], may be NULL*/, int nseg, const int32_t *d_seg,
+                             const double *d_aik, double *d_out /*[nz][nseg][SOSGPU_IRRADIANCE_COLS]*/, void *stream);
+
 /* Sensor channels of a spectrum: response-weighted sums of recomposition blocks over the wavelengths, on the device.
  * A call adds the terms of nchan channels onto an accumulator that lives for the whole spectrum:
  *   d_acc[c][k][iphi][q][t] += sum_m wgt[m] * block(job[m], k)[iphi][q][t],   q = 0, 1, 2 (XIT, XQT, XUT),

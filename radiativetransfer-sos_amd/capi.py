@@ -30,11 +30,12 @@ EXPORTS = [
     "sosgpu_trans_spectrum", "sosgpu_trans_spectrum_work_bytes",
     "sosgpu_surface_batch", "sosgpu_surface_batch_work_bytes",
     "sosgpu_albedo_spectrum", "sosgpu_albedo_spectrum_work_bytes", "sosgpu_albedo_band",
-    "sosgpu_level_absorption",
+    "sosgpu_level_absorption", "sosgpu_level_irradiance",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
 SCAL_BASE = 10          # SOSGPU_SCAL_BASE: scalar block of sosgpu_aggregate = SCAL_BASE + N doubles
+IRRADIANCE_COLS = 14   # SOSGPU_IRRADIANCE_COLS: columns of sosgpu_level_irradiance's block per slot and segment
 
 
 class GranuJob(C.Structure):
@@ -277,6 +278,9 @@ def lib():
         L.sosgpu_albedo_band.argtypes = [i32, vp, vp, vp, vp, i32, vp]
         L.sosgpu_level_absorption.restype = i32
         L.sosgpu_level_absorption.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.sosgpu_level_irradiance.restype = i32
+        L.sosgpu_level_irradiance.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
+                                              vp, vp]
         L.sosgpu_debug_stage_blocks.restype = i32
         L.sosgpu_debug_stage_blocks.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
         L.sosgpu_debug_solve_plan.restype = i32

@@ -14,33 +14,7 @@
 #pragma clang fp contract(off)
 
 #include "tree256.h"
-
-// The four terms of bin b at one slot: t[0] = a_dir, t[1] = a_dn, t[2] = a_up, t[3] = q; false: the bin adds nothing (a
-// standard-output slot, jout = 0, mixes the ground and the top of the atmosphere; a jout outside 0..NT or an NT outside
-// 1..lp-1 is a malformed bin).  row: the order-0 intensity row of the bin's record, direction jj at offset jj + N as in
-// flux_body, whose statements a_dn / a_up repeat without the factor mu.  The single-scattering albedo is a LEVEL quantity of
-// the solver's discretisation (XDEL + YDEL at level j), interpolated between the two levels that bracket z as the field is;
-// the slope is that of the layer between them, 0 where the two altitudes coincide.
-__device__ __forceinline__ bool absorption_terms(const int n, const int n0, const double *__restrict__ mu,
-                                                 const double *__restrict__ ga, const double *__restrict__ row, const int lp,
-                                                 const int nt, const double *__restrict__ prof, const double *__restrict__ zprof,
-                                                 const int j, const double zz, const double tauout, double t[4])
-{
-    if (nt < 1 || nt >= lp || j < 1 || j > nt) return false;
-    double s_dn = 0., s_up = 0.;
-    for (int jj = 1; jj <= n; jj++) s_dn = s_dn + ga[jj - 1] * row[n - jj];
-    for (int jj = 1; jj <= n; jj++) s_up = s_up + ga[jj - 1] * row[n + jj];
-    const double tab = -mu[n0 - 1];
-    const double a_dn = -s_dn * 2 / tab, a_up = -s_up * 2 / tab;
-    const double mus = mu[n0 - 1];
-    const double a_dir = exp(-tauout / mus) / mus;
-    const double *h = prof, *xdel = prof + lp, *ydel = prof + 2 * (size_t)lp;
-    const double om = (1 - zz) * (xdel[j - 1] + ydel[j - 1]) + zz * (xdel[j] + ydel[j]);
-    const double slope = zprof[j - 1] <= zprof[j] ? 0. : (h[j] - h[j - 1]) / (zprof[j - 1] - zprof[j]);
-    t[0] = a_dir; t[1] = a_dn; t[2] = a_up;
-    t[3] = slope * (1 - om) * (a_dn + a_up + a_dir);
-    return true;
-}
+#include "level_terms.h"      // absorption_terms: the four terms of a bin at one slot, shared with k_level_irradiance
 
 // cx: the context of every bin (table null), or what the entries of `table` share (N, iborm_max: the record layout); bin b then
 // takes mu, ga and n0 from entry ctx_of_bin[b].  out[k][g][0..3] = sum aik * {a_dir, a_dn, a_up, q} over the bins of segment g

@@ -67,8 +67,9 @@ __global__ void k_aggregate_final(int nel, int nchunk, const double *partial, do
 #define SCB 10
 // The two pieces k_aggregate_scal and k_level_transmission share, so that equal depths give equal bits: the term of a bin in a
 // band transmission, and the fixed-shape tree over the 256 per-thread partials (columns in MAXMASK combine with MAX).
-// (the tree: tree256.h, which k_albedo_band of albedo.hip shares)
-__device__ __forceinline__ double transmission_term(double w, double tau) { return w * exp(-tau); }
+// (the tree: tree256.h, which k_albedo_band of albedo.hip shares; the term: transmission_term of level_terms.h, which
+// k_level_irradiance of irradiance.hip shares)
+#include "level_terms.h"
 
 __global__ void k_aggregate_scal(int n, const int32_t *seg, const double *aik, const int32_t *norders,
                                  const double *flux, const double *scal, const double *tdifmug, double *out)

@@ -1591,6 +1591,30 @@ extern "C" int sosgpu_level_absorption(sosgpu_ctx *cx, const void *d_table, cons
     return SOSGPU_OK;
 }
 
+// Every irradiance quantity at the output slots of a levels solve (k_level_irradiance): one launch, no allocation, no work
+// area.  Everything is checked before anything is queued.
+extern "C" int sosgpu_level_irradiance(sosgpu_ctx *cx, const void *d_table, const int32_t *d_ctx_of_bin, int nb, int lp,
+                                       const int32_t *d_nt, const double *d_prof, const double *d_zprof, int nz,
+                                       const int32_t *d_jout, const double *d_zz, const double *d_tauout, const double *d_rec,
+                                       const int32_t *d_norders, const double *d_flux, const double *d_scal,
+                                       const double *d_tauvrai, int nseg, const int32_t *d_seg, const double *d_aik,
+                                       double *d_out, void *stream)
+{
+    if (!cx || !d_nt || !d_prof || !d_zprof || !d_jout || !d_zz || !d_tauout || !d_rec || !d_norders || !d_seg || !d_aik || !d_out)
+        return SOSGPU_E_ARG;
+    if (!d_flux || !d_scal) return SOSGPU_E_ARG;
+    if (nz < 1 || nz > SOSGPU_MAX_OUTPUT_LEVELS || lp < 2 || nb < 0 || nseg < 0) return SOSGPU_E_ARG;
+    if (d_table && !d_ctx_of_bin) return SOSGPU_E_ARG;
+    if (nb == 0 || nseg == 0) return SOSGPU_OK;
+    HIPCHK(hipSetDevice(cx->device));
+    launch_level_irradiance(cx->d, static_cast<const SosDev *>(d_table), d_ctx_of_bin, nb, lp, d_nt, d_prof, d_zprof, nz, d_jout,
+                            d_zz, d_tauout, d_rec, d_norders, d_flux, d_scal, d_tauvrai, nseg, d_seg, d_aik, d_out,
+                            (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    note_stream(cx, (hipStream_t)stream);       // the kernel reads the context's mu and ga: sosgpu_destroy waits for this stream
+    return SOSGPU_OK;
+}
+
 static bool channel_shape_ok(int nchan, int nslots, int nphi, int w)
 {
     if (nchan < 1 || nchan > 65535 || nslots < 1 || nslots > 65535 || nphi < 1 || w < 1) return false;   // (grid y and z)

@@ -11,16 +11,7 @@
 
 #pragma clang fp contract(off)
 
-// up = 0: down-going hemisphere, E- from I(-j); up = 1: up-going, E+ from I(+j).  row: the order-0 intensity row, direction jj
-// at offset jj + N.  tab = -mu[n0 - 1], the reference's TAB (the solar cosine as the solvers use it, SosDev::mus).
-__device__ __forceinline__ double flux_body(const int n, const int n0, const double *__restrict__ mu, const double *__restrict__ ga,
-                                            const double *__restrict__ row, const int up)
-{
-    double e = 0.;
-    for (int j = 1; j <= n; j++) e = e + mu[j - 1] * ga[j - 1] * row[up ? n + j : n - j];
-    const double tab = -mu[n0 - 1];
-    return -e * 2 / tab;
-}
+#include "level_terms.h"      // flux_body: the quadrature of one hemisphere, shared with k_level_irradiance
 
 // out[0] = E-, out[1] = E+ of one record: threads 0 and 1 of one workgroup
 __global__ void k_level_flux(SosDev cx, const double *__restrict__ rec, double *__restrict__ out)

@@ -173,6 +173,14 @@ void launch_level_absorption(const SosDev &cx, const SosDev *d_table, const int3
                              const int32_t *d_nt, const double *d_prof, const double *d_zprof, int nz, const int32_t *d_jout,
                              const double *d_zz, const double *d_tauout, const double *d_rec, const int32_t *d_norders, int nseg,
                              const int32_t *d_seg, const double *d_aik, double *d_out, hipStream_t st);
+// Every irradiance quantity of nz output slots (irradiance.hip k_level_irradiance): d_out[nz][nseg][SOSGPU_IRRADIANCE_COLS], the
+// four sums above, sum aik {E-, E+} formed per bin from the same order-0 row (d_flux[nb][2] in a standard-output slot) and
+// the band scalars of d_scal[nb][4], d_tauout and d_tauvrai[nz][nb] (may be null); one launch, the other arguments as above
+void launch_level_irradiance(const SosDev &cx, const SosDev *d_table, const int32_t *d_ctx_of_bin, int nb, int lp,
+                             const int32_t *d_nt, const double *d_prof, const double *d_zprof, int nz, const int32_t *d_jout,
+                             const double *d_zz, const double *d_tauout, const double *d_rec, const int32_t *d_norders,
+                             const double *d_flux, const double *d_scal, const double *d_tauvrai, int nseg, const int32_t *d_seg,
+                             const double *d_aik, double *d_out, hipStream_t st);
 
 // Sensor channels of a spectrum (channels.hip).  launch_channel_accumulate: acc[nchan][nslots][nphi][3][W] += the terms
 // first[c] .. first[c + 1] - 1 of every channel c, term m = wgt[m] x rows 0..2 of block (job[m], slot) of d_blocks

@@ -89,8 +89,21 @@ def finish_scalars(scal):
     n_orders, min_orders (< 0: a bin failed, the reference's IER = -1), TDIFMUG[N]; tauvrai_out = -ln of element 9, the
     untruncated optical depth down to the slot's output altitude where sosgpu_level_transmission wrote it (inf where not)."""
     s = scal.detach().cpu().numpy() if isinstance(scal, torch.Tensor) else np.asarray(scal)
+    return dict(tdifmus=s[:, 0], emoins=s[:, 1], eplus=s[:, 2], sum_aik=s[:, 6], n_orders=s[:, 7].astype(np.int32),
+                tdifmug=s[:, 10:], **finish_depths(s[:, 3], s[:, 4], s[:, 5], s[:, 9], s[:, 8]))
+
+
+def finish_depths(t_tronc, t_vrai, t_out, t_vrai_out, neg_min_orders):
+    """The band values a scalar block holds as sums of transmissions, as SOS_AGGREGATE leaves them (-ln applied,
+    SOS_AGGREGATE.F:467-488), and the failure flag: the one statement of these for finish_scalars (elements 3, 4, 5, 9 and 8
+    of sosgpu_aggregate's block) and finish_irradiance (columns 6, 7, 8, 11 and 10 of sosgpu_level_irradiance's)."""
     with np.errstate(divide="ignore"):
-        return dict(tdifmus=s[:, 0], emoins=s[:, 1], eplus=s[:, 2], ttot_tronc=-np.log(s[:, 3]),
-                    ttot_vrai=-np.log(s[:, 4]), tauout=-np.log(s[:, 5]), sum_aik=s[:, 6],
-                    n_orders=s[:, 7].astype(np.int32), min_orders=(-s[:, 8]).astype(np.int64), tdifmug=s[:, 10:],
-                    tauvrai_out=-np.log(s[:, 9]))
+        return dict(ttot_tronc=-np.log(t_tronc), ttot_vrai=-np.log(t_vrai), tauout=-np.log(t_out),
+                    tauvrai_out=-np.log(t_vrai_out), min_orders=(-neg_min_orders).astype(np.int64))
+
+
+def finish_irradiance(block):
+    """block [nseg][capi.IRRADIANCE_COLS] of sosgpu_level_irradiance for one output slot -> the finish_scalars entries the
+    flux rows read (ttot_tronc, ttot_vrai, tauout, tauvrai_out, min_orders, sum_aik), by finish_depths."""
+    s = block.detach().cpu().numpy() if isinstance(block, torch.Tensor) else np.asarray(block)
+    return dict(sum_aik=s[:, 9], **finish_depths(s[:, 6], s[:, 7], s[:, 8], s[:, 11], s[:, 10]))

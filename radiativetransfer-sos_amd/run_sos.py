@@ -1266,10 +1266,17 @@ def _prepare_surface(pl):
     pl.rsurf = rsurf
 
 
-def _prepare_context(pl, defer_operators):
-    """The device context of the wavelength (SOS_PREPA_OS), unbuilt where the pass builds the operators of a whole part."""
+def _prepare_context(pl, defer_operators, order0=False):
+    """The device context of the wavelength (SOS_PREPA_OS), unbuilt where the pass builds the operators of a whole part.
+    order0 (the irradiance pass): the context holds the Fourier order 0 alone -- iborm_max = 0, record 0 of the surface
+    matrices (formed as they are: an order-limited sosgpu_surface_batch does not exist) -- and the profile stage, which takes
+    the highest order from it, gives every bin iborm = 0."""
     from .solver import SosContext
     p = pl.p
+    if order0:
+        pl.iborm = 0
+        if pl.rsurf is not None:
+            pl.rsurf = pl.rsurf[:1].contiguous()
     isurf = int(p["isurf"])
     alpha, beta, gamma, zeta = pl.phase
     pl.want_trans = str(p["fictrans"]).strip() != "NO_OUTPUT"
@@ -1384,7 +1391,7 @@ def _prepare_profiles(pl, shard_bins, true_depth):
 
 
 def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False,
-             device_gas_tables=False, defer_operators=False, true_depth=False):
+             device_gas_tables=False, defer_operators=False, true_depth=False, order0=False):
     """Everything of one SOS_PROC call up to the CKD bin loop (SOS_PROC.F:1310-3458): parameter checks, SOS_ANGLES,
     SOS_AEROSOLS, SOS_SURFACE, SOS_PREPA_ABSPROFILE, SOS_PREPA_OS, and the profiles of every bin of the band on the device
     (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Every stage fills its fields of the _Plan that comes back, whose `ctx`
@@ -1403,7 +1410,9 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     before the truncation rescale (SosContext.make_profiles(true_depth=True); the aerosol-layer profile uploads its own).
     defer_operators (_spectrum_pass only): the context comes back unbuilt (SosContext(build=False)) and the pass fills the
     operator tables of a whole part in one solver.build_operators call -- unless this function uses the operators itself, which
-    only a -SOS.Trans call does (diffuse_transmissions in _prepare_profiles)."""
+    only a -SOS.Trans call does (diffuse_transmissions in _prepare_profiles).
+    order0 (the irradiance mode of _spectrum_pass only): the context and the bins hold the Fourier order 0 alone
+    (_prepare_context)."""
     _seg(None)
     missing = [k for k in SOS_PROC_KWARGS if k not in kw]
     if missing:
@@ -1422,7 +1431,7 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     _seg('gas tables')
     _prepare_surface(pl)
     _seg('surface')
-    _prepare_context(pl, defer_operators)
+    _prepare_context(pl, defer_operators, **(dict(order0=True) if order0 else {}))
     _seg('context')
     try:
         _prepare_profiles(pl, shard_bins, true_depth)
@@ -2068,17 +2077,63 @@ def _download_scalars(ch, nz):
                           [len(gp) for gp, _ in ch.salb_bands], [len(pls) for _, pls in ch.ckd_checks])
 
 
-def _stage_todo(ch, nz, blocks, albs, status, trans_out, salb):
-    """The sections of the download read: the CKD status check first, the spherical albedos, then the jobs of the chunk's
-    recompositions [(plan, slot, record, finish_scalars, segment)] with the malformed-bin check, and (trans_out not None) the
-    trans_entry of every call."""
-    from . import dist as _dist
+def _check_ckd_status(ch, status):
+    """The status words of the chunk's device gas tables: a wavelength COEFF_ABS_CKD failed for raises sos_proc's error."""
     from . import absorption as _abs
     for (_, pls), codes in zip(ch.ckd_checks, status):
         for pl, code in zip(pls, codes):
             if code != 0:                           # COEFF_ABS_CKD failed for this wavelength: sos_proc's error for it
                 ch.where = pl.index
                 raise SosProcError(_abs.CKD_STATUS_MESSAGES.get(int(code), "COEFF_ABS_CKD failed"), ier=-1)
+
+
+def _check_bins(ch, pl, fins, g):
+    """The malformed-bin check of plan pl, segment g of the per-slot dictionaries fins (min_orders < 0: a bin failed)."""
+    if any(f["min_orders"][g] < 0 for f in fins):
+        ch.where = pl.index
+        raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
+                           "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
+
+
+def _stage_irradiance_rows(ch, nz, blocks, status, alts, flux_rows, flux_row, ncol, absorb_rows):
+    """irr: the rows of the chunk's calls from the downloaded blocks [K][calls][14] of sosgpu_level_irradiance -- the CKD status
+    check and the malformed-bin check of _stage_todo, then per (call, altitude) the host statements of the levels pass:
+    flux_row (_level_flux_row / _level_flux_split_row) on the pair (columns 4, 5) and on dist.finish_irradiance of the
+    block's band scalars, _level_absorption_row on columns 0..3."""
+    from . import dist as _dist
+    _check_ckd_status(ch, status)
+    for (gp, _, _, _), blk in zip(ch.solved, blocks):
+        fins = [_dist.finish_irradiance(blk[k]) for k in range(nz)]
+        for g, pl in enumerate(gp):
+            _check_bins(ch, pl, fins, g)
+            flux_rows[pl.index] = np.empty((nz, ncol))
+            if absorb_rows is not None:
+                absorb_rows[pl.index] = np.empty((nz, len(LEVEL_ABSORPTION_NAMES)))
+            for k in range(nz):
+                flux_rows[pl.index][k] = flux_row(pl, alts[k], fins[k], g, blk[k][g][4:6])
+                if absorb_rows is not None:
+                    absorb_rows[pl.index][k] = _level_absorption_row(alts[k], blk[k][g][0:4])
+
+
+def _gather_rows(mine, world, *rows):
+    """Every rank receives the rows of the calls the other ranks computed (all_gather_object, as _gather_results lets the flux
+    rows travel): rows, the per-call lists of the pass, are filled in place."""
+    import torch.distributed as dist
+    parts = [None] * world
+    dist.all_gather_object(parts, [(i, tuple(x[i] for x in rows)) for i in mine])
+    for pr in parts:
+        for i, vals in pr:
+            for x, v in zip(rows, vals):
+                if x[i] is None:
+                    x[i] = v
+
+
+def _stage_todo(ch, nz, blocks, albs, status, trans_out, salb):
+    """The sections of the download read: the CKD status check first, the spherical albedos, then the jobs of the chunk's
+    recompositions [(plan, slot, record, finish_scalars, segment)] with the malformed-bin check, and (trans_out not None) the
+    trans_entry of every call."""
+    from . import dist as _dist
+    _check_ckd_status(ch, status)
     s_alb = {}
     for (gp, _), vals in zip(ch.salb_bands, albs):
         s_alb.update((pl.index, float(v)) for pl, v in zip(gp, vals))
@@ -2087,10 +2142,7 @@ def _stage_todo(ch, nz, blocks, albs, status, trans_out, salb):
         fins = [_dist.finish_scalars(blk[k]) for k in range(nz)]
         recs = [rec[k] for k in range(nz)]
         for g, pl in enumerate(gp):
-            if any(f["min_orders"][g] < 0 for f in fins):
-                ch.where = pl.index
-                raise SosProcError("SOS_OS: wavelength %d (%r microns) holds a malformed bin (NT outside 1..CTE_OS_NT, "
-                                   "IBORM or an output level out of range)" % (pl.index, pl.p["wa_simu"]), ier=-1)
+            _check_bins(ch, pl, fins, g)
             todo += [(pl, k, recs[k][g], fins[k], g) for k in range(nz)]
             if trans_out is not None:               # (the same values in every slot: they ignore the altitude)
                 trans_out[pl.index] = trans_entry(pl.p["tetas"], pl.mu, float(fins[0]["ttot_tronc"][g]),
@@ -2165,7 +2217,7 @@ def _stage_tuples(ch, todo, flat, shapes, results, nrows, nz):
 
 
 def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts, alts=None, fluxes=False,
-                   split=False, chan=None, trans=False, salb=False, absorption=False):
+                   split=False, chan=None, trans=False, salb=False, absorption=False, irr=False):
     """The one pass behind sos_spectrum (alts None) and sos_spectrum_levels (alts: the K output altitudes), whose docstrings
     describe it.  After the solves both modes share one layout, rec[K][nw][S][3][W] / scal[K][nw][10+N] device tensors per
     launch with K = 1 for sos_spectrum (views of what its solves return); what differs is decided here, ahead of the loop.
@@ -2182,7 +2234,12 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     the part; they ride the groups' and the singles' aggregates, and the pass also returns one trans_entry per call.
     salb (spherical_albedo=True, only with trans): next to it ONE solver.spherical_albedo_many call per such group and one
     solver.albedo_band launch for the group's calls; the band values come down with the chunk's band scalars and become the
-    key s_alb of the entries."""
+    key s_alb of the entries.
+    irr (sos_spectrum_irradiances: alts and fluxes given, no chan, no trans): the irradiance rows alone.  The contexts and bins
+    hold the Fourier order 0 alone (_prepare(order0=True)); a solved group is ONE sosgpu_os_solve_multi_levels launch and ONE
+    sosgpu_level_irradiance launch behind it, whose block [K][calls][14] takes the place of the scalar blocks in the chunk's one
+    download.  No aggregate, no flux launch, no recomposition, no table, no 23-tuple: the rows are formed from the block by
+    _stage_irradiance_rows, and the pass returns the flux rows (with absorption: the pair of flux and absorption rows)."""
     import time
     import torch
     from . import capi, solver
@@ -2241,7 +2298,21 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
             if absorption:
                 ch.absorb.append(pl.ctx.level_absorption(pl.bins, pl.levels, out, pl.aik))
             return res
+
+        if irr:
+            # irradiances alone: the order-0 solve, then ONE sosgpu_level_irradiance launch; its block stands where the scalar
+            # blocks stand in ch.solved, and there are no aggregated records
+            def solve_group(table, gp, bins, cob, seg, aik):
+                levels = solver.concat_levels([pl.levels for pl in gp])
+                out = solver.solve_spectrum_order0(table, bins, cob, levels)
+                zbins = dict(bins, zprof=torch.cat([solver.level_altitudes(pl.bins, bins["lp"]) for pl in gp]))
+                return None, solver.level_irradiance_spectrum(table, zbins, cob, seg, aik, levels, out)
+
+            def solve_single(pl):
+                out = pl.ctx.solve_levels(pl.bins, pl.levels) if pl.bins["nb"] else None
+                return None, pl.ctx.level_irradiance(pl.bins, pl.levels, out, pl.aik)
     true_kw = dict(true_depth=True) if split else {}    # (split=False: the calls as they were)
+    prep_kw = dict(true_kw, order0=True) if irr else true_kw
     flux_row, flux_names = (_level_flux_split_row, LEVEL_FLUX_SPLIT_NAMES) if split else (_level_flux_row, LEVEL_FLUX_NAMES)
     level_keys = ("jout", "zz", "tauout") + (("tauvrai",) if split else ())
     rank, world = _dist_rank_world()
@@ -2315,7 +2386,7 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 # (at least 32 wavelengths per part -- a launch per kernel variant each; SOS_SPECTRUM_MIN_PART: the tests' override)
                 for s0, s1 in _part_bounds(len(idx), parts, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32"))):
                     part = _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, aer_st, aer_wa, alts,
-                                          true_kw, batch_profiles, device_tables, batch_operators, debug)
+                                          prep_kw, batch_profiles, device_tables, batch_operators, debug)
                     _stage_profiles(ch, part, alts, level_keys, true_kw, dev)
                     for st in side:
                         main_st.wait_stream(st)
@@ -2328,6 +2399,14 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                     _stage_solves(fn, ch, groups, single, solve_group, solve_single, alts, level_keys, dev, debug)
                     t0 = time.perf_counter()
                     tm["solve_launch"] += t0 - t1
+                if irr:                             # the blocks come down once; the rows are host statements on them
+                    t2 = time.perf_counter()
+                    blocks, _, status = _download_scalars(ch, nz)
+                    t3 = time.perf_counter()
+                    tm["wait"] += t3 - t2
+                    _stage_irradiance_rows(ch, nz, blocks, status, alts, flux_rows, flux_row, len(flux_names), absorb_rows)
+                    tm["fluxes"] += time.perf_counter() - t3
+                    continue
                 flux_dev = None
                 if fluxes:
                     tf = time.perf_counter()
@@ -2386,6 +2465,11 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     if chan is not None:
         return _channel_results(kwargs_list[0], chan, mine, acc, ang_rows, call_scal, alts, len(flux_names) if fluxes else 0,
                                 dev, world, lead)
+    if irr:
+        rows = (flux_rows,) + ((absorb_rows,) if absorption else ())
+        if world > 1 and gather:
+            _gather_rows(mine, world, *rows)
+        return rows if absorption else flux_rows
     if alts is None:
         results = [None if r is None else r[0] for r in results]
     if world > 1 and gather:
@@ -2713,6 +2797,133 @@ def sos_spectrum_levels(altitudes, kwargs_list, aer_phases=None, device=0, gathe
     alts = _levels_arguments("sos_spectrum_levels", altitudes, kwargs_list, fluxes, split, absorption)
     return _spectrum_pass("sos_spectrum_levels", kwargs_list, aer_phases, device, gather, chunk, timings, prep_streams, parts,
                           alts, bool(fluxes), bool(split), trans=trans, salb=salb, absorption=bool(absorption))
+
+
+def _altitude_groups(k, size):
+    """The (k0, k1) bounds of the groups K altitudes go to the solver in: `size` output slots per solve, the last group the
+    remainder."""
+    return [(k0, min(k0 + size, k)) for k0 in range(0, k, size)]
+
+
+def _irradiance_weights(fn, weights, normalize, nwl, k):
+    """The rule of `weights` of sos_spectrum_irradiances, checked before any device work: None, or finite numbers [R][nwl]
+    (one weight per sum and call, the same at every altitude) or [R][K][nwl]; normalize (a bool) divides every weight row --
+    the nwl weights of a sum, or of a sum at one altitude -- by its left-to-right sum, as sos_spectrum_channels does.  Returns
+    the weights [R][K][nwl] as they are applied, or None."""
+    if not isinstance(normalize, (bool, np.bool_)):
+        raise ValueError("%s: normalize must be True or False, got %r" % (fn, normalize))
+    if weights is None:
+        return None
+    shapes = "[R][%d] or [R][%d][%d] (sums, altitudes, calls)" % (nwl, k, nwl)
+    try:
+        wts = np.array(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: weights must be an array of numbers %s" % (fn, shapes))
+    if wts.ndim == 2 and wts.shape[0] >= 1 and wts.shape[1] == nwl:
+        wts = np.repeat(wts[:, None, :], k, axis=1)
+    elif not (wts.ndim == 3 and wts.shape[0] >= 1 and wts.shape[1:] == (k, nwl)):
+        raise ValueError("%s: weights must be %s, got %s" % (fn, shapes, tuple(wts.shape)))
+    bad = np.argwhere(~np.isfinite(wts))
+    if len(bad):
+        raise ValueError("%s: the weight of sum %d at altitude %d for call %d is not finite" % ((fn,) + tuple(bad[0])))
+    if normalize:
+        for r in range(wts.shape[0]):
+            for j in range(k):
+                total = np.cumsum(wts[r, j])[-1] if nwl else 0.0      # the left-to-right sum
+                if total == 0.0 or not np.isfinite(total):
+                    raise ValueError("%s: the weights of sum %d at altitude %d sum to %r: they cannot be normalised"
+                                     % (fn, r, j, float(total)))
+                wts[r, j] = wts[r, j] / total
+    return wts
+
+
+def _weighted_rows(wts, rows):
+    """The weighted sums [R][K][ncol] of the per-call rows (a list of arrays [K][ncol]) with the weights [R][K][nwl] of
+    _irradiance_weights: per sum and altitude a = a + w * x over the calls in ascending call index, one multiply and one add
+    per column; a call of weight 0 is skipped (it adds nothing, not even a NaN row); a NaN row of non-zero weight stays NaN."""
+    nr, k, nwl = wts.shape
+    ncol = rows[0].shape[1] if nwl else 0
+    out = np.zeros((nr, k, ncol))
+    for r in range(nr):
+        a = out[r]
+        for i in range(nwl):
+            w = wts[r, :, i]
+            on = w != 0.0
+            if on.any():
+                a[on] = a[on] + w[on, None] * np.asarray(rows[i], dtype=np.float64)[on]
+    return out
+
+
+def sos_spectrum_irradiances(altitudes, kwargs_list, aer_phases=None, device=0, gather=True, chunk=256, timings=None,
+                             prep_streams=16, parts=4, split=False, absorption=False, weights=None, normalize=False):
+    """The irradiances of a spectrum at any number of altitudes, WITHOUT the radiances: the flux rows -- and with split=True /
+    absorption=True the split and the actinic-flux / absorbed-power rows -- of
+    sos_spectrum_levels(altitudes, kwargs_list, fluxes=True, ...), from Fourier order-0 solves alone.  Every column of these rows
+    is an angular moment of the order-0 field at the altitude or a band scalar, and the Fourier orders do not couple in the
+    solver; so the contexts are created with iborm_max = 0 (order-0 source operators, record 0 of the surface matrices), every
+    bin gets iborm = 0, and a solved group is ONE sosgpu_os_solve_multi_levels launch followed by ONE sosgpu_level_irradiance
+    launch that forms every moment per bin and sums it with aik next to the band scalars: no aggregate, no flux launch, no
+    azimuth recomposition, no table and no 23-tuple.  The blocks [K][calls][14] come down once per chunk and the rows are the
+    host statements of the levels pass on them.
+
+      flux = sos_spectrum_irradiances(altitudes, kwargs_list)                 flux[i]: numpy [K][5], LEVEL_FLUX_NAMES
+      flux, absorb = sos_spectrum_irradiances(..., split=True, absorption=True)   [K][7] LEVEL_FLUX_SPLIT_NAMES, [K][5]
+                                                                              LEVEL_ABSORPTION_NAMES
+    Against sos_spectrum_levels: a call of one bin (no gas, -SOS.AbsModeCKD 2) gives the same bits in every column; in a CKD
+    band the two diffuse-flux columns are the aik-weighted sum of the bins' moments where the levels pass takes the moment of
+    the summed record -- at most (bins + 2 N) roundings of non-negative terms apart, 1e-12 relative -- and the columns formed
+    from them follow; every other column keeps its bits.
+
+    altitudes: any number >= 1 (-1 = the standard output, whose absorption row is NaN), each passing the -SOS.OutputAlt rule.
+    More than 16 go to the solver in groups of 16 output slots: one more pass over the same call list per group (every call is
+    prepared again; an order-0 solve is cheap next to it), the rows concatenated in the order of `altitudes`.
+    kwargs_list: the rules of sos_spectrum_levels -- no result files, zout = -1 -- and -SOS.Trans at NO_OUTPUT (ValueError
+    otherwise).  Calls that keep their per-wavelength preparation there (-SOS.AbsModeCKD 2, an aerosol layer) keep it here.
+    A failing call raises SosProcError naming its index.  aer_phases, device, gather, chunk, timings, prep_streams, parts: as
+    sos_spectrum_levels (timings: the phases of the last altitude group).
+
+    weights (None, or finite numbers [R][calls] or [R][K][calls]): returns the R weighted sums over the calls instead of the
+    rows -- a numpy array [R][K][5 | 7], with absorption=True the pair of it and [R][K][5] -- formed on the host as
+    a = a + w * x over the rows in ascending call index, a call of weight 0 skipped; actinic_tot and the NaN row of altitude -1
+    are summed like any other.  With w = cross section x quantum yield x solar irradiance x band width the actinic_tot column
+    is a photolysis frequency J(z), with w = solar irradiance x band width the absorbed_per_km column a broadband heating rate.
+    normalize=True divides each weight row by its sum first, as sos_spectrum_channels does.  Under torch.distributed the
+    wavelengths are dealt as in sos_spectrum_levels, the rows gathered on every rank (with weights whatever `gather` says),
+    and every rank forms the sums in ascending call index: the bits of one process.
+
+    ValueError, before any device work: split, absorption or normalize not a bool, weights of another shape or not finite, an
+    empty altitude list."""
+    from . import capi
+    fn = "sos_spectrum_irradiances"
+    try:
+        alts_all = [float(z) for z in altitudes]
+    except (TypeError, ValueError):
+        raise ValueError("%s: altitudes must be a list of numbers" % fn)
+    if not alts_all:
+        raise ValueError("%s: at least one altitude" % fn)
+    groups = _altitude_groups(len(alts_all), capi.MAX_OUTPUT_LEVELS)
+    for k0, k1 in groups:                           # (the flag rules, the call rules and the -SOS.OutputAlt rule, per group)
+        _levels_arguments(fn, alts_all[k0:k1], kwargs_list, True, split, absorption)
+    for i, kw in enumerate(kwargs_list):
+        if str(kw.get("fictrans", "NO_OUTPUT")).strip() != "NO_OUTPUT":
+            raise ValueError("%s: call %d asks for the -SOS.Trans file %r: the pass solves the Fourier order 0 of the call's own "
+                             "incidence alone (leave it at NO_OUTPUT)" % (fn, i, kw["fictrans"]))
+    wts = _irradiance_weights(fn, weights, normalize, len(kwargs_list), len(alts_all))
+    split, absorption = bool(split), bool(absorption)
+    nwl = len(kwargs_list)
+    flux, absorb = [[] for _ in range(nwl)], [[] for _ in range(nwl)]
+    for k0, k1 in groups if nwl else []:
+        res = _spectrum_pass(fn, kwargs_list, aer_phases, device, gather or wts is not None, chunk, timings, prep_streams, parts,
+                             alts_all[k0:k1], True, split, absorption=absorption, irr=True)
+        for rows, got in zip((flux, absorb), res if absorption else (res,)):
+            for i in range(nwl):
+                rows[i].append(got[i])
+    join = lambda rows: [None if any(x is None for x in r) else np.concatenate(r) for r in rows]
+    flux, absorb = join(flux), join(absorb) if absorption else None
+    if wts is not None:
+        flux = _weighted_rows(wts, flux)
+        absorb = _weighted_rows(wts, absorb) if absorption else None
+    return (flux, absorb) if absorption else flux
 
 
 def trans_quantities(tetas, mu, ttot_tronc, ttot_vrai, tdifmus, tdifmug):

@@ -622,6 +622,16 @@ class SosContext:
         the unit of the flux columns; zeros in a standard-output slot (altitude -1).  Nothing is waited for."""
         return _level_absorption(self, None, None, bins, levels, out, aik, seg)
 
+    def level_irradiance(self, bins, levels, out, aik, seg=None):
+        """Every irradiance quantity of a band at the K output slots of solve_levels (sosgpu_level_irradiance, ONE launch behind
+        the solve, no aggregate): bins / levels as solve_levels took them (bins["scal"]: the per-bin scalars, zeros when there
+        are none; levels["tauvrai"], where the bins carry hvrai, fills the last column), out its result (the per-bin records,
+        norders and flux pairs), aik[nb] and seg as aggregate takes them.  Only the order-0 row of every record is read: the
+        context may have been created with iborm_max = 0.  Returns a device tensor [K][nseg][capi.IRRADIANCE_COLS], columns as
+        include/sosgpu.h lists them: level_absorption's four, sum aik {E-, E+}, the band scalars of aggregate's block and
+        of sosgpu_level_transmission.  Nothing is waited for."""
+        return _level_irradiance(self, None, None, bins, levels, out, aik, seg)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             capi.lib().sosgpu_destroy(self._h)            # waits for the streams this context's work was queued on
@@ -912,6 +922,61 @@ def level_absorption_spectrum(table, bins, ctx_of_bin, seg, aik, levels, out):
     not carry them, see level_altitudes), out its per-bin result (rec [K][nb][smax+1][3][W], norders).  Bin b is read with mu,
     ga and n0 of table.ctxs[ctx_of_bin[b]].  Returns a device tensor [K][nwavelengths][4]; nothing is waited for."""
     return _level_absorption(table.ctxs[0], table, ctx_of_bin, bins, levels, out, aik, seg)
+
+
+def _level_irradiance(cx, table, ctx_of_bin, bins, levels, out, aik, seg):
+    """The one caller of sosgpu_level_irradiance: SosContext.level_irradiance (table None) and level_irradiance_spectrum."""
+    d = cx.device
+    nz, nb = levels["nz"], bins["nb"]
+    if seg is None:
+        seg = np.array([0, nb], dtype=np.int32)
+    seg_t = _dev_i32(seg, d)
+    nseg = int(seg_t.numel()) - 1
+    res = torch.zeros((nz, max(nseg, 0), capi.IRRADIANCE_COLS), dtype=torch.float64, device=d)
+    if nb == 0 or nseg < 1:
+        return res
+    zprof = level_altitudes(bins)
+    aik_t = _dev_f64(aik, d)
+    scal = torch.zeros((nb, 4), dtype=torch.float64, device=d) if bins.get("scal") is None else _dev_f64(bins["scal"], d)
+    lv = [levels[k].contiguous() for k in ("jout", "zz", "tauout")]     # (views of a part's block: [K][nb] of their own here)
+    tv = None if levels.get("tauvrai") is None else levels["tauvrai"].contiguous()
+    if tuple(zprof.shape) != (nb, bins["lp"]) or aik_t.numel() != nb or tuple(out["rec"].shape[:2]) != (nz, nb) or \
+            tuple(scal.shape) != (nb, 4) or tuple(out["flux"].shape) != (nb, 2):
+        raise ValueError("level_irradiance: zprof [nb][lp], aik [nb], scal [nb][4] and the records [K][nb] and flux [nb][2] of "
+                         "solve_levels are needed")
+    capi.check(capi.lib().sosgpu_level_irradiance(cx._h, None if table is None else _ptr(table.table), _ptr(ctx_of_bin), nb,
+                                                  bins["lp"], _ptr(bins["nt"]), _ptr(bins["prof"]), _ptr(zprof), nz,
+                                                  _ptr(lv[0]), _ptr(lv[1]), _ptr(lv[2]), _ptr(out["rec"]), _ptr(out["norders"]),
+                                                  _ptr(out["flux"]), _ptr(scal), _ptr(tv), nseg, _ptr(seg_t), _ptr(aik_t),
+                                                  _ptr(res), cx._stream()), "sosgpu_level_irradiance")
+    return res
+
+
+def level_irradiance_spectrum(table, bins, ctx_of_bin, seg, aik, levels, out):
+    """SosContext.level_irradiance for the bins of many wavelengths in ONE launch, behind the sosgpu_os_solve_multi_levels call
+    of solve_spectrum_order0: table, bins (with `scal`, and the level altitudes `zprof` [nb][lp], see level_altitudes),
+    ctx_of_bin, seg, aik and levels as that call took them, out its per-bin result.  Bin b is read with mu, ga and n0 of
+    table.ctxs[ctx_of_bin[b]].  Returns a device tensor [K][nwavelengths][capi.IRRADIANCE_COLS]; nothing is waited for."""
+    return _level_irradiance(table.ctxs[0], table, ctx_of_bin, bins, levels, out, aik, seg)
+
+
+def solve_spectrum_order0(table, bins, ctx_of_bin, levels, out=None):
+    """The solve alone of solve_spectrum_levels, for level_irradiance_spectrum: ONE sosgpu_os_solve_multi_levels launch over the
+    bins of many wavelengths in the order given, no aggregate behind it.  The contexts of an irradiance pass hold the order-0
+    operators alone (iborm_max = 0) and every bin has iborm = 0, so the records are [K][nb][1][3][W]; the Fourier orders do not
+    couple, so their order-0 rows and the flux pairs are those of a solve of every order.  Returns the per-bin result dict
+    (rec, norders, iglast, flux); no synchronisation."""
+    cx = table.ctxs[0]
+    nz, nb = levels["nz"], bins["nb"]
+    if out is None:
+        out = cx.alloc_outputs(nb, zero=False)
+        out["rec"] = torch.empty((nz, nb, cx.smax + 1, 3, cx.w), dtype=torch.float64, device=cx.device)
+    capi.check(capi.lib().sosgpu_os_solve_multi_levels(cx._h, _ptr(table.table), _ptr(ctx_of_bin), None, nb, bins["lp"],
+                                                       _ptr(bins["nt"]), _ptr(bins["iborm"]), _ptr(bins["prof"]), nz,
+                                                       _ptr(levels["jout"]), _ptr(levels["zz"]), _ptr(out["rec"]),
+                                                       _ptr(out["norders"]), _ptr(out["iglast"]), _ptr(out["flux"]),
+                                                       cx._stream()), "sosgpu_os_solve_multi_levels")
+    return out
 
 
 def release_scratch():

@@ -92,14 +92,28 @@ __device__ __forceinline__ int block_or_bits(bool b1, int *red, int wv, int lane
 //
 // Stop tests: "max_k |y_k| > thr" is the same decision as "exists k: |num_k| > thr |den_k|".
 // SOS_PARAM_CONV (SOS_OS.F:3434-3453): y = ((g/d - d/a) / (1 - g/d)^2) (g/x3) = (g a - d^2) d g / (a (d-g)^2 x3)
-// for a, d, x3 != 0.  (Differs from the quotient form only by rounding at the 1e-16 level of a 1e-5 threshold;
-// operands below ~1e-77 underflow in the products and are then ignored -- they are 1e-60 of the radiance scale.)
+// for a, d, x3 != 0.  (Differs from the quotient form only by rounding at the 1e-16 level of a 1e-5 threshold.)
+// Both sides are of degree four in the operands, so operands below ~1e-77 underflow in the products although the quotients
+// are ordinary numbers: the down-going rows at the ground of a bin of total depth ~200 are 1e-80, and while their series
+// still grows the rows at the top have long converged.  Ignoring them ends the series early and adds a tail with g > d, a
+// NEGATIVE EMOINS where the reference has 1e-79 (tests/test_incidence_sweep.py, cell `opaque`).  A denominator below 1e-200
+// therefore repeats the test on the operands times one power of two (exact); above it nothing underflows that could decide
+// (den >= 1e-200 with num flushed to 0 is `false` either way), so every other decision keeps its bits.
 __device__ __forceinline__ bool conv_exceeds(double a, double d, double g, double x3, double thr)
 {
     if (a != 0.0 && d != 0.0 && x3 != 0.0) {
-        const double dg = d - g;
-        const double num = (g * a - d * d) * (d * g);
-        const double den = (a * x3) * (dg * dg);
+        double dg = d - g;
+        double num = (g * a - d * d) * (d * g);
+        double den = (a * x3) * (dg * dg);
+        if (fabs(den) < 1e-200) {
+            int e;
+            (void)frexp(fmax(fmax(fabs(a), fabs(d)), fmax(fabs(g), fabs(x3))), &e);
+            const double sc = ldexp(1.0, e < -1000 ? 1000 : -e);
+            a = a * sc; d = d * sc; g = g * sc; x3 = x3 * sc;
+            dg = d - g;
+            num = (g * a - d * d) * (d * g);
+            den = (a * x3) * (dg * dg);
+        }
         return fabs(num) > thr * fabs(den);
     }
     return false;

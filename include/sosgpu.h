@@ -841,6 +841,13 @@ typedef struct sosgpu_solve_plan {
     size_t  off_i3, i3_doubles, off_queue, queue_doubles, off_slots, slot_stride, need;
 } sosgpu_solve_plan;
 int  sosgpu_debug_solve_plan(int n, int smax, int nb, int lp, int nz, int table, int nt_max, sosgpu_solve_plan *plan);
+/* Diagnostic: k-pairs (8 columns each) the LDS-resident solver contracts at Fourier order 0 in a context of `nwgt` directions
+ * with a non-zero quadrature weight: ceil(2 nwgt / 8), the I and Q columns -- U is exactly zero at order 0 -- or, with BRDF/BPDF
+ * matrices (imat_surf != 0), all ceil(3 nwgt / 8).  Needs no context and no device.  Returns the count, or SOSGPU_E_ARG (< 0).
+ * sosgpu_debug_ctx_order0_kpairs: the count of a context; mode > 0 first sets it to the full ceil(3 nwgt / 8) for the context's
+ * later solves (A/B of the two contractions), mode = 0 first sets it back to the rule, mode < 0 only reads. */
+int  sosgpu_debug_order0_kpairs(int nwgt, int imat_surf);
+int  sosgpu_debug_ctx_order0_kpairs(sosgpu_ctx *cx, int mode);
 /* Diagnostic accessor: the per-wavelength tables of a context (built by sosgpu_create, sosgpu_noyaux and
  * sosgpu_set_surface_matrices; csrc/sos_common.h documents every layout) and the numbers that describe them, copied to the
  * HOST.  Read-only: nothing in the context changes.  Like sosgpu_noyaux_fetch it waits for the streams the context's work was

@@ -31,6 +31,7 @@ EXPORTS = [
     "sosgpu_surface_batch", "sosgpu_surface_batch_work_bytes",
     "sosgpu_albedo_spectrum", "sosgpu_albedo_spectrum_work_bytes", "sosgpu_albedo_band",
     "sosgpu_level_absorption", "sosgpu_level_irradiance",
+    "sosgpu_debug_order0_kpairs", "sosgpu_debug_ctx_order0_kpairs",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -285,6 +286,10 @@ def lib():
         L.sosgpu_debug_stage_blocks.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
         L.sosgpu_debug_solve_plan.restype = i32
         L.sosgpu_debug_solve_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(SolvePlan)]
+        L.sosgpu_debug_order0_kpairs.restype = i32
+        L.sosgpu_debug_order0_kpairs.argtypes = [i32, i32]
+        L.sosgpu_debug_ctx_order0_kpairs.restype = i32
+        L.sosgpu_debug_ctx_order0_kpairs.argtypes = [vp, i32]
         L.sosgpu_debug_roundtrip.restype = i32
         L.sosgpu_debug_roundtrip.argtypes = [i32, i32, C.c_size_t, vp, vp, vp]
         L.sosgpu_debug_tables.restype = i32

@@ -285,6 +285,7 @@ extern "C" int sosgpu_create(sosgpu_ctx **out, int device, const sosgpu_wave *wv
     d.os_nb = B; d.smax = iborm_max;
     d.n0 = wv->n0; d.imat_surf = wv->imat_surf == 1; d.ifresnel = wv->ifresnel == 1 ? 1 : 0;
     d.igmax = wv->igmax; d.ipolar = wv->ipolar ? 1 : 0;
+    d.ks2h0 = sos_order0_kpairs(nwgt, d.ks2h, d.imat_surf != 0);      // order 0: the I and Q columns only (solve_variant.h)
     d.mus = mu[wv->n0 - 1];
     d.ro = wv->ro;
     // molecular phase-matrix coefficients, SOS_OS.F:678-684
@@ -2378,6 +2379,23 @@ extern "C" int sosgpu_debug_solve_plan(int n, int smax, int nb, int lp, int nz, 
     if (!plan || smax < 0 || nb < 1 || lp < 2 || nz < 0 || nz > SOSGPU_MAX_OUTPUT_LEVELS) return SOSGPU_E_ARG;
     const SolveShape sh = {n, smax, nb, lp, nz, table != 0};
     return solve_plan(sh, read_solve_overrides(), nt_max, plan);
+}
+
+// Diagnostic: the k-pair count of the order-0 contraction -- the rule itself (no context, no device), and a context's count
+// with the switch back to the full contraction that the A/B of the two needs (include/sosgpu.h).
+extern "C" int sosgpu_debug_order0_kpairs(int nwgt, int imat_surf)
+{
+    if (nwgt < 1 || nwgt > 85) return SOSGPU_E_ARG;
+    return sos_order0_kpairs(nwgt, (3 * nwgt + 7) / 8, imat_surf != 0);
+}
+
+extern "C" int sosgpu_debug_ctx_order0_kpairs(sosgpu_ctx *cx, int mode)
+{
+    if (!cx) return SOSGPU_E_ARG;
+    SosDev &d = cx->d;
+    if (mode == 0) d.ks2h0 = sos_order0_kpairs(d.nwgt, d.ks2h, d.imat_surf != 0);
+    else if (mode > 0) d.ks2h0 = d.ks2h;
+    return d.ks2h0;
 }
 
 extern "C" int sosgpu_debug_scratch(sosgpu_ctx *cx, double **d_scratch, size_t *doubles, size_t *spec_i3_offset)

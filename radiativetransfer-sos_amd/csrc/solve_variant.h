@@ -21,6 +21,21 @@ inline size_t lds_bytes_for(int nw, int rtw, int ct)
     return ((size_t)cols * fs + 3 * ns + 2 + 2 * ns + 16 + 2 * ns + (size_t)cols * ns + 7 * cols) * sizeof(double);
 }
 
+// k-pairs of the source contraction at Fourier order 0 (SosDev::ks2h0, set by sosgpu_create; sosgpu_debug_order0_kpairs reports
+// the rule).  At s = 0 the function T^0_l is zero for every l (noyaux.hip gsf_body: it starts from zeros and its recurrence has
+// F = 2 s / (l (l + 1)) = 0), so the kernels GT and ART that couple U to I and Q, the U rows of the order-1 vectors and the U
+// terms of the molecular factors are exact zeros (noyaux_dev.h ktab_sum, sv_rows; noyaux.hip ray_vt_element, pack_ray_body).  The
+// Lambert ground reflects into I only and the flat Fresnel matrix takes U into U (F33), so U(s = 0) stays exactly zero through
+// every scattering order and the K positions of the U columns, 2 Nw ... 3 Nw - 1 in rowmap's component-major order, contribute
+// products with an exact zero factor: the contraction stops after the k-pairs that hold the I and Q columns.  The accumulators
+// start from +0 and a sum never gives -0 from there, so the dropped terms would not even have changed a sign bit.  A BRDF/BPDF
+// surface (imat_surf) reflects through REAL*4 matrices in which nothing guarantees the zeros: the full count.
+inline int sos_order0_kpairs(int nwgt, int ks2h, bool imat_surf)
+{
+    const int iq = (2 * nwgt + 7) / 8;
+    return (imat_surf || iq > ks2h) ? ks2h : iq;
+}
+
 // ---- streamed kernel (sos_stream.hip) -----------------------------------------------------------------------------------
 #ifndef SOS_STREAM_COLS
 #define SOS_STREAM_COLS 32

@@ -33,6 +33,9 @@ struct SosDev {                 // per-wavelength device context, passed by valu
     int nwgt;                   // Nw: directions with a non-zero quadrature weight
     int prow;                   // first of four PADDING rows (>= 3N, same 16-row tile as row 3N-1, multiple of 4) that carry the
                                 // rank-4 projection V^T of the molecular operator in the packed A operand, or -1
+    int ks2h0;                  // k-pairs the LDS-resident solver contracts at Fourier order 0 (sos_order0_kpairs, solve_variant.h):
+                                // the I and Q columns only where U(s = 0) is exactly zero, else ks2h.  (In the alignment gap
+                                // before the pointer: the layout of every other field is what it was.)
     const int32_t *rowmap;      // [kh] half-system position -> c*N + (k-1) (weighted directions first), -1 = padding
     int os_nb, smax;            // OS_NB, iborm_max
     int n0, imat_surf, ifresnel, igmax, ipolar;

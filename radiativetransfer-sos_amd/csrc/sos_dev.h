@@ -146,8 +146,10 @@ template <int NA, int RAY, bool FOLD, int RTWH, int CT, int NW, int FS, int KHM,
 __device__ __forceinline__ void gemm_source(v4d (&acc)[2][RTWH][CT], const double *__restrict__ mp, bool do_aer,
                                             const double *__restrict__ vt, const double *__restrict__ uf,
                                             int ks2h, int rtph, const double *bx, const double *xdel,
-                                            const double *ydel, int lane, int tile0, int prow, double *pcb)
+                                            const double *ydel, int lane, int tile0, int prow, double *pcb, int kc = -1)
 {
+    // kc: k-pairs to contract when fewer than the ks2h the operator is packed with (order 0: SosDev::ks2h0); ks2h stays the stride
+    const int nk = kc < 0 ? ks2h : kc;
     // fold: the projection rows V^T sit in padding rows prow..prow+3 of the packed aerosol operator (api.hip), so the
     // dense pass below already computes V^T X^sr in the accumulator quad of those rows; pcb = this lane's slot in the
     // (unused) padding rows of the LDS buffer through which the owning wave hands the projections to the others
@@ -235,43 +237,43 @@ __device__ __forceinline__ void gemm_source(v4d (&acc)[2][RTWH][CT], const doubl
         int m = 0;
         if (PIPE_B) {
             load_b(b0, 0);
-            if (ks2h >= 2) {                                  // peeled first pair of k-pairs
+            if (nk >= 2) {                                    // peeled first pair of k-pairs
                 load_a(f1, 1);
                 load_b(b1, 1);
                 mma(f0, b0, first);
-                if (2 < ks2h) { load_a(f0, 2); load_b(b0, 2); }
+                if (2 < nk) { load_a(f0, 2); load_b(b0, 2); }
                 mma(f1, b1, next);
                 m = 2;
 #pragma unroll 1
-                for (; m + 1 < ks2h; m += 2) {
+                for (; m + 1 < nk; m += 2) {
                     load_a(f1, m + 1);
                     load_b(b1, m + 1);
                     mma(f0, b0, next);
-                    if (m + 2 < ks2h) { load_a(f0, m + 2); load_b(b0, m + 2); }
+                    if (m + 2 < nk) { load_a(f0, m + 2); load_b(b0, m + 2); }
                     mma(f1, b1, next);
                 }
-                if (m < ks2h) mma(f0, b0, next);
+                if (m < nk) mma(f0, b0, next);
             } else mma(f0, b0, first);
         } else {
             // four column tiles: one set of B registers (32 VGPRs) -- the second set costs more in spills than it hides
-            if (ks2h >= 2) {
+            if (nk >= 2) {
                 load_a(f1, 1);
                 load_b(b0, 0);
                 mma(f0, b0, first);
-                if (2 < ks2h) load_a(f0, 2);
+                if (2 < nk) load_a(f0, 2);
                 load_b(b0, 1);
                 mma(f1, b0, next);
                 m = 2;
 #pragma unroll 1
-                for (; m + 1 < ks2h; m += 2) {
+                for (; m + 1 < nk; m += 2) {
                     load_a(f1, m + 1);
                     load_b(b0, m);
                     mma(f0, b0, next);
-                    if (m + 2 < ks2h) load_a(f0, m + 2);
+                    if (m + 2 < nk) load_a(f0, m + 2);
                     load_b(b0, m + 1);
                     mma(f1, b0, next);
                 }
-                if (m < ks2h) { load_b(b0, m); mma(f0, b0, next); }
+                if (m < nk) { load_b(b0, m); mma(f0, b0, next); }
             } else { load_b(b0, 0); mma(f0, b0, first); }
         }
         if (fold) {
@@ -315,14 +317,14 @@ __device__ __forceinline__ void gemm_source(v4d (&acc)[2][RTWH][CT], const doubl
         };
         int m = 0;
 #pragma unroll 1
-        for (; m + 1 < ks2h; m += 2) {
+        for (; m + 1 < nk; m += 2) {
             v1 = vp[(size_t)(m + 1) * 64];
             load_b(b1, m + 1);
             prj(v0, b0);
-            if (m + 2 < ks2h) { v0 = vp[(size_t)(m + 2) * 64]; load_b(b0, m + 2); }
+            if (m + 2 < nk) { v0 = vp[(size_t)(m + 2) * 64]; load_b(b0, m + 2); }
             prj(v1, b1);
         }
-        if (m < ks2h) prj(v0, b0);
+        if (m < nk) prj(v0, b0);
     }
     if (RAY >= 0) {
         if (fold) __syncthreads();             // every wave of the workgroup passes exactly one barrier here (see the call site)
@@ -357,8 +359,10 @@ template <int RAY, bool FOLD, int CT, int NW, int FS, int KHM, bool PRE = false>
 __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&accs)[2], const int R, const int usy, const int uct,
                                                   const double *__restrict__ mp, bool do_aer, const double *__restrict__ vt,
                                                   const double *__restrict__ uf, int ks2h, int rtph, const double *bx,
-                                                  const double *xdel, const double *ydel, int lane, int tile0, int prow, double *pcb)
+                                                  const double *xdel, const double *ydel, int lane, int tile0, int prow, double *pcb,
+                                                  int kc = -1)
 {
+    const int nk = kc < 0 ? ks2h : kc;                    // as in gemm_source
     // (usy, uct are wave-uniform run-time values: as template arguments they would quadruple the already large kernels.  The
     //  unit's B operand X^usy of column tile uct is read from the field a second time instead of being selected out of the
     //  registers of the own tile's operands: one or two more LDS reads per k-pair.)
@@ -440,22 +444,22 @@ __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&ac
         load_a(f0, 0);
         int m = 0;
         load_b(b0, 0);
-        if (ks2h >= 2) {                                  // peeled first pair of k-pairs (as in gemm_source, PIPE_B form)
+        if (nk >= 2) {                                    // peeled first pair of k-pairs (as in gemm_source, PIPE_B form)
             load_a(f1, 1);
             load_b(b1, 1);
             mma(f0, b0, first);
-            if (2 < ks2h) { load_a(f0, 2); load_b(b0, 2); }
+            if (2 < nk) { load_a(f0, 2); load_b(b0, 2); }
             mma(f1, b1, next);
             m = 2;
 #pragma unroll 1
-            for (; m + 1 < ks2h; m += 2) {
+            for (; m + 1 < nk; m += 2) {
                 load_a(f1, m + 1);
                 load_b(b1, m + 1);
                 mma(f0, b0, next);
-                if (m + 2 < ks2h) { load_a(f0, m + 2); load_b(b0, m + 2); }
+                if (m + 2 < nk) { load_a(f0, m + 2); load_b(b0, m + 2); }
                 mma(f1, b1, next);
             }
-            if (m < ks2h) mma(f0, b0, next);
+            if (m < nk) mma(f0, b0, next);
         } else mma(f0, b0, first);
         if (fold) {
             // the projection rows sit in register 3 of the tile holding prow: this wave's own tile (all columns), or a left-over
@@ -498,14 +502,14 @@ __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&ac
         };
         int m = 0;
 #pragma unroll 1
-        for (; m + 1 < ks2h; m += 2) {
+        for (; m + 1 < nk; m += 2) {
             v1 = vp[(size_t)(m + 1) * 64];
             load_b(b1, m + 1);
             prj(v0, b0);
-            if (m + 2 < ks2h) { v0 = vp[(size_t)(m + 2) * 64]; load_b(b0, m + 2); }
+            if (m + 2 < nk) { v0 = vp[(size_t)(m + 2) * 64]; load_b(b0, m + 2); }
             prj(v1, b1);
         }
-        if (m < ks2h) prj(v0, b0);
+        if (m < nk) prj(v0, b0);
     }
     if (RAY >= 0) {
         if (fold) __syncthreads();             // every wave of the workgroup passes exactly one barrier here (see the call site)

@@ -373,11 +373,18 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
                     const double *ufp = cx.mp_uf + (size_t)(s <= 2 ? s : 0) * cx.rtph * 64;
                     // RAY: half system the molecular operator acts on (A for even s, B for odd s), none for s > 2
                     const bool fold = s <= 2 && has_aer && cx.prow >= 0;       // projection rows ride in the dense pass
+                    // k-pairs contracted: at order 0 those of the I and Q columns only, where U is exactly zero (SosDev::ks2h0;
+                    // with surface matrices that count is ks2h, so the SURF kernels do not read it)
+#ifdef SOS_NO_ORDER0_TRIM                                  // diagnostic build: the full contraction at every order (A/B measurements)
+                    const int kc = cx.ks2h;
+#else
+                    const int kc = (!SURF && s == 0) ? cx.ks2h0 : cx.ks2h;
+#endif
                     auto contract = [&](auto na_tag) {
                         constexpr int NA = decltype(na_tag)::value;
 #define SOS_GEMM(RAYV, FOLDV)                                                                                          \
     gemm_source<NA, RAYV, FOLDV, RTWH, CT, NW, FS, KHM, (CT < 4), (SOS_PRECOMBINE_LDS != 0)>(acc, mpa, has_aer != 0, vtp, ufp, cx.ks2h, cx.rtph, bx,        \
-                                                        xdel, ydel, lane, wv, cx.prow, pcb)
+                                                        xdel, ydel, lane, wv, cx.prow, pcb, kc)
                         if (s > 2) SOS_GEMM(-1, false);
                         else if (s & 1) { if (fold) SOS_GEMM(1, true); else SOS_GEMM(1, false); }
                         else { if (fold) SOS_GEMM(0, true); else SOS_GEMM(0, false); }
@@ -396,7 +403,7 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
                             {
 #define SOS_GEMM_S(RAYV, FOLDV)                                                                                        \
     gemm_source_split<RAYV, FOLDV, CT, NW, FS, KHM, (SOS_PRECOMBINE_LDS != 0)>(own, accs, R, wv >> 1, wv & 1, mpa, has_aer != 0, vtp, ufp, cx.ks2h, \
-                                                               cx.rtph, bx, xdel, ydel, lane, wv, cx.prow, pcb)
+                                                               cx.rtph, bx, xdel, ydel, lane, wv, cx.prow, pcb, kc)
                                 if (s > 2) SOS_GEMM_S(-1, false);
                                 else if (s & 1) { if (fold) SOS_GEMM_S(1, true); else SOS_GEMM_S(1, false); }
                                 else { if (fold) SOS_GEMM_S(0, true); else SOS_GEMM_S(0, false); }

@@ -37,10 +37,7 @@ inline int sos_order0_kpairs(int nwgt, int ks2h, bool imat_surf)
 }
 
 // ---- streamed kernel (sos_stream.hip) -----------------------------------------------------------------------------------
-#ifndef SOS_STREAM_COLS
-#define SOS_STREAM_COLS 32
-#endif
-constexpr int COLS = SOS_STREAM_COLS;      // levels per chunk (two 16-column MFMA tiles; 16 = experiment: three workgroups per CU)
+constexpr int COLS = 32;      // levels per chunk (two 16-column MFMA tiles)
 constexpr int VPAD = 8;       // level vectors are stored with a +1 offset (entry e = level e-1) and a few spare entries
 
 // Row capacity of the field layout.  Round 2 sized it by the wave shape alone, KHM = 16 NW RTWH rows per half: 64, 128, 256.  A half
@@ -114,19 +111,11 @@ inline int solve_variant(const SolveShape &sh, const SolveOverrides &ov, SolvePl
         p->kht = p->nw * p->rtw;
         if (kh > 64 && kh <= 128) {
             p->kht = kh <= 80 ? 5 : kh <= 96 ? 6 : 8;
-#ifdef SOS_STREAM_WIDE
-            p->kht = 8;                                    // round 2's layout (A/B measurements)
-#endif
             if (ov.persist != 0) p->kht = 8;
         }
         p->lds_bytes = stream_lds_bytes(p->kht);
     } else {
-#ifdef SOS_WIDE_REGS                                       // diagnostic build: <8,1,4> runs as the 512-register <4,2,4>
-        if (p->nw == 8 && p->ct == 4) { p->nw = 4; p->rtw = 2; }      // same KHM, same LDS layout
-#endif
-#ifndef SOS_NO_SPLIT
         p->split = p->nw == 4 && p->rtw == 2 && p->ct == 2 && rtph > 4 && rtph <= 6 && 16 * rtph + 16 * (rtph - 4) <= sos_khm(4, 2);
-#endif
         p->lds_bytes = lds_bytes_for(p->nw, p->rtw, p->ct);
     }
     p->threads = 64 * p->nw;

@@ -7,16 +7,6 @@
 #include "sos_common.h"
 #include "solve_variant.h"   // capacity constants of the variants: sos_khm / sos_fs / sos_ns, the streamed layout's COLS, skhm ...
 
-// Parity sums X+ +- X- of the B operands: formed by every wave inside the contraction (8 vector sums per k-pair and wave), or
-// once per step / chunk in LDS.  Measured (profiles/r02_flagship_instmix.txt): in the LDS-resident kernel the combine pass needs
-// a workgroup barrier of its own and LOSES 2.1 % (194.1 vs 198.2 k bins/s) -- off; in the streamed kernel it rides in the
-// fix-up pass that closes the up-going rows anyway, no barrier added: +0.5 % -- on.
-#ifndef SOS_PRECOMBINE_LDS
-#define SOS_PRECOMBINE_LDS 0
-#endif
-#ifndef SOS_PRECOMBINE_STREAM
-#define SOS_PRECOMBINE_STREAM 1
-#endif
 #ifdef SOS_PROFILE_PHASES
 // s_memrealtime: constant 100 MHz counter (s_memtime is NOT wall-clock on gfx950 when waves share a SIMD: it advances
 // at 1/k of the shader clock with k MFMA-streaming waves per SIMD -- scripts/ubench_mfma_peak.hip)
@@ -142,6 +132,10 @@ __device__ __forceinline__ double queue_term(double d, double g)
 // L2 nor the LDS round trip sits between two k-pairs.  The rank-4 projection of the molecular operator (RAY = half
 // system it acts on, -1 = none) either comes for free (FOLD: its four rows are packed into padding rows of the dense
 // operator) or rides in the same loop as 2 CT extra MFMAs per k-pair fed by one more prefetched 16-byte fragment.
+// PRE: the parity sums X+ +- X- of the B operands are already in the buffer instead of being formed by every wave here (8 vector
+// sums per k-pair and wave).  The streamed kernel combines them in the fix-up pass that closes the up-going rows anyway, no
+// barrier added: +0.5 %; in the LDS-resident kernel a combine pass needs a workgroup barrier of its own and lost 2.1 % (194.1 vs
+// 198.2 k bins/s, profiles/r02_flagship_instmix.txt), so that kernel passes PRE = false.
 template <int NA, int RAY, bool FOLD, int RTWH, int CT, int NW, int FS, int KHM, bool PIPE_B, bool PRE = false>
 __device__ __forceinline__ void gemm_source(v4d (&acc)[2][RTWH][CT], const double *__restrict__ mp, bool do_aer,
                                             const double *__restrict__ vt, const double *__restrict__ uf,
@@ -199,11 +193,7 @@ __device__ __forceinline__ void gemm_source(v4d (&acc)[2][RTWH][CT], const doubl
             // PRE: the buffer already holds X^A = X+ + X- where X+ used to be and X^B = X+ - X- where X- used to be (combined
             // once per step for all four waves instead of by every wave for itself: 8 sums per k-pair and wave less)
             for (int ct = 0; ct < CT; ct++) {
-#ifdef SOS_EXP_NOADD                                       // timing experiment only (wrong physics): the contraction without its sums
-                if (true) { ba[ct] = b.xp[ct]; bb[ct] = b.xm[ct]; }
-#else
                 if (PRE) { ba[ct] = b.xp[ct]; bb[ct] = b.xm[ct]; }
-#endif
                 else { ba[ct] = b.xp[ct] + b.xm[ct]; bb[ct] = b.xp[ct] - b.xm[ct]; }
             }
 #pragma unroll
@@ -355,7 +345,7 @@ __device__ __forceinline__ void gemm_source(v4d (&acc)[2][RTWH][CT], const doubl
 // through the field buffer: the partials go to the pad rows [16 rtph, 16 rtph + 16 R) of the half USY (rows no operand,
 // sweep or projection slot ever touches: write_back_shared), and after a barrier combine_shared adds them up in place.
 // Everything else -- operand layout, software pipeline, the folded molecular projection, XDEL / YDEL scaling -- is gemm_source's.
-template <int RAY, bool FOLD, int CT, int NW, int FS, int KHM, bool PRE = false>
+template <int RAY, bool FOLD, int CT, int NW, int FS, int KHM>
 __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&accs)[2], const int R, const int usy, const int uct,
                                                   const double *__restrict__ mp, bool do_aer, const double *__restrict__ vt,
                                                   const double *__restrict__ uf, int ks2h, int rtph, const double *bx,
@@ -369,7 +359,7 @@ __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&ac
     static_assert(CT == 2 && NW == 4, "units are (half system, column tile) of four waves");
     constexpr bool fold = FOLD;
     struct BRaw { v2d xp[CT], xm[CT], up, um; };
-    const double *bxu = bx + uct * 16 * FS + (PRE && usy ? KHM : 0);
+    const double *bxu = bx + uct * 16 * FS;
     const double sgn = usy ? -1. : 1.;
     auto load_b = [&](BRaw &b, int m) {
 #pragma unroll
@@ -378,7 +368,7 @@ __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&ac
             b.xm[ct] = *reinterpret_cast<const v2d *>(bx + ct * 16 * FS + KHM + 8 * m);
         }
         b.up = *reinterpret_cast<const v2d *>(bxu + 8 * m);
-        if (!PRE) b.um = *reinterpret_cast<const v2d *>(bxu + KHM + 8 * m);
+        b.um = *reinterpret_cast<const v2d *>(bxu + KHM + 8 * m);
     };
     const v2d *vp = reinterpret_cast<const v2d *>(vt) + lane;
     const bool ray_unit = RAY >= 0 && usy == (RAY > 0 ? 1 : 0);      // this wave's unit lies in the half system the molecular operator acts on
@@ -407,13 +397,9 @@ __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&ac
             const v4d zero = {0., 0., 0., 0.};
             v2d ba[CT], bb[CT];
 #pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                if (PRE) { ba[ct] = b.xp[ct]; bb[ct] = b.xm[ct]; }
-                else { ba[ct] = b.xp[ct] + b.xm[ct]; bb[ct] = b.xp[ct] - b.xm[ct]; }
-            }
+            for (int ct = 0; ct < CT; ct++) { ba[ct] = b.xp[ct] + b.xm[ct]; bb[ct] = b.xp[ct] - b.xm[ct]; }
             v2d bu;
-            if (PRE) bu = b.up;
-            else { bu.x = __builtin_fma(sgn, b.um.x, b.up.x); bu.y = __builtin_fma(sgn, b.um.y, b.up.y); }   // X+ +- X-, exact
+            bu.x = __builtin_fma(sgn, b.um.x, b.up.x); bu.y = __builtin_fma(sgn, b.um.y, b.up.y);   // X+ +- X-, exact
 #pragma unroll
             for (int ct = 0; ct < CT; ct++) {
                 acc[0][0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.a[0].x, ba[ct].x, FIRST ? zero : acc[0][0][ct], 0, 0, 0);
@@ -495,7 +481,7 @@ __device__ __forceinline__ void gemm_source_split(v4d (&acc)[2][1][CT], v4d (&ac
         auto prj = [&](const v2d &v, const BRaw &b) {
 #pragma unroll
             for (int ct = 0; ct < CT; ct++) {
-                const v2d bq = PRE ? (RAY ? b.xm[ct] : b.xp[ct]) : (RAY ? b.xp[ct] - b.xm[ct] : b.xp[ct] + b.xm[ct]);
+                const v2d bq = RAY ? b.xp[ct] - b.xm[ct] : b.xp[ct] + b.xm[ct];
                 pr[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, bq.x, pr[ct], 0, 0, 0);
                 pr[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, bq.y, pr[ct], 0, 0, 0);
             }
@@ -556,26 +542,6 @@ __device__ __forceinline__ void combine_shared(double *cbuf, int t, int nth, int
         const double a = c[16 * rtph + row], b = c[KHM + 16 * rtph + row];
         c[16 * NW + row] = a + b;
         c[KHM + 16 * NW + row] = a - b;
-    }
-}
-
-// Parity combination of the whole field buffer in place, once per step (flagship: between the stop tests and the contraction;
-// one more workgroup barrier after it): wave w takes levels w, w + NW, ..., a lane two adjacent rows of both halves.
-template <int NW, int FS, int KHM, int LEVELS>
-__device__ __forceinline__ void combine_field(double *fld, int lane, int wv)
-{
-    static_assert(KHM % 16 == 0, "rows per half");
-#pragma unroll
-    for (int l = 0; l < LEVELS / NW; l++) {
-        double *row = fld + (size_t)(wv + l * NW) * FS;
-#pragma unroll
-        for (int r = 0; r < KHM; r += 128) {
-            if (KHM - r >= 128 || 2 * lane < KHM - r) {
-                v2d *pp = reinterpret_cast<v2d *>(row + r + 2 * lane), *pm = reinterpret_cast<v2d *>(row + KHM + r + 2 * lane);
-                const v2d xp = *pp, xm = *pm;
-                *pp = xp + xm; *pm = xp - xm;
-            }
-        }
     }
 }
 
@@ -663,10 +629,7 @@ __device__ __forceinline__ void ground_mfma(const double *__restrict__ gp, int k
     const char *ab = reinterpret_cast<const char *>(gp) + (size_t)tile0 * rts * 16;
     unsigned loff = (unsigned)lane * 16u;
     const double *bp = gndk + (lane >> 4);
-#ifndef SOS_GROUND_MB
-#define SOS_GROUND_MB 5
-#endif
-    constexpr int MB = SOS_GROUND_MB;         // k-pairs requested together
+    constexpr int MB = 5;                     // k-pairs requested together
 #pragma unroll 1
     for (int m = 0; m < ks2h; m += MB) {
         v2d a[MB][NA];

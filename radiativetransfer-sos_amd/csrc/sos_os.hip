@@ -44,27 +44,19 @@
 //             read back from the field after every formal solution.
 // Register bound: 256 architectural VGPRs (two workgroups per CU for NW = 4 when the LDS allows it).  The 512-register
 // form (256 VGPRs + 256 AGPRs, one workgroup per CU) of the 4-wave CT = 4 variants was measured slower in round 1 (60.2k vs
-// 63.6k bins/s at N = 41, NT = 60) and one instantiation gave wrong down-going rows then.  Re-examined in round 2 with
-// -DSOS_WIDE_REGS (below; builds <4,2,4,.> in that form and routes the <8,1,4> cases to it): all 85 parity and fuzz
-// tests pass, zout_n25_nt60 included (gpurun log wide_regs.log, profiles/r02_wide_regs.txt) -- the round-1 failure does not
-// reproduce on the current code (its write-back and ZOUT read-back were rewritten since), so there is no evidence of an
-// ordering bug hidden by register allocation in the shipped variants; the form stays unused because it is slower.
-#ifdef SOS_WIDE_REGS                                       // diagnostic build: 512-register form of the 4-wave CT = 4 variants
-#define SOS_MIN_WG(NW, CT) (((NW) == 4 && (CT) != 4) ? 2 : 1)
-#else
+// 63.6k bins/s at N = 41, NT = 60) and one instantiation gave wrong down-going rows then.  Re-examined in round 2 with a
+// build that ran <4,2,4,.> in that form in place of <8,1,4>: all 85 parity and fuzz tests passed, zout_n25_nt60 included
+// (profiles/r02_wide_regs.txt) -- the round-1 failure did not reproduce (the write-back and ZOUT read-back were rewritten
+// since), so there is no evidence of an ordering bug hidden by register allocation in the shipped variants; the form is not
+// built because it is slower.
 #define SOS_MIN_WG(NW, CT) (((NW) == 4) ? 2 : 1)
-#endif
 // The one-row-tile variants of up to 32 levels (N <= 21: 41 KB of LDS per workgroup) run THREE workgroups per CU (round 3): 168
 // registers per lane instead of 256 cost 19-61 spilled registers, the third wave per SIMD hides more of the formal solution's
 // latency than that costs -- N = 13 / 17 / 21 at NT = 30: 700 / 602 / 482 -> 820 / 687 / 541 k bins/s (profiles/r03_n_sweep.txt).
 // (The same for N = 22 ... 26 -- a five-tile field layout as in sos_stream.hip, 51 KB per workgroup, three workgroups per CU, wave 0
 // carrying the fifth tile -- was built and measured against the shared-tile form on two workgroups: 375.7 vs 371.1 k bins/s at
 // N = 25, 335.1 vs 336.5 at N = 26, with 132-185 spilled registers; a wash, not kept.)
-#ifdef SOS_NO_3WG
-#define SOS_MIN_WG_R(NW, RTWH, CT) SOS_MIN_WG(NW, CT)
-#else
 #define SOS_MIN_WG_R(NW, RTWH, CT) (((NW) == 4 && (RTWH) == 1 && (CT) == 2) ? 3 : SOS_MIN_WG(NW, CT))
-#endif
 // ZM: output mode -- 0 standard output (TOA up-going, ground down-going), 1 one output altitude (ZO above: bn.jout / bn.zz),
 //     2 bn.nz output slots (sosgpu_os_solve_levels, sosgpu_os_solve_multi_levels): every slot runs the statements of ZO = true with its own (jout, zz), its
 //     i3lo / dlo / i3hi / dhi kept lane-private in bn.zst (no registers across the order loop: there are none to spare), a slot
@@ -119,9 +111,7 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
     // shared-tile form of the contraction (sos_dev.h gemm_source_split): four waves, five or six row tiles (N = 22 ... 32).
     // A template argument, chosen by the launcher from the context's tile count (sos_split_applies): an instantiation of its own,
     // so that the kernels of the other direction counts are compiled exactly as without it.
-    constexpr bool SPLIT_OK = SPLIT;
     static_assert(!SPLIT || (NW == 4 && RTWH == 2 && CT == 2), "shared-tile form: four waves, two column tiles");
-    constexpr bool split = SPLIT;
     // contraction tiles of this wave: tile wv, and tile wv + NW for the larger N of a variant (wave-uniform)
     const bool tile_a = wv * 16 < KH;
     const bool tile_b = RTWH > 1 && (wv + NW) * 16 < KH;
@@ -355,11 +345,6 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
                 if (ig > cx.igmax) break;
                 iglast = ig;
                 // source function of order ig: dense FP64 contraction on the matrix cores (SOS_FSOURCE_ORDREIG)
-                if (SOS_PRECOMBINE_LDS) {
-                    // X^A, X^B formed once for the four waves (sos_dev.h combine_field); the barrier ends the pass
-                    combine_field<NW, FS, KHM, CT * 16>(fld, lane, wv);
-                    __syncthreads();
-                }
                 {
                     v4d acc[2][RTWH][CT];       // (zero for a bin without aerosol operator; the dense pass starts from the MFMA zero operand)
 #pragma unroll
@@ -375,51 +360,44 @@ __global__ __launch_bounds__(64 * NW, SOS_MIN_WG_R(NW, RTWH, CT)) void k_sos_os(
                     const bool fold = s <= 2 && has_aer && cx.prow >= 0;       // projection rows ride in the dense pass
                     // k-pairs contracted: at order 0 those of the I and Q columns only, where U is exactly zero (SosDev::ks2h0;
                     // with surface matrices that count is ks2h, so the SURF kernels do not read it)
-#ifdef SOS_NO_ORDER0_TRIM                                  // diagnostic build: the full contraction at every order (A/B measurements)
-                    const int kc = cx.ks2h;
-#else
                     const int kc = (!SURF && s == 0) ? cx.ks2h0 : cx.ks2h;
-#endif
                     auto contract = [&](auto na_tag) {
                         constexpr int NA = decltype(na_tag)::value;
 #define SOS_GEMM(RAYV, FOLDV)                                                                                          \
-    gemm_source<NA, RAYV, FOLDV, RTWH, CT, NW, FS, KHM, (CT < 4), (SOS_PRECOMBINE_LDS != 0)>(acc, mpa, has_aer != 0, vtp, ufp, cx.ks2h, cx.rtph, bx,        \
-                                                        xdel, ydel, lane, wv, cx.prow, pcb, kc)
+    gemm_source<NA, RAYV, FOLDV, RTWH, CT, NW, FS, KHM, (CT < 4), false>(acc, mpa, has_aer != 0, vtp, ufp, cx.ks2h, cx.rtph, bx,    \
+                                                                         xdel, ydel, lane, wv, cx.prow, pcb, kc)
                         if (s > 2) SOS_GEMM(-1, false);
                         else if (s & 1) { if (fold) SOS_GEMM(1, true); else SOS_GEMM(1, false); }
                         else { if (fold) SOS_GEMM(0, true); else SOS_GEMM(0, false); }
 #undef SOS_GEMM
                     };
-                    if constexpr (SPLIT_OK) {
-                        if (split) {
-                            // more row tiles than waves, fewer than two per wave (N = 22 ... 32): one own tile per wave, the
-                            // left-over tiles shared out by (half system, column tile) -- sos_dev.h gemm_source_split
-                            v4d own[2][1][CT], accs[2] = {{0., 0., 0., 0.}, {0., 0., 0., 0.}};
+                    if constexpr (SPLIT) {
+                        // more row tiles than waves, fewer than two per wave (N = 22 ... 32): one own tile per wave, the
+                        // left-over tiles shared out by (half system, column tile) -- sos_dev.h gemm_source_split
+                        v4d own[2][1][CT], accs[2] = {{0., 0., 0., 0.}, {0., 0., 0., 0.}};
 #pragma unroll
-                            for (int sy = 0; sy < 2; sy++)
+                        for (int sy = 0; sy < 2; sy++)
 #pragma unroll
-                                for (int ct = 0; ct < CT; ct++) own[sy][0][ct] = (v4d){0., 0., 0., 0.};
-                            const int R = cx.rtph - NW;
-                            {
+                            for (int ct = 0; ct < CT; ct++) own[sy][0][ct] = (v4d){0., 0., 0., 0.};
+                        const int R = cx.rtph - NW;
+                        {
 #define SOS_GEMM_S(RAYV, FOLDV)                                                                                        \
-    gemm_source_split<RAYV, FOLDV, CT, NW, FS, KHM, (SOS_PRECOMBINE_LDS != 0)>(own, accs, R, wv >> 1, wv & 1, mpa, has_aer != 0, vtp, ufp, cx.ks2h, \
-                                                               cx.rtph, bx, xdel, ydel, lane, wv, cx.prow, pcb, kc)
-                                if (s > 2) SOS_GEMM_S(-1, false);
-                                else if (s & 1) { if (fold) SOS_GEMM_S(1, true); else SOS_GEMM_S(1, false); }
-                                else { if (fold) SOS_GEMM_S(0, true); else SOS_GEMM_S(0, false); }
+    gemm_source_split<RAYV, FOLDV, CT, NW, FS, KHM>(own, accs, R, wv >> 1, wv & 1, mpa, has_aer != 0, vtp, ufp, cx.ks2h,        \
+                                                    cx.rtph, bx, xdel, ydel, lane, wv, cx.prow, pcb, kc)
+                            if (s > 2) SOS_GEMM_S(-1, false);
+                            else if (s & 1) { if (fold) SOS_GEMM_S(1, true); else SOS_GEMM_S(1, false); }
+                            else { if (fold) SOS_GEMM_S(0, true); else SOS_GEMM_S(0, false); }
 #undef SOS_GEMM_S
-                            }
-                            __syncthreads();         // every wave has read the field
-                            PH(2);
-                            const double *xd = (s > 2 && has_aer) ? xdel : nullptr;
-                            write_back_source<1, CT, NW, FS, KHM>(own, cbuf, lane, wv, KH, xd);
-                            write_back_shared<FS, KHM>(accs, R, wv >> 1, wv & 1, cbuf, lane, cx.rtph, xd);
-                            __syncthreads();
-                            combine_shared<NW, FS, KHM, CT * 16>(cbuf, t, NTH, cx.rtph);
-                            __syncthreads();
                         }
-                    }
-                    if (!(SPLIT_OK && split)) {
+                        __syncthreads();         // every wave has read the field
+                        PH(2);
+                        const double *xd = (s > 2 && has_aer) ? xdel : nullptr;
+                        write_back_source<1, CT, NW, FS, KHM>(own, cbuf, lane, wv, KH, xd);
+                        write_back_shared<FS, KHM>(accs, R, wv >> 1, wv & 1, cbuf, lane, cx.rtph, xd);
+                        __syncthreads();
+                        combine_shared<NW, FS, KHM, CT * 16>(cbuf, t, NTH, cx.rtph);
+                        __syncthreads();
+                    } else {
                         if (tile_b) contract(std::integral_constant<int, RTWH>());
                         else if (tile_a) contract(std::integral_constant<int, 1>());
                         else if (fold) __syncthreads();                        // the barrier of the folded projection
@@ -544,9 +522,6 @@ int launch_sos_os(const SosDev &cx, const SosBins &bn, const SolvePlan &pl, hipS
         return SOS_LAUNCH_ZM_SURF(launch_variant, NWV, R, C, bn.nz, bn.jout, cx.imat_surf, cx, bn, pl, st, hip_err);
     V(4, 1, 2) V(4, 2, 2) V(8, 2, 2)
     V(4, 1, 4) V(8, 1, 4)
-#ifdef SOS_WIDE_REGS
-    V(4, 2, 4)
-#endif
 #undef V
     return SOSGPU_E_UNSUPPORTED;
 }

@@ -40,25 +40,16 @@
 #define launch_sos_stream launch_sos_stream_multi
 #endif
 
-#ifndef SOS_STREAM_NT
-#define SOS_STREAM_NT 2
-#endif
-#ifndef SOS_STREAM_TOP_BARRIER
-#define SOS_STREAM_TOP_BARRIER 0   // 1: workgroup barrier between the store pass of a chunk and the staging of the next one
-#endif
-#ifndef SOS_STREAM_PREFETCH
-#define SOS_STREAM_PREFETCH 0      // 1: request chunk c+1 from inside the store pass of chunk c.  Measured 3.4 % SLOWER (21.4 k vs
-                                   // 22.1 k bins/s, profiles/r02_stream_experiments.txt): the per-unit address arithmetic of the
-                                   // requests costs more vector issue than the hidden latency returns.  Kept as an experiment switch.
-#endif
+// aux operand of the LDS-DMA loads of the field (glds_copy): non-temporal, like the stores that write it back
+constexpr int FIELD_LOAD_AUX = 2;
 // COLS levels per chunk, VPAD, the row capacity KHM = skhm(KHT) of the field layout and the sizes of the scratch and of the LDS
 // are those of solve_variant.h.
 
 // Homogeneous part of the up-going field of U levels: P <- P (1 - a), X = Q + P xin (see the header); q, qa move upwards.
 // (bases moved to the low end of the block and pinned: non-negative immediate offsets, see scan_block)
-// KHM > 0: the closed level is stored in parity form at once, X^A = X+ + X- in its own slot and X^B = X+ - X- in the slot of
+// The closed level is stored in parity form at once, X^A = X+ + X- in its own slot and X^B = X+ - X- in the slot of
 // the down-going row with the same index (KHM doubles further): the contraction that follows reads its B operands without
-// forming the sums (SOS_PRECOMBINE_STREAM), and no extra pass or barrier is needed -- every (row, level) of the chunk is closed here
+// forming the sums (gemm_source's PRE), and no extra pass or barrier is needed -- every (row, level) of the chunk is closed here
 // by exactly one thread.
 template <int U, int FS, int NS, int KHM>
 __device__ __forceinline__ void fix_block(lds_f64 *&q, const lds_f64 *&qa, double &P, double xi)
@@ -69,15 +60,12 @@ __device__ __forceinline__ void fix_block(lds_f64 *&q, const lds_f64 *&qa, doubl
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         av[u] = qa[(U - 1 - u) * NS]; qv[u] = q[(U - 1 - u) * FS];
-        if (KHM) xm[u] = q[(U - 1 - u) * FS + KHM];
+        xm[u] = q[(U - 1 - u) * FS + KHM];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) { P = P - P * av[u]; qv[u] = qv[u] + P * xi; }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        if (KHM) { q[(U - 1 - u) * FS] = qv[u] + xm[u]; q[(U - 1 - u) * FS + KHM] = qv[u] - xm[u]; }
-        else q[(U - 1 - u) * FS] = qv[u];
-    }
+    for (int u = 0; u < U; ++u) { q[(U - 1 - u) * FS] = qv[u] + xm[u]; q[(U - 1 - u) * FS + KHM] = qv[u] - xm[u]; }
     qa -= NS;
 }
 
@@ -110,10 +98,8 @@ __device__ __forceinline__ void glds_copy(const double *g, double *l, int units,
 // Workgroups per CU.  The four-tile layout (N <= 21: 42 KB of LDS per workgroup) runs THREE (round 3): 168 instead of 256
 // registers per lane, and the third wave per SIMD hides more latency than the spills cost -- N = 13 / 17 / 21 at NT = 120:
 // 103 / 93 / 81 -> 114 / 103 / 87 k bins/s -- and so does the five-tile layout (N <= 26: 52 KB): N = 25 60.1 -> 65.4 k bins/s
-// (profiles/r03_n_sweep.txt).  SOS_STREAM_3WG_KHT: the widest layout that does.
-#ifndef SOS_STREAM_3WG_KHT
-#define SOS_STREAM_3WG_KHT 5
-#endif
+// (profiles/r03_n_sweep.txt).  STREAM_3WG_KHT: the widest layout that does.
+constexpr int STREAM_3WG_KHT = 5;
 // Output slots (ZM = 2, below): this thread's row at the slots' levels inside the chunk [l0, L] -> XLO / XHI (for the up-going
 // rows the particular part Q; the link pass adds P Xin)
 template <int NTH, int FS>
@@ -150,7 +136,7 @@ __device__ __forceinline__ void lv_step(const SosBins &bn, int b, double *zs, bo
     }
 }
 
-#define SOS_STREAM_MIN_WG(NW, KHT) ((NW) == 4 ? ((COLS == 16 || (KHT) <= SOS_STREAM_3WG_KHT) ? 3 : 2) : 1)
+#define SOS_STREAM_MIN_WG(NW, KHT) ((NW) == 4 ? ((KHT) <= STREAM_3WG_KHT ? 3 : 2) : 1)
 // ZM: output mode as in sos_os.hip -- 0 standard output, 1 one output altitude (ZO), 2 bn.nz output slots.  Mode 2 keeps a
 // slot's two captured levels, the attenuations plo / phi and i3lo / dlo / i3hi / dhi lane-private in bn.zst of the task's
 // work region; the up-going rows' homogeneous part is added from the chunk inflows the link pass leaves in xin.
@@ -455,15 +441,13 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
             for (int chk = 0; chk < nchunk; chk++) {
                 const int l0 = chk * COLS, L = min(l0 + COLS - 1, nt), nlev = L - l0 + 1;
                 // stage the chunk: field of order ig-1 (32 levels; the scratch is zero beyond nt), attenuations of layers
-                // l0-1 .. l0+30, level vectors of levels l0-1 .. l0+38.  In the passes of order >= 2 every chunk but the first
-                // was already requested by the store pass of the chunk before it (below).
-                if (O1 || !SOS_STREAM_PREFETCH || chk == 0) {
+                // l0-1 .. l0+30, level vectors of levels l0-1 .. l0+38.
+                {
                     // No barrier here: the only readers of the chunk buffer after the barrier that precedes the store pass are
                     // the store pass's own reads, and a 16-byte unit is stored and re-requested by the SAME thread (identical
                     // unit mapping in glds_copy and in the store loop); the attenuation / level-vector copies have no reader
                     // left.  The barrier after the staging wait below is the one every wave passes before anything is used.
-                    if (SOS_STREAM_TOP_BARRIER) __syncthreads();
-                    if (!O1) glds_copy<NTH, SOS_STREAM_NT>(fld + (size_t)l0 * FS, cbuf, COLS * FS / 2, t);
+                    if (!O1) glds_copy<NTH, FIELD_LOAD_AUX>(fld + (size_t)l0 * FS, cbuf, COLS * FS / 2, t);
                     glds_copy<NTH, 0>(att + (size_t)l0 * NS, catt, COLS * NS / 2, t);
                     stage_vec(l0);
                 }
@@ -485,14 +469,13 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                         int cnt = up ? L - mid - 1 : (L > l0 ? mid - l0 + 1 : 0);
                         if (cnt < 0) cnt = 0;
                         if (up) {                                       // level L: Q = 0, X = Xin
-                            if (SOS_PRECOMBINE_STREAM) { const double xm = q[KHM]; q[0] = xi + xm; q[KHM] = xi - xm; }
-                            else *q = xi;
+                            const double xm = q[KHM]; q[0] = xi + xm; q[KHM] = xi - xm;
                         }
 #pragma unroll 1
-                        for (; cnt >= 8; cnt -= 8) fix_block<8, FS, NS, SOS_PRECOMBINE_STREAM ? KHM : 0>(q, qa, P, xi);
-                        if (cnt & 4) fix_block<4, FS, NS, SOS_PRECOMBINE_STREAM ? KHM : 0>(q, qa, P, xi);
-                        if (cnt & 2) fix_block<2, FS, NS, SOS_PRECOMBINE_STREAM ? KHM : 0>(q, qa, P, xi);
-                        if (cnt & 1) fix_block<1, FS, NS, SOS_PRECOMBINE_STREAM ? KHM : 0>(q, qa, P, xi);
+                        for (; cnt >= 8; cnt -= 8) fix_block<8, FS, NS, KHM>(q, qa, P, xi);
+                        if (cnt & 4) fix_block<4, FS, NS, KHM>(q, qa, P, xi);
+                        if (cnt & 2) fix_block<2, FS, NS, KHM>(q, qa, P, xi);
+                        if (cnt & 1) fix_block<1, FS, NS, KHM>(q, qa, P, xi);
                     }
                     __syncthreads();
                     PH(1);
@@ -507,8 +490,8 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                     auto contract = [&](auto na_tag) {
                         constexpr int NA = decltype(na_tag)::value;
 #define SOS_GEMM(RAYV, FOLDV)                                                                                          \
-    gemm_source<NA, RAYV, FOLDV, RTWH, CT, NW, FS, KHM, true, (SOS_PRECOMBINE_STREAM != 0)>(acc, mpa, has_aer != 0, vtp, ufp, cx.ks2h, cx.rtph, bx,            \
-                                                        cxdel + 1, cydel + 1, lane, wv, cx.prow, pcb)
+    gemm_source<NA, RAYV, FOLDV, RTWH, CT, NW, FS, KHM, true, true>(acc, mpa, has_aer != 0, vtp, ufp, cx.ks2h, cx.rtph, bx,         \
+                                                                    cxdel + 1, cydel + 1, lane, wv, cx.prow, pcb)
                         if (s > 2) SOS_GEMM(-1, false);
                         else if (s & 1) { if (fold) SOS_GEMM(1, true); else SOS_GEMM(1, false); }
                         else { if (fold) SOS_GEMM(0, true); else SOS_GEMM(0, false); }
@@ -588,25 +571,14 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                 if (!O1) PH(4);
                 // the chunk [Q+ | X-] of this order goes back to the scratch (levels l0..L only).  After the barrier above nobody
                 // reads the attenuation / level-vector copies any more, and each 16-byte unit of the chunk is read here by ONE
-                // thread -- the same one the LDS-DMA mapping gives it to: so the next chunk is requested unit by unit as soon as
-                // this thread has sent the old content on its way, with no barrier in between, and its latency runs behind the
-                // store pass instead of in front of the next contraction.
+                // thread -- the same one the LDS-DMA mapping gives it to, so the staging of the next chunk needs no barrier.
+                // (Requesting the next chunk unit by unit from inside this pass was tried: 3.4 % slower, 21.4 k vs 22.1 k bins/s,
+                // profiles/r02_stream_experiments.txt -- the address arithmetic of the requests costs more vector issue than the
+                // hidden latency returns.)
                 {
-                    const bool pre = SOS_STREAM_PREFETCH && !O1 && chk + 1 < nchunk;
                     const int units = nlev * FS / 2;
                     const v2d *src = reinterpret_cast<const v2d *>(cbuf);
                     v2d *dst = reinterpret_cast<v2d *>(fld + (size_t)l0 * FS);
-                    const double *gnx = fld + (size_t)(l0 + COLS) * FS;
-                    auto fetch = [&](int u) {
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gnx + 2 * (size_t)u),
-                                                         (__attribute__((address_space(3))) void *)(cbuf + 2 * (size_t)(u - (t & 63))), 16, 0,
-                                                         SOS_STREAM_NT);
-                    };
-                    if (pre) {
-                        const int ln = l0 + COLS;
-                        glds_copy<NTH, 0>(att + (size_t)ln * NS, catt, COLS * NS / 2, t);
-                        stage_vec(ln);
-                    }
                     // wave-uniform trip count; global address = scalar base + one of two per-lane 32-bit offsets (the 4 KiB
                     // step between consecutive units of a thread exceeds the immediate range, so odd units use v1 = v0 + 16 NTH
                     // and every second pair a second scalar base): no vector address arithmetic (lane_ptr, sos_dev.h)
@@ -616,11 +588,7 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                     const v2d *sp = src + t;
                     auto put = [&](const v2d &a, char *base, unsigned &vo) {
                         v2d *d = reinterpret_cast<v2d *>(lane_ptr(base, vo));
-#if SOS_STREAM_NT
                         __builtin_nontemporal_store(a, d);
-#else
-                        *d = a;
-#endif
                     };
                     int i = 0;
 #pragma unroll 1
@@ -629,18 +597,15 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
                         size_t o0 = (size_t)i * (NTH * 16), o1 = o0 + 2 * (NTH * 16);
                         asm volatile("" : "+s"(o1));
                         put(a0, db + o0, v0); put(a1, db + o0, v1); put(a2, db + o1, v0); put(a3, db + o1, v1);
-                        if (pre) { fetch(t + i * NTH); fetch(t + (i + 1) * NTH); fetch(t + (i + 2) * NTH); fetch(t + (i + 3) * NTH); }
                     }
 #pragma unroll 1
                     for (; i < full; i++) {
                         const v2d a0 = sp[i * NTH];
                         put(a0, db + (size_t)i * (NTH * 16), v0);
-                        if (pre) fetch(t + i * NTH);
                     }
                     if (t < rem) {
                         const v2d a0 = sp[full * NTH];
                         put(a0, db + (size_t)full * (NTH * 16), v0);
-                        if (pre) fetch(t + full * NTH);
                     }
                 }
                 if (O1) PH(7); else PH(5);
@@ -813,12 +778,7 @@ __global__ __launch_bounds__(64 * NW, SOS_STREAM_MIN_WG(NW, KHT)) void k_sos_str
         if (t == 0) bn.norders[b] = nord;
     }
 #ifdef SOS_PROFILE_PHASES
-    // SOS_PHASE_ROLE = 1 / 2: stamps of the up-going / down-going waves only (diagnostic: skew between the two halves)
-#ifndef SOS_PHASE_ROLE
-#define SOS_PHASE_ROLE 0
-#endif
-    if (bn.phase && lane == 0 && (SOS_PHASE_ROLE == 0 || (SOS_PHASE_ROLE == 1) == up))
-        for (int k = 0; k < 8; k++) atomicAdd(&bn.phase[(size_t)b * 8 + k], ph_acc[k]);
+    if (bn.phase && lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&bn.phase[(size_t)b * 8 + k], ph_acc[k]);
 #endif
     return finished;
     };   // run_task

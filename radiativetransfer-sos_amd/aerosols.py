@@ -52,7 +52,7 @@ def _round_sig(x, sig):
 def mie_angles(nb_gauss):
     """Mie angle set without user angles: positive Gauss nodes of the 2 nb_gauss-point rule, ascending, as re-read from
     Aer_UsedAngles.txt (D21.14).  Returns xmu[-N:N], xhr[-N:N] as arrays of 2N+1 (index j + N; entry N unused = 0)."""
-    from .run_sos import sos_gauss
+    from .geometry import sos_gauss
     x, w = sos_gauss(nb_gauss)                             # the reference's own Gauss-Legendre routine (SOS_ANGLES.F:1022)
     mu, wt = _round_sig(x, 14), _round_sig(w, 14)
     n = nb_gauss

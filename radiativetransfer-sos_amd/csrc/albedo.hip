@@ -2,7 +2,7 @@
 //
 // Per bin, S = 2 sum_j ga_j mu_j A_j, where A_j is the up-going flux EPLUS at the lit boundary of an order-0 solve over a
 // black ground with incidence mu_j.  sosgpu_trans_spectrum (trans.hip) queues exactly those solves and keeps the other flux;
-// sosgpu_albedo_spectrum (api.hip) shares its child table (k_trans_table, k_trans_sv) and differs in the items:
+// sosgpu_albedo_spectrum (api_solve.hip) shares its child table (k_trans_table, k_trans_sv) and differs in the items:
 //   k_albedo_items  k_trans_items, and with from_below the profile rows of every item MIRRORED in the vertical about the
 //                   item's own nt -- the atmosphere lit from the ground, which is the S of the coupling formula
 //                   rho_toa = rho_path + T_down T_up rho_s / (1 - S rho_s); items of weight-0 directions (the inserted solar

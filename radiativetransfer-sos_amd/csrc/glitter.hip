@@ -4,7 +4,7 @@
 // temporary files:
 //   SOS_GSF          (SOS_GLITTER.F:451-711)  wave-facet azimuth quadrature, one Fourier series per angle pair
 //   SOS_MAT_FRESNEL  (SOS_SURFACE.F:1235-1603) Legendre expansion of the Fresnel matrix -- O(N*OS_NS) work with a
-//                    4(E15.8) TEXT round trip: done on the host in api.hip (host_mat_fresnel), bit for bit
+//                    4(E15.8) TEXT round trip: done on the host in api_surface.hip (sosgpu_mat_fresnel_host), bit for bit
 //   SOS_MAT_REFLEXION + SOS_NOYAUX_FRESNEL (SOS_SURFACE.F:1708-1973, 2029-2227)  per-pair Fourier matrices
 //   SOS_MISE_FORMAT  (SOS_SURFACE.F:2307-2443) re-layout into per-order N x N REAL*4 matrices (81 re-reads of
 //                    a 12 MB file in the reference; here it is just the store index)

@@ -265,7 +265,7 @@ __device__ double scan_first_wave(double tr, double hr, double ta, double ha, co
 // aerosols, the shares of the two in every layer.  One wavefront, all lanes in lockstep on the same values (stores of one
 // instruction go to one address), SOS_DISC by the 64 lanes (disc_wave).  Rounds 1-2 ran this loop on the host inside
 // sosgpu_profile -- NT x 25 bisection steps x 2 exp, 0.3-0.4 ms of every wavelength of a spectrum plus a waited-for upload;
-// the level count and the two steps are closed forms of (TR, TA) and stay there (api.hip, profile_nogas_grid).
+// the level count and the two steps are closed forms of (TR, TA) and stay there (api_atmosphere.hip, profile_nogas_grid).
 //   z, h, pca, pcm [nt + 1]: altitude, cumulative optical depth, aerosol and molecular share of the layer ending at the level
 // (the body is shared by k_profile_nogas and the table form k_profile_nogas_table: one statement sequence, one result)
 __device__ __forceinline__ void profile_nogas_body(double tr, double hr, double ta, double ha, int nt, double t_first,

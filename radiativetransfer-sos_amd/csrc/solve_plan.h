@@ -1,6 +1,6 @@
 // csrc/solve_plan.h -- launch form and scratch layout of the fused solver, stated once (host only).
-// os_solve_impl (api.hip) follows the plan; sosgpu_debug_solve_plan reports it.  Nothing here calls HIP, reads the environment
-// or touches a context: the plan is a function of the problem shape and of the overrides api.hip has read.  The kernel variant
+// os_solve_impl (api_solve.hip) follows the plan; sosgpu_debug_solve_plan reports it.  Nothing here calls HIP, reads the environment
+// or touches a context: the plan is a function of the problem shape and of the overrides api_solve.hip has read.  The kernel variant
 // in it is solve_variant's (solve_variant.h), which the launchers follow.
 #pragma once
 #include "solve_variant.h"

@@ -1,6 +1,6 @@
 // csrc/solve_variant.h -- which instantiation of the fused solver runs for a problem, and the sizes that go with it, stated
 // once.  The capacity formulas are shared with the kernels (sos_dev.h includes this file); solve_variant() is host only, calls
-// no HIP and reads no environment: it is a function of the problem shape and of the switches api.hip has read.  solve_plan
+// no HIP and reads no environment: it is a function of the problem shape and of the switches api_solve.hip has read.  solve_plan
 // (solve_plan.h) builds on it, sosgpu_debug_solve_plan reports it, and the launchers of sos_os.hip / sos_stream.hip dispatch
 // on what it says -- they refuse a context it does not fit, they do not choose.
 #pragma once

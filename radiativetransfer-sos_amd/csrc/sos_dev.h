@@ -614,7 +614,7 @@ __device__ __forceinline__ void write_back_source(const v4d (&acc)[2][RTWH][CT],
 // are four row quads of one 16-row tile, the vector is broadcast to the four columns, so an instruction does 64 useful
 // multiply-adds in a quarter of the time the 16 x 16 x 4 form needs for the same 64.  Operand layout (probed on gfx950,
 // scripts/probe_mfma4x4.hip): A[blk][i][k] in lane i + 4 blk + 16 k, B[blk][k][j] in lane j + 4 blk + 16 k,
-// D[blk][i][j] in lane j + 4 blk + 16 i.  Packed operator (api.hip k_pack_ground):
+// D[blk][i][j] in lane j + 4 blk + 16 i.  Packed operator (api_operators.hip k_pack_ground):
 //   gp[((tile * KS2H + m) * 64 + lane) * 2 + e] = G[tile*16 + 4 ((lane>>2)&3) + (lane&3)][8 m + 4 e + (lane>>4)]
 // Wave w does row tiles {w, w + NW}; gndk = ground vector in half-system order (LDS); the lanes of column 0 publish bcv.
 template <int NA, int NW>

@@ -5,7 +5,7 @@
 // touch the solar slot, so those of order 0 are the wavelength's; what changes is the solar cosine and with it the order-1
 // source vectors, which need the solar column of P, R, T (c = -mu_J) next to the table columns +-1..N of order 0.
 //
-// sosgpu_trans_spectrum (api.hip) therefore makes every (context, direction) pair a CHILD entry of a device context table
+// sosgpu_trans_spectrum (api_solve.hip) therefore makes every (context, direction) pair a CHILD entry of a device context table
 // and every (bin, direction) pair an ITEM of one multi-wavelength solve:
 //   k_trans_table   child entries: the parent's with n0 = J, mus = mu[J-1], smax = 0, ro = 0, no surface, its own sv
 //   k_trans_sv      sv[4][kp] of every child, by the statements of noyaux.hip (noyaux_dev.h): the same bits as the tables of

@@ -26,6 +26,18 @@ def test_version_and_errors(pkg):
     assert L.sosgpu_strerror(-3)
 
 
+def test_error_slot_is_shared_between_units(pkg):
+    """The C ABI layer is several translation units with ONE error slot (csrc/api_internal.h): what an entry point records
+    is what sosgpu_last_hip_error reads.  Without a GPU sosgpu_device_count fails inside the HIP runtime and says so."""
+    import pytest
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is visible: sosgpu_device_count succeeds and records nothing")
+    L = pkg.capi.lib()
+    assert L.sosgpu_device_count() == -4          # SOSGPU_E_NODEVICE
+    assert L.sosgpu_last_hip_error() != 0
+
+
 def test_create_rejects_bad_arguments(pkg):
     """Validation happens before any device work; without a GPU the only other outcome is NODEVICE."""
     L = pkg.capi.lib()

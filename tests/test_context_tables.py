@@ -1,5 +1,5 @@
 """Oracle and edge sweep of the per-wavelength context tables: what k_gsf, k_pack, k_pack_ray, k_sv (csrc/noyaux.hip) and
-k_pack_ground (csrc/api.hip) build once per wavelength and every solve then reads as given -- prt, mp_aer, mp_vt, mp_uf, sv,
+k_pack_ground (csrc/api_operators.hip) build once per wavelength and every solve then reads as given -- prt, mp_aer, mp_vt, mp_uf, sv,
 mp_gnd, rdir -- fetched with SosContext.debug_tables (sosgpu_debug_tables).
 
 The bar.  Nothing is compared with a tolerance except two things that have a derived one:
@@ -22,7 +22,7 @@ Finding of this sweep: the molecular order-1 vectors sv[1], sv[3] multiplied the
 SOS_FSOURCE_ORDRE1 / SOS_FSOURCE_DIFF_FRESNEL1 write them (gamma2*P(0)*R(j) for the reference's gamma2*R(j)*P(0), ...), one ulp
 off in 142 of the 738 entries of sv[1] at N = 41 (e.g. -0x1.3a283042a2856p-5 for -0x1.3a283042a2855p-5, Q of s = 1 at
 mu = 0.99422754096569); k_sv now follows the reference term by term.
-Second finding: k_pack_ground fused the Lambertian term into the BRDF term (api.hip is compiled with contraction on): 31 of
+Second finding: k_pack_ground fused the Lambertian term into the BRDF term (its unit, now api_operators.hip, is compiled with contraction on): 31 of
 the 240 weighted I<-I entries of gnd_n16 (ro = 0.3, s = 0) were one ulp off the plain evaluation; the kernel now runs with
 contraction off.
 """
@@ -670,7 +670,7 @@ def test_tables_vs_oracle(gpu_pkg, oracle, name):
 
 
 def _size_class(nbytes):
-    """Size classes of the table pool (api.hip): 256 B steps up to 4 KiB, then eighths of the leading power of two."""
+    """Size classes of the table pool (api_mem.hip): 256 B steps up to 4 KiB, then eighths of the leading power of two."""
     if nbytes <= 4096:
         return (max(nbytes, 1) + 255) // 256 * 256
     step = (1 << (nbytes.bit_length() - 1)) >> 3

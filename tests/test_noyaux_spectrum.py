@@ -1,5 +1,5 @@
 """The operator tables of many contexts in one call (sosgpu_noyaux_spectrum, solver.build_operators): the table forms
-k_gsf_table, k_pack_table, k_pack_ray_table, k_sv_table (csrc/noyaux.hip) and k_pack_ground_table (csrc/api.hip) against the
+k_gsf_table, k_pack_table, k_pack_ray_table, k_sv_table (csrc/noyaux.hip) and k_pack_ground_table (csrc/api_operators.hip) against the
 per-context calls bit for bit and against the oracle, on batches that mix every size, next to other contexts' tables on
 recycled pool blocks, the refusals of the entry point, and the wiring into run_sos.sos_spectrum / sos_spectrum_levels (call
 counts, outputs).

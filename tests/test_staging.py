@@ -1,4 +1,4 @@
-"""The pinned staging path of the table-form entry points (the Staged blocks of csrc/api.hip, counted by
+"""The pinned staging path of the table-form entry points (the Staged blocks of csrc/api_mem.hip, counted by
 sosgpu_debug_stage_blocks): the number of blocks stays bounded on a living context, a block is not reused before its copy has
 passed on a backlogged stream, no context owns a block, a refused call takes none, and sosgpu_trim frees the idle ones."""
 import ctypes as C

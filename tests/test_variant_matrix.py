@@ -405,7 +405,7 @@ def _poison_scratch(pkg, cx):
 @pytest.mark.parametrize("batch", UNREAD_BATCHES, ids=_batch_id)
 def test_results_ignore_pad_levels_and_stale_scratch(gpu_pkg, monkeypatch, batch):
     """Levels NT+1 ... lp-1 of every bin hold NaN: the records are bit for bit those of the zero-padded upload.  Streamed
-    layouts: after a solve, the scratch (reused from solve to solve without clearing, csrc/api.hip) is overwritten with NaN
+    layouts: after a solve, the scratch (reused from solve to solve without clearing, csrc/api_solve.hip) is overwritten with NaN
     bytes and the next solve is again bit for bit the clean one -- in the default and the one-workgroup-per-bin form."""
     b = make_batch(*batch)
     rows = range(len(b["bins"]))

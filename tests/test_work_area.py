@@ -28,7 +28,7 @@ COUNTS = (0, 1, 2, 7, 64)
 def test_queries_equal_the_sizes_the_parent_stated(pkg):
     """solver.build_operators: n * (sosgpu_ctx_table_entry_bytes() + 8); solver._ckd_launch: nwl * sosgpu_ckd_table_entry_bytes()
     + 8 * nslots; solver.make_profiles_spectrum: nwl * 4 * ng doubles of no-gas blocks, then -(-nwl * entry // 8) doubles of
-    table; api.hip: njobs * sizeof(TrphiJobDev), njobs * sizeof(FluxJobDev).  A zero (or negative) count gives 0."""
+    table; api_outputs.hip: njobs * sizeof(TrphiJobDev), njobs * sizeof(FluxJobDev).  A zero (or negative) count gives 0."""
     L = pkg.capi.lib()
     assert L.sosgpu_ctx_table_entry_bytes() == CTX_ENTRY
     for n in COUNTS:

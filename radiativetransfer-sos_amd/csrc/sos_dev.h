@@ -108,10 +108,23 @@ __device__ __forceinline__ bool conv_exceeds(double a, double d, double g, doubl
     }
     return false;
 }
-// SOS_AJOUT_QUEUE (SOS_OS.F:3959-3975): g / (1 - g/d) = g d / (d - g)
+// SOS_AJOUT_QUEUE (SOS_OS.F:3959-3975): g / (1 - g/d) = g d / (d - g).  The product is of degree two in the operands: the
+// down-going rows at the ground of a bin of total depth ~400 on 48 or more levels are 1e-171 and less, g d underflowed to 0
+// and the geometric tail of the series was dropped where the reference adds it -- EMOINS and the down half of the record
+// 3e-4 off (tests/test_deep_bins.py).  A product below 1e-200 of a non-zero g is therefore formed again on the operands times
+// one power of two and the quotient scaled back (exact both ways).  Above that nothing has underflowed and every result keeps
+// its bits; a product that is small because g alone is small gets the bits of the plain form from the scaled one.
 __device__ __forceinline__ double queue_term(double d, double g)
 {
-    return (d == 0.) ? 0. : (g * d) / (d - g);
+    if (d == 0.) return 0.;
+    const double p = g * d;
+    if (fabs(p) < 1e-200 && g != 0.) {
+        int e;
+        (void)frexp(fmax(fabs(d), fabs(g)), &e);
+        const double ds = ldexp(d, -e), gs = ldexp(g, -e);
+        return ldexp((gs * ds) / (ds - gs), e);
+    }
+    return p / (d - g);
 }
 
 // Field storage convention: half-system order kk = c*N + (k-1) in both direction halves, and the U component of the

@@ -610,8 +610,9 @@ int  sosgpu_last_solve_ms(sosgpu_ctx *cx, float *ms);
  * d_jout[nb] / d_zz[nb] (NULL when zout = -1), d_scal[nb][4] = {0, TTOT_TRONC, TTOT_VRAI, TAUOUT} (the layout
  * sosgpu_aggregate takes).  The no-gas profile of the wavelength (SOS_PROFIL.F:349-489) is made by one wavefront queued on
  * `stream` in front of the bins' kernel, or taken from d_nogas (sosgpu_profile_nogas below); nothing is waited for (a second call on the same context from ANOTHER stream first
- * waits for the context's earlier work).  IPROFIL = 2 (aerosol layer between two altitudes) is not implemented
- * (the reference's branch reads an unassigned Hmol(0), its output is not reproducible). */
+ * waits for the context's earlier work).  IPROFIL = 2 (aerosol layer between two altitudes) is made by
+ * sosgpu_profile_layer / sosgpu_profile_layer_spectrum below.  (The reference's branch reads Hmol(0) before it assigns it;
+ * they start its recurrence from Hmol(0) = 0, the value on a fresh stack.) */
 int  sosgpu_profile(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, double ha, int absprofil,
                     int nblev, const double *d_altabs, const double *d_tabs,
                     double a_tronc, double piz, double piztr, double zout, int lp,
@@ -691,6 +692,42 @@ int  sosgpu_profile_spectrum_true(int device, int nwl, const sosgpu_profile_wl *
                                   void *d_work, size_t work_bytes, double *d_tabs, double *d_prof, int32_t *d_nt,
                                   int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
                                   int *bad_wl, double *d_hvrai, void *stream);
+
+/* SOS_PROFILE for IPROFIL = 2 (src/SOS_PROFIL.F:800-946): a homogeneous layer of aerosols and molecules between zmin and zmax
+ * (km) inside a molecular atmosphere, without gas absorption (the reference refuses the combination).  The recurrence
+ * Hmol(I) = Hmol(I-1) + VR_SC of the reference reads Hmol(0) before it is assigned; it starts from Hmol(0) = 0 here, the value
+ * on a fresh stack, and Hmol(0) = TR exp(-120 / HR) is assigned afterwards, as there.
+ *
+ * sosgpu_profile_layer_grid: the level counts, host arithmetic (no device): counts = {NT, sublayers above the layer, inside
+ * it, below it (0 for zmin = 0)}.  Returns NT (<= CTE_OS_NT), SOSGPU_E_ARG unless 0 <= zmin < zmax (and tr, hr > 0, ta >= 0),
+ * SOSGPU_E_UNSUPPORTED when the layer gets no sublayer or less than 1e-5 of aerosol per sublayer (the reference's ERROR 1020).
+ *
+ * sosgpu_profile_layer: one bin, by one wavefront; tr, hr, ta, a_tronc, piz, piztr, zout, lp and the outputs as
+ * sosgpu_profile_true with nb = 1 (d_hvrai NULL allowed; d_jout / d_zz are written when zout != -1 only and may be NULL
+ * otherwise).  What follows the level placement -- round trip, rescale, IBORM, output level, d_scal -- is the device code of
+ * sosgpu_profile.  The refusals of the grid are returned before anything is queued; a profile that does not fit lp
+ * (lp <= NT) comes back with nt = -1.  Asynchronous on `stream`; nothing is waited for.
+ *
+ * sosgpu_profile_layer_spectrum: nwl such bins, one per entry of wl (HOST), in ONE launch of the same device code: bin w has
+ * the bits sosgpu_profile_layer gives for wl[w] on a context with iborm_max = smax.  No context is needed.
+ *   d_work, work_bytes   see "Work areas": the per-wavelength table, sosgpu_profile_layer_spectrum_work_bytes(nwl) bytes
+ *   outputs              for the nwl bins, as sosgpu_profile_spectrum_true; d_jout / d_zz are written for wavelengths with
+ *                        zout != -1 only (both may be NULL when no wavelength has one)
+ * A wavelength the grid refuses, or with smax < 0, is reported in *bad_wl (NULL allowed; -1 = none) with the grid's code and
+ * nothing is queued.  Asynchronous on `stream`; the work area stays allocated until the kernel has run. */
+typedef struct sosgpu_layer_wl {
+    double tr, hr, ta, zmin, zmax;
+    double a_tronc, piz, piztr, zout;
+    int32_t smax, reserved;
+} sosgpu_layer_wl;
+int  sosgpu_profile_layer_grid(double tr, double hr, double ta, double zmin, double zmax, int32_t counts[4]);
+int  sosgpu_profile_layer(sosgpu_ctx *cx, double tr, double hr, double ta, double zmin, double zmax, double a_tronc,
+                          double piz, double piztr, double zout, int lp, double *d_prof, int32_t *d_nt, int32_t *d_iborm,
+                          double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal, double *d_hvrai, void *stream);
+size_t sosgpu_profile_layer_spectrum_work_bytes(int nwl);
+int  sosgpu_profile_layer_spectrum(int device, int nwl, const sosgpu_layer_wl *wl, int lp, void *d_work, size_t work_bytes,
+                                   double *d_prof, int32_t *d_nt, int32_t *d_iborm, double *d_zprof, int32_t *d_jout,
+                                   double *d_zz, double *d_scal, double *d_hvrai, int *bad_wl, void *stream);
 
 /* Replaces the calls `CALL COEFF_ABS_CKD` of SOS_ABSPROFILE's gas and layer loops (src/SOS_ABSPROFILE.F:325-353; the routine:
  * src/SOS_SUB_TRS.F:171-393) for MANY wavelengths in one launch: k_i of every (gas, exponential term) table of every

@@ -6,6 +6,8 @@ raises at first use, loudly.  Build it with `python -m <pkg>.build` / __graft_en
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SOSGPU_LIB selects an alternative build of the same library (A/B experiments); default = in-tree libsosgpu.so
 SO_PATH = os.environ.get("SOSGPU_LIB") or os.path.join(HERE, "libsosgpu.so")
@@ -32,6 +34,7 @@ EXPORTS = [
     "sosgpu_albedo_spectrum", "sosgpu_albedo_spectrum_work_bytes", "sosgpu_albedo_band",
     "sosgpu_level_absorption", "sosgpu_level_irradiance",
     "sosgpu_debug_order0_kpairs", "sosgpu_debug_ctx_order0_kpairs",
+    "sosgpu_profile_layer_grid", "sosgpu_profile_layer", "sosgpu_profile_layer_spectrum", "sosgpu_profile_layer_spectrum_work_bytes",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -57,6 +60,17 @@ class ProfileWl(C.Structure):
                 ("a_tronc", C.c_double), ("piz", C.c_double), ("piztr", C.c_double), ("zout", C.c_double),
                 ("xk_off", C.c_int64), ("ro_off", C.c_int64), ("alt_off", C.c_int64),
                 ("nterm", C.c_int32), ("nbins", C.c_int32), ("absprofil", C.c_int32), ("smax", C.c_int32)]
+
+
+class LayerWl(C.Structure):
+    """sosgpu_layer_wl (include/sosgpu.h): one wavelength of sosgpu_profile_layer_spectrum."""
+    _fields_ = [("tr", C.c_double), ("hr", C.c_double), ("ta", C.c_double), ("zmin", C.c_double), ("zmax", C.c_double),
+                ("a_tronc", C.c_double), ("piz", C.c_double), ("piztr", C.c_double), ("zout", C.c_double),
+                ("smax", C.c_int32), ("reserved", C.c_int32)]
+
+
+LAYER_WL_DTYPE = np.dtype(LayerWl)       # sosgpu_layer_wl as a numpy record
+LAYER_ENTRY_BYTES = 96                   # sosgpu_profile_layer_spectrum_work_bytes(n) = n * this: the entry with its level grid
 
 
 class CkdWl(C.Structure):
@@ -226,6 +240,14 @@ def lib():
                                               vp, vp, vp, vp, C.POINTER(i32), vp]
         L.sosgpu_profile_spectrum_true.restype = i32
         L.sosgpu_profile_spectrum_true.argtypes = L.sosgpu_profile_spectrum.argtypes[:-1] + [vp, vp]
+        L.sosgpu_profile_layer_grid.restype = i32
+        L.sosgpu_profile_layer_grid.argtypes = [dbl, dbl, dbl, dbl, dbl, C.POINTER(i32)]
+        L.sosgpu_profile_layer.restype = i32
+        L.sosgpu_profile_layer.argtypes = [vp] + [dbl] * 9 + [i32] + [vp] * 9
+        L.sosgpu_profile_layer_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_profile_layer_spectrum_work_bytes.argtypes = [i32]
+        L.sosgpu_profile_layer_spectrum.restype = i32
+        L.sosgpu_profile_layer_spectrum.argtypes = [i32, i32, vp, i32, vp, C.c_size_t] + [vp] * 8 + [C.POINTER(i32), vp]
         L.sosgpu_ckd_layer_tables_work_bytes.restype = C.c_size_t
         L.sosgpu_ckd_layer_tables_work_bytes.argtypes = [i32, i32]
         L.sosgpu_ckd_layer_tables.restype = i32

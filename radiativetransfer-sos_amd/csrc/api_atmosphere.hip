@@ -25,7 +25,106 @@ int profile_nogas_grid(double tr, double ta, double *t_first, double *t_layer)
     if (nt > kOsNt || !(ttot > 0.)) return -1;
     return nt;
 }
+
+// The device entry of one layer profile: the caller's parameters and the grid of sosgpu_profile_layer_grid; its status.
+int layer_entry(double tr, double hr, double ta, double zmin, double zmax, double a_tronc, double piz, double piztr, double zout,
+                int smax, LayerWl *t)
+{
+    int32_t c[4];
+    const int nt = sosgpu_profile_layer_grid(tr, hr, ta, zmin, zmax, c);
+    if (nt < 0) return nt;
+    t->tr = tr; t->hr = hr; t->ta = ta; t->zmin = zmin; t->zmax = zmax;
+    t->a_tronc = a_tronc; t->piz = piz; t->piztr = piztr; t->zout = zout;
+    t->smax = smax; t->nt = c[0]; t->c1 = c[1]; t->c2 = c[2]; t->c3 = c[3]; t->pad = 0;
+    return SOSGPU_OK;
+}
 }  // namespace
+
+// Level counts of the aerosol-layer profile (SOS_PROFIL.F:800-870): closed forms of the five parameters, host arithmetic with the
+// C library's exp, so that they are the integers of the Python restatement (geometry.layer_grid).
+#pragma clang fp contract(off)
+extern "C" int sosgpu_profile_layer_grid(double tr, double hr, double ta, double zmin, double zmax, int32_t counts[4])
+{
+    if (!counts || !(hr > 0.) || !(tr > 0.) || !(ta >= 0.)) return SOSGPU_E_ARG;
+    if (!(zmin >= 0.0) || !(zmax > zmin)) return SOSGPU_E_ARG;             // 0 <= Zmin < Zmax
+    const double ttot = tr + ta;
+    const double q = ttot / kTcouche;
+    const int nt = q >= (double)kOsNt ? kOsNt : (int)q;
+    const double dzt = (double)0.010f;                                     // CTE_DZTRANSI
+    const double vr_c1 = tr * exp(-(zmax + dzt) / hr);
+    double vr_c3 = 0.;
+    int nb_tr = 1;
+    if (zmin != 0.0) { vr_c3 = tr * (1.0 - exp(-(zmin - dzt) / hr)); nb_tr = 2; }
+    const int c1 = std::max(3, (int)((nt - nb_tr) * vr_c1 / (tr + ta)));   // CTE_PROFIL_MIN_NBC = 3
+    const int c3 = zmin == 0.0 ? 0 : std::max(3, (int)((nt - nb_tr) * vr_c3 / (tr + ta)));
+    const int c2 = (nt - nb_tr) - c1 - c3;
+    if (c2 <= 0 || (ta / c2) < (double)0.00001f) return SOSGPU_E_UNSUPPORTED;   // not enough sublayers (ERROR 1020)
+    counts[0] = nt; counts[1] = c1; counts[2] = c2; counts[3] = c3;
+    return nt;
+}
+
+extern "C" int sosgpu_profile_layer(sosgpu_ctx *cx, double tr, double hr, double ta, double zmin, double zmax, double a_tronc,
+                                    double piz, double piztr, double zout, int lp, double *d_prof, int32_t *d_nt,
+                                    int32_t *d_iborm, double *d_zprof, int32_t *d_jout, double *d_zz, double *d_scal,
+                                    double *d_hvrai, void *stream)
+{
+    if (!cx || lp < 2 || !d_prof || !d_nt || !d_iborm || !d_zprof || !d_scal) return SOSGPU_E_ARG;
+    if ((d_jout == nullptr) != (d_zz == nullptr) || (zout != -1.0 && !d_jout)) return SOSGPU_E_ARG;
+    LayerArgs q;
+    if (const int rc = layer_entry(tr, hr, ta, zmin, zmax, a_tronc, piz, piztr, zout, 0, &q.one)) return rc;
+    q.one.smax = cx->d.smax;
+    HIPCHK(hipSetDevice(cx->device));
+    hipStream_t st = (hipStream_t)stream;
+    q.nb = 1; q.lp = lp; q.tab = nullptr;
+    q.prof = d_prof; q.zprof = d_zprof; q.zz = d_zz; q.scal = d_scal; q.nt = d_nt; q.iborm = d_iborm; q.jout = d_jout;
+    q.hvrai = d_hvrai;
+    launch_profile_layer(q, st);
+    HIPCHK(hipGetLastError());
+    note_stream(cx, st);
+    return SOSGPU_OK;
+}
+
+// work area: the per-wavelength table
+extern "C" size_t sosgpu_profile_layer_spectrum_work_bytes(int nwl)
+{
+    static_assert(sizeof(LayerWl) % 8 == 0, "entries of doubles and int32 pairs");
+    return nwl < 1 ? 0 : (size_t)nwl * sizeof(LayerWl);
+}
+
+extern "C" int sosgpu_profile_layer_spectrum(int device, int nwl, const sosgpu_layer_wl *wl, int lp, void *d_work, size_t work_bytes,
+                                             double *d_prof, int32_t *d_nt, int32_t *d_iborm, double *d_zprof, int32_t *d_jout,
+                                             double *d_zz, double *d_scal, double *d_hvrai, int *bad_wl, void *stream)
+{
+    if (bad_wl) *bad_wl = -1;
+    if (nwl < 1 || !wl || lp < 2) return SOSGPU_E_ARG;
+    const size_t need = sosgpu_profile_layer_spectrum_work_bytes(nwl);
+    if (!work_area_ok(d_work, work_bytes, need)) return SOSGPU_E_ARG;
+    if (!d_prof || !d_nt || !d_iborm || !d_zprof || !d_scal) return SOSGPU_E_ARG;
+    if ((d_jout == nullptr) != (d_zz == nullptr)) return SOSGPU_E_ARG;
+    // --- the rules of sosgpu_profile_layer, per wavelength, before anything is queued
+    std::vector<LayerWl> tab((size_t)nwl);
+    for (int w = 0; w < nwl; w++) {
+        const sosgpu_layer_wl &s = wl[w];
+        if (bad_wl) *bad_wl = w;
+        if (s.smax < 0 || (s.zout != -1.0 && !d_jout)) return SOSGPU_E_ARG;
+        if (const int rc = layer_entry(s.tr, s.hr, s.ta, s.zmin, s.zmax, s.a_tronc, s.piz, s.piztr, s.zout, s.smax, &tab[w])) return rc;
+    }
+    if (bad_wl) *bad_wl = -1;
+    if (const int rc = use_device(device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    Staged s(device, need);
+    if (s.rc) return s.rc;
+    memcpy(s.host(), tab.data(), need);
+    HIPCHK(s.send(d_work, st));
+    LayerArgs q;
+    memset(&q.one, 0, sizeof q.one);
+    q.nb = nwl; q.lp = lp; q.tab = static_cast<const LayerWl *>(d_work);
+    q.prof = d_prof; q.zprof = d_zprof; q.zz = d_zz; q.scal = d_scal; q.nt = d_nt; q.iborm = d_iborm; q.jout = d_jout;
+    q.hvrai = d_hvrai;
+    launch_profile_layer(q, st);
+    HIPCHK(hipGetLastError());
+    return SOSGPU_OK;
+}
 
 extern "C" int sosgpu_profile_true(sosgpu_ctx *cx, int nb, double tr, double hr, double ta, double ha, int absprofil,
                                    int nblev, const double *d_altabs, const double *d_tabs,

@@ -225,6 +225,21 @@ void launch_profile_nogas_table(const ProfileWl *d_tab, int nwl, double *d_ng, i
 void launch_absprofile_table(const ProfileWl *d_tab, int nwl, const int32_t *d_wl_of_bin, int nb, int nlev, const int32_t *d_ik,
                              const double *d_gas, double *d_tabs, hipStream_t st);
 void launch_profile_table(const ProfileTableArgs &q, hipStream_t st);
+// Aerosol-layer profile (IPROFIL = 2, profile.hip k_profile_layer): one wavefront per bin, a bin being one wavelength.  The
+// level counts are the host's (sosgpu_profile_layer_grid): nt = nb_tr + c1 + c2 + c3 with nb_tr = 1 (zmin = 0, c3 = 0) or 2.
+struct LayerWl {
+    double tr, hr, ta, zmin, zmax, a_tronc, piz, piztr, zout;
+    int smax, nt, c1, c2, c3, pad;
+};
+struct LayerArgs {
+    int nb, lp;
+    const LayerWl *tab;                          // [nb] (table form), or null: the one bin is `one`
+    LayerWl one;
+    double *prof, *zprof, *zz, *scal;            // outputs as ProfileArgs; jout / zz written for bins with zout != -1 only
+    int32_t *nt, *iborm, *jout;
+    double *hvrai;
+};
+void launch_profile_layer(const LayerArgs &q, hipStream_t st);
 // output levels of nz altitudes (profile.hip k_output_levels): jout / zz / tauout[nz][nb] from zprof[nb][lp], prof[nb][3][lp], nt[nb]
 struct OutputLevelArgs {
     int nb, lp, nz;

@@ -596,6 +596,97 @@ void launch_profile(const ProfileArgs &a, hipStream_t st)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// SOS_PROFILE for IPROFIL = 2 (SOS_PROFIL.F:800-946): a homogeneous layer of aerosols and molecules between ZMIN and ZMAX
+// inside a molecular atmosphere, no gas.  Three zones of sublayers -- c1 of equal molecular depth above ZMAX + 10 m, c2 of equal
+// height inside the layer, c3 of equal molecular depth below ZMIN - 10 m (none for a layer on the ground) -- whose counts are
+// closed forms the host evaluates (sosgpu_profile_layer_grid).  The reference's recurrence Hmol(I) = Hmol(I-1) + VR_SC starts
+// from an Hmol(0) it assigns afterwards; as on a fresh stack, it starts from 0 here.
+// One wavefront.  The serial chains keep the reference's order, all lanes in lockstep on the same values (stores of one
+// instruction go to one address): the repeated sums of zones 1 and 3, Z = Z - DELTA_Z through the layer, Haer(I) = Haer(I-1) + ...
+// What depends on one level alone -- the exponential of a level of the layer, the aerosol increment, the closing pass with its
+// logarithm and shares -- is dealt to the lanes, level i to lane i mod 64.
+//   z, h, pca, pcm [nt + 1]: the block profile_bin_body takes in place of the no-gas profile;  hm, ha [nt + 1]: Hmol, Haer
+// (all six rows in LDS; z and h carry the layer's altitudes and increments until the closing pass overwrites them)
+// ---------------------------------------------------------------------------------------------------------------------
+#define SOS_LAYER_ROW 601         // CTE_OS_NT + 1 levels
+__device__ __forceinline__ void profile_layer_body(double tr, double hr, double ta, double zmin, double zmax, int nt, int c1, int c2,
+                                                   int c3, double *z, double *h, double *pca, double *pcm, double *hm, double *ha)
+{
+    const double TOA = 120.0, DZT = (double)0.010f;                  // CTE_DZTRANSI
+    const int lane = threadIdx.x & 63;
+    const int i1 = c1 + 1, i2 = c1 + c2 + 1, i3 = c1 + c2 + 2;       // top and bottom level of the layer, level at ZMIN - 10 m
+    const double vr_c1 = tr * exp(-(zmax + DZT) / hr);
+    const double vr_c2 = tr * (exp(-zmin / hr) - exp(-(zmax + DZT) / hr));
+    hm[0] = 0.; ha[0] = 0.;
+    double vr_sc = vr_c1 / c1, acc = 0.;
+    for (int i = 1; i <= c1; i++) { acc = acc + vr_sc; hm[i] = acc; }
+    hm[i1] = tr * exp(-zmax / hr);
+    const double delta_z = (zmax - zmin) / c2;
+    double zc = zmax;
+    for (int i = i1 + 1; i <= i2; i++) { zc = zc - delta_z; z[i] = zc; }
+    if (zmin != 0.0) {
+        const double vr_c3 = tr * (1.0 - exp(-(zmin - DZT) / hr));
+        acc = tr * exp(-(zmin - DZT) / hr);
+        hm[i3] = acc;
+        vr_sc = vr_c3 / c3;
+        for (int i = i3 + 1; i <= nt; i++) { acc = vr_sc + acc; hm[i] = acc; }
+    }
+    __syncthreads();
+    for (int i = i1 + 1 + lane; i <= i2; i += 64) hm[i] = tr * exp(-z[i] / hr);
+    __syncthreads();
+    for (int i = i1 + lane; i <= i2; i += 64) h[i] = ta * (hm[i] - hm[i - 1]) / vr_c2;
+    __syncthreads();
+    for (int i = 1; i <= c1; i++) ha[i] = 0.;
+    acc = 0.;
+    for (int i = i1; i <= i2; i++) { acc = acc + h[i]; ha[i] = acc; }
+    for (int i = i3; i <= nt; i++) ha[i] = acc;
+    __syncthreads();
+    for (int i = lane; i <= nt; i += 64) {
+        if (i == 0) {
+            z[0] = TOA; h[0] = tr * exp(-TOA / hr) + ha[0];          // Hmol(0), assigned after the chains: H(0) != 0
+            pca[0] = 0.; pcm[0] = 1.;
+            continue;
+        }
+        h[i] = hm[i] + ha[i];
+        z[i] = hr * log(tr / hm[i]);
+        if (ha[i] == ha[i - 1]) { pca[i] = 0.; pcm[i] = 1.; }
+        else { const double ym = 1 / (1 + (ta / vr_c2)); pcm[i] = ym; pca[i] = 1 - ym; }
+    }
+    __syncthreads();
+}
+
+// The bin of one layer profile, shared by the single form (the entry as a kernel argument) and the table form (the entry of
+// bin b): the block above, then the no-gas branch of profile_bin_body on it -- round trip, hvrai, rescale, IBORM, output level,
+// scal -- with the layer's NT in place of nt_ng.  An entry whose counts do not add up to its NT, or whose NT does not fit the
+// rows, makes no block and comes back flagged (nt = -1), as a no-gas profile that does not fit lp.
+__global__ __launch_bounds__(64) void k_profile_layer(LayerArgs q)
+{
+    const int b = blockIdx.x;
+    if (b >= q.nb) return;
+    const LayerWl &t = q.tab ? q.tab[b] : q.one;
+    __shared__ double rows[6][SOS_LAYER_ROW];
+    const int nb_tr = t.zmin == 0.0 ? 1 : 2;
+    const bool grid_ok = t.c1 >= 1 && t.c2 >= 1 && (nb_tr == 1 ? t.c3 == 0 : t.c3 >= 1) && t.nt == nb_tr + t.c1 + t.c2 + t.c3 &&
+                         t.nt < SOS_LAYER_ROW;
+    const bool fits = grid_ok && t.nt < q.lp;
+    if (fits) profile_layer_body(t.tr, t.hr, t.ta, t.zmin, t.zmax, t.nt, t.c1, t.c2, t.c3, rows[0], rows[1], rows[2], rows[3], rows[4], rows[5]);
+    ProfileArgs a;
+    a.nb = q.nb; a.lp = q.lp; a.nblev = 0; a.absprofil = 7; a.smax = t.smax; a.nt_ng = grid_ok ? t.nt : -1;
+    a.tr = t.tr; a.hr = t.hr; a.ta = t.ta; a.ha = 1.; a.a_tronc = t.a_tronc; a.piz = t.piz; a.piztr = t.piztr; a.zout = t.zout;
+    a.altabs = nullptr; a.tabs = nullptr;
+    a.z_ng = rows[0]; a.h_ng = rows[1]; a.pca_ng = rows[2]; a.pcm_ng = rows[3];
+    a.prof = q.prof; a.zprof = q.zprof; a.scal = q.scal; a.nt = q.nt; a.iborm = q.iborm; a.hvrai = q.hvrai;
+    const bool lev = t.zout != -1.0 && q.jout;
+    a.jout = lev ? q.jout : nullptr; a.zz = lev ? q.zz : nullptr;
+    profile_bin_body<true>(a, b, nullptr, nullptr);
+}
+
+void launch_profile_layer(const LayerArgs &q, hipStream_t st)
+{
+    k_profile_layer<<<q.nb, 64, 0, st>>>(q);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // SOS_ABSPROFILE (src/SOS_ABSPROFILE.F:325-371) for every CKD bin of a wavelength: the absorption coefficient XK of a gas
 // depends on the gas, on the exponential term chosen for it and on the layer only, so the host tabulates
 // xk[gas][term][layer] (COEFF_ABS_CKD, SOS_SUB_TRS.F:171) once and a bin is one term index per gas.  Per bin, exactly the

@@ -203,14 +203,10 @@ def profile_nogas(tr, hr, ta, ha):
     return _round_sig(h, 8), _round_sig(pcaer, 8), _round_sig(pcmol, 8), np.round(z, 5)
 
 
-def profile_layer(tr, hr, ta, zmin, zmax):
-    """SOS_PROFILE for IPROFIL=2 (SOS_PROFIL.F:800-946): a homogeneous aerosol + molecule layer between zmin and zmax (km)
-    inside a molecular atmosphere, no gas absorption, then the PROFIL_TMP text round trip.  Returns h, xdel, ydel, zprof.
-
-    The reference starts its recurrence `Hmol(I)=Hmol(I-1)+VR_SC` (:873) from an Hmol(0) it assigns only at :926 -- a local
-    array element read before it is written.  On a fresh stack it is 0, which is also the evident intent (the optical
-    depth at the top of the atmosphere, assigned TR*exp(-120/HR) ~ 1e-7 TR afterwards); this restatement starts from 0 and
-    is pinned against the reference's routine called on a fresh stack (tests/golden/profile_layer.npz)."""
+def layer_grid(tr, hr, ta, zmin, zmax):
+    """The level counts of profile_layer (SOS_PROFIL.F:800-870): (nt, nbsc_c1, nbsc_c2, nbsc_c3), the levels of the profile
+    and the sublayers above the layer, inside it and below it (0 for a layer on the ground).  Raises the routine's two refusals.
+    The C library states the same closed forms (sosgpu_profile_layer_grid)."""
     if zmin < 0.0 or zmax <= zmin:
         raise SosProcError("SOS_PROFIL: -AP.AerLayer.Zmin / Zmax must satisfy 0 <= Zmin < Zmax", ier=-1)
     ttot = tr + ta
@@ -219,7 +215,6 @@ def profile_layer(tr, hr, ta, zmin, zmax):
         nt = CTE_OS_NT
     dzt = _F(0.010)                                   # CTE_DZTRANSI (REAL*4 literal, SOS.h:240)
     vr_c1 = tr * math.exp(-(zmax + dzt) / hr)
-    vr_c2 = tr * (math.exp(-zmin / hr) - math.exp(-(zmax + dzt) / hr))
     if zmin == 0.0:
         vr_c3, nb_tr = 0.0, 1
     else:
@@ -229,6 +224,22 @@ def profile_layer(tr, hr, ta, zmin, zmax):
     nbsc_c2 = (nt - nb_tr) - nbsc_c1 - nbsc_c3
     if nbsc_c2 <= 0 or (ta / nbsc_c2) < _F(0.00001):
         raise SosProcError("SOS_PROFIL: not enough sublayers in the aerosol layer (ERROR 1020)", ier=-1)
+    return nt, nbsc_c1, nbsc_c2, nbsc_c3
+
+
+def profile_layer(tr, hr, ta, zmin, zmax):
+    """SOS_PROFILE for IPROFIL=2 (SOS_PROFIL.F:800-946): a homogeneous aerosol + molecule layer between zmin and zmax (km)
+    inside a molecular atmosphere, no gas absorption, then the PROFIL_TMP text round trip.  Returns h, xdel, ydel, zprof.
+
+    The reference starts its recurrence `Hmol(I)=Hmol(I-1)+VR_SC` (:873) from an Hmol(0) it assigns only at :926 -- a local
+    array element read before it is written.  On a fresh stack it is 0, which is also the evident intent (the optical
+    depth at the top of the atmosphere, assigned TR*exp(-120/HR) ~ 1e-7 TR afterwards); this restatement starts from 0 and
+    is pinned against the reference's routine called on a fresh stack (tests/golden/profile_layer.npz)."""
+    nt, nbsc_c1, nbsc_c2, nbsc_c3 = layer_grid(tr, hr, ta, zmin, zmax)
+    dzt = _F(0.010)                                   # CTE_DZTRANSI (REAL*4 literal, SOS.h:240)
+    vr_c1 = tr * math.exp(-(zmax + dzt) / hr)
+    vr_c2 = tr * (math.exp(-zmin / hr) - math.exp(-(zmax + dzt) / hr))
+    vr_c3 = 0.0 if zmin == 0.0 else tr * (1.0 - math.exp(-(zmin - dzt) / hr))
     hmol = np.zeros(nt + 1); haer = np.zeros(nt + 1)
     vr_sc = vr_c1 / nbsc_c1
     for i in range(1, nbsc_c1 + 1):

@@ -31,7 +31,7 @@ import threading
 
 import numpy as np
 
-from .geometry import angles, profile_layer, profile_nogas, rayleigh_optical_thickness, sos_gauss  # noqa: F401
+from .geometry import angles, layer_grid, profile_layer, profile_nogas, rayleigh_optical_thickness, sos_gauss  # noqa: F401
 from .params import (CTE_DEFAULT_IGMAX, CTE_DEFAULT_NBMU_LUM, CTE_DEFAULT_NBMU_MIE, CTE_DEFAULT_OS_NB,  # noqa: F401
                      CTE_DEFAULT_OS_NM, CTE_DEFAULT_OS_NS, CTE_DELTA_Z, CTE_HT_STD_PSURF, CTE_LENFIC2, CTE_OS_NBMU_MAX,
                      CTE_OS_NT, CTE_OS_NT_MIN, CTE_TCOUCHE, CTE_TOA_ALT, CTE_TOA_FIRST_LAYER, EXTRA_KEYS,
@@ -461,9 +461,11 @@ def _gas_rule(p):
 
 
 def _defers_by_keywords(p, use_gas):
-    """The keyword part of "the pass makes the profiles of this call": -AP.AerProfile.Type 1, no -SOS.Trans, -SOS.AbsModeCKD 1
-    where the call has gas.  (_prepare adds what needs the optical thicknesses, the rank split and the table sizes.)"""
-    return int(p["iprofil"]) == 1 and str(p["fictrans"]).strip() == "NO_OUTPUT" and (not use_gas or p["imode_ckd_calcul"] == 1)
+    """The keyword part of "the pass makes the profiles of this call": -AP.AerProfile.Type 1 or 2 (an aerosol layer never has
+    gas: ERROR 2513), no -SOS.Trans, -SOS.AbsModeCKD 1 where the call has gas.  (_prepare adds what needs the optical
+    thicknesses, the rank split and the table sizes.)"""
+    return int(p["iprofil"]) in (1, 2) and str(p["fictrans"]).strip() == "NO_OUTPUT" and \
+        (not use_gas or p["imode_ckd_calcul"] == 1)
 
 
 def _aerosol_rule(p, aer_phase):
@@ -546,6 +548,17 @@ def _profiles_deferrable(tr, hr, ta, ha):
     try:
         ok = float(hr) > 0.0 and float(ha) > 0.0 and float(tr) >= 0.0 and float(ta) >= 0.0
         return bool(ok) and capi.lib().sosgpu_profile_nogas_levels(float(tr), float(ta)) >= 1
+    except Exception:
+        return False
+
+
+def _layer_deferrable(tr, hr, ta, zmin, zmax):
+    """True when sosgpu_profile_layer_spectrum takes this aerosol layer: its level grid exists (geometry.layer_grid, the closed
+    forms the library states too).  A layer that fails here keeps the per-wavelength path, which raises the grid's refusal."""
+    if os.environ.get("SOS_LAYER_PROFILE_HOST"):
+        return False
+    try:
+        return float(hr) > 0.0 and float(tr) > 0.0 and layer_grid(tr, hr, ta, float(zmin), float(zmax))[0] >= 1
     except Exception:
         return False
 
@@ -650,7 +663,8 @@ def _prepare_thickness(pl, defer_profiles):
     # runs while the host prepares gas tables, surface and context (a refused profile is reported by make_profiles below)
     pl.nogas = None
     pl.defer = bool(defer_profiles) and _defers_by_keywords(p, pl.absprofil != 7) and \
-        _profiles_deferrable(pl.tr, p["hr"], pl.ta, pl.ha)
+        (_profiles_deferrable(pl.tr, p["hr"], pl.ta, pl.ha) if pl.iprofil == 1 else
+         _layer_deferrable(pl.tr, p["hr"], pl.ta, p["zmin"], p["zmax"]))
     if pl.iprofil == 1 and not pl.defer:
         try:
             from .solver import nogas_profile
@@ -734,9 +748,18 @@ def _prepare_context(pl, defer_operators, order0=False):
 
 
 def _layer_profile(pl, true_depth):
-    """The single profile of an aerosol layer between -AP.AerLayer.Zmin and Zmax (-AP.AerProfile.Type 2, no gas): made on the
-    host and uploaded.  Returns its bins."""
+    """The single profile of an aerosol layer between -AP.AerLayer.Zmin and Zmax (-AP.AerProfile.Type 2, no gas): on the device
+    (SosContext.make_layer_profile), after the refusals of its level grid.  SOS_LAYER_PROFILE_HOST=1 (environment, for A/B
+    timing and as the checker): made on the host by geometry.profile_layer and uploaded.  Returns its bins."""
     p, zout = pl.p, pl.zout
+    if not os.environ.get("SOS_LAYER_PROFILE_HOST"):
+        from .solver import layer_lp
+        nt = layer_grid(pl.tr, p["hr"], pl.ta, float(p["zmin"]), float(p["zmax"]))[0]
+        try:
+            return pl.ctx.make_layer_profile(pl.tr, p["hr"], pl.ta, float(p["zmin"]), float(p["zmax"]), a_tronc=pl.a_tronc,
+                                             piz=pl.piz, piztr=pl.piztr, zout=zout, lp=layer_lp(nt), true_depth=bool(true_depth))
+        except Exception as e:
+            raise SosProcError("SOS_PROFILE: %s" % e, ier=-1)
     h, xdel, ydel, zprof = profile_layer(pl.tr, p["hr"], pl.ta, float(p["zmin"]), float(p["zmax"]))
     ttot_vrai = h[-1]
     h_kw = dict(hvrai=np.array(h, dtype=np.float64)[None]) if true_depth else {}   # H before the rescale
@@ -801,7 +824,13 @@ def _prepare_profiles(pl, shard_bins, true_depth):
     common = dict(tr=pl.tr, hr=p["hr"], ta=pl.ta, ha=pl.ha, a_tronc=pl.a_tronc, piz=pl.piz, piztr=pl.piztr, zout=pl.zout,
                   smax=ctx.smax)
     true_kw = dict(true_depth=True) if true_depth else {}      # (split=False: the calls as they were)
-    if pl.defer and not pl.use_gas:
+    if pl.defer and not pl.use_gas and pl.iprofil == 2:
+        # (an aerosol layer: the request of solver.make_layer_profiles_spectrum -- `ha` has no meaning there)
+        from .solver import layer_lp
+        pl.profile_request = dict(common, zmin=float(p["zmin"]), zmax=float(p["zmax"]), layer=True,
+                                  lp=layer_lp(layer_grid(pl.tr, p["hr"], pl.ta, float(p["zmin"]), float(p["zmax"]))[0]))
+        pl.bins, pl.aik = None, np.ones(1)
+    elif pl.defer and not pl.use_gas:
         pl.profile_request = dict(common, ik=None, absprofil=7)
         pl.bins, pl.aik = None, np.ones(1)
     elif pl.defer:
@@ -844,9 +873,10 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     aer_stream: HIP stream (torch.cuda.Stream) for the aerosol step, whose device calls are host-synchronous -- sos_spectrum keeps
     them off the streams its asynchronous work is queued on.
     aer_at_wa: the result of SOS_AEROSOLS at the simulation wavelength when sos_spectrum has formed it already (aerosols_many).
-    defer_profiles (_spectrum_pass only): a call that qualifies -- -AP.AerProfile.Type 1, no -SOS.Trans, -SOS.AbsModeCKD 1 or
-    no gas, band not sharded -- gets no profile launches here: the plan comes back with `bins` None and `profile_request`, the
-    request solver.make_profiles_spectrum takes, and the pass makes the profiles of a whole part in three launches.
+    defer_profiles (_spectrum_pass only): a call that qualifies -- no -SOS.Trans, -SOS.AbsModeCKD 1 or no gas, band not sharded
+    -- gets no profile launches here: the plan comes back with `bins` None and `profile_request`, the request
+    solver.make_profiles_spectrum takes (for an aerosol layer: solver.make_layer_profiles_spectrum), and the pass makes the
+    profiles of a whole part in three launches (the layers: one more).
     device_gas_tables (with defer_profiles): a deferred gas wavelength hands over its `prep` instead of the layer tables xk --
     COEFF_ABS_CKD then runs on the device for the whole part (sosgpu_ckd_layer_tables) and absorption.layer_tables not at all.
     true_depth (the levels calls with split=True): the bins also carry `hvrai`, the cumulative optical depth of every level
@@ -1367,15 +1397,27 @@ def _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, a
 
 def _stage_profiles(ch, part, alts, level_keys, true_kw, dev):
     """The profiles of the part's qualifying wavelengths: three launches for all their bins (the operators the side streams
-    are still building are not needed for them), one more for the output slots."""
+    are still building are not needed for them), one more for the output slots.  The aerosol layers among them are made by a
+    call of their own (solver.make_layer_profiles_spectrum: one launch), with output slots of their own -- one call per row
+    length (solver.layer_lp: layers below 32, below 64 levels, the others), which is one where the layers of a part are alike."""
+    import functools
     from . import solver
-    deferred = [pl for pl in part if pl.bins is None]
+    waiting = [pl for pl in part if pl.bins is None]
+    _stage_profiles_of(ch, [pl for pl in waiting if not pl.profile_request.get("layer")], solver.make_profiles_spectrum, alts,
+                       level_keys, true_kw, dev)
+    for lp in sorted({pl.profile_request["lp"] for pl in waiting if pl.profile_request.get("layer")}):
+        _stage_profiles_of(ch, [pl for pl in waiting if pl.profile_request.get("layer") and pl.profile_request["lp"] == lp],
+                           functools.partial(solver.make_layer_profiles_spectrum, lp=lp), alts, level_keys, true_kw, dev)
+
+
+def _stage_profiles_of(ch, deferred, make, alts, level_keys, true_kw, dev):
+    """_stage_profiles for the calls one table-form profile call `make` covers."""
     if not deferred:
         return
     ch.where = deferred[0].index
     info = {}
     try:
-        made = solver.make_profiles_spectrum([pl.profile_request for pl in deferred], dev, part=info, **true_kw)
+        made = make([pl.profile_request for pl in deferred], dev, part=info, **true_kw)
     except Exception as e:
         if info.get("bad") is not None:
             ch.where = deferred[info["bad"]].index

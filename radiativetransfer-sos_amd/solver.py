@@ -374,6 +374,31 @@ class SosContext:
             capi.check(capi.lib().sosgpu_profile(*args, self._stream()), "sosgpu_profile")
         return bins
 
+    def make_layer_profile(self, tr, hr, ta, zmin, zmax, *, a_tronc=0.0, piz=1.0, piztr=1.0, zout=-1.0, lp=608,
+                           true_depth=False):
+        """SOS_PROFILE for IPROFIL = 2 (an aerosol layer between zmin and zmax km, no gas) + the SOS.F rescale ON THE DEVICE
+        (sosgpu_profile_layer): the dict make_profiles returns for one bin -- device `zprof` and `scal`, `hvrai` with
+        true_depth=True.  The refusals of the level grid (geometry.layer_grid) come back as the library's error before
+        anything is queued; a profile that does not fit lp has nt = -1."""
+        d = self.device
+        # (one cleared block: the doubles, then nt, iborm and jout as int32 in its last two doubles)
+        nd = 4 * lp + 5 + (lp if true_depth else 0)
+        fb = torch.zeros(nd + 2, dtype=torch.float64, device=d)
+        ib = fb[nd:].view(torch.int32)
+        prof, zprof, scal = fb[:3 * lp].view(1, 3, lp), fb[3 * lp:4 * lp].view(1, lp), fb[4 * lp:4 * lp + 4].view(1, 4)
+        nt, iborm = ib[0:1], ib[1:2]
+        jout = zz = None
+        if zout != -1.0:
+            jout, zz = ib[2:3], fb[4 * lp + 4:4 * lp + 5]
+        bins = dict(nb=1, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=jout, zz=zz, zprof=zprof, scal=scal)
+        if true_depth:
+            bins["hvrai"] = fb[4 * lp + 5:nd].view(1, lp)
+        capi.check(capi.lib().sosgpu_profile_layer(self._h, float(tr), float(hr), float(ta), float(zmin), float(zmax),
+                                                   float(a_tronc), float(piz), float(piztr), float(zout), lp, _ptr(prof), _ptr(nt),
+                                                   _ptr(iborm), _ptr(zprof), _ptr(jout), _ptr(zz), _ptr(scal),
+                                                   _ptr(bins.get("hvrai")), self._stream()), "sosgpu_profile_layer")
+        return bins
+
     def solve_band(self, bins, aik, seg=None, group=None, tdifmug=None, reduce=True):
         """The whole per-wavelength bin loop of SOS_PROC (SOS_PROC.F:3459-3594) for bins already on the device
         (upload_bins / make_profiles): fused SOS_OS of every bin, AIK-weighted SOS_AGGREGATE, and -- when
@@ -1316,6 +1341,88 @@ def make_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None, t
     part.update(bins=dict(nb=nb, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=None, zz=None, zprof=zprof, scal=scal),
                 tabs=tabs_l, seg=seg, upload=up, ckd_status=status, ckd_index=pk["ckd_index"],
                 ckd_keep=(work, [t[2] for t in tables.values()]))
+    if true_depth:
+        part["bins"]["hvrai"] = hvrai
+    return out
+
+
+def layer_lp(nt):
+    """Row length for an aerosol-layer profile of nt levels: 32, 64 or 608 -- the level class (lp <= 32, <= 64, above) of the
+    row upload_bins gives the host profile (16 ceil((nt + 1) / 16)), which is what selects the solver kernel.  A thin layer
+    (tr + ta < 0.32) so keeps the LDS-resident kernels, and the device profile the solve of the host profile."""
+    return 32 if nt < 32 else 64 if nt < 64 else 608
+
+
+def pack_layer_requests(requests, lp=608, true_depth=False):
+    """Host side of make_layer_profiles_spectrum (pure numpy): the table and the layout of the one device block of a list of
+    aerosol-layer requests.  A request is a dict with the arguments of SosContext.make_layer_profile of one wavelength -- tr, hr,
+    ta, zmin, zmax, a_tronc, piz, piztr, zout -- and `smax`, the highest Fourier order of its context.  Returns a dict:
+      wl        structured array [nwl] (capi.LAYER_WL_DTYPE = sosgpu_layer_wl): the one buffer that is uploaded
+      nb, seg   a wavelength is one bin: nb = nwl, seg = 0..nwl
+      off       where the sections of the cleared block start, in doubles: prof[nb][3][lp], zprof[nb][lp], scal[nb][4], zz[nb],
+                hvrai[nb][lp] (true_depth, else empty), work (the call's work area, work_doubles long), ints (nt, iborm and
+                jout[nb] as int32)
+      doubles   length of the block."""
+    nwl = len(requests)
+    wl = np.zeros(nwl, dtype=capi.LAYER_WL_DTYPE)
+    for w, r in enumerate(requests):
+        for k in ("tr", "hr", "ta", "zmin", "zmax", "a_tronc", "piz", "piztr", "zout"):
+            wl[k][w] = float(r[k])
+        wl["smax"][w] = int(r["smax"])
+    nb = nwl
+    work_doubles = -(-nwl * capi.LAYER_ENTRY_BYTES // 8)
+    off, at = {}, 0
+    for name, n in (("prof", nb * 3 * lp), ("zprof", nb * lp), ("scal", nb * 4), ("zz", nb),
+                    ("hvrai", nb * lp if true_depth else 0), ("work", work_doubles), ("ints", -(-3 * nb // 2))):
+        off[name] = at
+        at += n
+    return dict(wl=wl, nb=nb, seg=np.arange(nwl + 1, dtype=np.int64), off=off, work_doubles=work_doubles, doubles=at)
+
+
+def make_layer_profiles_spectrum(requests, device=0, stream=None, lp=608, part=None, true_depth=False):
+    """The aerosol-layer profiles (IPROFIL = 2) of MANY wavelengths in one launch (sosgpu_profile_layer_spectrum), shaped like
+    make_profiles_spectrum.  requests: see pack_layer_requests.  One upload (the table, by the library), one cleared allocation
+    for all bins and the work area, queued on `stream` (a torch stream; None: the current one), nothing waited for.  Returns one
+    `bins` dict per request, as SosContext.make_layer_profile returns it for that wavelength alone -- the same keys, dtypes and,
+    bit for bit, values; the tensors are views of the shared block.
+    part: optional dict, filled with `bins` (all bins as one dict, for output_levels), `tabs` (None per request), `seg`, and --
+    when the library refuses a wavelength -- `bad`, its index in requests."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    pk = pack_layer_requests(requests, lp, true_depth)
+    nwl, nb, off = len(requests), pk["nb"], pk["off"]
+    L = capi.lib()
+    need = int(L.sosgpu_profile_layer_spectrum_work_bytes(nwl))
+    if need > 8 * pk["work_doubles"]:
+        raise RuntimeError("sosgpu_profile_layer_spectrum_work_bytes: the table entry is not capi.LAYER_ENTRY_BYTES long")
+    if part is None:
+        part = {}
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        fb = torch.zeros(pk["doubles"], dtype=torch.float64, device=dev)
+        prof, zprof = fb[:off["zprof"]].view(nb, 3, lp), fb[off["zprof"]:off["scal"]].view(nb, lp)
+        scal, zz = fb[off["scal"]:off["zz"]].view(nb, 4), fb[off["zz"]:off["hvrai"]]
+        hvrai = fb[off["hvrai"]:off["work"]].view(nb, lp) if true_depth else None
+        work = fb[off["work"]:off["ints"]]
+        ib = fb[off["ints"]:].view(torch.int32)
+        nt, iborm, jout = ib[:nb], ib[nb:2 * nb], ib[2 * nb:3 * nb]
+        any_out = bool((pk["wl"]["zout"] != -1.0).any())
+        bad = C.c_int(-1)
+        rc = L.sosgpu_profile_layer_spectrum(dev.index or 0, nwl, pk["wl"].ctypes.data_as(C.c_void_p), lp, _ptr(work), need,
+                                             _ptr(prof), _ptr(nt), _ptr(iborm), _ptr(zprof), _ptr(jout) if any_out else None,
+                                             _ptr(zz) if any_out else None, _ptr(scal), _ptr(hvrai), C.byref(bad), st)
+    if rc != 0 and bad.value >= 0:
+        part["bad"] = int(bad.value)
+    capi.check(rc, "sosgpu_profile_layer_spectrum")
+    out = []
+    for w in range(nwl):
+        lev = float(pk["wl"]["zout"][w]) != -1.0
+        out.append(dict(nb=1, lp=lp, perm=None, nt=nt[w:w + 1], iborm=iborm[w:w + 1], prof=prof[w:w + 1],
+                        jout=jout[w:w + 1] if lev else None, zz=zz[w:w + 1] if lev else None, zprof=zprof[w:w + 1],
+                        scal=scal[w:w + 1]))
+        if true_depth:
+            out[-1]["hvrai"] = hvrai[w:w + 1]
+    part.update(bins=dict(nb=nb, lp=lp, perm=None, nt=nt, iborm=iborm, prof=prof, jout=None, zz=None, zprof=zprof, scal=scal),
+                tabs=[None] * nwl, seg=pk["seg"], ckd_status=None, ckd_index=[])
     if true_depth:
         part["bins"]["hvrai"] = hvrai
     return out

@@ -43,6 +43,7 @@
  *   sosgpu_ckd_layer_tables <- COEFF_ABS_CKD      src/SOS_SUB_TRS.F:171 (every gas, term and layer of many wavelengths)
  *   sosgpu_noyaux      <- SOS_NOYAUX              src/SOS_OS.F:1857   (phase-matrix Fourier kernels,
  *                                                                     hoisted out of the bin loop)
+ *   sosgpu_create_spectrum    the contexts (SOS_PREPA_OS) of a part of a spectrum: one asynchronous call, one launch
  *   sosgpu_os_solve    <- SOS_OS (+ leaves)       src/SOS_OS.F:303    (one call = a batch of CKD bins,
  *                                                                     i.e. the loop SOS_PROC.F:3459-3594)
  *   sosgpu_aggregate   <- SOS_AGGREGATE           src/SOS_AGGREGATE.F:172
@@ -105,6 +106,32 @@ int  sosgpu_create(sosgpu_ctx **out, int device, const sosgpu_wave *wv, const do
                    const double *alpha, const double *beta, const double *gamma, const double *zeta,
                    int iborm_max);
 int  sosgpu_destroy(sosgpu_ctx *cx);
+/* sosgpu_create for the nctx contexts of a part of a spectrum in ONE asynchronous call: the small tables of all of them travel
+ * to the work area in one staged copy, and one launch (k_ctx_fill) moves each into its context's block and clears what
+ * sosgpu_create clears.  The contexts are, field for field and bit for bit, those nctx sosgpu_create calls make; each has its
+ * own block of the pool, and sosgpu_destroy, sosgpu_ctx_bytes and every later call treat them alike.
+ *  out[nctx]       receives the contexts
+ *  specs[nctx]     HOST array; the contexts may differ in every size and flag
+ *  d_work, work_bytes   see "Work areas": the job table and the images of the small tables,
+ *                  sosgpu_create_spectrum_work_bytes(specs, nctx) bytes
+ * Asynchronous on `stream`: nothing is waited for (see "Streams").  On return every context is in the host-side state
+ * sosgpu_create leaves and `stream` is noted for sosgpu_destroy, so a context may be destroyed at once (the destroy waits for
+ * the fill); its device tables are in place once `stream` has passed the call.  Work queued later on the same stream sees
+ * them; work that reads them on OTHER streams (sosgpu_noyaux, a solve, sosgpu_ctx_table's readers) must be ordered after the
+ * call by the caller (event / synchronise).
+ * Every spec is checked before any device call, allocation or staging block, by the rules of sosgpu_create (sizes, n0, igmax,
+ * iborm_max, NULL arrays, no direction with a weight).  SOSGPU_E_ARG for: NULL out, NULL specs with nctx > 0, nctx < 0 or
+ * nctx > 65535, a bad spec, the work area's rules.  On any refusal or failure every out[i] is NULL and no context survives
+ * (a HIP failure after some contexts were made destroys them).  nctx = 0 returns SOSGPU_OK with nothing queued.  The query is
+ * host arithmetic and returns 0 for a list the call would refuse. */
+typedef struct sosgpu_ctx_spec {      /* the arguments of one sosgpu_create */
+    sosgpu_wave wv;
+    const double *mu, *ga, *alpha, *beta, *gamma, *zeta;   /* HOST arrays, as sosgpu_create takes them */
+    int32_t iborm_max, reserved;
+} sosgpu_ctx_spec;
+size_t sosgpu_create_spectrum_work_bytes(const sosgpu_ctx_spec *specs, int nctx);
+int    sosgpu_create_spectrum(sosgpu_ctx **out, int device, const sosgpu_ctx_spec *specs, int nctx,
+                              void *d_work, size_t work_bytes, void *stream);
 
 /* Surface reflection matrices for imat_surf=1: REAL*4, reference FICSURF record order
  * d_rsurf[s][ab][(J-1)*N+(I-1)] = R_ab(I,J), s = 0..iborm_max (SOS_OS.F:916-925).  Device pointer; the call

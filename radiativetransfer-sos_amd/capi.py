@@ -35,6 +35,7 @@ EXPORTS = [
     "sosgpu_level_absorption", "sosgpu_level_irradiance",
     "sosgpu_debug_order0_kpairs", "sosgpu_debug_ctx_order0_kpairs",
     "sosgpu_profile_layer_grid", "sosgpu_profile_layer", "sosgpu_profile_layer_spectrum", "sosgpu_profile_layer_spectrum_work_bytes",
+    "sosgpu_create_spectrum", "sosgpu_create_spectrum_work_bytes",
 ]
 NOGAS_LEVELS = 608     # SOSGPU_NOGAS_LEVELS
 MAX_OUTPUT_LEVELS = 16  # SOSGPU_MAX_OUTPUT_LEVELS: output slots of one sosgpu_os_solve_levels call
@@ -112,6 +113,12 @@ class Wave(C.Structure):
                 ("ro", C.c_double), ("ind_surf", C.c_double), ("ron", C.c_double)]
 
 
+class CtxSpec(C.Structure):
+    """sosgpu_ctx_spec (include/sosgpu.h): the arguments of one sosgpu_create, an entry of sosgpu_create_spectrum."""
+    _fields_ = [("wv", Wave)] + [(k, C.c_void_p) for k in ("mu", "ga", "alpha", "beta", "gamma", "zeta")] + \
+               [("iborm_max", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Land(C.Structure):
     """struct sosgpu_land"""
     _fields_ = [("isurf", C.c_int32), ("reserved", C.c_int32), ("k0", C.c_double), ("k1", C.c_double), ("k2", C.c_double),
@@ -162,6 +169,10 @@ def lib():
         L.sosgpu_device_count.restype = i32
         L.sosgpu_create.restype = i32
         L.sosgpu_create.argtypes = [C.POINTER(vp), i32, C.POINTER(Wave), vp, vp, vp, vp, vp, vp, i32]
+        L.sosgpu_create_spectrum_work_bytes.restype = C.c_size_t
+        L.sosgpu_create_spectrum_work_bytes.argtypes = [C.POINTER(CtxSpec), i32]
+        L.sosgpu_create_spectrum.restype = i32
+        L.sosgpu_create_spectrum.argtypes = [C.POINTER(vp), i32, C.POINTER(CtxSpec), i32, vp, C.c_size_t, vp]
         L.sosgpu_destroy.restype = i32
         L.sosgpu_destroy.argtypes = [vp]
         L.sosgpu_set_surface_matrices.restype = i32

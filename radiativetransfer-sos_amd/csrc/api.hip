@@ -102,17 +102,138 @@ hipError_t sync_ctx_streams(sosgpu_ctx *cx)
 }
 }   // namespace sosgpu_internal
 
-extern "C" int sosgpu_create(sosgpu_ctx **out, int device, const sosgpu_wave *wv, const double *mu, const double *ga,
-                             const double *alpha, const double *beta, const double *gamma, const double *zeta,
-                             int iborm_max)
-{
-    if (!out || !wv || !mu || !ga || !alpha || !beta || !gamma || !zeta) return SOSGPU_E_ARG;
-    const int N = wv->n, B = wv->os_nb;
-    if (N < 1 || N > 85 || B < 2 || B > 400 || iborm_max < 0 || iborm_max > B) return SOSGPU_E_ARG;
-    if (wv->n0 < 1 || wv->n0 > N) return SOSGPU_E_ARG;          // the solar direction must be one of mu[]
-    if (wv->igmax < 1) return SOSGPU_E_ARG;
-    if (const int rc = use_device(device)) return rc;
+// The host half of a new context, shared by sosgpu_create and sosgpu_create_spectrum (the same statements, so the same bits):
+// the argument rules (ctx_args_ok, and ctx_plan's "no direction has a weight"), the layout numbers and scalars of SosDev with
+// the offsets of the context's one allocation (ctx_plan), the image of its small tables (ctx_image), the host-side state of a
+// context that has its block (ctx_new, ctx_place).  None of them makes a device call.
+namespace {
+struct CtxArgs {                // the arguments of one sosgpu_create
+    const sosgpu_wave *wv;
+    const double *mu, *ga, *alpha, *beta, *gamma, *zeta;
+    int iborm_max;
+};
 
+// Offsets in doubles, each a multiple of 32 (256-byte alignment of the operator fragments).  The context's small tables share
+// ONE allocation: [mu | ga | coef | fres | rowmap] copied, [mp_vt | mp_uf] cleared (a spectrum creates one context per
+// wavelength: five pageable uploads, two fills and ten pool requests were 0.2 ms of each) ...
+struct CtxPlan {
+    SosDev d;                   // everything but the pointers
+    size_t o_mu, o_ga, o_coef, o_fres, o_map, o_vt, o_uf, n_small;
+    // ... followed, in the same allocation, by the tables the kernels of sosgpu_noyaux / sosgpu_set_surface_matrices fill
+    // (one pool request -- in a cold process one hipMalloc -- per context instead of six)
+    size_t o_prt, o_aer, o_sv, o_gop, o_gdir, n_all;
+};
+
+bool ctx_args_ok(const CtxArgs &a)
+{
+    const sosgpu_wave *wv = a.wv;
+    if (!wv || !a.mu || !a.ga || !a.alpha || !a.beta || !a.gamma || !a.zeta) return false;
+    const int N = wv->n, B = wv->os_nb;
+    if (N < 1 || N > 85 || B < 2 || B > 400 || a.iborm_max < 0 || a.iborm_max > B) return false;
+    if (wv->n0 < 1 || wv->n0 > N) return false;          // the solar direction must be one of mu[]
+    if (wv->igmax < 1) return false;
+    return true;
+}
+
+// flat-sea Fresnel matrix at direction cosine m, SOS_MAT_FRESNEL_PLAN_REFL (SOS_OS.F:1753-1780)
+void ctx_fresnel(double ind_surf, int ipolar, double m, double *f11, double *f12, double *f33)
+{
+    const double ind2 = ind_surf * ind_surf, mu2 = m * m;
+    const double x = sqrt(ind2 - 1.0 + mu2);
+    const double rl = (ind2 * m - x) / (ind2 * m + x);
+    const double rr = (m - x) / (m + x);
+    *f11 = (rl * rl + rr * rr) / 2.;
+    *f12 = ipolar ? (rl * rl - rr * rr) / 2. : 0.;
+    *f33 = ipolar ? rl * rr : 0.;
+}
+
+// SOSGPU_E_ARG for arguments ctx_args_ok refuses and when no direction has a weight
+int ctx_plan(CtxPlan &p, const CtxArgs &a)
+{
+    if (!ctx_args_ok(a)) return SOSGPU_E_ARG;
+    const sosgpu_wave *wv = a.wv;
+    const double *mu = a.mu, *ga = a.ga;
+    const int N = wv->n, B = wv->os_nb;
+    SosDev &d = p.d;
+    memset(&d, 0, sizeof(d));
+    d.n = N; d.w = 2 * N + 1; d.r6 = 6 * N;
+    d.kp = sos_round_up(6 * N, 8);
+    d.kh = sos_round_up(3 * N, 8);
+    // half-system row order: directions with a non-zero quadrature weight first (component-major), the zero-weight
+    // ones (the solar direction, user angles: SOS_ANGLES gives them weight 0) last.  Their operator COLUMNS vanish, so
+    // the contraction only runs over K = 3 Nw (N = 41: 15 k-pairs instead of 16); their rows are still computed.
+    int nwgt = 0;
+    for (int j = 0; j < N; j++) nwgt += ga[j] != 0.0;
+    if (nwgt < 1) return SOSGPU_E_ARG;
+    d.nwgt = nwgt;
+    d.ks2h = (3 * nwgt + 7) / 8;
+    {   // projection rows ride in the last quad of the last row tile when that quad is padding
+        const int cand = ((3 * N - 1) / 16) * 16 + 12;
+        d.prow = cand >= 3 * N ? cand : -1;
+    }
+    d.rtph = (d.kh + 15) / 16;
+    d.os_nb = B; d.smax = a.iborm_max;
+    d.n0 = wv->n0; d.imat_surf = wv->imat_surf == 1; d.ifresnel = wv->ifresnel == 1 ? 1 : 0;
+    d.igmax = wv->igmax; d.ipolar = wv->ipolar ? 1 : 0;
+    d.ks2h0 = sos_order0_kpairs(nwgt, d.ks2h, d.imat_surf != 0);      // order 0: the I and Q columns only (solve_variant.h)
+    d.mus = mu[wv->n0 - 1];
+    d.ro = wv->ro;
+    // molecular phase-matrix coefficients, SOS_OS.F:678-684
+    double aaa = wv->ron / (2 - wv->ron);
+    aaa = (1 - aaa) / (1 + 2 * aaa);
+    d.beta2 = 0.5 * aaa; d.gamma2 = -aaa * sqrt(1.5); d.alpha2 = 3. * aaa;
+    if (!d.ipolar) { d.gamma2 = 0.; d.alpha2 = 0.; }    // SOS_OS.F:689-699
+    // thresholds: REAL*4 literals widened (SOS.h:389,394,400), D literal (SOS.h:395)
+    d.thr_cv = (double)0.00001f; d.thr_sum = (double)0.00001f; d.thr_sf = (double)0.00001f; d.thr_val = 1.0e-50;
+    if (d.ifresnel) {
+        double f33;
+        ctx_fresnel(wv->ind_surf, d.ipolar, d.mus, &d.f11sun, &d.f12sun, &f33);
+    }
+    auto up32 = [](size_t v) { return (v + 31) & ~(size_t)31; };
+    const size_t n_coef = (size_t)4 * (B + 1), n_fres = (size_t)3 * N, n_map = (size_t)d.kh;
+    p.o_mu = 0; p.o_ga = up32(p.o_mu + N); p.o_coef = up32(p.o_ga + N); p.o_fres = up32(p.o_coef + n_coef);
+    p.o_map = up32(p.o_fres + n_fres); p.o_vt = up32(p.o_map + (n_map + 1) / 2);
+    const size_t n_vt = (size_t)3 * d.ks2h * 128, n_uf = (size_t)3 * d.rtph * 64;
+    p.o_uf = up32(p.o_vt + n_vt); p.n_small = p.o_uf + n_uf;
+    const size_t per = (size_t)2 * d.rtph * d.ks2h * 128, S1c = (size_t)d.smax + 1;
+    p.o_prt = up32(p.n_small); p.o_aer = up32(p.o_prt + S1c * 3 * (B + 1) * d.w); p.o_sv = up32(p.o_aer + S1c * per);
+    p.o_gop = up32(p.o_sv + S1c * 4 * d.kp);
+    const size_t n_gop = d.imat_surf ? S1c * (per / 2) : 0, n_gdir = d.imat_surf ? S1c * 3 * N : 0;
+    p.o_gdir = up32(p.o_gop + n_gop); p.n_all = p.o_gdir + n_gdir;
+    return SOSGPU_OK;
+}
+
+// the small-table image [mu | ga | coef | fres | rowmap] of p.o_vt doubles, padding zero
+void ctx_image(const CtxPlan &p, const CtxArgs &a, double *img)
+{
+    const SosDev &d = p.d;
+    const int N = d.n, B = d.os_nb;
+    memset(img, 0, p.o_vt * sizeof(double));
+    memcpy(img + p.o_mu, a.mu, (size_t)N * sizeof(double));
+    memcpy(img + p.o_ga, a.ga, (size_t)N * sizeof(double));
+    double *coef = img + p.o_coef;                       // IPOLAR = 0 (SOS_OS.F:689-699): beta alone, the other rows stay 0
+    memcpy(coef + (B + 1), a.beta, (size_t)(B + 1) * sizeof(double));
+    if (d.ipolar) {
+        memcpy(coef, a.alpha, (size_t)(B + 1) * sizeof(double));
+        memcpy(coef + 2 * (B + 1), a.gamma, (size_t)(B + 1) * sizeof(double));
+        memcpy(coef + 3 * (B + 1), a.zeta, (size_t)(B + 1) * sizeof(double));
+    }
+    if (d.ifresnel) {
+        double *fres = img + p.o_fres;
+        for (int j = 0; j < N; j++) ctx_fresnel(a.wv->ind_surf, d.ipolar, a.mu[j], fres + j, fres + N + j, fres + 2 * N + j);
+    }
+    int32_t *rowmap = reinterpret_cast<int32_t *>(img + p.o_map);
+    for (int q = 0; q < d.kh; q++) rowmap[q] = -1;
+    int pos = 0;
+    for (int pass = 0; pass < 2; pass++)
+        for (int c = 0; c < 3; c++)
+            for (int j = 0; j < N; j++)
+                if ((a.ga[j] != 0.0) == (pass == 0)) rowmap[pos++] = c * N + j;
+}
+
+// a context in the host-side state sosgpu_create leaves, before it has its block
+sosgpu_ctx *ctx_new(int device, const CtxPlan &p, const sosgpu_wave *wv)
+{
     sosgpu_ctx *cx = new sosgpu_ctx();
     cx->device = device;
     cx->bytes = 0;
@@ -129,120 +250,151 @@ extern "C" int sosgpu_create(sosgpu_ctx **out, int device, const sosgpu_wave *wv
     cx->prof_ng_stream = nullptr;
     cx->gnd_op = nullptr;
     cx->gnd_dir = nullptr;
+    cx->ev0 = cx->ev1 = nullptr;                           // (created by the first solve)
+    cx->d = p.d;
+    return cx;
+}
+
+// the context's pointers into its block `small` of p.n_all doubles
+void ctx_place(sosgpu_ctx *cx, const CtxPlan &p, double *small)
+{
     SosDev &d = cx->d;
-    memset(&d, 0, sizeof(d));
-    d.n = N; d.w = 2 * N + 1; d.r6 = 6 * N;
-    d.kp = sos_round_up(6 * N, 8);
-    d.kh = sos_round_up(3 * N, 8);
-    // half-system row order: directions with a non-zero quadrature weight first (component-major), the zero-weight
-    // ones (the solar direction, user angles: SOS_ANGLES gives them weight 0) last.  Their operator COLUMNS vanish, so
-    // the contraction only runs over K = 3 Nw (N = 41: 15 k-pairs instead of 16); their rows are still computed.
-    int nwgt = 0;
-    for (int j = 0; j < N; j++) nwgt += ga[j] != 0.0;
-    if (nwgt < 1) { delete cx; return SOSGPU_E_ARG; }
-    d.ks2h = (3 * nwgt + 7) / 8;
-    {   // projection rows ride in the last quad of the last row tile when that quad is padding
-        const int cand = ((3 * N - 1) / 16) * 16 + 12;
-        d.prow = cand >= 3 * N ? cand : -1;
-    }
-    std::vector<int32_t> rowmap(d.kh, -1);
-    {
-        int pos = 0;
-        for (int pass = 0; pass < 2; pass++)
-            for (int c = 0; c < 3; c++)
-                for (int j = 0; j < N; j++)
-                    if ((ga[j] != 0.0) == (pass == 0)) rowmap[pos++] = c * N + j;
-    }
-    d.rtph = (d.kh + 15) / 16;
-    d.os_nb = B; d.smax = iborm_max;
-    d.n0 = wv->n0; d.imat_surf = wv->imat_surf == 1; d.ifresnel = wv->ifresnel == 1 ? 1 : 0;
-    d.igmax = wv->igmax; d.ipolar = wv->ipolar ? 1 : 0;
-    d.ks2h0 = sos_order0_kpairs(nwgt, d.ks2h, d.imat_surf != 0);      // order 0: the I and Q columns only (solve_variant.h)
-    d.mus = mu[wv->n0 - 1];
-    d.ro = wv->ro;
-    // molecular phase-matrix coefficients, SOS_OS.F:678-684
-    double aaa = wv->ron / (2 - wv->ron);
-    aaa = (1 - aaa) / (1 + 2 * aaa);
-    d.beta2 = 0.5 * aaa; d.gamma2 = -aaa * sqrt(1.5); d.alpha2 = 3. * aaa;
-    std::vector<double> coef((size_t)4 * (B + 1));
-    for (int l = 0; l <= B; l++) {
-        coef[l] = alpha[l]; coef[(B + 1) + l] = beta[l]; coef[2 * (B + 1) + l] = gamma[l]; coef[3 * (B + 1) + l] = zeta[l];
-    }
-    if (!d.ipolar) {    // SOS_OS.F:689-699
-        d.gamma2 = 0.; d.alpha2 = 0.;
-        for (int l = 0; l <= B; l++) { coef[l] = 0.; coef[2 * (B + 1) + l] = 0.; coef[3 * (B + 1) + l] = 0.; }
-    }
-    // thresholds: REAL*4 literals widened (SOS.h:389,394,400), D literal (SOS.h:395)
-    d.thr_cv = (double)0.00001f; d.thr_sum = (double)0.00001f; d.thr_sf = (double)0.00001f; d.thr_val = 1.0e-50;
-    // flat-sea Fresnel matrix, SOS_MAT_FRESNEL_PLAN_REFL (SOS_OS.F:1753-1780)
-    std::vector<double> fres((size_t)3 * N, 0.);
-    if (d.ifresnel) {
-        for (int j = 0; j <= N; j++) {
-            const double m = (j == 0) ? d.mus : mu[j - 1];
-            const double ind2 = wv->ind_surf * wv->ind_surf, mu2 = m * m;
-            const double x = sqrt(ind2 - 1.0 + mu2);
-            const double rl = (ind2 * m - x) / (ind2 * m + x);
-            const double rr = (m - x) / (m + x);
-            const double f11 = (rl * rl + rr * rr) / 2.;
-            const double f12 = d.ipolar ? (rl * rl - rr * rr) / 2. : 0.;
-            const double f33 = d.ipolar ? rl * rr : 0.;
-            if (j == 0) { d.f11sun = f11; d.f12sun = f12; }
-            else { fres[j - 1] = f11; fres[N + j - 1] = f12; fres[2 * N + j - 1] = f33; }
-        }
-    }
+    d.mu = small + p.o_mu; d.ga = small + p.o_ga; d.coef = small + p.o_coef; d.fres = small + p.o_fres;
+    d.rowmap = reinterpret_cast<int32_t *>(small + p.o_map);
+    d.mp_vt = small + p.o_vt; d.mp_uf = small + p.o_uf;
+    d.prt = small + p.o_prt; d.mp_aer = small + p.o_aer; d.sv = small + p.o_sv;
+    if (d.imat_surf) { cx->gnd_op = small + p.o_gop; cx->gnd_dir = small + p.o_gdir; }
+}
+}   // namespace
+
+extern "C" int sosgpu_create(sosgpu_ctx **out, int device, const sosgpu_wave *wv, const double *mu, const double *ga,
+                             const double *alpha, const double *beta, const double *gamma, const double *zeta,
+                             int iborm_max)
+{
+    const CtxArgs a = {wv, mu, ga, alpha, beta, gamma, zeta, iborm_max};
+    if (!out || !ctx_args_ok(a)) return SOSGPU_E_ARG;
+    if (const int rc = use_device(device)) return rc;
+    CtxPlan p;
+    if (const int rc = ctx_plan(p, a)) return rc;
     int rc;
     hipStream_t us = util_stream(device);
-    if (!us) { delete cx; return SOSGPU_E_HIP; }
-    // The context's small tables share ONE allocation, filled by ONE copy from a pinned block of the calling thread and one
-    // memset: [mu | ga | coef | fres | rowmap] copied, [mp_vt | mp_uf] cleared (a spectrum creates one context per
-    // wavelength: five pageable uploads, two fills and ten pool requests were 0.2 ms of each).  Offsets in doubles, each
-    // a multiple of 32 (256-byte alignment of the operator fragments).
-    auto up32 = [](size_t v) { return (v + 31) & ~(size_t)31; };
-    const size_t o_mu = 0, o_ga = up32(o_mu + N), o_coef = up32(o_ga + N), o_fres = up32(o_coef + coef.size()),
-                 o_map = up32(o_fres + fres.size()), o_vt = up32(o_map + (rowmap.size() + 1) / 2),
-                 n_vt = (size_t)3 * d.ks2h * 128, n_uf = (size_t)3 * d.rtph * 64, o_uf = up32(o_vt + n_vt), n_small = o_uf + n_uf;
-    // ... followed, in the same allocation, by the tables the kernels of sosgpu_noyaux / sosgpu_set_surface_matrices fill
-    // (one pool request -- in a cold process one hipMalloc -- per context instead of six)
-    const size_t per = (size_t)2 * d.rtph * d.ks2h * 128, S1c = (size_t)d.smax + 1;
-    const size_t o_prt = up32(n_small), o_aer = up32(o_prt + S1c * 3 * (B + 1) * d.w), o_sv = up32(o_aer + S1c * per),
-                 o_gop = up32(o_sv + S1c * 4 * d.kp), n_gop = d.imat_surf ? S1c * (per / 2) : 0, o_gdir = up32(o_gop + n_gop),
-                 n_gdir = d.imat_surf ? S1c * 3 * N : 0, n_all = o_gdir + n_gdir;
+    if (!us) return SOSGPU_E_HIP;
+    sosgpu_ctx *cx = ctx_new(device, p, wv);
     double *small = nullptr;
-    if ((rc = dev_alloc(cx, &small, n_all))) { sosgpu_destroy(cx); return rc; }
+    if ((rc = dev_alloc(cx, &small, p.n_all))) { sosgpu_destroy(cx); return rc; }
+    // filled by ONE copy from a pinned block of the calling thread and one memset
+    auto up32 = [](size_t v) { return (v + 31) & ~(size_t)31; };
     static thread_local double *stage = nullptr;           // (kept for the life of the thread: 64 KB at the largest N and OS_NB)
     static thread_local size_t stage_n = 0;
-    if (stage_n < o_vt) {
+    if (stage_n < p.o_vt) {
         if (stage) (void)hipHostFree(stage);
         stage = nullptr; stage_n = 0;
-        if (hipHostMalloc((void **)&stage, up32(o_vt + 4096) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        if (hipHostMalloc((void **)&stage, up32(p.o_vt + 4096) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
             g_last_hip = (int)hipGetLastError(); sosgpu_destroy(cx); return SOSGPU_E_HIP; }
-        stage_n = up32(o_vt + 4096);
+        stage_n = up32(p.o_vt + 4096);
     }
-    memset(stage, 0, o_vt * sizeof(double));
-    memcpy(stage + o_mu, mu, (size_t)N * sizeof(double));
-    memcpy(stage + o_ga, ga, (size_t)N * sizeof(double));
-    memcpy(stage + o_coef, coef.data(), coef.size() * sizeof(double));
-    memcpy(stage + o_fres, fres.data(), fres.size() * sizeof(double));
-    memcpy(stage + o_map, rowmap.data(), rowmap.size() * sizeof(int32_t));
-    d.mu = small + o_mu; d.ga = small + o_ga; d.coef = small + o_coef; d.fres = small + o_fres;
-    d.rowmap = reinterpret_cast<int32_t *>(small + o_map);
-    d.nwgt = nwgt;
-    d.mp_vt = small + o_vt; d.mp_uf = small + o_uf;
-    d.prt = small + o_prt; d.mp_aer = small + o_aer; d.sv = small + o_sv;
-    if (d.imat_surf) { cx->gnd_op = small + o_gop; cx->gnd_dir = small + o_gdir; }
+    ctx_image(p, a, stage);
+    ctx_place(cx, p, small);
     // The upload and the fill run on the calling thread's utility stream and are waited for here (the pinned block is reused by
     // the thread's next call): when the call returns every table is in place, whatever stream sosgpu_noyaux and the solves are
     // queued on afterwards.  (Round 2 filled on the null stream: a non-blocking caller stream does not wait for it, and a fill
     // could land on top of the molecular operator sosgpu_noyaux had already packed.)
-    if (hipMemcpyAsync(small, stage, o_vt * sizeof(double), hipMemcpyHostToDevice, us) != hipSuccess ||
-        hipMemsetAsync(small + o_vt, 0, (n_small - o_vt) * sizeof(double), us) != hipSuccess ||
+    if (hipMemcpyAsync(small, stage, p.o_vt * sizeof(double), hipMemcpyHostToDevice, us) != hipSuccess ||
+        hipMemsetAsync(small + p.o_vt, 0, (p.n_small - p.o_vt) * sizeof(double), us) != hipSuccess ||
         wait_short(us) != hipSuccess) {
         g_last_hip = (int)hipGetLastError();
         sosgpu_destroy(cx);
         return SOSGPU_E_HIP;
     }
-    cx->ev0 = cx->ev1 = nullptr;                           // (created by the first solve)
     *out = cx;
+    return SOSGPU_OK;
+}
+
+// sosgpu_create for the nctx contexts of a part of a spectrum: d_work = [job table | images], each image 256-byte aligned IN
+// DEVICE MEMORY (k_ctx_fill moves 16 bytes per lane, and an area need only be 8-byte aligned: the layout keeps 248 bytes spare and
+// starts at the first 256-byte address of the area), filled by one copy from a recycled pinned block (Staged); one k_ctx_fill
+// launch then does for every context what the copy and the memset of sosgpu_create do.  Nothing is waited for.
+namespace {
+struct CreateLayout {
+    size_t jobs, table_bytes, total;         // table_bytes: what the one copy moves; total: with the spare bytes
+    std::vector<size_t> image;               // byte offset of every image from the aligned start
+    size_t max_doubles;                      // largest n_small of the contexts (the grid of k_ctx_fill)
+};
+constexpr size_t kImageAlign = 256;
+
+// the plans and the layout of a list of specs; SOSGPU_E_ARG when the call would refuse the list (nctx = 0: an empty layout)
+int create_layout(const sosgpu_ctx_spec *specs, int nctx, std::vector<CtxPlan> &plans, CreateLayout &L)
+{
+    if (nctx < 0 || nctx > 65535 || (!specs && nctx > 0)) return SOSGPU_E_ARG;
+    plans.resize((size_t)nctx);
+    L.image.resize((size_t)nctx);
+    L.max_doubles = 0;
+    WorkLayout w;
+    L.jobs = w.take((size_t)nctx * sizeof(CtxFillJob), kImageAlign);
+    for (int i = 0; i < nctx; i++) {
+        const sosgpu_ctx_spec &s = specs[i];
+        const CtxArgs a = {&s.wv, s.mu, s.ga, s.alpha, s.beta, s.gamma, s.zeta, s.iborm_max};
+        if (const int rc = ctx_plan(plans[i], a)) return rc;
+        L.image[i] = w.take(plans[i].o_vt * sizeof(double), kImageAlign);
+        L.max_doubles = std::max(L.max_doubles, plans[i].n_small);
+    }
+    L.table_bytes = w.total;
+    w.take(kImageAlign - 8, 8);
+    L.total = nctx > 0 ? w.total : 0;
+    return SOSGPU_OK;
+}
+}   // namespace
+
+extern "C" size_t sosgpu_create_spectrum_work_bytes(const sosgpu_ctx_spec *specs, int nctx)
+{
+    std::vector<CtxPlan> plans;
+    CreateLayout L;
+    return create_layout(specs, nctx, plans, L) == SOSGPU_OK ? L.total : 0;
+}
+
+extern "C" int sosgpu_create_spectrum(sosgpu_ctx **out, int device, const sosgpu_ctx_spec *specs, int nctx, void *d_work,
+                                      size_t work_bytes, void *stream)
+{
+    if (!out) return SOSGPU_E_ARG;
+    for (int i = 0; i < nctx; i++) out[i] = nullptr;
+    std::vector<CtxPlan> plans;
+    CreateLayout L;
+    if (const int rc = create_layout(specs, nctx, plans, L)) return rc;
+    if (nctx == 0) return SOSGPU_OK;
+    if (!work_area_ok(d_work, work_bytes, L.total)) return SOSGPU_E_ARG;
+    if (const int rc = use_device(device)) return rc;
+    Staged s(device, L.table_bytes);
+    if (s.rc) return s.rc;
+    char *stage = static_cast<char *>(s.host());
+    char *d_base = static_cast<char *>(d_work) + ((kImageAlign - ((uintptr_t)d_work & (kImageAlign - 1))) & (kImageAlign - 1));
+    CtxFillJob *jobs = reinterpret_cast<CtxFillJob *>(stage + L.jobs);
+    std::vector<sosgpu_ctx *> made;
+    auto undo = [&made](int rc) { for (sosgpu_ctx *cx : made) sosgpu_destroy(cx); return rc; };
+    for (int i = 0; i < nctx; i++) {
+        const sosgpu_ctx_spec &sp = specs[i];
+        const CtxArgs a = {&sp.wv, sp.mu, sp.ga, sp.alpha, sp.beta, sp.gamma, sp.zeta, sp.iborm_max};
+        const CtxPlan &p = plans[i];
+        sosgpu_ctx *cx = ctx_new(device, p, &sp.wv);
+        made.push_back(cx);
+        double *small = nullptr;
+        if (const int rc = dev_alloc(cx, &small, p.n_all)) return undo(rc);
+        ctx_image(p, a, reinterpret_cast<double *>(stage + L.image[i]));
+        ctx_place(cx, p, small);
+        jobs[i].dst = small;
+        jobs[i].src_off = (uint32_t)(L.image[i] / sizeof(double));
+        jobs[i].n_copy = (uint32_t)p.o_vt;
+        jobs[i].n_clear = (uint32_t)(p.n_small - p.o_vt);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = s.send(d_base, st);
+    if (e == hipSuccess) {
+        launch_ctx_fill(reinterpret_cast<const CtxFillJob *>(d_base + L.jobs), reinterpret_cast<const double *>(d_base), nctx,
+                        L.max_doubles, st);
+        e = hipGetLastError();
+        for (sosgpu_ctx *cx : made) note_stream(cx, st);          // (a destroy -- undo's too -- waits for the fill)
+    }
+    if (e != hipSuccess) { g_last_hip = (int)e; return undo(SOSGPU_E_HIP); }
+    for (int i = 0; i < nctx; i++) out[i] = made[i];
     return SOSGPU_OK;
 }
 

@@ -14,6 +14,15 @@ struct NoyauxTableGrid {
 };
 void launch_noyaux_table(const SosDev *d_tab, int nctx, const NoyauxTableGrid &g, hipStream_t st);
 
+// The small tables of many new contexts (ctx_fill.hip k_ctx_fill, sosgpu_create_spectrum): job i copies n_copy doubles from
+// d_images + src_off to dst and clears the n_clear doubles behind them.  dst, d_images + src_off: 16-byte aligned; the three
+// counts: multiples of 32 doubles.  One launch of (tiles of the largest n_copy + n_clear = max_doubles, nctx) workgroups.
+struct CtxFillJob {
+    double *dst;
+    uint32_t src_off, n_copy, n_clear;
+};
+void launch_ctx_fill(const CtxFillJob *d_jobs, const double *d_images, int nctx, size_t max_doubles, hipStream_t st);
+
 // Fused successive-orders solver, LDS-resident variants (sos_os.hip).  `pl`: the solve's plan -- the launcher runs the
 // instantiation its variant fields name (solve_variant.h) and derives nothing itself.  Returns 0, SOSGPU_E_UNSUPPORTED when the
 // context does not fit that variant, or -2 with the HIP error code in *hip_err.

@@ -723,8 +723,11 @@ def _prepare_surface(pl):
     pl.rsurf = rsurf
 
 
-def _prepare_context(pl, defer_operators, order0=False):
+def _prepare_context(pl, defer_operators, order0=False, defer_context=False):
     """The device context of the wavelength (SOS_PREPA_OS), unbuilt where the pass builds the operators of a whole part.
+    defer_context: the context is left pending (SosContext(create=False)) where nothing in _prepare needs its handle -- a call
+    that defers its profiles (pl.defer: _prepare_profiles then reads ctx.smax alone) and its operators; the pass makes the
+    contexts of a whole part in one call (_stage_contexts).
     order0 (the irradiance pass): the context holds the Fourier order 0 alone -- iborm_max = 0, record 0 of the surface
     matrices (formed as they are: an order-limited sosgpu_surface_batch does not exist) -- and the profile stage, which takes
     the highest order from it, gives every bin iborm = 0."""
@@ -737,10 +740,11 @@ def _prepare_context(pl, defer_operators, order0=False):
     isurf = int(p["isurf"])
     alpha, beta, gamma, zeta = pl.phase
     pl.want_trans = str(p["fictrans"]).strip() != "NO_OUTPUT"
+    build = not (defer_operators and not pl.want_trans)
     pl.ctx = SosContext(pl.mu, pl.ga, pl.n0, alpha, beta, gamma, zeta, iborm_max=pl.iborm, ro=p["rho"], imat_surf=pl.imat,
                         ifresnel=pl.ifresnel, ind_surf=p["surf_ind"] if isurf in (1, 2) or isurf >= 4 else 1.34, ron=MDF_DEFAULT,
                         ipolar=int(p["ipolar"]), igmax=pl.igmax, rsurf=pl.rsurf, device=pl.device,
-                        build=not (defer_operators and not pl.want_trans))
+                        build=build, create=not (defer_context and pl.defer and not build))
     pl.tdifmug = None
     # (_spectrum_pass with trans: the plan's rows of the part's diffuse_transmissions_many; a scalar block that came from the host)
     pl.trans_rows = None
@@ -863,7 +867,7 @@ def _prepare_profiles(pl, shard_bins, true_depth):
 
 
 def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer_at_wa=None, defer_profiles=False,
-             device_gas_tables=False, defer_operators=False, true_depth=False, order0=False):
+             device_gas_tables=False, defer_operators=False, true_depth=False, order0=False, defer_context=False):
     """Everything of one SOS_PROC call up to the CKD bin loop (SOS_PROC.F:1310-3458): parameter checks, SOS_ANGLES,
     SOS_AEROSOLS, SOS_SURFACE, SOS_PREPA_ABSPROFILE, SOS_PREPA_OS, and the profiles of every bin of the band on the device
     (SOS_ABSPROFILE + SOS_PROFILE + the rescale of SOS).  Every stage fills its fields of the _Plan that comes back, whose `ctx`
@@ -885,7 +889,10 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     operator tables of a whole part in one solver.build_operators call -- unless this function uses the operators itself, which
     only a -SOS.Trans call does (diffuse_transmissions in _prepare_profiles).
     order0 (the irradiance mode of _spectrum_pass only): the context and the bins hold the Fourier order 0 alone
-    (_prepare_context)."""
+    (_prepare_context).
+    defer_context (_spectrum_pass only): a call that defers both its profiles and its operators comes back with a PENDING context
+    (SosContext(create=False)): nothing here needs its handle, and the pass creates the contexts of a whole part in one
+    solver.create_contexts call.  Every other call makes its own sosgpu_create, as sos_proc does."""
     _seg(None)
     missing = [k for k in SOS_PROC_KWARGS if k not in kw]
     if missing:
@@ -904,7 +911,8 @@ def _prepare(kw, aer_phase=None, device=0, shard_bins=True, aer_stream=None, aer
     _seg('gas tables')
     _prepare_surface(pl)
     _seg('surface')
-    _prepare_context(pl, defer_operators, **(dict(order0=True) if order0 else {}))
+    _prepare_context(pl, defer_operators, **(dict(order0=True) if order0 else {}),
+                     **(dict(defer_context=True) if defer_context else {}))
     _seg('context')
     try:
         _prepare_profiles(pl, shard_bins, true_depth)
@@ -1372,9 +1380,10 @@ def _part_bounds(n, parts, min_part):
 
 
 def _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, aer_st, aer_wa, alts, true_kw, batch_profiles,
-                   device_tables, batch_operators, debug):
+                   device_tables, batch_operators, debug, batch_contexts=False):
     """The calls idx[s0:s1] of a chunk prepared on the side streams (_prepare; output_levels of the calls that have their
-    bins).  Returns the plans of the part."""
+    bins).  Returns the plans of the part.  batch_contexts: the calls that can wait for it leave their context to
+    _stage_contexts (the keyword reaches _prepare only then, so that the calls are as they were without it)."""
     import torch
     part = []
     for k, i in enumerate(idx[s0:s1], s0):
@@ -1382,7 +1391,7 @@ def _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, a
         with torch.cuda.stream(side[k % len(side)]):
             pl = _prepare(kwargs_list[i], aer_phases[i], device, shard_bins=False, aer_stream=aer_st,
                           aer_at_wa=aer_wa.get(i), defer_profiles=batch_profiles, device_gas_tables=device_tables,
-                          defer_operators=batch_operators, **true_kw)
+                          defer_operators=batch_operators, **(dict(defer_context=True) if batch_contexts else {}), **true_kw)
             pl.writes_files = True
             pl.index = i
             ch.plans.append(pl)
@@ -1393,6 +1402,38 @@ def _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, a
             print("[%s] prepared" % fn, i, flush=True)
         part.append(pl)
     return part
+
+
+def _stage_contexts(ch, part, fn="sos_spectrum", debug=False):
+    """The contexts of the part's calls that _prepare left pending (defer_context: the calls that defer both their profiles and
+    their operators): ONE solver.create_contexts call on the main stream -- one staged copy, one launch, no host wait -- where
+    every such call made a sosgpu_create that waited for its copy.
+    Ordering: the fill of a context's block is queued on the main stream, so whatever reads the block must come behind it on
+    that stream.  Between _stage_prepare and _stage_operators nothing queued on a side stream does: what _prepare queues there
+    for a pending call is the upload of its surface matrices and its aerosol work, neither of which touches the context (a
+    pending context has no handle to pass); _stage_profiles and the output levels behind it run on the main stream, after this
+    stage; _stage_operators, the first reader of the small tables, runs on the main stream after the main stream has waited for
+    the side streams.  The blocks come from the pool, which holds only blocks whose last work has been waited for.
+    debug (SOS_SPECTRUM_DEBUG): the main stream is waited for and the calls whose contexts were made are printed."""
+    from . import capi, solver
+    pending = [pl for pl in part if pl.ctx._pending is not None]
+    if not pending:
+        return
+    ch.where = pending[0].index
+    _seg(None)
+    try:
+        solver.create_contexts([pl.ctx for pl in pending])
+    except Exception as e:
+        for pl in pending:           # a refused call is named: the one whose spec the library's query refuses on its own
+            if not capi.lib().sosgpu_create_spectrum_work_bytes(pl.ctx._pending, 1):
+                ch.where = pl.index
+                break
+        raise SosProcError("SOS_PREPA_OS: %s" % e, ier=getattr(e, "ier", -1))
+    _seg("stage: contexts")
+    if debug:
+        import torch
+        torch.cuda.current_stream(pending[0].ctx.device).synchronize()
+        print("[%s] contexts of wavelengths" % fn, [pl.index for pl in pending], flush=True)
 
 
 def _stage_profiles(ch, part, alts, level_keys, true_kw, dev):
@@ -1844,6 +1885,10 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
     # the sea and land surface matrices of a chunk's calls come from one asynchronous sosgpu_surface_batch per angle set, queued by
     # the prefetch; SOS_SPECTRUM_SURFACE_PER_CALL=1: every call that misses the cache makes its own synchronous call (A/B timing)
     batch_surfaces = not os.environ.get("SOS_SPECTRUM_SURFACE_PER_CALL")
+    # the contexts of a part's calls that defer both profiles and operators are made by one asynchronous sosgpu_create_spectrum on
+    # the main stream (_stage_contexts); SOS_SPECTRUM_CONTEXTS_PER_CALL=1: every call makes its own sosgpu_create, which waits for
+    # its copy (A/B timing, and the checker of the batch)
+    batch_contexts = batch_profiles and batch_operators and not os.environ.get("SOS_SPECTRUM_CONTEXTS_PER_CALL")
     ch, err = _Chunk(), None
     ch.where = -1                                       # the wavelength being worked on (named by a failure)
     # The cyclic garbage collector is paused for the pass: a spectrum allocates tens of container objects per wavelength next to
@@ -1871,7 +1916,8 @@ def _spectrum_pass(fn, kwargs_list, aer_phases, device, gather, chunk, timings, 
                 # (at least 32 wavelengths per part -- a launch per kernel variant each; SOS_SPECTRUM_MIN_PART: the tests' override)
                 for s0, s1 in _part_bounds(len(idx), parts, int(os.environ.get("SOS_SPECTRUM_MIN_PART", "32"))):
                     part = _stage_prepare(fn, ch, kwargs_list, aer_phases, device, idx, s0, s1, side, aer_st, aer_wa, alts,
-                                          prep_kw, batch_profiles, device_tables, batch_operators, debug)
+                                          prep_kw, batch_profiles, device_tables, batch_operators, debug, batch_contexts)
+                    _stage_contexts(ch, part, fn, debug)
                     _stage_profiles(ch, part, alts, level_keys, true_kw, dev)
                     for st in side:
                         main_st.wait_stream(st)
@@ -2198,6 +2244,9 @@ def sos_spectrum(kwargs_list, aer_phases=None, device=0, gather=True, chunk=256,
     and solver.build_operators fills the operator tables of a part in at most five launches on the stream of the solves
     (sosgpu_noyaux_spectrum), after the side streams -- which produce the surface matrices -- have been waited for; a -SOS.Trans
     call builds its own, and SOS_SPECTRUM_OPERATORS_PER_CALL=1 gives every call its four or five launches on its side stream.
+    The contexts of the calls that defer both their profiles and their operators are created for a whole part by one
+    asynchronous call on the stream of the solves (solver.create_contexts, sosgpu_create_spectrum: one staged copy, one launch,
+    no host wait); every other call makes its own sosgpu_create, and SOS_SPECTRUM_CONTEXTS_PER_CALL=1 makes all of them do.
 
     transmissions=True (a bool; every call with -SOS.Trans at NO_OUTPUT: ValueError naming the call otherwise, before any
     library call): returns (tuples, trans) with trans[i] the trans_entry of call i -- the diffuse transmittances TOA -> surface

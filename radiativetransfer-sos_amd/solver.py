@@ -166,10 +166,15 @@ class SosContext:
     surface), resident on one GPU, with the Fourier kernels of every order precomputed
     (sosgpu_noyaux, replaces SOS_NOYAUX SOS_OS.F:1857).
     build=False: the constructor stops after sosgpu_create -- the surface matrices are kept, nothing is queued -- and
-    build_operators() fills the operator tables of many such contexts in one call; solving before that is an error."""
+    build_operators() fills the operator tables of many such contexts in one call; solving before that is an error.
+    create=False (with build=False): the constructor does everything but sosgpu_create -- the context is PENDING, its handle
+    null and its arguments kept -- and create_contexts() makes the contexts of many such objects in one sosgpu_create_spectrum
+    call; a method that needs the handle before that raises, close() does nothing."""
 
     def __init__(self, mu, ga, n0, alpha, beta, gamma, zeta, *, iborm_max=None, ro=0.0, imat_surf=0,
-                 ifresnel=0, ind_surf=1.34, ron=MDF_DEFAULT, ipolar=1, igmax=100, rsurf=None, device=0, build=True):
+                 ifresnel=0, ind_surf=1.34, ron=MDF_DEFAULT, ipolar=1, igmax=100, rsurf=None, device=0, build=True, create=True):
+        if not create and build:
+            raise ValueError("create=False needs build=False: the operators are built on a created context")
         if not torch.cuda.is_available():
             raise RuntimeError("SosContext needs a GPU (gfx950); there is no CPU fallback in the product path")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -189,14 +194,21 @@ class SosContext:
         wv = capi.Wave(n=self.n, os_nb=self.os_nb, n0=self.n0, imat_surf=int(imat_surf), ifresnel=int(ifresnel),
                        ipolar=int(ipolar), igmax=int(igmax), reserved=0, ro=float(ro), ind_surf=float(ind_surf),
                        ron=float(ron))
-        self._h = C.c_void_p()
+        self._handle = C.c_void_p()
+        self._pending = None
         L = capi.lib()
         dp = lambda a: a.ctypes.data_as(C.c_void_p)
         SEG and SEG("context: python")
-        capi.check(L.sosgpu_create(C.byref(self._h), self.device.index or 0, C.byref(wv), dp(self.mu), dp(self.ga),
-                                   dp(coefs[0]), dp(coefs[1]), dp(coefs[2]), dp(coefs[3]), self.smax),
-                   "sosgpu_create")
-        SEG and SEG("context: sosgpu_create")
+        if create:
+            capi.check(L.sosgpu_create(C.byref(self._handle), self.device.index or 0, C.byref(wv), dp(self.mu), dp(self.ga),
+                                       dp(coefs[0]), dp(coefs[1]), dp(coefs[2]), dp(coefs[3]), self.smax),
+                       "sosgpu_create")
+            SEG and SEG("context: sosgpu_create")
+        else:
+            # (the arrays the spec points to are the object's own: they live as long as it does)
+            self._pending = capi.CtxSpec(wv=wv, mu=self.mu.ctypes.data, ga=self.ga.ctypes.data, alpha=coefs[0].ctypes.data,
+                                         beta=coefs[1].ctypes.data, gamma=coefs[2].ctypes.data, zeta=coefs[3].ctypes.data,
+                                         iborm_max=self.smax, reserved=0)
         self._rsurf = None
         self._built = False
         if int(imat_surf) == 1:
@@ -219,6 +231,13 @@ class SosContext:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    @property
+    def _h(self):
+        """The library's handle of the context: every call that takes one reads it here."""
+        if self._pending is not None:
+            raise RuntimeError("this context was created with create=False: call solver.create_contexts first")
+        return self._handle
 
     def noyaux(self):
         capi.check(capi.lib().sosgpu_noyaux(self._h, self._stream()), "sosgpu_noyaux")
@@ -658,9 +677,10 @@ class SosContext:
         return _level_irradiance(self, None, None, bins, levels, out, aik, seg)
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.lib().sosgpu_destroy(self._h)            # waits for the streams this context's work was queued on
-            self._h = C.c_void_p()
+        h = getattr(self, "_handle", None)                 # (a pending context has no handle: nothing to do)
+        if h is not None and h.value:
+            capi.lib().sosgpu_destroy(h)                  # waits for the streams this context's work was queued on
+            self._handle = C.c_void_p()
             self._rsurf = None
 
     def __del__(self):
@@ -798,6 +818,37 @@ def channel_finish(acc, angdiff_block):
     capi.check(capi.lib().sosgpu_channel_finish(d.index or 0, _ptr(acc), _ptr(blk), nchan, K, nphi, W, _ptr(out),
                                                 C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "sosgpu_channel_finish")
     return out
+
+
+def create_contexts(ctxs):
+    """The library contexts of the objects made with create=False, in ONE sosgpu_create_spectrum call on the current stream:
+    one staged copy of all their small tables and one launch; the same contexts, bit for bit, sosgpu_create makes.  The
+    objects live on one device and may differ in every size.  One that has its handle already is an error (ValueError, before
+    the call); an empty list does nothing.  Nothing is waited for: the tables are in place once the current stream has passed
+    the call, so work that reads them on another stream must be ordered behind it.  Returns the number of contexts made."""
+    ctxs = list(ctxs)
+    for cx in ctxs:
+        if cx._pending is None:
+            raise ValueError("create_contexts: a context of the list has its handle already (or was closed)")
+        if cx.device != ctxs[0].device:
+            raise ValueError("create_contexts: the contexts must live on one device")
+    if len({id(cx) for cx in ctxs}) != len(ctxs):
+        raise ValueError("create_contexts: a context appears twice in the list")
+    if not ctxs:
+        return 0
+    L = capi.lib()
+    n = len(ctxs)
+    first = ctxs[0]
+    specs =(capi.CtxSpec * n)(*[cx._pending for cx in ctxs])
+    need = int(L.sosgpu_create_spectrum_work_bytes(specs, n))
+    work = _work_area(need, first.device)
+    hs = (C.c_void_p * n)()
+    capi.check(L.sosgpu_create_spectrum(hs, first.device.index or 0, specs, n, _ptr(work), need, first._stream()),
+               "sosgpu_create_spectrum")
+    for cx, h in zip(ctxs, hs):
+        cx._handle = C.c_void_p(h)
+        cx._pending = None
+    return n
 
 
 def build_operators(ctxs):
